@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — analysis frames/s of the eaQHM hot path on N MI355X (one process per GPU).
 
-    python bench.py [--workload W] --gpus N --steps K --warmup W
+    python bench.py [--workload W] --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Called as plain `python bench.py --gpus N` with N > 1 (no WORLD_SIZE in the environment) it starts the N ranks
@@ -9,13 +9,21 @@ itself, as fresh child processes, before anything touches a GPU; rank 0 prints t
 
 A "step" is one complete run of the adaptation loop (functions.py:163-402) over the workload: adaptation
 0..maxAdpt or until the reference's stop rule fires.  Inputs (signal, pitch grid, frame tables) are resident in HBM
-before the timed region; result packing into Python structs is outside it — what lies outside is
-timed once and reported next to the metric in `host_stages_s` (SWIPE', VUV + frame plan, upload, collecting the final
-arrays, packing the Deterministic structs) together with the end-to-end rate a caller of eaQHMAnalysisAndSynthesis sees.
+before the timed region; result packing into Python structs is outside it.  `ms_per_step` is the
+wall time of one timed step.
 
-`roofline.frac` is the rate of the adaptation >= 1 launches (the kernel that executes the complex algorithm F(N, Kc)
-counts); the figure over all launches, which credits adaptation 0 with flops its closed-form real algorithm does not
-execute, is kept as `frac_all_launches_F_credit`.
+A plain run sets up, warms up, times the K steps and prints the headline (frames/s, ms_per_step, the run's SRER).
+`--dump-outputs DIR` then also writes what the last timed step computed — the arrays a caller of the analysis
+receives: a0, am, fm, pk, s_recon and SRER — as DIR/<name>.npy in float64 (at most 64 MB: see dump_outputs).
+`--full` adds everything else, as separate figures of the same line: HIP events around every launch of the timed
+steps and the roofline from them, the SRER of the reference's own run where a fixture has it, what lies outside the
+timed region timed once in `host_stages_s` (SWIPE', VUV + frame plan, upload, collecting the final arrays, packing the
+Deterministic structs) together with the end-to-end rate a caller of eaQHMAnalysisAndSynthesis sees, and the CPU
+baseline.
+
+`roofline.frac` (--full) is the rate of the adaptation >= 1 launches (the kernel that executes the complex algorithm
+F(N, Kc) counts); the figure over all launches, which credits adaptation 0 with flops its closed-form real algorithm
+does not execute, is kept as `frac_all_launches_F_credit`.
 
 Workloads (BASELINE.json configs):
     synth16k_60s  (default) synthetic 60 s speech @16 kHz, `female`, maxAdpt=5 — configs[3], the workload
@@ -188,6 +196,110 @@ def cpu_baseline(workload):
             "srer_db": [float(v) for v in runs[best][2]["SRER"]]}
 
 
+def launch_figures(eng, plan, n_adpt):
+    """--full: per-rank figures from the events of the timed region (LS launches on the launch stream)."""
+    import torch
+    torch.cuda.synchronize()
+    ls_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "ls"]
+    post_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "post"]
+    gather_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "gather"]
+    N = 2 * plan.frame_wl[eng.f_lo:eng.f_hi].astype(np.int64) + 1
+    n_act = [plan.frame_K[eng.f_lo:eng.f_hi].astype(np.int64)]          # adaptation 0: K harmonics
+    for nc in eng.ncol_hist[:max(n_adpt - 1, 0)]:                         # adaptations >= 1: active slots per frame
+        n_act.append(nc.cpu().numpy().astype(np.int64))
+    flops_per_launch = [float(ls_flops(N, 2 * n + 1).sum()) for n in n_act]
+    # algorithmic bytes per launch (SURVEY.md §8d): 8N signal window + 16 N n_active track windows (a >= 1) +
+    # 32 Kc amplitudes and slopes out
+    bytes_per_launch = [float(np.sum(8 * N) + (np.sum(16 * N * n) if a > 0 else 0) + np.sum(32 * (2 * n + 1)))
+                        for a, n in enumerate(n_act)]
+    return {"ls_ms": ls_ms, "post_ms": post_ms, "gather_ms": gather_ms, "flops_per_launch": flops_per_launch,
+            "bytes_per_launch": bytes_per_launch, "flops_step": sum(flops_per_launch)}
+
+
+def roofline_figures(lf, eng, plan, fs, workload, world, allr):
+    """--full: the roofline of the dominant kernel from launch_figures() of all ranks (`allr`: one row per rank)."""
+    ls_ms, post_ms, gather_ms = lf["ls_ms"], lf["post_ms"], lf["gather_ms"]
+    flops_per_launch, bytes_per_launch, flops_step = lf["flops_per_launch"], lf["bytes_per_launch"], lf["flops_step"]
+    # roofline of the dominant kernel: algorithmic flops of ALL ranks' launches / (sum of their durations / ranks),
+    # i.e. per-GPU achieved rate averaged over the ranks
+    ls_total_s = float(allr[:, 2].sum())
+    achieved = float(allr[:, 3].sum()) / ls_total_s / 1e12 if ls_total_s > 0 else 0.0
+    kernel = "eaqhm_ls_tile_kernel" if fs <= 16000 else "eaqhm_ls_mfma_kernel"
+    # Adaptation 0 is solved by a cheaper algorithm than the one F(N, Kc) counts (closed-form Gramian, two real systems of
+    # half the order), so its launch "achieves" more algorithmic flops per second than the matrix pipe does work: the
+    # rate of the adaptation >= 1 launches alone (rank 0) is reported next to the overall one
+    ls_a = [a for (a, st, e0, e1) in eng.timeline if st == "ls"]
+    t_ge1 = sum(t for a, t in zip(ls_a, ls_ms) if a >= 1) / 1e3
+    f_ge1 = sum(flops_per_launch[a] for a in ls_a if a >= 1 and a < len(flops_per_launch))
+    frac_ge1 = (f_ge1 / t_ge1 / 1e12 / PEAK_FP64_TFLOPS) if t_ge1 > 0 else None
+    ms0 = [t for a, t in zip(ls_a, ls_ms) if a == 0]
+    # HBM traffic of that kernel: not measurable from inside this process; taken from the committed rocprofv3 PMC
+    # passes of this same command and workload (profiles/r03_<workload>/pmc_hbm_traffic.json), N = 1 only
+    # (the PMC passes of tools/profile_round.sh; used only if they were taken with exactly these kernel sources)
+    traffic, traffic_src = None, None
+    pmc = os.path.join(ROOT, "profiles", "r03_%s" % workload, "pmc_hbm_traffic.json")
+    src = source_hash()
+    if world == 1 and os.path.exists(pmc):
+        j = json.load(open(pmc))
+        traffic_src = {"file": os.path.relpath(pmc, ROOT), "profile_source_hash": j.get("source_hash"),
+                       "tree_source_hash": src}
+        if j.get("source_hash") == src:
+            traffic = j.get(kernel, {}).get("hbm_bytes_per_launch_fetch_doubled")
+        else:
+            traffic_src["stale"] = "kernel sources changed since the counter passes: traffic withheld"
+    achieved_all = achieved
+    if frac_ge1 is not None:
+        achieved = frac_ge1 * PEAK_FP64_TFLOPS
+    roofline = {"bound": "mfma", "kernel": kernel, "achieved": achieved, "peak": PEAK_FP64_TFLOPS,
+                "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_TFLOPS,
+                "frac_definition": "algorithmic flops F(N,Kc) of the adaptation >= 1 launches / their HIP-event time "
+                                   "(rank 0); all launches incl. the cheaper closed-form adaptation 0: frac_all_launches_F_credit",
+                "frac_all_launches_F_credit": achieved_all / PEAK_FP64_TFLOPS, "traffic": traffic,
+                "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)",
+                "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": float(np.mean(bytes_per_launch)),
+                "algorithmic_bytes_launch0": bytes_per_launch[0],
+                "flops_per_launch_mean": flops_step / max(len(flops_per_launch), 1),
+                "launch_ms_mean": float(np.mean(ls_ms)) if ls_ms else None,
+                "launch_ms_adaptation0": float(np.mean(ms0)) if ms0 else None,
+                "frac_adaptation_ge1_launches": frac_ge1,
+                "source_hash": src,
+                "launches_timed": len(ls_ms),
+                "post_stage_ms_mean": float(np.mean(post_ms)) if post_ms else None,
+                # the bandwidth-type stage (SURVEY 8d: spline + interpolation + synthesis + SRER, functions.py:337-388):
+                # algorithmic bytes = records read (1+3 Kmax) 8 No_ti + tracks and reconstruction written (1+2 Kmax) 8 L
+                "post_stage_hbm": (lambda b, t: {"bound": "hbm", "algorithmic_bytes": b, "achieved_GBps": b / t / 1e6,
+                                                 "peak_GBps": 8000.0, "frac": b / t / 1e6 / 8000.0})(
+                    float((1 + 3 * plan.Kmax) * 8 * plan.No_ti + (1 + 2 * plan.Kmax) * 8 * (eng.t_hi - eng.t_lo)),
+                    float(np.mean(post_ms))) if post_ms else None,
+                "all_gather_ms_mean": float(np.mean(gather_ms)) if gather_ms else None,
+                "ls_ms_mean_per_rank": [float(v) for v in allr[:, 4]],
+                "ls_frames_per_rank": [int(v) for v in allr[:, 5]],
+                "ls_imbalance_max_over_mean": float(allr[:, 4].max() / allr[:, 4].mean()) if allr[:, 4].mean() > 0 else None}
+    return roofline
+
+
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs writes at most this many bytes in all
+
+
+def dump_outputs(outdir, arrays):
+    """`arrays` as outdir/<name>.npy in float64.  The arrays of more than 1 MiB share what the small ones leave of
+    DUMP_BYTES; where they do not fit, each keeps the same fraction of its rows (elements of a 1-D array): a fixed
+    sample, numpy.random.default_rng(0).choice without replacement, kept in order — the same rows for the same length,
+    so am / fm / pk keep the same instants."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    big = [k for k, a in arrays.items() if a.nbytes > 2 ** 20]
+    room = DUMP_BYTES - 1024 * len(arrays) - sum(a.nbytes for k, a in arrays.items() if k not in big)   # .npy headers
+    need = sum(arrays[k].nbytes for k in big)
+    frac = min(1.0, room / need) if need else 1.0
+    for k, a in arrays.items():
+        if k in big and frac < 1.0:
+            n = a.shape[0]
+            a = a[np.sort(np.random.default_rng(0).choice(n, int(n * frac), replace=False))]
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as child processes (nothing in this process
     has touched a GPU yet) and pass rank 0's JSON line through.  The children are polled: the first one that fails takes
@@ -239,11 +351,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--max-adpt", type=int, default=5)
     ap.add_argument("--workload", default="synth16k_60s", choices=WORKLOADS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-stages", action="store_true", help="skip the one-off timing of SWIPE' / VUV / packing")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (HIP events in the timed steps), the SRER of the reference, the host "
+                         "stages and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-stages", action="store_true",
+                    help="with --full: skip the one-off timing of SWIPE' / VUV / packing")
     ap.add_argument("--track-budget-mb", type=float, default=0.0,
                     help="time-block streaming of the dense tracks under this budget (0: resident) — SURVEY 8f row 4")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -306,7 +426,7 @@ def main():
     for _ in range(args.warmup):
         eng.reset()
         eng.run()
-    eng.profile = True               # HIP events around every LS launch, on the launch stream
+    eng.profile = args.full          # --full: HIP events around every LS launch, on the launch stream
     barrier()
     t0 = time.perf_counter()
     frames_done = 0
@@ -318,23 +438,16 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
 
-    # ---- per-rank figures from the events of the timed region (LS launches on the launch stream)
-    torch.cuda.synchronize()
-    ls_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "ls"]
-    post_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "post"]
-    gather_ms = [e0.elapsed_time(e1) for (a, st, e0, e1) in eng.timeline if st == "gather"]
-    N = 2 * plan.frame_wl[eng.f_lo:eng.f_hi].astype(np.int64) + 1
-    n_act = [plan.frame_K[eng.f_lo:eng.f_hi].astype(np.int64)]          # adaptation 0: K harmonics
-    for nc in eng.ncol_hist[:max(n_adpt - 1, 0)]:                         # adaptations >= 1: active slots per frame
-        n_act.append(nc.cpu().numpy().astype(np.int64))
-    flops_per_launch = [float(ls_flops(N, 2 * n + 1).sum()) for n in n_act]
-    # algorithmic bytes per launch: 8N signal window + 16 N n_active track windows (a >= 1) +
-    # 32 Kc amplitudes and slopes out
-    bytes_per_launch = [float(np.sum(8 * N) + (np.sum(16 * N * n) if a > 0 else 0) + np.sum(32 * (2 * n + 1)))
-                        for a, n in enumerate(n_act)]
-    flops_step = sum(flops_per_launch)
-    mine = [dt, float(frames_done), sum(ls_ms) / 1e3, flops_step * args.steps,
-            float(np.mean(ls_ms)) if ls_ms else 0.0, float(eng.nf)]
+    if args.dump_outputs:        # every rank takes part (the final arrays are merged over the ranks); rank 0 writes
+        fin = eng.final_arrays()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(fin, SRER=np.array(eng.SRER, dtype=np.float64)))
+
+    mine = [dt, float(frames_done)]
+    if args.full:
+        lf = launch_figures(eng, plan, n_adpt)
+        mine += [sum(lf["ls_ms"]) / 1e3, lf["flops_step"] * args.steps,
+                 float(np.mean(lf["ls_ms"])) if lf["ls_ms"] else 0.0, float(eng.nf)]
     if use_dist:
         allr = [None] * world
         dist.all_gather_object(allr, mine)      # (any backend; a few floats per rank, after the timed region)
@@ -343,64 +456,7 @@ def main():
         allr = np.array([mine], dtype=np.float64)
     dt = float(allr[:, 0].max())
     frames_total = float(allr[:, 1].sum())
-    # roofline of the dominant kernel: algorithmic flops of ALL ranks' launches / (sum of their durations / ranks),
-    # i.e. per-GPU achieved rate averaged over the ranks
-    ls_total_s = float(allr[:, 2].sum())
-    achieved = float(allr[:, 3].sum()) / ls_total_s / 1e12 if ls_total_s > 0 else 0.0
     srer = [float(v) for v in eng.SRER]
-    kernel = "eaqhm_ls_tile_kernel" if fs <= 16000 else "eaqhm_ls_mfma_kernel"
-    # Adaptation 0 is solved by a cheaper algorithm than the one F(N, Kc) counts (closed-form Gramian, two real systems of
-    # half the order), so its launch "achieves" more algorithmic flops per second than the matrix pipe does work: the
-    # rate of the adaptation >= 1 launches alone (rank 0) is reported next to the overall one
-    ls_a = [a for (a, st, e0, e1) in eng.timeline if st == "ls"]
-    t_ge1 = sum(t for a, t in zip(ls_a, ls_ms) if a >= 1) / 1e3
-    f_ge1 = sum(flops_per_launch[a] for a in ls_a if a >= 1 and a < len(flops_per_launch))
-    frac_ge1 = (f_ge1 / t_ge1 / 1e12 / PEAK_FP64_TFLOPS) if t_ge1 > 0 else None
-    ms0 = [t for a, t in zip(ls_a, ls_ms) if a == 0]
-    # HBM traffic of that kernel: not measurable from inside this process; taken from the committed rocprofv3 PMC
-    # passes of this same command and workload (profiles/r03_<workload>/pmc_hbm_traffic.json), N = 1 only
-    # (the PMC passes of tools/profile_round.sh; used only if they were taken with exactly these kernel sources)
-    traffic, traffic_src = None, None
-    pmc = os.path.join(ROOT, "profiles", "r03_%s" % args.workload, "pmc_hbm_traffic.json")
-    src = source_hash()
-    if world == 1 and os.path.exists(pmc):
-        j = json.load(open(pmc))
-        traffic_src = {"file": os.path.relpath(pmc, ROOT), "profile_source_hash": j.get("source_hash"),
-                       "tree_source_hash": src}
-        if j.get("source_hash") == src:
-            traffic = j.get(kernel, {}).get("hbm_bytes_per_launch_fetch_doubled")
-        else:
-            traffic_src["stale"] = "kernel sources changed since the counter passes: traffic withheld"
-    achieved_all = achieved
-    if frac_ge1 is not None:
-        achieved = frac_ge1 * PEAK_FP64_TFLOPS
-    roofline = {"bound": "mfma", "kernel": kernel, "achieved": achieved, "peak": PEAK_FP64_TFLOPS,
-                "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_TFLOPS,
-                "frac_definition": "algorithmic flops F(N,Kc) of the adaptation >= 1 launches / their HIP-event time "
-                                   "(rank 0); all launches incl. the cheaper closed-form adaptation 0: frac_all_launches_F_credit",
-                "frac_all_launches_F_credit": achieved_all / PEAK_FP64_TFLOPS, "traffic": traffic,
-                "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)",
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": float(np.mean(bytes_per_launch)),
-                "algorithmic_bytes_launch0": bytes_per_launch[0],
-                "flops_per_launch_mean": flops_step / max(len(flops_per_launch), 1),
-                "launch_ms_mean": float(np.mean(ls_ms)) if ls_ms else None,
-                "launch_ms_adaptation0": float(np.mean(ms0)) if ms0 else None,
-                "frac_adaptation_ge1_launches": frac_ge1,
-                "source_hash": src,
-                "launches_timed": len(ls_ms),
-                "post_stage_ms_mean": float(np.mean(post_ms)) if post_ms else None,
-                # the bandwidth-type stage (spline + interpolation + synthesis + SRER, functions.py:337-388):
-                # algorithmic bytes = records read (1+3 Kmax) 8 No_ti + tracks and reconstruction written (1+2 Kmax) 8 L
-                "post_stage_hbm": (lambda b, t: {"bound": "hbm", "algorithmic_bytes": b, "achieved_GBps": b / t / 1e6,
-                                                 "peak_GBps": 8000.0, "frac": b / t / 1e6 / 8000.0})(
-                    float((1 + 3 * plan.Kmax) * 8 * plan.No_ti + (1 + 2 * plan.Kmax) * 8 * (eng.t_hi - eng.t_lo)),
-                    float(np.mean(post_ms))) if post_ms else None,
-                "all_gather_ms_mean": float(np.mean(gather_ms)) if gather_ms else None,
-                "ls_ms_mean_per_rank": [float(v) for v in allr[:, 4]],
-                "ls_frames_per_rank": [int(v) for v in allr[:, 5]],
-                "ls_imbalance_max_over_mean": float(allr[:, 4].max() / allr[:, 4].mean()) if allr[:, 4].mean() > 0 else None}
-
     out = {"metric": "analysis_frames_per_sec", "value": frames_total / dt, "unit": "frames/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
@@ -412,15 +468,17 @@ def main():
                       "Kmax": int(plan.Kmax), "track_bytes": int(eng.track_bytes()), "time_blocks": len(eng.blocks),
                       "parallelism": "instants sharded x%d by LS cost; boundary records all-gathered per adaptation"
                                      % world},
-           "final_srer_db": max(srer), "srer_db": srer, "roofline": roofline}
-    ref, ref_src = reference_srer(args.workload)
+           "final_srer_db": max(srer), "srer_db": srer}
+    if args.full:
+        out["roofline"] = roofline_figures(lf, eng, plan, fs, args.workload, world, allr)
+    ref, ref_src = reference_srer(args.workload) if args.full else (None, None)
     if ref is not None and args.max_adpt == 5:
         out["srer_ref_db"] = ref
         out["srer_ref_source"] = ref_src
         out["final_srer_ref_db"] = max(ref)
         out["srer_abs_diff_db"] = ([abs(a - b) for a, b in zip(srer, ref)] if len(ref) == len(srer) else None)
         out["final_srer_abs_diff_db"] = abs(max(srer) - max(ref))
-    if rank == 0 and world == 1 and not args.no_host_stages:
+    if args.full and rank == 0 and world == 1 and not args.no_host_stages:
         hs = host_stages(args.workload, eng, plan, s, fs)
         loop_s = dt / args.steps
         out["host_stages_s"] = hs
@@ -430,10 +488,9 @@ def main():
                                      "adaptation loop + final arrays + struct packing (wav decoding excluded)"}
     if rehearsal:
         out["rehearsal"] = "all ranks on one GPU, collectives staged through the host: code-path check only"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(args.workload)
-    else:
-        out["cpu_baseline"] = None
+    if args.full:
+        out["cpu_baseline"] = (cpu_baseline(args.workload) if rank == 0 and world == 1 and not args.no_cpu_baseline
+                               else None)
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
     if rank == 0:

@@ -313,6 +313,32 @@ def test_bench_self_launch_returns_a_failed_rank_promptly():
     assert b"needs an MI355X" in r.stderr and r.stdout.strip() == b""
 
 
+def test_bench_dump_outputs_stay_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float64 files of at most DUMP_BYTES in all; arrays too large for the budget keep the
+    same seeded rows (am / fm / pk of one instant stay together), small ones are written whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    am = rng.standard_normal((8000, 59))
+    arrays = dict(a0=np.arange(8000.0), am=am, fm=2 * am, s_recon=rng.standard_normal(300000),
+                  SRER=np.arange(5, dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v), k
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 10 ** 6)
+    bench.dump_outputs(str(tmp_path / "sample"), arrays)
+    files = sorted((tmp_path / "sample").iterdir())
+    assert sum(f.stat().st_size for f in files) <= 4 * 10 ** 6
+    got = {f.stem: np.load(f) for f in files}
+    assert set(got) == set(arrays) and all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["a0"], arrays["a0"]) and np.array_equal(got["SRER"], arrays["SRER"])
+    n = len(got["am"])
+    assert 0 < n < 8000 and np.array_equal(got["fm"], 2 * got["am"])
+    assert np.array_equal(got["am"], am[np.sort(np.random.default_rng(0).choice(8000, n, replace=False))])
+    assert 0 < len(got["s_recon"]) < 300000
+
+
 def _pitch_profile(t, profile):
     f0 = 220.0 + 40.0 * np.sin(2 * np.pi * 0.31 * t) + 10.0 * np.sin(2 * np.pi * 1.7 * t)
     if profile == "step":      # a pitch track that drops to 0.7 of the true pitch half way: the second half's frames

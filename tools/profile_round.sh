@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o p -- \
-  python3 "$ROOT/bench.py" --workload "$WL" --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log" || exit 1
+  python3 "$ROOT/bench.py" --workload "$WL" --steps 3 --warmup 1 --full --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log" || exit 1
 echo "stats pass done"
 timeout -k 10 500 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o p -- \
   python3 "$ROOT/bench.py" --workload "$WL" --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> "$OUT/pmc_fetch.log" || exit 1
