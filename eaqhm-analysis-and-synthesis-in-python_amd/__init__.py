@@ -7,3 +7,4 @@ from .functions import (eaQHMAnalysisAndSynthesis, eaQHMAnalysisAndSynthesisBatc
                         iqhmLS_complexamps, phase_integr_interpolation)
 from .hip import HipUnavailable, load_library  # noqa: F401
 from .structs import Deterministic, Frame  # noqa: F401
+from .model import eaQHMSynthesis, unpack_model  # noqa: F401

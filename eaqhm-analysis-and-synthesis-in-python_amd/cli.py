@@ -3,7 +3,8 @@
     python eaqhm_amd.py <file.wav> [--gender female] [--max-adpt 10] ...
 
 prints the per-adaptation SRER lines in the reference's format (functions.py:391-392, :415-416) and writes
-`<name>_reconstructed.wav` as float32 next to the input (main.py:72)."""
+`<name>_reconstructed.wav` as float32 next to the input (main.py:72).  With --time-scale / --pitch-scale it also
+resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wav` (float32)."""
 import argparse
 
 import numpy as np
@@ -27,7 +28,16 @@ def main(argv=None):
     ap.add_argument("--track-budget-mb", type=float, default=0.0,
                     help="long files: device memory for the dense tracks (streamed in time blocks, same results); 0 = automatic: "
                          "resident while they fit comfortably, streamed otherwise")
+    ap.add_argument("--time-scale", type=float, default=None, help="also write <name>_modified.wav: durations x R")
+    ap.add_argument("--pitch-scale", type=float, default=None, help="also write <name>_modified.wav: pitch x B")
+    ap.add_argument("--no-envelope", action="store_true",
+                    help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
     a = ap.parse_args(argv)
+    modify = a.time_scale is not None or a.pitch_scale is not None
+    if modify:   # reject bad scales before the analysis runs
+        from .model import _scale
+        _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
+        _scale(1.0 if a.pitch_scale is None else a.pitch_scale, "--pitch-scale")
     gender = a.gender
     if "," in gender:
         lo, hi = gender.split(",")
@@ -42,4 +52,12 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
+        if modify:
+            from .model import eaQHMSynthesis
+            s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=1.0 if a.time_scale is None else a.time_scale,
+                                   pitch_scale=1.0 if a.pitch_scale is None else a.pitch_scale,
+                                   preserve_envelope=not a.no_envelope)
+            out = a.wav[:len(a.wav) - 4] + "_modified.wav"
+            wavfile.write(out, fs, np.float32(s_mod))
+            print("wrote", out)
     return 0

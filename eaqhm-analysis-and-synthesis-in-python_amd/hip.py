@@ -34,6 +34,9 @@ SYMBOLS = (
     ("eaqhm_eval_synth", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _I64, _I64, _I64, _I64, _I64, _P, _F64,
                                     _P, _P, _I64, _I64, _P, _P, _P, _P]),
     ("eaqhm_eval_partials_len", _I64, [_I64, _I64, _I32]),
+    ("eaqhm_modify_prep", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _I32, _P, _P, _P]),
+    ("eaqhm_modify_synth", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64, _I64,
+                                      _P]),
 )
 
 
@@ -172,6 +175,15 @@ class Context:
                                            step, float(fs), L, t_lo, t_hi, s_lo, s_hi, _ptr(target), float(std_det),
                                            _ptr(am_out), _ptr(fm_out), track_t0, track_len, _ptr(ph_knot), _ptr(s_hat),
                                            _ptr(partials), _ptr(sums_out)))
+
+    def modify_prep(self, records, code, mom, No_ti, Kmax, step, fs, beta, preserve_envelope, amp, R, ph0):
+        self._ck(self.lib.eaqhm_modify_prep(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step, float(fs),
+                                            float(beta), int(bool(preserve_envelope)), _ptr(amp), _ptr(R), _ptr(ph0)))
+
+    def modify_synth(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi, out):
+        self._ck(self.lib.eaqhm_modify_synth(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R), _ptr(ph0),
+                                             No_ti, Kmax, step, float(fs), float(rho), float(beta), L_out, t_lo, t_hi,
+                                             _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

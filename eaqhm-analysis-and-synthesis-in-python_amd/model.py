@@ -1,0 +1,169 @@
+"""Resynthesis from an analysed eaQHM model, with time and pitch scaling (not in the reference).
+
+    unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
+    eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
+                   *, device_index=0) -> float64[rint(time_scale * length)]
+
+`DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
+the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
+own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model").  The work runs in
+libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep, eaqhm_modify_synth); there is no CPU path.
+"""
+from itertools import chain, compress, repeat
+from operator import itemgetter
+
+import numpy as np
+
+SCALE_RANGE = (0.25, 4.0)
+
+
+def _cells(rows, mask=None):
+    """Values of the SURVEY Q9 cells of every row that are not the int 0 of an inactive slot (shape-(1,) arrays), in
+    row-major order, and the mask of those cells over all cells.  The cells are read by NumPy and itertools, not by a
+    loop over them; `mask` (from the amplitudes) saves the type scan for the other two fields.  Cells edited by hand
+    into plain numbers take a slower per-cell path."""
+    if mask is None:
+        flat = chain.from_iterable(r for r in rows if r is not None)
+        mask = ~np.fromiter(map(isinstance, flat, repeat(int)), dtype=bool)
+    n = int(np.count_nonzero(mask))
+    try:
+        v = np.fromiter(map(itemgetter(0), compress(chain.from_iterable(r for r in rows if r is not None), mask)),
+                        dtype=np.float64, count=n)
+    except (TypeError, IndexError, ValueError):
+        v = np.array([np.asarray(c, dtype=np.float64).reshape(-1)[0] if np.size(c) == 1 else np.nan
+                      for c in compress(chain.from_iterable(r for r in rows if r is not None), mask)])
+        if np.isnan(v).any() or len(v) != n:
+            raise ValueError("every cell of a Deterministic row must be a single number (a shape-(1,) array)") from None
+    return v, mask
+
+
+def unpack_model(DetComponents):
+    """The inverse of functions.pack_results / pack_arrays: the model as records in the layout of include/eaqhm_hip.h
+    (|a| (Kmax), f (Kmax), phase (Kmax), a0 per instant).
+
+    A slot is active at an instant iff its amplitude is nonzero and its frequency is > 0; every other cell is zero.
+    Cells with a nonzero amplitude and a frequency <= 0 are the reference's seeded slot-0 entries that reach the model
+    when the loop stops in an adaptation that seeded empty rows (functions.py:210 through the aliasing at :383): the
+    synthesis that produced s_recon never used them.  They come back inactive and are counted in `quirk_cells`.
+
+    Returns dict(records=(No_ti, 3*Kmax+1) float64, step=int, Kmax=int, ti=int64[No_ti], quirk_cells=int)."""
+    if isinstance(DetComponents, dict):
+        d = DetComponents
+        ti = np.asarray(d["ti"], dtype=np.int64).reshape(-1)
+        am = np.array(d["amplitudes"], dtype=np.float64, ndmin=2)
+        fm = np.array(d["frange"], dtype=np.float64, ndmin=2)
+        pk = np.array(d["pk"], dtype=np.float64, ndmin=2)
+        a0 = np.array(d["a0"], dtype=np.float64).reshape(-1)
+        if not (am.shape == fm.shape == pk.shape) or am.shape[0] != len(ti) or len(a0) != len(ti):
+            raise ValueError("det_format='arrays' model: amplitudes / frange / pk must be (No_ti, Kmax), a0 (No_ti,)")
+        if "isVoiced" in d:
+            v = np.asarray(d["isVoiced"], dtype=bool)
+            am[~v] = 0.0
+            a0 = np.where(v, a0, 0.0)
+        n, K = am.shape
+    else:
+        det = list(DetComponents)
+        n = len(det)
+        ti = np.fromiter((int(x.ti) for x in det), dtype=np.int64, count=n)
+        voiced = np.fromiter((bool(x.isVoiced) for x in det), dtype=bool, count=n)
+        fields = []
+        for name in ("amplitudes", "frange", "pk"):
+            fields.append([getattr(x, name, None) if v else None for x, v in zip(det, voiced)])
+        lens = np.array([0 if r is None else len(r) for r in fields[0]], dtype=np.int64)
+        for rows in fields[1:]:
+            if not np.array_equal(lens, [0 if r is None else len(r) for r in rows]):
+                raise ValueError("amplitudes, frange and pk of an instant must have the same length")
+        K = int(lens.max()) if n else 0
+        a0 = np.array([float(x.a0) if v else 0.0 for x, v in zip(det, voiced)], dtype=np.float64)
+        r_of = np.repeat(np.arange(n), lens)
+        k_of = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+        am = np.zeros((n, K))
+        fm = np.zeros((n, K))
+        pk = np.zeros((n, K))
+        mask = None
+        flat_idx = r_of * K + k_of
+        for out, rows in zip((am, fm, pk), fields):
+            vals, mask = _cells(rows, mask)
+            out.reshape(-1)[flat_idx[mask]] = vals
+    if n < 2:
+        raise ValueError("the model needs at least two analysis instants")
+    step = int(ti[1] - ti[0])
+    if step <= 0 or np.any(np.diff(ti) != step):
+        raise ValueError("the model's instants ti must be uniformly spaced")
+    if ti[0] != 0:
+        raise ValueError("the model's first instant must be sample 0 (ti[0] == 0), as the analysis returns it")
+    nonzero = am != 0
+    active = nonzero & (fm > 0)
+    quirk = int(np.count_nonzero(nonzero & ~active))
+    rec = np.zeros((n, 3 * K + 1))
+    rec[:, :K] = np.where(active, am, 0.0)
+    rec[:, K:2 * K] = np.where(active, fm, 0.0)
+    rec[:, 2 * K:3 * K] = np.where(active, pk, 0.0)
+    rec[:, 3 * K] = a0
+    return dict(records=rec, step=step, Kmax=int(K), ti=ti, quirk_cells=quirk)
+
+
+def _scale(x, name):
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number" % name) from None
+    if not np.isfinite(v) or not (SCALE_RANGE[0] <= v <= SCALE_RANGE[1]):
+        raise ValueError("%s must be finite and in [%g, %g], got %r" % (name, SCALE_RANGE[0], SCALE_RANGE[1], x))
+    return v
+
+
+def check_arguments(model, fs, length, time_scale, pitch_scale):
+    """Validates everything eaQHMSynthesis gets (no device work): returns (rho, beta, fs, length)."""
+    rho = _scale(time_scale, "time_scale")
+    beta = _scale(pitch_scale, "pitch_scale")
+    try:
+        fs = float(fs)
+    except (TypeError, ValueError):
+        raise ValueError("fs must be a number") from None
+    if not np.isfinite(fs) or fs <= 0:
+        raise ValueError("fs must be finite and > 0")
+    if isinstance(length, bool) or not float(length).is_integer():
+        raise ValueError("length must be an integer number of samples")
+    length = int(length)
+    if length < int(model["ti"][-1]) + 1:
+        raise ValueError("length (%d) must be >= the last instant + 1 (%d)" % (length, int(model["ti"][-1]) + 1))
+    rec = model["records"]
+    if len(rec) < 4:
+        raise ValueError("the model needs at least 4 analysis instants (the cubic interpolation of the tracks)")
+    if not np.all(np.isfinite(rec)):
+        raise ValueError("the model holds non-finite values")
+    if np.any(rec[:, :model["Kmax"]] < 0):
+        raise ValueError("amplitudes must be >= 0 (the model holds |a_k|)")
+    return rho, beta, fs, length
+
+
+def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True, *,
+                   device_index=0):
+    """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
+    frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
+    off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
+    its own amplitude.  Partials pushed to or above fs/2 are muted.  Returns float64[rint(time_scale * length)]."""
+    model = unpack_model(DetComponents)
+    rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    rec_h = model["records"]
+    n, K, D = rec_h.shape[0], model["Kmax"], model["step"]
+    L_out = int(np.rint(rho * length))
+    if K == 0:                                   # no slot at all: keep one empty slot so the a0 spline still runs
+        rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
+        K = 1
+    rec = torch.as_tensor(np.ascontiguousarray(rec_h), device=dev)
+    code = torch.empty(n * K, dtype=torch.uint8, device=dev)
+    mom = torch.empty(n * (K + 1), dtype=torch.float64, device=dev)
+    amp = torch.empty(n * K, dtype=torch.float64, device=dev)
+    R = torch.empty(n * K, dtype=torch.float64, device=dev)
+    ph0 = torch.empty(n * K, dtype=torch.float64, device=dev)
+    out = torch.empty(L_out, dtype=torch.float64, device=dev)
+    c.spline_solve(rec, n, K, D, code, mom)
+    c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
+    c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, 0, L_out, out)
+    return out.cpu().numpy()

@@ -176,6 +176,27 @@ int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
 /* number of 8-byte words `partials` must hold for a given range */
 int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step);
 
+/* resynthesis from the model with a time scale rho and a pitch scale beta (additive to ABI 3) --------------------
+ * Generalises functions.py:337-385 (track interpolation and additive synthesis) and :537-575 (phase integration) from
+ * the analysed timeline to output samples n' = rho * tau; the definition is DESIGN.md "Resynthesis from the model".
+ * Both calls take the records of an analysed (possibly edited) model and the code / mom that eaqhm_spline_solve
+ * produced from them; at rho = beta = 1 the synthesis is eaqhm_eval_synth's s_hat of the same records.
+ * eaqhm_modify_prep (kernels: prep, segmented scan of the phase increments)
+ *   amp        double[No_ti][Kmax]  knot amplitudes A' after the pitch scale: beta == 1: |a|; otherwise, with
+ *                                   preserve_envelope, exp of the instant's piecewise-linear log-amplitude envelope at
+ *                                   beta*f, without it |a|; zero where beta*f >= fs/2 (or the slot is inactive)
+ *   R          double[No_ti][Kmax]  unwrapped knot phase along each run of consecutive active instants (0 at the run's
+ *                                   first knot, R_{j+1} = R_j + (ph_{j+1} - ph_j) + 2 pi M_j); 0 outside runs
+ *   ph0        double[No_ti][Kmax]  phase of the first knot of the run each knot belongs to; 0 outside runs
+ * eaqhm_modify_synth writes out[t_lo, t_hi) of the L_out-sample signal (out is double[L_out]).
+ * EAQHM_EINVAL for rho or beta <= 0 or not finite, and for a range outside [0, L_out).                           */
+int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, int32_t No_ti,
+                      int32_t Kmax, int32_t step, double fs, double beta, int32_t preserve_envelope, double* amp,
+                      double* R, double* ph0);
+int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, const double* amp,
+                       const double* R, const double* ph0, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
+                       double rho, double beta, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,112 @@
+"""Resynthesis from the model: device time of eaqhm_modify_prep (prep + scan) and eaqhm_modify_synth against
+eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
+
+    python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--out FILE]
+
+Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
+{0.5, 1, 2} x beta in {1, 1.25}.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
+times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def analyse(workload):
+    import eaqhm_amd
+    from eaqhm_amd.functions import pack_arrays, pack_results
+    from eaqhm_amd.synth import synth_speech_int16
+    from scipy.io import wavfile
+    import tempfile
+    fs, fix, key, adpt = {"synth16k_60s": (16000, "prep_fixtures.npz", "synth16k_60s_f0s_5ms", 5),
+                          "synth48k_60s": (48000, "prep_synth48k_60s.npz", "synth48k_60s_f0s_5ms", 1)}[workload]
+    grid = np.load(os.path.join(GOLDEN, fix))[key]
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, workload + ".wav")
+        wavfile.write(path, fs, synth_speech_int16(60.0, fs))
+        s_recon, _, _, _, eng = eaqhm_amd.eaQHMAnalysisAndSynthesis(path, "female", maxAdpt=adpt, printPrompts=False,
+                                                                    pitch_track=grid, _return_engine=True)
+    fin = eng.final_arrays()
+    t = time.perf_counter()
+    det = pack_results(eng.plan, fin)
+    t_pack = time.perf_counter() - t
+    return fs, len(s_recon), det, pack_arrays(eng.plan, fin), t_pack
+
+
+def timed(torch, fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def probe(workload, reps):
+    import torch
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.model import unpack_model
+    fs, L, det, arrays, t_pack = analyse(workload)
+    t = time.perf_counter()
+    m = unpack_model(det)
+    t_unpack = time.perf_counter() - t
+    c = _ctx(0)
+    dev = c.device
+    rec_h = m["records"]
+    n, K, D = rec_h.shape[0], m["Kmax"], m["step"]
+    rec = torch.as_tensor(rec_h, device=dev)
+    code = torch.empty(n * K, dtype=torch.uint8, device=dev)
+    mom = torch.empty(n * (K + 1), dtype=torch.float64, device=dev)
+    amp, R, ph0 = (torch.empty(n * K, dtype=torch.float64, device=dev) for _ in range(3))
+    c.spline_solve(rec, n, K, D, code, mom)
+    # eaqhm_eval_synth on the same records: synthesis + SRER, no track output (what the analysis's last pass runs)
+    target = torch.zeros(L, dtype=torch.float64, device=dev)
+    s_hat = torch.empty(L, dtype=torch.float64, device=dev)
+    ph_knot = torch.empty(n * K, dtype=torch.float64, device=dev)
+    partials = torch.empty(c.eval_partials_len(0, L, D), dtype=torch.int64, device=dev)
+    sums = torch.empty(16, dtype=torch.float64, device=dev)
+    t_eval = timed(torch, lambda: c.eval_synth(rec, code, mom, n, K, D, fs, L, 0, L, 0, L, target, 1.0, None, None, 0, 0,
+                                               ph_knot, s_hat, partials, sums), reps)
+    rows = []
+    for beta in (1.0, 1.25):
+        t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0), reps)
+        for rho in (0.5, 1.0, 2.0):
+            Lo = int(np.rint(rho * L))
+            out = torch.empty(Lo, dtype=torch.float64, device=dev)
+            t_syn = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo,
+                                                        out), reps)
+            rows.append(dict(rho=rho, beta=beta, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3),
+                             total_ms=round(t_prep + t_syn, 3), out_samples=Lo,
+                             msamples_per_s=round(Lo / ((t_prep + t_syn) * 1e-3) / 1e6, 1),
+                             ratio_to_eval_synth=round((t_prep + t_syn) / t_eval, 3)))
+    return dict(workload=workload, fs=fs, L=L, No_ti=n, Kmax=K, eval_synth_ms=round(t_eval, 3),
+                pack_results_s=round(t_pack, 3), unpack_model_s=round(t_unpack, 3), settings=rows)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="synth16k_60s,synth48k_60s")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = [probe(w, a.reps) for w in a.workloads.split(",")]
+    for r in res:
+        print(json.dumps(r))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
