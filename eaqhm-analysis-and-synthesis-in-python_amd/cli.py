@@ -4,7 +4,9 @@
 
 prints the per-adaptation SRER lines in the reference's format (functions.py:391-392, :415-416) and writes
 `<name>_reconstructed.wav` as float32 next to the input (main.py:72).  With --time-scale / --pitch-scale it also
-resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wav` (float32)."""
+resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wav` (float32).  --time-scale-curve /
+--pitch-scale-curve FILE take a breakpoint curve instead (two whitespace-separated columns, seconds and value; lines
+starting with # are comments), turned into a per-instant contour with model.scale_contour."""
 import argparse
 
 import numpy as np
@@ -28,16 +30,26 @@ def main(argv=None):
     ap.add_argument("--track-budget-mb", type=float, default=0.0,
                     help="long files: device memory for the dense tracks (streamed in time blocks, same results); 0 = automatic: "
                          "resident while they fit comfortably, streamed otherwise")
-    ap.add_argument("--time-scale", type=float, default=None, help="also write <name>_modified.wav: durations x R")
-    ap.add_argument("--pitch-scale", type=float, default=None, help="also write <name>_modified.wav: pitch x B")
+    ts = ap.add_mutually_exclusive_group()
+    ts.add_argument("--time-scale", type=float, default=None, help="also write <name>_modified.wav: durations x R")
+    ts.add_argument("--time-scale-curve", default=None, metavar="FILE",
+                    help="like --time-scale, with a curve: lines 'seconds value' (# comments)")
+    ps = ap.add_mutually_exclusive_group()
+    ps.add_argument("--pitch-scale", type=float, default=None, help="also write <name>_modified.wav: pitch x B")
+    ps.add_argument("--pitch-scale-curve", default=None, metavar="FILE",
+                    help="like --pitch-scale, with a curve: lines 'seconds value' (# comments)")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
     a = ap.parse_args(argv)
-    modify = a.time_scale is not None or a.pitch_scale is not None
-    if modify:   # reject bad scales before the analysis runs
+    modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve))
+    curves = {}
+    if modify:   # reject bad scales and curves before the analysis runs
         from .model import _scale
         _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
         _scale(1.0 if a.pitch_scale is None else a.pitch_scale, "--pitch-scale")
+        for key, path in (("time", a.time_scale_curve), ("pitch", a.pitch_scale_curve)):
+            if path is not None:
+                curves[key] = read_scale_curve(path, "--%s-scale-curve %s" % (key, path))
     gender = a.gender
     if "," in gender:
         lo, hi = gender.split(",")
@@ -53,11 +65,28 @@ def main(argv=None):
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
         if modify:
-            from .model import eaQHMSynthesis
-            s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=1.0 if a.time_scale is None else a.time_scale,
-                                   pitch_scale=1.0 if a.pitch_scale is None else a.pitch_scale,
+            from .model import eaQHMSynthesis, scale_contour
+            rho = 1.0 if a.time_scale is None else a.time_scale
+            beta = 1.0 if a.pitch_scale is None else a.pitch_scale
+            if "time" in curves:
+                rho = scale_contour(det, fs, *curves["time"])
+            if "pitch" in curves:
+                beta = scale_contour(det, fs, *curves["pitch"])
+            s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope)
             out = a.wav[:len(a.wav) - 4] + "_modified.wav"
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)
     return 0
+
+
+def read_scale_curve(path, name):
+    """A breakpoint curve file: (times, values), validated as model.check_curve does."""
+    from .model import check_curve
+    try:
+        xy = np.loadtxt(path, comments="#", ndmin=2)
+    except (OSError, ValueError) as e:
+        raise ValueError("%s: cannot read two numeric columns (%s)" % (name, e)) from None
+    if xy.shape[1] != 2:
+        raise ValueError("%s: expected two columns (seconds, value), got %d" % (name, xy.shape[1]))
+    return check_curve(xy[:, 0], xy[:, 1], name)

@@ -12,6 +12,9 @@
 //   eaqhm_modify_eval_kernel   blocks of output samples: the touched intervals are integrated once into LDS (as
 //                              stage 1 of eaqhm_eval_kernel), then per (sample, slot) A * cos(phase), per sample the
 //                              a0 spline and the sum over slots in slot order.
+// Time and pitch scale contours use eaqhm_modify_prep_curve_kernel (the prep body with beta per
+// instant and the phase increments weighted by g_j), the same scan and carry kernels, and
+// eaqhm_modify_eval_curve_kernel (the eval body with the cumulative time map C in place of tau = n'/rho).
 #include "eaqhm_common.h"
 #include "eaqhm_pieces.h"
 
@@ -77,84 +80,8 @@ __device__ inline void interval_close(const SlotT& S, const FmPiece& P, int j, i
 //             frequency), without it am; both muted where beta f >= fs/2.
 //   dR[i+1][k] Delta of the interval (i, i+1) when it is in a run: (ph_{i+1} - ph_i) + 2 pi Mr.  Other rows 0.
 //   P0[i][k]  ph_i at the first knot of a run (code != 0, previous instant inactive), else 0.
+// The body is in eaqhm_modify_body.inc (compiled below once per variant).
 #define PREP_WAVES 4
-extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
-    eaqhm_modify_prep_kernel(ModArgs A, double beta, int envelope, double* __restrict__ amp, double* __restrict__ dR,
-                             double* __restrict__ P0) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int K = A.Kmax, D = A.step, RS = 3 * K + 1;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * PREP_WAVES + w;
-  double* nf = lds + (size_t)w * 2 * K;   // sorted node frequencies [K] and log amplitudes [K] of this wave's instant
-  double* nv = nf + K;
-  const bool live = i < A.No_ti;
-  const double* row = A.records + (size_t)(live ? i : 0) * RS;
-  const bool env = live && beta != 1.0 && envelope;
-  int nn = 0;
-  if (env) {
-    // rank of every active slot in (f, k) order: slots are nearly sorted already, K is at most a few hundred
-    for (int k = lane; k < K; k += 64) {
-      const double ak = row[k], fk = row[K + k];
-      if (ak != 0.0 && fk > 0.0) {
-        int rank = 0;
-        for (int q = 0; q < K; ++q) {
-          const double aq = row[q], fq = row[K + q];
-          rank += (aq != 0.0 && fq > 0.0 && (fq < fk || (fq == fk && q < k))) ? 1 : 0;
-        }
-        nf[rank] = fk;
-        nv[rank] = log(ak);
-      }
-    }
-    for (int k = lane; k < K; k += 64) nn += (row[k] != 0.0 && row[K + k] > 0.0) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o);
-  }
-  __syncthreads();
-  if (!live) return;
-  const double scale = 2.0 * M_PI / A.fs;
-  for (int k = lane; k < K; k += 64) {
-    // ---- A'
-    const double ak = row[k], fk = row[K + k];
-    double a = ak;
-    if (beta != 1.0) {
-      a = 0.0;
-      if (ak != 0.0 && fk > 0.0) {
-        const double q = beta * fk;
-        a = ak;
-        if (envelope) {
-          int lo = 0, hi = nn;   // first node with f >= q
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (nf[mid] < q) lo = mid + 1; else hi = mid;
-          }
-          double E;
-          if (lo < nn && nf[lo] == q) E = nv[lo];
-          else if (lo == 0) E = nv[0];
-          else if (lo == nn) E = nv[nn - 1];
-          else E = nv[lo - 1] + (nv[lo] - nv[lo - 1]) * ((q - nf[lo - 1]) / (nf[lo] - nf[lo - 1]));
-          a = exp(E);
-        }
-        if (q >= 0.5 * A.fs) a = 0.0;
-      }
-    }
-    amp[(size_t)i * K + k] = a;
-    // ---- Delta of the interval (i, i+1), first-knot phase
-    GSlot S{A, k};
-    const int ci = S.code(i);
-    const bool head = ci != 0 && S.code(i - 1) == 0;
-    P0[(size_t)i * K + k] = (head && ci != 1) ? S.ph(i) : 0.0;
-    if (i == 0) dR[k] = 0.0;
-    if (i + 1 < A.No_ti) {
-      double d = 0.0;
-      if (ci != 0 && S.code(i + 1) != 0) {
-        const FmPiece P = make_piece(S, i, ci);
-        double w0, acc, emis, Mr;
-        interval_close(S, P, i, D, scale, w0, acc, emis, Mr);
-        d = (S.ph(i + 1) - S.ph(i)) + 2.0 * M_PI * Mr;
-      }
-      dR[(size_t)(i + 1) * K + k] = d;
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Segmented scan of dR along the instants, per slot.  A segment starts at every knot whose interval to the previous
@@ -257,154 +184,121 @@ struct MEvalArgs {
   double rho; double beta; long long t_lo; long long t_hi; double* out;
 };
 
-// Block of TBS consecutive output samples x all slots.
-//   stage 0  per sample: interval j and offset r (LDS).
-//   stage 1  one thread per (interval, slot) touching the block: the interval's local phase
-//            Psi(u) = R_j + sum_{v=1..u} w(v) - sum_{v=0..u} sin(pi v/D) er, u = 0..D, in the eval kernel's summation
-//            order; at each of the block's samples in the interval the phase P0 + beta rho ((1-fr) Psi(u0) + fr Psi(u0+1))
-//            goes to X[k][s].  A run's last knot (tau = c_b) is the end u = D of its last interval.
-//   stage 2  one thread per (sample, slot group): amplitude, A cos(phase), isolated knots; then one thread per sample
-//            adds the slots in slot order and the a0 spline.
-extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEvalArgs E, int TBS, int NR) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const ModArgs& A = E.M;
-  const int D = A.step, K = A.Kmax, TP = TBS + 1;
-  double* ft = lds;                                   // D+1
-  double* X = lds + ((D + 1 + 1) & ~1);               // [K][TP]
-  double* sr = X + (size_t)K * TP;                    // [TBS] r of each sample
-  double* crec = sr + TBS;                            // [NR][3K+1]
-  double* cmom = crec + (size_t)NR * (3 * K + 1);     // [NR][K+1]
-  int* sj = (int*)(cmom + (size_t)NR * (K + 1));      // [TBS] interval of each sample
-  unsigned char* ccode = (unsigned char*)(sj + ((TBS + 1) & ~1));   // [NR][K]
-  const int tid = threadIdx.x;
-  const long long t0 = E.t_lo + (long long)blockIdx.x * TBS;
-  const long long t1 = (t0 + TBS < E.t_hi) ? (t0 + TBS) : E.t_hi;
-  const int ns = (int)(t1 - t0);
-  int jfirst, jlast;
-  double rdummy;
-  locate(t0, E.rho, D, jfirst, rdummy);
-  locate(t1 - 1, E.rho, D, jlast, rdummy);
-  // intervals met by the block: one before the first sample's (a run's last knot) up to the last sample's
-  const int jlo = max(0, jfirst - 1), jhi = min(A.No_ti - 2, jlast);
-  MCache C;
-  {
-    C.r0 = max(0, jlo - 1);
-    C.r1 = min(A.No_ti - 1, jhi + 2);
-    if (C.r1 > C.r0 + NR - 1) C.r1 = C.r0 + NR - 1;
-    if (C.r1 < C.r0) C.r1 = C.r0 - 1;
-    C.rec = crec; C.mom = cmom; C.code = ccode;
-    const int nrow = C.r1 - C.r0 + 1, RS = 3 * K + 1;
-    for (int q = tid; q < nrow * RS; q += blockDim.x) crec[q] = A.records[(size_t)C.r0 * RS + q];
-    for (int q = tid; q < nrow * (K + 1); q += blockDim.x) cmom[q] = A.mom[(size_t)C.r0 * (K + 1) + q];
-    for (int q = tid; q < nrow * K; q += blockDim.x) ccode[q] = A.code[(size_t)C.r0 * K + q];
+// The contour time map of DESIGN.md §9.1: output knots C_j (C_0 = 0, C_{j+1} = C_j + r_j D), rate r_j per interval
+// (the last entry is rho_{n-1}, past the last knot) and phase weight g_j per interval.
+struct MCurve { const double* C; const double* rate; const double* gain; };
+
+struct CurveMap {
+  MCurve G;
+  int last;          // No_ti - 1
+  int dstep;         // D
+  int jb0, jb1;      // search bounds of the block's in-map samples
+  const double* cx;  // staged rows [r0, r1] of (C_j, r_j, g_j)
+  int r0, r1;
+  __device__ bool in(int i) const { return i >= r0 && i <= r1; }
+  __device__ double Cv(int i) const { return in(i) ? cx[(size_t)(i - r0) * 3] : G.C[i]; }
+  __device__ double gv(int i) const { return in(i) ? cx[(size_t)(i - r0) * 3 + 2] : G.gain[i]; }
+  // j = max{j : C_j <= n'} and r = (n' - C_j) / r_j (clamped below D); past the last knot j = last, r unbounded
+  __device__ void locate(long long n, int D, int& j, double& r) const {
+    const double x = (double)n;
+    if (x >= G.C[last]) { j = last; r = (x - G.C[last]) / G.rate[last]; return; }
+    int lo = jb0, hi = jb1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (G.C[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    j = lo;
+    r = (x - G.C[j]) / G.rate[j];
+    const double dd = (double)D;
+    if (r >= dd) r = nextafter(dd, 0.0);
   }
-  for (int u = tid; u <= D; u += blockDim.x) ft[u] = sin(M_PI * (double)u / (double)D);
-  for (int s = tid; s < ns; s += blockDim.x) {
-    int j; double r;
-    locate(t0 + s, E.rho, D, j, r);
-    sj[s] = j; sr[s] = r;
-  }
-  __syncthreads();
-  const double br = E.beta * E.rho;
-  // ---- stage 1
-  if (jhi >= jlo) {
-    const int nint = jhi - jlo + 1;
-    const double scale = 2.0 * M_PI / A.fs;
-    double S = 0.0;   // sum_{v=0..D} sin(pi v/D), in order
-    for (int u = 0; u <= D; ++u) S += ft[u];
-    for (int p = tid; p < nint * K; p += blockDim.x) {
-      const int jj = p / K, k = p - jj * K, j = jlo + jj;
-      CSlot Sl{A, C, k};
-      const int cj = Sl.code(j);
-      if (cj == 0 || Sl.code(j + 1) == 0) continue;
-      // the block's samples in this interval: [sa, sb), plus the run's last knot when j+1 ends the run
-      int sa = 0, hi = ns;
-      while (sa < hi) { const int mid = (sa + hi) >> 1; if (sj[mid] < j) sa = mid + 1; else hi = mid; }
-      int sb = sa;
-      while (sb < ns && sj[sb] == j) ++sb;
-      const bool ends = Sl.code(j + 2) == 0;
-      const int sl = (ends && sb < ns && sj[sb] == j + 1 && sr[sb] == 0.0) ? sb : -1;
-      if (sa == sb && sl < 0) continue;
-      const FmPiece P = make_piece(Sl, j, cj);
-      double w0, acc, emis, Mr;
-      interval_close(Sl, P, j, D, scale, w0, acc, emis, Mr);
-      // a run's last interval closes its mismatch completely: the model's phase at that knot is the integrated one
-      const double er = ends ? emis / S : M_PI * emis / (2.0 * (double)D);
-      const double Rj = E.R[(size_t)j * K + k], ph0 = E.P0[(size_t)j * K + k];
-      acc = w0;
-      double c = ft[0] * er;
-      double prev = Rj + ((acc - w0) - c);
-      int q = sa;
-      // u = 0: samples on the knot itself
-      while (q < sb && sr[q] == 0.0) { X[(size_t)k * TP + q] = ph0 + br * prev; ++q; }
-      for (int u = 1; u <= D; ++u) {
-        acc += scale * P(u);
-        c += ft[u] * er;
-        const double psi = Rj + ((acc - w0) - c);
-        while (q < sb) {
-          const double rq = sr[q], u0 = floor(rq), fr = rq - u0;
-          if ((int)u0 == u - 1 && fr > 0.0) X[(size_t)k * TP + q] = ph0 + br * ((1.0 - fr) * prev + fr * psi);
-          else if ((int)u0 == u && fr == 0.0) X[(size_t)k * TP + q] = ph0 + br * psi;
-          else break;
-          ++q;
-        }
-        prev = psi;
-      }
-      if (sl >= 0) X[(size_t)k * TP + sl] = ph0 + br * prev;
+  __device__ void bound(int jfirst, int jlast, int No_ti) { jb0 = min(jfirst, No_ti - 2); jb1 = min(jlast, No_ti - 2); }
+  __device__ void stage(double* lds_rows, int rs0, int rs1, int tid, int nthr) {
+    cx = lds_rows; r0 = rs0; r1 = rs1;
+    const int nrow = r1 - r0 + 1;
+    for (int q = tid; q < nrow * 3; q += nthr) {
+      const int i = r0 + q / 3, c = q - (q / 3) * 3;
+      lds_rows[q] = (c == 0) ? G.C[i] : (c == 1) ? G.rate[i] : (i < last ? G.gain[i] : 0.0);
     }
   }
-  __syncthreads();
-  // ---- stage 2
-  const int s = tid % TBS, g = tid / TBS, G = blockDim.x / TBS;
-  const bool live = s < ns;
-  const long long n = t0 + s;
-  if (live) {
-    const int j = sj[s];
-    const double r = sr[s];
-    const double tau = (double)n / E.rho;
-    const double hw = 0.5 / E.rho + 1.0;
-    const int ilo = max(0, (int)floor((tau - hw) / (double)D)), ihi = min(A.No_ti - 1, (int)floor((tau + hw) / (double)D) + 1);
-    for (int k = g; k < K; k += G) {
-      CSlot Sl{A, C, k};
-      auto inrun = [&](int q) { return q >= 0 && q <= A.No_ti - 2 && Sl.code(q) != 0 && Sl.code(q + 1) != 0; };
-      double cell = 0.0;
-      int jj = -1;
-      double rr = r;
-      if (inrun(j)) jj = j;
-      else if (r == 0.0 && inrun(j - 1)) { jj = j - 1; rr = (double)D; }
-      if (jj >= 0) {
-        const double a0v = E.amp[(size_t)jj * K + k], a1v = E.amp[(size_t)(jj + 1) * K + k];
-        const double Av = ((a1v - a0v) / (double)D) * rr + a0v;
-        cell = (Av != 0.0) ? Av * cos(X[(size_t)k * TP + s]) : 0.0;
-      }
-      for (int i = ilo; i <= ihi; ++i) {   // isolated accepted knots land on the output sample nearest to rho c_i
-        if (Sl.code(i) == 1 && (long long)rint(E.rho * ((double)i * (double)D)) == n)
-          cell += E.amp[(size_t)i * K + k] * cos(Sl.ph(i));
-      }
-      X[(size_t)k * TP + s] = cell;   // this thread is the only reader of the cell
-    }
+  // every knot with rint(C_i) == n' lies in [n' - 0.5, n' + 0.5]: walk out from the sample's interval (several knots
+  // can share one sample when r_j D < 1)
+  __device__ void iso_range(long long n, int j, int No_ti, int& ilo, int& ihi) const {
+    const double lo = (double)n - 0.5, hi = (double)n + 0.5;
+    ilo = j;
+    while (ilo > 0 && Cv(ilo - 1) >= lo) --ilo;
+    ihi = j;
+    while (ihi + 1 < No_ti && Cv(ihi + 1) <= hi) ++ihi;
   }
-  __syncthreads();
-  if (tid < TBS && live) {
-    double synth = 0.0;
-#pragma unroll 8
-    for (int k = 0; k < K; ++k) synth += X[(size_t)k * TP + s];
-    const double tau = (double)n / E.rho;
-    int ia = sj[s];
-    if (ia > A.No_ti - 2) ia = A.No_ti - 2;
-    if (ia < 0) ia = 0;
-    CSlot S0{A, C, K};   // column K of mom = the a0 spline; its knots are the last record column
-    const int RS = 3 * K + 1;
-    const double a0v = spline_piece(S0.recv(ia, RS - 1), S0.recv(ia + 1, RS - 1), S0.mom(ia), S0.mom(ia + 1),
-                                    tau - (double)ia * (double)D, (double)D);
-    E.out[n] = a0v + 2.0 * synth;
-  }
-}
+  __device__ double tau(int j, double r) const { return (double)j * (double)dstep + r; }
+};
+
+
+// ---- the scalar kernels: tau = n'/rho, phase weight beta rho
+#define EAQHM_MODIFY_CURVE 0
+#define MAP_INIT
+#define MAP_LOCATE(n, j, r) locate(n, E.rho, D, j, r)
+#define MAP_BOUND
+#define MAP_STAGE
+#define MAP_BLOCK_WEIGHT const double br = E.beta * E.rho;
+#define MAP_INTERVAL_WEIGHT
+#define MAP_PSI(loc) Rj + (loc)
+#define MAP_OFF ph0
+#define MAP_ISO_RANGE                                                                                               \
+  const double tau = (double)n / E.rho;                                                                             \
+  const double hw = 0.5 / E.rho + 1.0;                                                                              \
+  const int ilo = max(0, (int)floor((tau - hw) / (double)D)), ihi = min(A.No_ti - 1, (int)floor((tau + hw) / (double)D) + 1);
+#define MAP_ISO_AT(i) (long long)rint(E.rho * ((double)i * (double)D)) == n
+#define MAP_TAU (double)n / E.rho
+#include "eaqhm_modify_body.inc"
+#undef EAQHM_MODIFY_CURVE
+#undef MAP_INIT
+#undef MAP_LOCATE
+#undef MAP_BOUND
+#undef MAP_STAGE
+#undef MAP_BLOCK_WEIGHT
+#undef MAP_INTERVAL_WEIGHT
+#undef MAP_PSI
+#undef MAP_OFF
+#undef MAP_ISO_RANGE
+#undef MAP_ISO_AT
+#undef MAP_TAU
+
+// ---- the contour kernels: R holds the weighted phase G, the phase weight g_j is per interval, and
+// the staged rows [NR][3] (C_j, r_j, g_j) follow the codes
+#define EAQHM_MODIFY_CURVE 1
+#define MAP_INIT CurveMap Mp{Cu, A.No_ti - 1, D, 0, A.No_ti - 2, nullptr, 0, -1};
+#define MAP_LOCATE(n, j, r) Mp.locate(n, D, j, r)
+#define MAP_BOUND Mp.bound(jfirst, jlast, A.No_ti);
+#define MAP_STAGE Mp.stage((double*)(ccode + (((size_t)NR * K + 7) & ~(size_t)7)), C.r0, C.r1, tid, blockDim.x);
+#define MAP_BLOCK_WEIGHT
+#define MAP_INTERVAL_WEIGHT const double br = Mp.gv(j), o = ph0 + Rj;
+#define MAP_PSI(loc) (loc)
+#define MAP_OFF o
+#define MAP_ISO_RANGE                                                                                               \
+  int ilo, ihi;                                                                                                     \
+  Mp.iso_range(n, j, A.No_ti, ilo, ihi);
+#define MAP_ISO_AT(i) (long long)rint(Mp.Cv(i)) == n
+#define MAP_TAU Mp.tau(sj[s], sr[s])
+#include "eaqhm_modify_body.inc"
+#undef EAQHM_MODIFY_CURVE
+#undef MAP_INIT
+#undef MAP_LOCATE
+#undef MAP_BOUND
+#undef MAP_STAGE
+#undef MAP_BLOCK_WEIGHT
+#undef MAP_INTERVAL_WEIGHT
+#undef MAP_PSI
+#undef MAP_OFF
+#undef MAP_ISO_RANGE
+#undef MAP_ISO_AT
+#undef MAP_TAU
 }  // namespace eaqhm
 
 using namespace eaqhm;
 
 static bool finite_pos(double x) { return std::isfinite(x) && x > 0.0; }
+static int modify_scan(eaqhm_ctx* ctx, const uint8_t* code, int32_t No_ti, int32_t Kmax, double* R, double* ph0);
 
 extern "C" int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                                  int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta,
@@ -420,6 +314,11 @@ extern "C" int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const ui
   hipLaunchKernelGGL(eaqhm_modify_prep_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)), dim3(64 * PREP_WAVES),
                      lds, ctx->stream, A, beta, (int)(preserve_envelope != 0), amp, R, ph0);
   HIP_TRY(ctx, hipGetLastError());
+  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
+}
+
+// the segmented scan of dR (scan pass 0, carry, scan pass 1) into R and ph0
+static int modify_scan(eaqhm_ctx* ctx, const uint8_t* code, int32_t No_ti, int32_t Kmax, double* R, double* ph0) {
   const int nchunks = (No_ti + SCAN_CH - 1) / SCAN_CH;
   const size_t agg_bytes = (size_t)3 * nchunks * Kmax * sizeof(double);
   if (int rc = ctx->reserve(agg_bytes)) return rc;
@@ -438,18 +337,20 @@ extern "C" int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const ui
 }
 
 // samples per block of eaqhm_modify_eval_kernel and staged rows: the largest of 64/32/16 whose tables fit; the staged
-// rows follow the block's tau-span (TBS / rho samples), capped by the LDS budget (rows beyond it are read from memory)
-static size_t modify_lds_bytes(int K, int step, int tbs, int nr) {
+// rows follow the block's tau-span (TBS / rho samples), capped by the LDS budget (rows beyond it are read from memory).
+// The contour kernel's staged rows also hold C_j, r_j, g_j (crow = 3 doubles per row; 0 for the scalar kernel).
+static size_t modify_lds_bytes(int K, int step, int tbs, int nr, int crow) {
   return (((size_t)step + 2) & ~(size_t)1) * 8 + (size_t)K * (tbs + 1) * 8 + (size_t)tbs * 8 +
          (size_t)nr * ((3 * (size_t)K + 1) + (K + 1)) * 8 + (((size_t)tbs + 1) & ~(size_t)1) * 4 +
-         (((size_t)nr * K + 7) & ~(size_t)7);
+         (((size_t)nr * K + 7) & ~(size_t)7) + (size_t)nr * crow * 8;
 }
 
-static int modify_block_samples(int Kmax, int step, double rho, size_t* lds_bytes, int* nr) {
+// rho: the smallest rate of the time map (the contour's fewest output samples per knot interval)
+static int modify_block_samples(int Kmax, int step, double rho, int crow, size_t* lds_bytes, int* nr) {
   for (int tbs = 64; tbs >= 16; tbs >>= 1) {
     int NR = (int)ceil((double)(tbs - 1) / (rho * (double)step)) + 6;
-    while (NR > 4 && modify_lds_bytes(Kmax, step, tbs, NR) > 78 * 1024) --NR;
-    const size_t bytes = modify_lds_bytes(Kmax, step, tbs, NR);
+    while (NR > 4 && modify_lds_bytes(Kmax, step, tbs, NR, crow) > 78 * 1024) --NR;
+    const size_t bytes = modify_lds_bytes(Kmax, step, tbs, NR, crow);
     if (bytes <= 78 * 1024 || tbs == 16) {
       *lds_bytes = bytes; *nr = NR;
       return tbs;
@@ -471,7 +372,7 @@ extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const u
     return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: [t_lo, t_hi) outside [0, L_out)");
   size_t lds_bytes = 0;
   int NR = 0;
-  const int TBS = modify_block_samples(Kmax, step, rho, &lds_bytes, &NR);
+  const int TBS = modify_block_samples(Kmax, step, rho, 0, &lds_bytes, &NR);
   if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: Kmax too large for the LDS tables");
   const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, rho, beta, (long long)t_lo,
                     (long long)t_hi, out};
@@ -479,6 +380,54 @@ extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const u
   HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds_bytes));
   hipLaunchKernelGGL(eaqhm_modify_eval_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, TBS, NR);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+// ---- time and pitch scale contours
+extern "C" int eaqhm_modify_prep_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                       int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
+                                       const double* gain, int32_t preserve_envelope, double* amp, double* R,
+                                       double* ph0) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !code || !mom || !beta || !gain || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 ||
+      !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_curve: bad argument");
+  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
+  const size_t lds = (size_t)PREP_WAVES * 2 * Kmax * sizeof(double);
+  if (lds > 64 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_curve: Kmax too large for the envelope nodes");
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_curve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_modify_prep_curve_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, gain, (int)(preserve_envelope != 0), amp, R, ph0);
+  HIP_TRY(ctx, hipGetLastError());
+  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
+}
+
+extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                        const double* amp, const double* R, const double* ph0, int32_t No_ti,
+                                        int32_t Kmax, int32_t step, double fs, const double* C, const double* rate,
+                                        const double* gain, double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi,
+                                        double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !code || !mom || !amp || !R || !ph0 || !C || !rate || !gain || !out || No_ti < 4 || Kmax <= 0 ||
+      step <= 0 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: bad argument");
+  if (!finite_pos(rate_min)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: rate_min must be finite and > 0");
+  if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: [t_lo, t_hi) outside [0, L_out)");
+  size_t lds_bytes = 0;
+  int NR = 0;
+  const int TBS = modify_block_samples(Kmax, step, rate_min, 3, &lds_bytes, &NR);
+  if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: Kmax too large for the LDS tables");
+  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, 0.0, 0.0, (long long)t_lo,
+                    (long long)t_hi, out};
+  const MCurve Cu{C, rate, gain};
+  const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds_bytes));
+  hipLaunchKernelGGL(eaqhm_modify_eval_curve_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu,
+                     TBS, NR);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -1,0 +1,249 @@
+// eaqhm_modify_body.inc — the prep and eval kernel bodies of eaqhm_modify.hip, compiled twice: EAQHM_MODIFY_CURVE 0
+// gives the scalar kernels (DESIGN.md §9), 1 the contour kernels (§9.1).  The time map enters the eval body through the
+// MAP_* macros that eaqhm_modify.hip defines for each variant.  The body is shared as text rather than as an inlined
+// device template because inlining reorders the scalar kernels' code; compiled from this text with the flag at 0,
+// their ISA is the one they had before the contour kernels existed.
+// No include guard: included once per variant.
+
+#if EAQHM_MODIFY_CURVE
+// beta: [No_ti] per instant; gain: [No_ti-1] g_j of interval j
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_modify_prep_curve_kernel(ModArgs A, const double* __restrict__ betav, const double* __restrict__ gain,
+                                   int envelope, double* __restrict__ amp, double* __restrict__ dR,
+                                   double* __restrict__ P0) {
+#else
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_modify_prep_kernel(ModArgs A, double beta, int envelope, double* __restrict__ amp, double* __restrict__ dR,
+                             double* __restrict__ P0) {
+#endif
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int K = A.Kmax, D = A.step, RS = 3 * K + 1;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * PREP_WAVES + w;
+  double* nf = lds + (size_t)w * 2 * K;   // sorted node frequencies [K] and log amplitudes [K] of this wave's instant
+  double* nv = nf + K;
+  const bool live = i < A.No_ti;
+#if EAQHM_MODIFY_CURVE
+  const double beta = betav[live ? i : 0];   // wave-uniform: one wave per instant
+#endif
+  const double* row = A.records + (size_t)(live ? i : 0) * RS;
+  const bool env = live && beta != 1.0 && envelope;
+  int nn = 0;
+  if (env) {
+    // rank of every active slot in (f, k) order: slots are nearly sorted already, K is at most a few hundred
+    for (int k = lane; k < K; k += 64) {
+      const double ak = row[k], fk = row[K + k];
+      if (ak != 0.0 && fk > 0.0) {
+        int rank = 0;
+        for (int q = 0; q < K; ++q) {
+          const double aq = row[q], fq = row[K + q];
+          rank += (aq != 0.0 && fq > 0.0 && (fq < fk || (fq == fk && q < k))) ? 1 : 0;
+        }
+        nf[rank] = fk;
+        nv[rank] = log(ak);
+      }
+    }
+    for (int k = lane; k < K; k += 64) nn += (row[k] != 0.0 && row[K + k] > 0.0) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o);
+  }
+  __syncthreads();
+  if (!live) return;
+  const double scale = 2.0 * M_PI / A.fs;
+  for (int k = lane; k < K; k += 64) {
+    // ---- A'
+    const double ak = row[k], fk = row[K + k];
+    double a = ak;
+    if (beta != 1.0) {
+      a = 0.0;
+      if (ak != 0.0 && fk > 0.0) {
+        const double q = beta * fk;
+        a = ak;
+        if (envelope) {
+          int lo = 0, hi = nn;   // first node with f >= q
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (nf[mid] < q) lo = mid + 1; else hi = mid;
+          }
+          double E;
+          if (lo < nn && nf[lo] == q) E = nv[lo];
+          else if (lo == 0) E = nv[0];
+          else if (lo == nn) E = nv[nn - 1];
+          else E = nv[lo - 1] + (nv[lo] - nv[lo - 1]) * ((q - nf[lo - 1]) / (nf[lo] - nf[lo - 1]));
+          a = exp(E);
+        }
+        if (q >= 0.5 * A.fs) a = 0.0;
+      }
+    }
+    amp[(size_t)i * K + k] = a;
+    // ---- Delta of the interval (i, i+1), first-knot phase
+    GSlot S{A, k};
+    const int ci = S.code(i);
+    const bool head = ci != 0 && S.code(i - 1) == 0;
+    P0[(size_t)i * K + k] = (head && ci != 1) ? S.ph(i) : 0.0;
+    if (i == 0) dR[k] = 0.0;
+    if (i + 1 < A.No_ti) {
+      double d = 0.0;
+      if (ci != 0 && S.code(i + 1) != 0) {
+        const FmPiece P = make_piece(S, i, ci);
+        double w0, acc, emis, Mr;
+        interval_close(S, P, i, D, scale, w0, acc, emis, Mr);
+        d = (S.ph(i + 1) - S.ph(i)) + 2.0 * M_PI * Mr;
+#if EAQHM_MODIFY_CURVE
+        d = gain[i] * d;
+#endif
+      }
+      dR[(size_t)(i + 1) * K + k] = d;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Block of TBS consecutive output samples x all slots.
+//   stage 0  per sample: interval j and offset r (LDS).
+//   stage 1  one thread per (interval, slot) touching the block: the interval's local phase
+//            Psi(u) = R_j + sum_{v=1..u} w(v) - sum_{v=0..u} sin(pi v/D) er, u = 0..D, in the eval kernel's summation
+//            order; at each of the block's samples in the interval the phase P0 + beta rho ((1-fr) Psi(u0) + fr Psi(u0+1))
+//            goes to X[k][s].  A run's last knot (tau = c_b) is the end u = D of its last interval.
+//   stage 2  one thread per (sample, slot group): amplitude, A cos(phase), isolated knots; then one thread per sample
+//            adds the slots in slot order and the a0 spline.
+#if EAQHM_MODIFY_CURVE
+extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_curve_kernel(MEvalArgs E, MCurve Cu, int TBS, int NR) {
+#else
+extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEvalArgs E, int TBS, int NR) {
+#endif
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const ModArgs& A = E.M;
+  const int D = A.step, K = A.Kmax, TP = TBS + 1;
+  double* ft = lds;                                   // D+1
+  double* X = lds + ((D + 1 + 1) & ~1);               // [K][TP]
+  double* sr = X + (size_t)K * TP;                    // [TBS] r of each sample
+  double* crec = sr + TBS;                            // [NR][3K+1]
+  double* cmom = crec + (size_t)NR * (3 * K + 1);     // [NR][K+1]
+  int* sj = (int*)(cmom + (size_t)NR * (K + 1));      // [TBS] interval of each sample
+  unsigned char* ccode = (unsigned char*)(sj + ((TBS + 1) & ~1));   // [NR][K]
+  const int tid = threadIdx.x;
+  const long long t0 = E.t_lo + (long long)blockIdx.x * TBS;
+  const long long t1 = (t0 + TBS < E.t_hi) ? (t0 + TBS) : E.t_hi;
+  const int ns = (int)(t1 - t0);
+  MAP_INIT
+  int jfirst, jlast;
+  double rdummy;
+  MAP_LOCATE(t0, jfirst, rdummy);
+  MAP_LOCATE(t1 - 1, jlast, rdummy);
+  MAP_BOUND
+  // intervals met by the block: one before the first sample's (a run's last knot) up to the last sample's
+  const int jlo = max(0, jfirst - 1), jhi = min(A.No_ti - 2, jlast);
+  MCache C;
+  {
+    C.r0 = max(0, jlo - 1);
+    C.r1 = min(A.No_ti - 1, jhi + 2);
+    if (C.r1 > C.r0 + NR - 1) C.r1 = C.r0 + NR - 1;
+    if (C.r1 < C.r0) C.r1 = C.r0 - 1;
+    C.rec = crec; C.mom = cmom; C.code = ccode;
+    const int nrow = C.r1 - C.r0 + 1, RS = 3 * K + 1;
+    for (int q = tid; q < nrow * RS; q += blockDim.x) crec[q] = A.records[(size_t)C.r0 * RS + q];
+    for (int q = tid; q < nrow * (K + 1); q += blockDim.x) cmom[q] = A.mom[(size_t)C.r0 * (K + 1) + q];
+    for (int q = tid; q < nrow * K; q += blockDim.x) ccode[q] = A.code[(size_t)C.r0 * K + q];
+    MAP_STAGE
+  }
+  for (int u = tid; u <= D; u += blockDim.x) ft[u] = sin(M_PI * (double)u / (double)D);
+  for (int s = tid; s < ns; s += blockDim.x) {
+    int j; double r;
+    MAP_LOCATE(t0 + s, j, r);
+    sj[s] = j; sr[s] = r;
+  }
+  __syncthreads();
+  MAP_BLOCK_WEIGHT
+  // ---- stage 1
+  if (jhi >= jlo) {
+    const int nint = jhi - jlo + 1;
+    const double scale = 2.0 * M_PI / A.fs;
+    double S = 0.0;   // sum_{v=0..D} sin(pi v/D), in order
+    for (int u = 0; u <= D; ++u) S += ft[u];
+    for (int p = tid; p < nint * K; p += blockDim.x) {
+      const int jj = p / K, k = p - jj * K, j = jlo + jj;
+      CSlot Sl{A, C, k};
+      const int cj = Sl.code(j);
+      if (cj == 0 || Sl.code(j + 1) == 0) continue;
+      // the block's samples in this interval: [sa, sb), plus the run's last knot when j+1 ends the run
+      int sa = 0, hi = ns;
+      while (sa < hi) { const int mid = (sa + hi) >> 1; if (sj[mid] < j) sa = mid + 1; else hi = mid; }
+      int sb = sa;
+      while (sb < ns && sj[sb] == j) ++sb;
+      const bool ends = Sl.code(j + 2) == 0;
+      const int sl = (ends && sb < ns && sj[sb] == j + 1 && sr[sb] == 0.0) ? sb : -1;
+      if (sa == sb && sl < 0) continue;
+      const FmPiece P = make_piece(Sl, j, cj);
+      double w0, acc, emis, Mr;
+      interval_close(Sl, P, j, D, scale, w0, acc, emis, Mr);
+      // a run's last interval closes its mismatch completely: the model's phase at that knot is the integrated one
+      const double er = ends ? emis / S : M_PI * emis / (2.0 * (double)D);
+      const double Rj = E.R[(size_t)j * K + k], ph0 = E.P0[(size_t)j * K + k];
+      MAP_INTERVAL_WEIGHT
+      acc = w0;
+      double c = ft[0] * er;
+      double prev = MAP_PSI((acc - w0) - c);
+      int q = sa;
+      // u = 0: samples on the knot itself
+      while (q < sb && sr[q] == 0.0) { X[(size_t)k * TP + q] = MAP_OFF + br * prev; ++q; }
+      for (int u = 1; u <= D; ++u) {
+        acc += scale * P(u);
+        c += ft[u] * er;
+        const double psi = MAP_PSI((acc - w0) - c);
+        while (q < sb) {
+          const double rq = sr[q], u0 = floor(rq), fr = rq - u0;
+          if ((int)u0 == u - 1 && fr > 0.0) X[(size_t)k * TP + q] = MAP_OFF + br * ((1.0 - fr) * prev + fr * psi);
+          else if ((int)u0 == u && fr == 0.0) X[(size_t)k * TP + q] = MAP_OFF + br * psi;
+          else break;
+          ++q;
+        }
+        prev = psi;
+      }
+      if (sl >= 0) X[(size_t)k * TP + sl] = MAP_OFF + br * prev;
+    }
+  }
+  __syncthreads();
+  // ---- stage 2
+  const int s = tid % TBS, g = tid / TBS, G = blockDim.x / TBS;
+  const bool live = s < ns;
+  const long long n = t0 + s;
+  if (live) {
+    const int j = sj[s];
+    const double r = sr[s];
+    MAP_ISO_RANGE
+    for (int k = g; k < K; k += G) {
+      CSlot Sl{A, C, k};
+      auto inrun = [&](int q) { return q >= 0 && q <= A.No_ti - 2 && Sl.code(q) != 0 && Sl.code(q + 1) != 0; };
+      double cell = 0.0;
+      int jj = -1;
+      double rr = r;
+      if (inrun(j)) jj = j;
+      else if (r == 0.0 && inrun(j - 1)) { jj = j - 1; rr = (double)D; }
+      if (jj >= 0) {
+        const double a0v = E.amp[(size_t)jj * K + k], a1v = E.amp[(size_t)(jj + 1) * K + k];
+        const double Av = ((a1v - a0v) / (double)D) * rr + a0v;
+        cell = (Av != 0.0) ? Av * cos(X[(size_t)k * TP + s]) : 0.0;
+      }
+      for (int i = ilo; i <= ihi; ++i) {   // isolated accepted knots land on the output sample nearest to their image
+        if (Sl.code(i) == 1 && MAP_ISO_AT(i))
+          cell += E.amp[(size_t)i * K + k] * cos(Sl.ph(i));
+      }
+      X[(size_t)k * TP + s] = cell;   // this thread is the only reader of the cell
+    }
+  }
+  __syncthreads();
+  if (tid < TBS && live) {
+    double synth = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < K; ++k) synth += X[(size_t)k * TP + s];
+    const double tau = MAP_TAU;
+    int ia = sj[s];
+    if (ia > A.No_ti - 2) ia = A.No_ti - 2;
+    if (ia < 0) ia = 0;
+    CSlot S0{A, C, K};   // column K of mom = the a0 spline; its knots are the last record column
+    const int RS = 3 * K + 1;
+    const double a0v = spline_piece(S0.recv(ia, RS - 1), S0.recv(ia + 1, RS - 1), S0.mom(ia), S0.mom(ia + 1),
+                                    tau - (double)ia * (double)D, (double)D);
+    E.out[n] = a0v + 2.0 * synth;
+  }
+}

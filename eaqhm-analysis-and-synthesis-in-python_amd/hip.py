@@ -37,6 +37,9 @@ SYMBOLS = (
     ("eaqhm_modify_prep", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _I32, _P, _P, _P]),
     ("eaqhm_modify_synth", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64, _I64,
                                       _P]),
+    ("eaqhm_modify_prep_curve", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P]),
+    ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
+                                            _I64, _I64, _P]),
 )
 
 
@@ -184,6 +187,17 @@ class Context:
         self._ck(self.lib.eaqhm_modify_synth(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R), _ptr(ph0),
                                              No_ti, Kmax, step, float(fs), float(rho), float(beta), L_out, t_lo, t_hi,
                                              _ptr(out)))
+
+    def modify_prep_curve(self, records, code, mom, No_ti, Kmax, step, fs, beta, gain, preserve_envelope, amp, R, ph0):
+        self._ck(self.lib.eaqhm_modify_prep_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step,
+                                                  float(fs), _ptr(beta), _ptr(gain), int(bool(preserve_envelope)),
+                                                  _ptr(amp), _ptr(R), _ptr(ph0)))
+
+    def modify_synth_curve(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, C, rate, gain, rate_min, L_out,
+                           t_lo, t_hi, out):
+        self._ck(self.lib.eaqhm_modify_synth_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
+                                                   _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C), _ptr(rate),
+                                                   _ptr(gain), float(rate_min), L_out, t_lo, t_hi, _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

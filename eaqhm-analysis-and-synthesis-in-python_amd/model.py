@@ -2,12 +2,15 @@
 
     unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
     eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   *, device_index=0) -> float64[rint(time_scale * length)]
+                   *, device_index=0) -> float64[L_out]
+    scale_contour(DetComponents, fs, times_s, values) -> float64[No_ti]
+    contour_time_map(rho, beta, step, length) -> dict(rate, gain, C, L_out, rate_min)
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
-own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model").  The work runs in
-libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep, eaqhm_modify_synth); there is no CPU path.
+own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
+also be a contour, one value per analysis instant (§9.1).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
+eaqhm_modify_prep / eaqhm_modify_synth, or their _curve variants for contours); there is no CPU path.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -113,6 +116,85 @@ def _scale(x, name):
     return v
 
 
+def _is_contour(x):
+    """True for an array-like scale (a contour); numbers and strings are scalars."""
+    return not isinstance(x, (str, bytes)) and np.ndim(x) > 0
+
+
+def _numeric_1d(x, name):
+    a = np.asarray(x)
+    if a.dtype.kind not in "iuf":
+        raise ValueError("%s must hold numbers" % name)
+    if a.ndim != 1:
+        raise ValueError("%s must be 1-D, got shape %s" % (name, a.shape))
+    return a.astype(np.float64)
+
+
+def _in_range(v, name):
+    if not np.all(np.isfinite(v)) or np.any(v < SCALE_RANGE[0]) or np.any(v > SCALE_RANGE[1]):
+        raise ValueError("%s must be finite and in [%g, %g]" % (name, SCALE_RANGE[0], SCALE_RANGE[1]))
+    return v
+
+
+def _contour(x, name, n):
+    """A scale as float64[n]: a number broadcast, or a 1-D array of n values."""
+    if not _is_contour(x):
+        return np.full(n, _scale(x, name))
+    v = _numeric_1d(x, name)
+    if len(v) != n:
+        raise ValueError("%s must have one value per analysis instant (%d), got %d" % (name, n, len(v)))
+    return _in_range(v, name)
+
+
+def check_curve(times_s, values, name="curve"):
+    """Validates a breakpoint curve (seconds, scale): returns (times, values) as float64 arrays.  The times must be
+    finite and strictly increasing, the values finite and in SCALE_RANGE."""
+    t = _numeric_1d(times_s, name + " times")
+    v = _numeric_1d(values, name + " values")
+    if len(t) == 0 or len(t) != len(v):
+        raise ValueError("%s: times and values must be non-empty and of the same length" % name)
+    if not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+        raise ValueError("%s: times must be finite and strictly increasing" % name)
+    return t, _in_range(v, name + " values")
+
+
+def _model_instants(DetComponents):
+    if isinstance(DetComponents, dict):
+        return np.asarray(DetComponents["ti"], dtype=np.float64).reshape(-1)
+    return np.array([float(x.ti) for x in DetComponents], dtype=np.float64)
+
+
+def scale_contour(DetComponents, fs, times_s, values):
+    """The per-instant contour of a breakpoint curve, for eaQHMSynthesis's time_scale or pitch_scale: the curve
+    (times_s in seconds, values in SCALE_RANGE) interpolated linearly at every analysis instant ti / fs of the model,
+    held flat before the first and after the last breakpoint.  Returns float64[No_ti]."""
+    t, v = check_curve(times_s, values)
+    try:
+        fs = float(fs)
+    except (TypeError, ValueError):
+        raise ValueError("fs must be a number") from None
+    if not np.isfinite(fs) or fs <= 0:
+        raise ValueError("fs must be finite and > 0")
+    return np.interp(_model_instants(DetComponents) / fs, t, v)
+
+
+def contour_time_map(rho, beta, step, length):
+    """The time map of DESIGN.md §9.1 for contours rho, beta (float64[n]) on knots c_i = i * step: per interval j
+    r_j = (rho_j + rho_{j+1}) / 2 and g_j = r_j (beta_j + beta_{j+1}) / 2; the output knots C_0 = 0,
+    C_{j+1} = C_j + r_j step (a float64 cumulative sum, the kernel's input); L_out = rint(C_{n-1} + rho_{n-1}
+    (length - c_{n-1})).  Returns dict(rate=float64[n] (r_j, then rho_{n-1}), gain=float64[n-1], C=float64[n], L_out,
+    rate_min)."""
+    rho = np.asarray(rho, dtype=np.float64)
+    beta = np.asarray(beta, dtype=np.float64)
+    n = len(rho)
+    r = (rho[:-1] + rho[1:]) / 2
+    g = r * ((beta[:-1] + beta[1:]) / 2)
+    C = np.concatenate(([0.0], np.cumsum(r * float(step))))
+    L_out = int(np.rint(C[-1] + rho[-1] * (length - (n - 1) * step)))
+    rate = np.append(r, rho[-1])
+    return dict(rate=rate, gain=g, C=C, L_out=L_out, rate_min=float(rate.min()))
+
+
 def check_arguments(model, fs, length, time_scale, pitch_scale):
     """Validates everything eaQHMSynthesis gets (no device work): returns (rho, beta, fs, length)."""
     rho = _scale(time_scale, "time_scale")
@@ -138,21 +220,48 @@ def check_arguments(model, fs, length, time_scale, pitch_scale):
     return rho, beta, fs, length
 
 
+def check_contour_arguments(model, fs, length, time_scale, pitch_scale):
+    """check_arguments for contours (no device work): either scale may be a number (broadcast) or a 1-D array of one
+    value per analysis instant.  Returns (rho, beta, fs, length) with rho, beta float64[No_ti]."""
+    n = len(model["ti"])
+    rho = _contour(time_scale, "time_scale", n)
+    beta = _contour(pitch_scale, "pitch_scale", n)
+    _, _, fs, length = check_arguments(model, fs, length, 1.0, 1.0)
+    return rho, beta, fs, length
+
+
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True, *,
-                   device_index=0):
+                   device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
-    its own amplitude.  Partials pushed to or above fs/2 are muted.  Returns float64[rint(time_scale * length)]."""
+    its own amplitude.  Partials pushed to or above fs/2 are muted.
+
+    Each scale is either a number (the result has rint(time_scale * length) samples) or a contour: a 1-D
+    array of one value per analysis instant of the model (len(det) for det_format="structs", len(det["ti"]) for
+    "arrays"), e.g. from scale_contour().  If either is a contour the other is broadcast and the contour path runs
+    (§9.1): interval j between two instants is stretched by the mean of their time scales and its frequencies are
+    multiplied by the mean of their pitch scales; the length is contour_time_map(...)["L_out"].
+
+    `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
+    Returns float64[L_out]."""
     model = unpack_model(DetComponents)
-    rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
+    contour = _is_contour(time_scale) or _is_contour(pitch_scale)
+    if contour:
+        rho, beta, fs, length = check_contour_arguments(model, fs, length, time_scale, pitch_scale)
+    else:
+        rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
     dev = c.device
     rec_h = model["records"]
     n, K, D = rec_h.shape[0], model["Kmax"], model["step"]
-    L_out = int(np.rint(rho * length))
+    if contour:
+        tm = contour_time_map(rho, beta, D, length)
+        L_out = tm["L_out"]
+    else:
+        L_out = int(np.rint(rho * length))
     if K == 0:                                   # no slot at all: keep one empty slot so the a0 spline still runs
         rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
         K = 1
@@ -163,7 +272,17 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     R = torch.empty(n * K, dtype=torch.float64, device=dev)
     ph0 = torch.empty(n * K, dtype=torch.float64, device=dev)
     out = torch.empty(L_out, dtype=torch.float64, device=dev)
+    ranges = [(0, L_out)] if _ranges is None else [(int(a), int(b)) for a, b in _ranges]
     c.spline_solve(rec, n, K, D, code, mom)
-    c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
-    c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, 0, L_out, out)
+    if contour:
+        beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                                       for x in (beta, tm["gain"], tm["C"], tm["rate"]))
+        c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, preserve_envelope, amp, R, ph0)
+        for t_lo, t_hi in ranges:
+            c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"], L_out,
+                                 t_lo, t_hi, out)
+    else:
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
+        for t_lo, t_hi in ranges:
+            c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
     return out.cpu().numpy()

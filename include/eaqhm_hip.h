@@ -197,6 +197,25 @@ int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* cod
                        const double* R, const double* ph0, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
                        double rho, double beta, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
 
+/* time and pitch scale contours: rho_i and beta_i per analysis instant (additive to ABI 3) ---------------------------
+ * The definition is DESIGN.md §9.1; with constant contours it is §9.  Per interval j: r_j = (rho_j + rho_{j+1}) / 2,
+ * b_j = (beta_j + beta_{j+1}) / 2, g_j = r_j b_j; output knots C_0 = 0, C_{j+1} = C_j + r_j step (the caller computes
+ * them in double, in this order); L_out = rint(C_{n-1} + rho_{n-1} (L - c_{n-1})).
+ * eaqhm_modify_prep_curve: as eaqhm_modify_prep with beta[No_ti] per instant (A' uses beta_i) and gain[No_ti-1] = g_j;
+ *   R holds the weighted knot phase G (0 at a run's first knot, G_{j+1} = G_j + g_j ((ph_{j+1} - ph_j) + 2 pi M_j)).
+ * eaqhm_modify_synth_curve: writes out[t_lo, t_hi) of the L_out-sample signal from the prep_curve outputs.
+ *   C[No_ti] output knot positions, rate[No_ti] = r_j with rate[No_ti-1] = rho_{n-1} (past the last knot),
+ *   gain[No_ti-1] = g_j, rate_min = the smallest entry of rate (sizes the staged rows).
+ * Device arrays are the caller's: every rate must be finite and > 0 and C strictly increasing.  EAQHM_EINVAL for null
+ * pointers, rate_min <= 0 or not finite, and a range outside [0, L_out).                                            */
+int eaqhm_modify_prep_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                            int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
+                            const double* gain, int32_t preserve_envelope, double* amp, double* R, double* ph0);
+int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                             const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
+                             int32_t step, double fs, const double* C, const double* rate, const double* gain,
+                             double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,12 @@
 """Resynthesis from the model: device time of eaqhm_modify_prep (prep + scan) and eaqhm_modify_synth against
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
-    python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--out FILE]
+    python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
-{0.5, 1, 2} x beta in {1, 1.25}.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
+{0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour kernels (eaqhm_modify_prep_curve / _synth_curve,
+DESIGN.md §9.1): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with beta ramping 0.85 -> 1.2,
+and both varying; eval_ms_per_msample normalises the eval time by the output length.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
 import json
@@ -52,7 +54,7 @@ def timed(torch, fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def probe(workload, reps):
+def probe(workload, reps, contours=False):
     import torch
     from eaqhm_amd.functions import _ctx
     from eaqhm_amd.model import unpack_model
@@ -87,19 +89,51 @@ def probe(workload, reps):
                                                         out), reps)
             rows.append(dict(rho=rho, beta=beta, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3),
                              total_ms=round(t_prep + t_syn, 3), out_samples=Lo,
+                             eval_ms_per_msample=round(t_syn / (Lo / 1e6), 4),
                              msamples_per_s=round(Lo / ((t_prep + t_syn) * 1e-3) / 1e6, 1),
                              ratio_to_eval_synth=round((t_prep + t_syn) / t_eval, 3)))
-    return dict(workload=workload, fs=fs, L=L, No_ti=n, Kmax=K, eval_synth_ms=round(t_eval, 3),
-                pack_results_s=round(t_pack, 3), unpack_model_s=round(t_unpack, 3), settings=rows)
+    res = dict(workload=workload, fs=fs, L=L, No_ti=n, Kmax=K, eval_synth_ms=round(t_eval, 3),
+               pack_results_s=round(t_pack, 3), unpack_model_s=round(t_unpack, 3), settings=rows)
+    if contours:
+        res["contours"] = probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval, reps)
+    return res
+
+
+def probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval, reps):
+    from eaqhm_amd.model import contour_time_map
+    dev = c.device
+    t = np.arange(n) * D / fs
+    one = np.ones(n)
+    sinus = 1.05 + 0.35 * np.sin(2 * np.pi * 0.5 * t)
+    ramp = np.interp(t, [0.0, t[-1]], [0.85, 1.2])
+    rows = []
+    for label, rho, beta in (("unit", one, one), ("rho_sinus", sinus, one), ("beta_ramp", one, ramp),
+                             ("both", sinus, ramp)):
+        tm = contour_time_map(rho, beta, D, L)
+        Lo = tm["L_out"]
+        beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                                       for x in (beta, tm["gain"], tm["C"], tm["rate"]))
+        out = torch.empty(Lo, dtype=torch.float64, device=dev)
+        t_prep = timed(torch, lambda: c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, True, amp, R,
+                                                          ph0), reps)
+        t_syn = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
+                                                          tm["rate_min"], Lo, 0, Lo, out), reps)
+        rows.append(dict(contour=label, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3),
+                         total_ms=round(t_prep + t_syn, 3), out_samples=Lo,
+                         eval_ms_per_msample=round(t_syn / (Lo / 1e6), 4),
+                         msamples_per_s=round(Lo / ((t_prep + t_syn) * 1e-3) / 1e6, 1),
+                         ratio_to_eval_synth=round((t_prep + t_syn) / t_eval, 3)))
+    return rows
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="synth16k_60s,synth48k_60s")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--contours", action="store_true", help="also time the contour kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
