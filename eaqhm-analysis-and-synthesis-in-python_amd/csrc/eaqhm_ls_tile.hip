@@ -16,7 +16,8 @@
 //   A3+B   chunks of 16 sample PAIRS (mid-d-1, mid+d), centre outwards, built in LDS by all threads: track values
 //          loaded directly, phase = running sum (16-lane DPP scan + per-slot carry); the pair shares its sincos
 //          because the negative-frequency column at u is the time-reversed positive one (functions.py:284-285);
-//          contracted with v_mfma_f64_16x16x4_f64, LDS operand reads software-pipelined one k-step ahead
+//          contracted with v_mfma_f64_16x16x4_f64, LDS operand reads software-pipelined one k-step ahead; frames of
+//          <= 10 tile rows: only X = w [E2 | s] in the chunk, three-weight Gramian G_p = X^H diag(n^p) X (TW in tile_frame)
 //   B0     adaptation 0: no basis at all — the Gramian in closed form from Toeplitz tables, then two real systems of
 //          half the order factorised side by side (a0_frame, eaqhm_ls_a0.h)
 //   C      right-looking tile Cholesky with look-ahead, 2 workgroup barriers per tile row: trailing update with the
@@ -60,7 +61,29 @@ __device__ inline void sys_tile_of(int x, int& P, int& Q) {
 
 // One frame with NS tiles per wave.  Not inlined: each register budget gets its own register allocation (inlining
 // the five budgets into one kernel body spills several hundred VGPRs).
-template <int NS>
+// TW = 0: the Gramian is contracted tile by tile from the stacked basis Y.  TW > 0: three-weight Gramian — the basis
+// chunk holds only X = w [E2 | s] (Kc + 1 columns, T = ceil((Kc + 1) / 16) tile columns), each wave contracts at most TW
+// lower-triangle pairs (I, J) of them into G_p = X_I^H diag(n^p) X_J, p = 0, 1, 2, and the system tiles of Y^H Y are
+// gathered from the G_p afterwards (see the comment at the gather).
+// One k-step of the three-weight contraction of a basis pair: a = X_I, b = X_J (this lane's row k), nk = n_k of that
+// row.  Three real products per complex one for each of G0 = a^H b, G1 = (n a)^H b, G2 = (n a)^H (n b):
+// g[3p] = re re', g[3p+1] = im im', g[3p+2] = (re + im)(im' - re')  ->  Re = g[3p] + g[3p+1], Im = g[3p+2] + g[3p] - g[3p+1]
+__device__ inline void tw_step(d4 (&g)[9], double aR, double aI, double bR, double bI, double nk) {
+  const double sA = aR + aI, dB = bI - bR;
+  const double naR = nk * aR, naI = nk * aI, nsA = nk * sA;
+  const double nbR = nk * bR, nbI = nk * bI, ndB = nk * dB;
+  g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g[0], 0, 0, 0);
+  g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g[1], 0, 0, 0);
+  g[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(sA, dB, g[2], 0, 0, 0);
+  g[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, bR, g[3], 0, 0, 0);
+  g[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, bI, g[4], 0, 0, 0);
+  g[5] = __builtin_amdgcn_mfma_f64_16x16x4f64(nsA, dB, g[5], 0, 0, 0);
+  g[6] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, nbR, g[6], 0, 0, 0);
+  g[7] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, nbI, g[7], 0, 0, 0);
+  g[8] = __builtin_amdgcn_mfma_f64_16x16x4f64(nsA, ndB, g[8], 0, 0, 0);
+}
+
+template <int NS, int TW>
 __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, int ldx_max_, double* lds, int f_) {
   const int TS = uni(TS_), ldx_max = uni(ldx_max_), f = uni(f_);
   const int tid = threadIdx.x, nt_thr = TL_THREADS;
@@ -117,7 +140,10 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     const int nt = (Ms + 15) >> 4;
     const int c = uni(A.frame_c[f]), wl = uni(A.frame_wl[f]), inst = uni(A.frame_inst[f]);
     const int N = 2 * wl + 1, mid = wl;
-    const int ldx = (nt << 4) + ((nt & 1) ? 0 : 16);  // ≡ 16 (mod 32): MFMA operand reads hit disjoint bank halves
+    const int T = (Kc + 16) >> 4;                      // three-weight basis: tile columns of X = w [E2 | s]
+    const int nb = TW ? T : nt;                        // tile columns of the basis chunk
+    const int ldx = (nb << 4) + ((nb & 1) ? 0 : 16);  // ≡ 16 (mod 32): MFMA operand reads hit disjoint bank halves
+    const int npair = T * (T + 1) / 2;
     const int ntiles = nt * (nt + 1) / 2;
     const int is = 2 * Kc - 16 * (nt - 1);  // position of the signal column inside the last tile row (2,6,10,14)
     const double f0 = uni(A.f0_stale);
@@ -160,6 +186,24 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       const int P = live[sl] ? (code >> 4) : 0, Q = live[sl] ? (code & 15) : 0;
       tP[sl] = __builtin_amdgcn_readfirstlane(P);   // wave-uniform: scalar registers, not spill slots
       tQ[sl] = __builtin_amdgcn_readfirstlane(Q);
+    }
+
+    // three-weight Gramian: basis pair x = wave + 8 slot (pairs numbered row by row, I >= J): pair counts per SIMD
+    // (waves w and w + 4) equal to within one
+    constexpr int TWA = TW ? TW : 1;
+    d4 g[TWA][9];
+    int gI[TWA], gJ[TWA];
+    bool glive[TWA];
+#pragma unroll
+    for (int sl = 0; sl < TWA; ++sl) {
+      const int x = wave + 8 * sl;
+      glive[sl] = TW && x < npair;
+      int I = 0, J = 0;
+      if (glive[sl]) sys_tile_of(x, I, J);
+      gI[sl] = __builtin_amdgcn_readfirstlane(I);
+      gJ[sl] = __builtin_amdgcn_readfirstlane(J);
+#pragma unroll
+      for (int p = 0; p < 9; ++p) g[sl][p] = (d4){0, 0, 0, 0};
     }
 
     // ================= Gramian =================
@@ -212,12 +256,12 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           const double wu = win[u], nu = (double)(u - mid);
           pur *= wu; pui *= wu; nur *= wu; nui *= wu;
           xr[cpos] = pur;      xi[cpos] = pui;      xr[cneg] = nur;      xi[cneg] = nui;
-          xr[spos] = nu * pur; xi[spos] = nu * pui; xr[sneg] = nu * nur; xi[sneg] = nu * nui;
+          if (!TW) { xr[spos] = nu * pur; xi[spos] = nu * pui; xr[sneg] = nu * nur; xi[sneg] = nu * nui; }
         }
         pvr *= wv; pvi *= wv; nvr *= wv; nvi *= wv;
         xr += ldx; xi += ldx;
         xr[cpos] = pvr;      xi[cpos] = pvi;      xr[cneg] = nvr;      xi[cneg] = nvi;
-        xr[spos] = nv * pvr; xi[spos] = nv * pvi; xr[sneg] = nv * nvr; xi[sneg] = nv * nvi;
+        if (!TW) { xr[spos] = nv * pvr; xi[spos] = nv * pvi; xr[sneg] = nv * nvr; xi[sneg] = nv * nvi; }
       }
       // DC / signal columns: one thread per chunk row, spread over the waves (lanes 0, 16, 32, 48)
       if ((tid & 15) == 0 && (tid >> 4) < TS) {
@@ -232,13 +276,16 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         double* xr = Xre + row * ldx;
         double* xi = Xim + row * ldx;
         xr[XCOL(n, el)] = w;               xi[XCOL(n, el)] = 0.0;            // DC column
-        xr[XCOL(Kc + n, el)] = w * nn;     xi[XCOL(Kc + n, el)] = 0.0;       // its slope copy
-        xr[XCOL(2 * Kc, el)] = w * sval;   xi[XCOL(2 * Kc, el)] = 0.0;       // signal column
+        if (!TW) {
+          xr[XCOL(Kc + n, el)] = w * nn;   xi[XCOL(Kc + n, el)] = 0.0;       // its slope copy
+        }
+        const int scol = TW ? Kc : 2 * Kc;
+        xr[XCOL(scol, el)] = w * sval;     xi[XCOL(scol, el)] = 0.0;         // signal column
       }
       // rows beyond the window (the virtual sample u = -1 and the tail of the last chunk): zero
       if (d0 + PE > mid) {
-        for (int q = tid; q < TS * 16 * nt; q += nt_thr) {
-          const int row = q / (16 * nt), col = q - row * (16 * nt);
+        for (int q = tid; q < TS * 16 * nb; q += nt_thr) {
+          const int row = q / (16 * nb), col = q - row * (16 * nb);
           const int d = d0 + (row >> 1);
           const int t = (row & 1) ? (mid + d) : (mid - d - 1);
           if (d > mid || t < 0) { Xre[row * ldx + col] = 0.0; Xim[row * ldx + col] = 0.0; }
@@ -249,6 +296,30 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       STAMP(1);
       const int pcs = (npairs - d0 < PE) ? (npairs - d0) : PE;   // sample pairs in this chunk
       const int ksl = (pcs + 1) >> 1;                             // k-steps (4 rows each) that hold samples
+      if constexpr (TW > 0) {
+#pragma unroll
+        for (int sl = 0; sl < TW; ++sl) {
+          if (!glive[sl]) continue;
+          const int ca = 16 * gI[sl], cb = 16 * gJ[sl];
+          int rb = lq * ldx;
+          const int sw0 = lcol + (lq >> 1);
+          // n_k of this lane's row 4 ks + lq: sample pair d = d0 + 2 ks + lq/2, odd rows t = mid + d, even rows t = mid - d - 1
+          int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
+          asm volatile("" : "+v"(rb), "+v"(nk));   // (hoisted out of the chunk loop, these spill)
+          const int plane = TS * ldx_max;
+          // (not software-pipelined: the operands of the next k-step do not fit beside 2 x 9 accumulators)
+          const int kn = (ksl < 8) ? ksl : 8;
+#pragma clang loop unroll(disable)
+          for (int ks = 0; ks < kn; ++ks) {
+            const int sw = (sw0 + 2 * ks) & 15;
+            const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
+            const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
+            rb += 4 * ldx;
+            tw_step(g[sl], aR, aI, bR, bI, (double)nk);
+            nk += (lq & 1) ? 2 : -2;
+          }
+        }
+      } else
 #pragma unroll
       for (int sl = 0; sl < NS; ++sl) {
         if (!live[sl]) continue;
@@ -309,13 +380,59 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       __syncthreads();
       STAMP(2);
     }
-    if constexpr (NM3 > 0) {   // Re = P1 + P2,  Im = aR bI - aI bR = P3 + P1 - P2
+    if constexpr (TW == 0 && NM3 > 0) {   // Re = P1 + P2,  Im = aR bI - aI bR = P3 + P1 - P2
 #pragma unroll
       for (int sl = 0; sl < NM3; ++sl) {
         const d4 p1 = accR[sl], p2 = acc3[sl];
         accR[sl] = p1 + p2;
         accI[sl] = accI[sl] + (p1 - p2);
       }
+    }
+    if constexpr (TW > 0) {
+      // The G_p tiles go through the workgroup's scratch area (the bridged track rows are dead now; <= 3 * 21 tiles of
+      // 16 x 16 complex values, see ls_tile_scratch_stride), then every wave gathers its system tiles.  Y = [X_E | n X_E | s]
+      // with X = [X_E | s], so entry (R, C) of Y^H Y is G_p[a][b]: a = R (amplitude row), R - Kc (slope row) or Kc
+      // (signal row), likewise b for C, p = the number of slope indices among R and C.  Every G_p is Hermitian (n is
+      // real): entries above the tile diagonal of G_p are conjugates of computed ones.
+      double* Gs = Qs;
+#pragma unroll
+      for (int sl = 0; sl < TWA; ++sl) {
+        if (!glive[sl]) continue;
+        const int x = wave + 8 * sl;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          const d4 p1 = g[sl][3 * p], p2 = g[sl][3 * p + 1];
+          const d4 re = p1 + p2, im = g[sl][3 * p + 2] + (p1 - p2);
+          double* gt = Gs + (size_t)(p * npair + x) * 512;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = 2 * (16 * (lq + 4 * r) + lcol);
+            gt[o] = re[r]; gt[o + 1] = im[r];
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int sl = 0; sl < NS; ++sl) {   // every slot, empty ones too: nothing of accR / accI lives through the contraction
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int R = 16 * tP[sl] + lq + 4 * r, C = 16 * tQ[sl] + lcol;
+          const bool pad = !live[sl] || R > 2 * Kc || C > 2 * Kc;
+          const bool rs = R >= Kc && R < 2 * Kc, cs = C >= Kc && C < 2 * Kc;
+          const int a = (R == 2 * Kc) ? Kc : rs ? R - Kc : R, b = (C == 2 * Kc) ? Kc : cs ? C - Kc : C;
+          const int p = (int)rs + (int)cs;
+          const bool lo = (a >> 4) >= (b >> 4);
+          const int I = lo ? (a >> 4) : (b >> 4), J = lo ? (b >> 4) : (a >> 4);
+          const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
+          double vr = 0.0, vi = 0.0;
+          if (!pad) {
+            const double2 v = *(const double2*)(Gs + (size_t)(p * npair + I * (I + 1) / 2 + J) * 512 + 2 * (16 * i + j));
+            vr = v.x; vi = lo ? v.y : -v.y;
+          }
+          accR[sl][r] = vr; accI[sl][r] = vi;
+        }
+      }
+      STAMP(2);
     }
 
     {
@@ -586,7 +703,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_ls_zero_prefix_kernel(co
 extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(LsArgs A, int TS, int ldx_max) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int nxt;
-#define RUN_CLASS(NSV, C)                                                                \
+#define RUN_CLASS(NSV, TWV, C)                                                             \
   for (;;) {                                                                             \
     if (threadIdx.x == 0) nxt = atomicAdd(A.cls + 8 + C, 1);                             \
     __syncthreads();                                                                     \
@@ -594,14 +711,14 @@ extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(Ls
     __syncthreads();                                                                     \
     if (item >= A.cls[C]) break;                                                         \
     if (A.mode == 0) a0_frame<A0_NS, A0_M, 2>(A, lds, A.cls[16 + (size_t)C * A.n_frames + item], TZ_TB, TZ_NCH, 520, 64 * CI_NCH);                          \
-    else tile_frame<NSV>(A, TS, ldx_max, lds, A.cls[16 + (size_t)C * A.n_frames + item]);               \
+    else tile_frame<NSV, TWV>(A, TS, ldx_max, lds, A.cls[16 + (size_t)C * A.n_frames + item]);          \
   }
-  RUN_CLASS(12, 5)   // 91 tiles
-  RUN_CLASS(10, 4)   // 78 tiles
-  RUN_CLASS(9, 3)    // 66 tiles
-  RUN_CLASS(7, 2)    // 55 tiles
-  RUN_CLASS(6, 1)    // 45 tiles
-  RUN_CLASS(5, 0)    // <= 36 tiles
+  RUN_CLASS(12, 0, 5)   // 91 tiles
+  RUN_CLASS(10, 0, 4)   // 78 tiles
+  RUN_CLASS(9, 0, 3)    // 66 tiles
+  RUN_CLASS(7, 2, 2)    // 55 tiles, T = 5: 15 basis pairs
+  RUN_CLASS(6, 2, 1)    // 45 tiles, T = 5
+  RUN_CLASS(5, 2, 0)    // <= 36 tiles, T <= 4: <= 10 basis pairs
 #undef RUN_CLASS
 }
 
@@ -624,7 +741,8 @@ bool ls_tile_applicable(int Kcmax, int Nmax) {
 
 size_t ls_tile_scratch_stride(int nmax, int Nmax) {
   const size_t Npad = (size_t)((Nmax + 63) >> 6) << 6;
-  return (2 * Npad * nmax + 15) & ~(size_t)15;
+  const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512;   // three-weight G_p tiles of T <= 6 (nt <= 12)
+  return ((bridged > gram ? bridged : gram) + 15) & ~(size_t)15;
 }
 
 // Frames into their size classes, and (adaptations >= 1) the zero counts of the tracks that the slot set-up of both
