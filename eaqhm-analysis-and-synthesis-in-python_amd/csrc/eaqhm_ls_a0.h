@@ -124,14 +124,6 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
   double* xs = sh + 18;                                // 4 * Kcmax
   unsigned long long* dbg = uni(A.debug);
   unsigned long long t_prev = 0;
-#define A0_STAMP(ph)                                                \
-  do {                                                              \
-    if (dbg && tid == 0) {                                          \
-      unsigned long long t_now = __builtin_amdgcn_s_memtime();      \
-      atomicAdd(dbg + (ph), t_now - t_prev);                        \
-      t_prev = t_now;                                               \
-    }                                                               \
-  } while (0)
   if (dbg && tid == 0) t_prev = __builtin_amdgcn_s_memtime();
 
   for (int t = tid; t < N; t += NTHR) {
@@ -139,10 +131,10 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
     sig[t] = uni(A.s)[(size_t)(c - wl) + t];
   }
   __syncthreads();
-  A0_STAMP(0);
+  LS_STAMP(0);
   toeplitz_tables(tab, part, W2, PA, PB, sh, win, sig, K, wl, f0 * (2.0 * M_PI / uni(A.fs)), tid, TB, NCH);
   const double ssq = sh[0];
-  A0_STAMP(1);
+  LS_STAMP(1);
 
   // this wave's tiles of its system (numbered column by column, tile y on wave y % WPS, slot y / WPS)
   int tP[NS], tQ[NS];
@@ -176,7 +168,7 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
       }
     }
     __syncthreads();   // (PAR = 2: the tables are dead, their space becomes panel / inverse storage)
-    A0_STAMP(2);
+    LS_STAMP(2);
 
 #define A0_UPDATE(sl)                                                                   \
   {                                                                                     \
@@ -200,7 +192,7 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
       }
       if (mine)
         diag_Dr(Rt, post + sp * 256, flags + sp, 16 * jb, dumpD + sp * 64, Ldl + sp * TL_TILE, jb == m - 1);
-      A0_STAMP(10);
+      LS_STAMP(10);
       if (jb > 0) {
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
@@ -212,9 +204,9 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
       if (!mine && wv == ((yd + 1) & (WPS - 1)))
         diag_Zr(post + sp * 256, flags + sp, 16 * jb, zs + sp * 64, Wt + (sp * M + jb) * TL_TILE,
                 dorig + sp * 16 * M + 16 * jb, (jb == m - 1) ? is : 16, uni(A.fault));
-      A0_STAMP(8);
+      LS_STAMP(8);
       __syncthreads();  // (A)
-      A0_STAMP(6);
+      LS_STAMP(6);
 #pragma unroll
       for (int sl = 0; sl < NS; ++sl) {   // panel tiles: X = T W^T, published k-major
         if (!live[sl] || tQ[sl] != jb || tP[sl] == jb) continue;
@@ -234,11 +226,11 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
 #pragma unroll
         for (int r = 0; r < 4; ++r) tr[lcol * TL_LD + lq + 4 * r] = x[r];
       }
-      A0_STAMP(7);
+      LS_STAMP(7);
       __syncthreads();  // (C)
     }
 #undef A0_UPDATE
-    A0_STAMP(3);
+    LS_STAMP(3);
 
     // ---- back substitution  L^T x = y,  y = row `is` of the last tile row
     double* zvs = zv + sp * 16 * M;
@@ -277,7 +269,7 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
       }
       __syncthreads();
     }
-    A0_STAMP(4);
+    LS_STAMP(4);
   }
   // ---- back to the complex amplitudes and slopes in the order of the complex code: [negative | DC | positive]
   {
@@ -298,8 +290,7 @@ __device__ __attribute__((noinline)) void a0_frame(const LsArgs& A, double* lds_
   }
   __syncthreads();
   write_record(A, xs, sh, nullptr, f, K, inst, c, f0, false);
-  A0_STAMP(5);
-#undef A0_STAMP
+  LS_STAMP(5);
 }
 
 }  // namespace eaqhm

@@ -177,12 +177,10 @@ __device__ inline bool spin_until(int* flag, int target) {
   return false;
 }
 
-//   postB    LDS: [7 steps][64 lanes][re-plane operand, im-plane operand]  the second MFMA operands of each elimination
-//            step, as this wave uses them itself: panel_follow applies the same steps to the panel tiles of the column
-#define DGB_DOUBLES (7 * 64 * 2)
-__device__ __attribute__((always_inline)) inline void diag_D(d4 R, d4 I, double* post, double* postB, int* flag,
-                                                              int flag_base, double* dump, double* LdR, double* LdI,
-                                                              bool want_L) {
+__device__ __attribute__((always_inline)) inline void diag_D(d4 R, d4 I, double* post,
+                                                              double* postB,   // always nullptr; removing its dead store moves the tile kernel's spills
+                                                              int* flag, int flag_base, double* dump, double* LdR,
+                                                              double* LdI, bool want_L) {
   const int lane = threadIdx.x & 63, lq = lane >> 4, lcol = lane & 15;
   const bool hi = lq >= 2, odd = (lq & 1) != 0;   // which of (c1, c2) / (re, im) this lane's operand entry is
   const double sg = hi ? 1.0 : -1.0;
@@ -315,79 +313,6 @@ __device__ __attribute__((always_inline)) inline void diag_Z(const double* post,
     const double wr = (ZR[r] - (lr * wpr - li * wpi)) * io, wi = (ZI[r] - (lr * wpi + li * wpr)) * io;
     WtR[lcol * TL_LD + row] = wr;
     WtI[lcol * TL_LD + row] = -wi;
-  }
-}
-
-
-// ---- panel tiles without the inverse: a third role in the pipeline ------------------------------------------------
-// A panel tile A = T[P][jb] (P > jb) becomes L[P][jb] = A L_jj^-H.  Instead of waiting for W = L_jj^-1 and multiplying
-// (two workgroup barriers and the tail of diag_Z on the critical path of every tile row), the tile's owner APPLIES THE
-// ELIMINATION STEPS of the diagonal tile to it as diag_D posts them: step (j, j+1) is
-//     A[i][k] -= A[i][j] c1[k] + A[i][j+1] c2[k],   k >= j+2,
-// with exactly the (c1, c2) operand diag_D uses on its own tile (postB); the first operand is the tile's own column pair
-// (j, j+1), handed to the MFMA operand lanes through 64 doubles of wave-private LDS.  What is left are the raw columns
-// of each pivot block, finished with the block's 2x2 Cholesky factor [[l11, 0], [l21, l22]]:
-//     L[:, j] = A[:, j] / l11,   L[:, j+1] = (A[:, j+1] - L[:, j] conj(l21)) / l22        (lane ^ 1 holds the partner column).
-// The wave may arrive late (after its trailing updates): the posts of all steps stay in LDS until the stage ends.
-//   tab  64 doubles, fac 64 doubles of wave-private LDS
-__device__ inline void panel_block_factors(const double* post, double* fac) {   // lane b <-> pivot block b
-  const int lane = threadIdx.x & 63, b = lane & 7, j = 2 * b;
-  const double* rows = post + b * 64;
-  double p = rows[2 * j];
-  const double qr = rows[2 * (j + 1)], qi = -rows[2 * (j + 1) + 1], r = rows[32 + 2 * (j + 1)];   // q = T[j+1][j]
-  p = (p > 0.0) ? p : 1.0;
-  const double i11 = rsqrt_nr(p);
-  const double l21r = qr * i11, l21i = qi * i11;
-  double s22 = r - (l21r * l21r + l21i * l21i);
-  s22 = (s22 > 0.0) ? s22 : 1.0;
-  const double i22 = rsqrt_nr(s22);
-  // per column of the tile: {iota, lambda re, lambda im, kappa};  first column of a block {i11, 0, 0, 0}, second {i22, l21, i11}
-  fac[j * 4 + 0] = i11; fac[j * 4 + 1] = 0.0; fac[j * 4 + 2] = 0.0; fac[j * 4 + 3] = 0.0;
-  fac[j * 4 + 4] = i22; fac[j * 4 + 5] = l21r; fac[j * 4 + 6] = l21i; fac[j * 4 + 7] = i11;
-  __builtin_amdgcn_wave_barrier();
-}
-__device__ __attribute__((always_inline)) inline bool panel_follow(d4& R, d4& I, const double* postB, int* flag,
-                                                                    int flag_base, double* tab) {
-  const int lane = threadIdx.x & 63, lq = lane >> 4, lcol = lane & 15;
-  bool ok = true;
-#pragma clang loop unroll(disable)
-  for (int st = 0; st < 7; ++st) {
-    const int j = 2 * st;
-    // the tile's columns j, j+1 (lanes lcol = j, j+1; rows lq + 4 r) -> tab[row][column][re, im]
-    if ((lcol >> 1) == st) {
-      const int cb = (lcol & 1) * 2;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        tab[(lq + 4 * r) * 4 + cb] = R[r];
-        tab[(lq + 4 * r) * 4 + cb + 1] = I[r];
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // first operand: row i = lcol, k-slot lq = (a1 re, a1 im, a2 re, a2 im)
-    const double asel = tab[lcol * 4 + lq];
-    if (!spin_until(flag, flag_base + st + 1)) ok = false;
-    const double bre = postB[(st * 64 + lane) * 2], bim = postB[(st * 64 + lane) * 2 + 1];
-    R = __builtin_amdgcn_mfma_f64_16x16x4f64(asel, bre, R, 0, 0, 0);
-    I = __builtin_amdgcn_mfma_f64_16x16x4f64(asel, bim, I, 0, 0, 0);
-    __builtin_amdgcn_wave_barrier();   // (tab is rewritten by the next step)
-    (void)j;
-  }
-  return ok;
-}
-// finish the columns of a followed tile with the pivot blocks' own factors (panel_block_factors)
-__device__ __attribute__((always_inline)) inline void panel_finish(d4& R, d4& I, const double* fac) {
-  const int lcol = threadIdx.x & 15;
-  const double io = fac[lcol * 4], lr = fac[lcol * 4 + 1], li = fac[lcol * 4 + 2], ka = fac[lcol * 4 + 3];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    // partner column (lcol ^ 1) of the same row sits in lane ^ 1, same register
-    const double pr = __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(R[r]), 0x041F),
-                                       __builtin_amdgcn_ds_swizzle(__double2loint(R[r]), 0x041F));
-    const double pi = __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(I[r]), 0x041F),
-                                       __builtin_amdgcn_ds_swizzle(__double2loint(I[r]), 0x041F));
-    const double wpr = ka * pr, wpi = ka * pi;                  // L[:, j] of the block (zero for a first column)
-    const double xr = (R[r] - (wpr * lr + wpi * li)) * io, xi = (I[r] - (wpi * lr - wpr * li)) * io;
-    R[r] = xr; I[r] = xi;
   }
 }
 
@@ -531,14 +456,21 @@ __device__ __attribute__((always_inline)) inline void diag_Zr(const double* post
 //  576; 1 x 4: 581; 1 x 5: 578; 3 x 2: 584; 2 x 4 with four products — two accumulators per tile — 593; 2 x 4 with three: 622, spills)
 #define CH_NTMAX 96      // tile rows the work space is sized for (system order 16 * 96)
 __device__ inline size_t tile_off(int P, int Q) { return ((size_t)P * (P + 1) / 2 + Q) * 512; }
-#define CH_LDS_DOUBLES (2 * DG_TILE + 4 * TL_TILE + 16 * 2 * TL_TILE + 2 * 16 * CH_NTMAX + 32 + 16)   // (up to 16 waves)
+// (P, Q) of the lower-triangle tile number q, tiles numbered row by row: q = P (P + 1) / 2 + Q
+__device__ inline void tile_of(int q, int& P, int& Q) {
+  P = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
+  while ((P + 1) * (P + 2) / 2 <= q) ++P;
+  while (P * (P + 1) / 2 > q) --P;
+  Q = q - P * (P + 1) / 2;
+}
+#define CH_LDS_DOUBLES (2 * DG_TILE + 4 * TL_TILE + 16 * 2 * TL_TILE + 2 * 16 * CH_NTMAX + 32 + 16)   // (room for 16 waves; 8 use it)
 
 // One register group of the block update (phase (1) of tile_cholesky_memory): rows Pg (and Pg + 8 when RB = 2), the CH_W
 // columns of the block, T[P][Q0+c] -= sum_{j<Q0} L[P][j] L[Q0+c][j]^H.  The K-loop is branch-free: every one of the
 // RB x CH_W tiles is accumulated (a tile above the diagonal or beyond the last column costs its MFMAs — three tiles
 // per block at most — and is simply not written back), the sums of the three-product form are formed before the MFMAs so
 // that those issue back to back, and two k-steps per trip ping-pong between two operand sets (no register copies).
-template <int RB, int RS>   // RB rows Pg, Pg + RS
+template <int RB>   // RB rows Pg, Pg + 8
 __device__ __attribute__((always_inline)) inline void chol_block_unit(double* __restrict__ T, int Q0, int Wc, int Pg, int lq, int lcol) {
   d4 cR[RB][CH_W], cI[RB][CH_W], c3[RB][CH_W];
 #pragma unroll
@@ -552,7 +484,7 @@ __device__ __attribute__((always_inline)) inline void chol_block_unit(double* __
 #pragma unroll
   for (int c = 0; c < CH_W; ++c) Bp[c] = T + tile_off((c < Wc) ? (Q0 + c) : Q0, 0) + lq * 16 + lcol;
 #pragma unroll
-  for (int m = 0; m < RB; ++m) Ap[m] = T + tile_off(Pg + RS * m, 0) + lq * 16 + lcol;
+  for (int m = 0; m < RB; ++m) Ap[m] = T + tile_off(Pg + 8 * m, 0) + lq * 16 + lcol;
   // operand sets x (current k-step) and y (next): tile j = it/4 of a row starts 512 j doubles after tile 0, k-step
   // ks = it%4 is 64 doubles further; the requests of step it+1 are issued before the MFMAs of step it
   double xbR[CH_W], xbI[CH_W], xaR[RB], xaI[RB], ybR[CH_W], ybI[CH_W], yaR[RB], yaI[RB];
@@ -591,7 +523,7 @@ __device__ __attribute__((always_inline)) inline void chol_block_unit(double* __
   // eight values of a tile are requested together
 #pragma unroll
   for (int m = 0; m < RB; ++m) {
-    const int P = Pg + RS * m;
+    const int P = Pg + 8 * m;
 #pragma unroll
     for (int c = 0; c < CH_W; ++c) {
       if (c >= Wc || Q0 + c > P) continue;   // (tile above the diagonal / beyond the last column)
@@ -611,30 +543,20 @@ __device__ __attribute__((always_inline)) inline void chol_block_unit(double* __
 // T: tiles; WT: nt * 2*TL_TILE doubles (W^H of every diagonal tile); D0: 16*nt doubles (original diagonal, for the
 // collapsed-pivot check); lds: CH_LDS_DOUBLES; xs: 4*Kc doubles out (pair_n: column order of the caller, see the back
 // substitution)
-template <int NW>
 __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __restrict__ WT, double* __restrict__ D0,
                                             int nt, int Kc, int nbk, double* lds, double* xs, int* fault,
-                                            unsigned long long* dbg = nullptr, int pair_n = -1) {
+                                            unsigned long long* debug = nullptr, int pair_n = -1) {
   const int tid = threadIdx.x, lane = tid & 63, lcol = lane & 15, lq = lane >> 4;
   // phase stamps of thread 0, slots 4-9 (diagnostic build -DEAQHM_EXPERIMENT_STAMPS only — compiled in they cost the
   // large-frame kernel 5 % through its register allocation; tools/phase_probe_big.py)
-#ifndef EAQHM_EXPERIMENT_STAMPS
-#define CH_STAMP(ph) do { } while (0)
-#else
+#ifdef EAQHM_EXPERIMENT_STAMPS
+  unsigned long long* const dbg = debug;
   unsigned long long t_prev = (dbg && tid == 0) ? __builtin_amdgcn_s_memtime() : 0ull;
-#define CH_STAMP(ph)                                              \
-  do {                                                            \
-    if (dbg && tid == 0) {                                        \
-      const unsigned long long t_now = __builtin_amdgcn_s_memtime(); \
-      atomicAdd(dbg + (ph), t_now - t_prev);                      \
-      t_prev = t_now;                                             \
-    }                                                             \
-  } while (0)
+#else
+  constexpr unsigned long long* dbg = nullptr;
+  unsigned long long t_prev = 0;
 #endif
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int RB = (NW == 8) ? CH_RB : 1;   // tile rows per wave and register group of the block update (NW * RB rows per group)
-  constexpr int MB = (8 * CH_MB) / NW;        // tiles per wave, column and register group (48 rows per group)
-  static_assert(NW == 8 || NW == 12 || NW == 16, "tile_cholesky_memory: 8, 12 or 16 waves");
   double* Dc = lds;
   double* Zc = Dc + DG_TILE;
   double* WtR = Zc + DG_TILE;
@@ -642,7 +564,7 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
   double* LdR = WtI + TL_TILE;
   double* LdI = LdR + TL_TILE;
   double* trb = LdI + TL_TILE + (size_t)wave * 2 * TL_TILE;   // this wave's transposition buffer
-  double* zv = LdI + TL_TILE + NW * 2 * TL_TILE;
+  double* zv = LdI + TL_TILE + 8 * 2 * TL_TILE;
   double* xv = zv + 2 * 16 * CH_NTMAX;
   // original diagonal of the whole system (the collapsed-pivot check of diag_coop compares against it)
   for (int q = tid; q < 16 * nt; q += blockDim.x) {
@@ -653,42 +575,38 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
 
   for (int Q0 = 0; Q0 < nt; Q0 += CH_W) {
    const int Wc = (nt - Q0 < CH_W) ? (nt - Q0) : CH_W;
-#ifdef EAQHM_EXPERIMENT_NOBLOCKUPD
-   if (false) {
-#else
    if (Q0 > 0) {
-#endif
     // ---- (1) block update of columns Q0 .. Q0+Wc-1 from the columns before the block.  Rows P = Q0 + wave + 8 x,
     //      CH_RB of them per register group; three accumulators per tile, three real products per complex one.
-    const int ngr = (nt - Q0 + NW * RB - 1) / (NW * RB);
+    const int ngr = (nt - Q0 + 8 * CH_RB - 1) / (8 * CH_RB);
     for (int g = 0; g < ngr; ++g) {
-      const int Pg = Q0 + wave + NW * RB * g;
+      const int Pg = Q0 + wave + 8 * CH_RB * g;
       if (Pg >= nt) continue;
-      if (RB == 2 && Pg + NW < nt) chol_block_unit<2, NW>(T, Q0, Wc, Pg, lq, lcol);
-      else chol_block_unit<1, NW>(T, Q0, Wc, Pg, lq, lcol);
+      if (Pg + 8 < nt) chol_block_unit<2>(T, Q0, Wc, Pg, lq, lcol);
+      else chol_block_unit<1>(T, Q0, Wc, Pg, lq, lcol);
     }
     __syncthreads();   // the block's tiles are up to date with every column before the block
-    CH_STAMP(4);
+    LS_STAMP(4);
    }
    for (int Q = Q0; Q < Q0 + Wc; ++Q) {
-    // ---- (2) column Q: tiles P = Q + wave + NW m, in groups of MB per wave (registers); the first group holds the
+    // ---- (2) column Q: tiles P = Q + wave + 8 m, in groups of CH_MB per wave (registers); the first group holds the
     // diagonal tile, which is factorised before any panel tile is finished.  Only the block's own earlier columns
     // are still to be subtracted.
     const double* dref = D0 + 16 * Q;
-    const int ngroups = (nt - Q + NW * MB - 1) / (NW * MB);
+    const int ngroups = (nt - Q + 8 * CH_MB - 1) / (8 * CH_MB);
     for (int grp = 0; grp < ngroups; ++grp) {
-      const int Pb = Q + wave + NW * MB * grp;   // this wave's first tile of the group
-      d4 p1[MB], p2[MB], p3[MB];
+      const int Pb = Q + wave + 8 * CH_MB * grp;   // this wave's first tile of the group
+      d4 p1[CH_MB], p2[CH_MB], p3[CH_MB];
 #pragma unroll
-      for (int m = 0; m < MB; ++m) { p1[m] = (d4){0, 0, 0, 0}; p2[m] = (d4){0, 0, 0, 0}; p3[m] = (d4){0, 0, 0, 0}; }
+      for (int m = 0; m < CH_MB; ++m) { p1[m] = (d4){0, 0, 0, 0}; p2[m] = (d4){0, 0, 0, 0}; p3[m] = (d4){0, 0, 0, 0}; }
       for (int j = Q0; j < Q; ++j) {
         const double* Bt = T + tile_off(Q, j);
         double bR[4], bI[4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) { const int o = (4 * ks + lq) * 16 + lcol; bR[ks] = Bt[o]; bI[ks] = Bt[256 + o]; }
 #pragma unroll
-        for (int m = 0; m < MB; ++m) {
-          const int P = Pb + NW * m;
+        for (int m = 0; m < CH_MB; ++m) {
+          const int P = Pb + 8 * m;
           if (P >= nt) continue;
           const double* At = T + tile_off(P, j);
 #pragma unroll
@@ -701,7 +619,7 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
           }
         }
       }
-      CH_STAMP(14);
+      LS_STAMP(14);
       // C = T[P][Q] - sum:  Re -= P1 + P2,  Im += P3 + P1 - P2   (kept in p1 / p3).  The eight values of the NEXT tile are
       // requested before this one is combined: one exposed round trip per column instead of one per tile: 515 -> 500 ms.
       // (The same arrangement for the A tiles of the j-loop above measured slower, 504.7 vs 499.7 ms, and for the
@@ -714,10 +632,10 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
           for (int r = 0; r < 4; ++r) { oR[r] = Ct[64 * r]; oI[r] = Ct[256 + 64 * r]; }
         }
 #pragma unroll
-        for (int m = 0; m < MB; ++m) {
-          const int P = Pb + NW * m, Pn = P + NW;
+        for (int m = 0; m < CH_MB; ++m) {
+          const int P = Pb + 8 * m, Pn = P + 8;
           double nR[4] = {0, 0, 0, 0}, nI[4] = {0, 0, 0, 0};
-          if (m + 1 < MB && Pn < nt) {
+          if (m + 1 < CH_MB && Pn < nt) {
             const double* Ct = T + tile_off(Pn, Q) + lq * 16 + lcol;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { nR[r] = Ct[64 * r]; nI[r] = Ct[256 + 64 * r]; }
@@ -735,7 +653,7 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
           for (int r = 0; r < 4; ++r) { oR[r] = nR[r]; oI[r] = nI[r]; }
         }
       }
-      CH_STAMP(5);
+      LS_STAMP(5);
       if (grp == 0) {
         if (wave == 0) {   // the diagonal tile is this wave's first tile of the first group
 #pragma unroll
@@ -746,18 +664,16 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
         }
         diag_init(Zc, tid);
         __syncthreads();
-        CH_STAMP(15);
+        LS_STAMP(15);
         // the last tile row is the right-hand side (row 0) plus identity padding: no real unknown there
-#ifndef EAQHM_EXPERIMENT_NOCHOLDIAG
         diag_coop(Dc, Zc, WtR, WtI, LdR, LdI, tid, dref, (Q == nt - 1) ? 0 : 16, fault);   // ends with a barrier
-#endif
         for (int q = tid; q < 2 * TL_TILE; q += blockDim.x) WT[(size_t)Q * 2 * TL_TILE + q] = WtR[q];   // WtR | WtI contiguous
-        CH_STAMP(6);
+        LS_STAMP(6);
       }
       // panel tiles: X = C W^H (three real products), stored k-major
 #pragma unroll
-      for (int m = 0; m < MB; ++m) {
-        const int P = Pb + NW * m;
+      for (int m = 0; m < CH_MB; ++m) {
+        const int P = Pb + 8 * m;
         if (P >= nt || P == Q) continue;
         double* tr = trb;
         double* ti = trb + TL_TILE;
@@ -784,10 +700,10 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
           Lt[256 + lcol * 16 + lq + 4 * r] = x3[r] - (x1[r] + x2[r]);
         }
       }
-      CH_STAMP(7);
+      LS_STAMP(7);
     }
     __syncthreads();   // factor column visible to every wave; Dc / Wt reusable
-    CH_STAMP(8);
+    LS_STAMP(8);
    }
   }
 
@@ -839,8 +755,7 @@ __device__ inline void tile_cholesky_memory(double* __restrict__ T, double* __re
     }
     __syncthreads();
   }
-  CH_STAMP(9);
-#undef CH_STAMP
+  LS_STAMP(9);
 }
 
 }  // namespace eaqhm

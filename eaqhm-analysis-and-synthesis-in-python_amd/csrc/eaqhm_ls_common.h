@@ -67,6 +67,17 @@ __device__ inline T* uni(T* p) {
   return (T*)(((unsigned long long)hi << 32) | lo);
 }
 
+// Phase stamp of thread 0 (LsArgs::debug): adds the cycles since the previous stamp to slot ph.  Needs dbg, tid and
+// t_prev in scope; where dbg is a compile-time nullptr it compiles to nothing.
+#define LS_STAMP(ph)                                              \
+  do {                                                            \
+    if (dbg && tid == 0) {                                        \
+      const unsigned long long t_now = __builtin_amdgcn_s_memtime(); \
+      atomicAdd(dbg + (ph), t_now - t_prev);                      \
+      t_prev = t_now;                                             \
+    }                                                             \
+  } while (0)
+
 // seed-aware track access (functions.py:209-210; see eaqhm_frame_prep): a seeded row shows 140 Hz / 10e-4
 // in slot 0 to the frames at or after it, exactly like the sequential write of the reference
 __device__ inline double track_fm(const LsArgs& A, int k, long long t, int c, bool seeds) {

@@ -49,12 +49,6 @@ namespace eaqhm {
 #define A0_NS 7        // adaptation 0: tiles per wave of a real system of <= 7 tile rows (order Kc + 1 <= 104) on 4 waves
 #define A0_M 7
 
-__device__ inline void sys_tile_of(int x, int& P, int& Q) {
-  P = (int)((sqrtf(8.0f * (float)x + 1.0f) - 1.0f) * 0.5f);
-  while ((P + 1) * (P + 2) / 2 <= x) ++P;
-  while (P * (P + 1) / 2 > x) --P;
-  Q = x - P * (P + 1) / 2;
-}
 // (adaptation 0: closed-form Gramian and two real systems — eaqhm_ls_a0.h; table sizes for frames of this kernel)
 #define TZ_TB 104     // table stride: m = 0 .. 2 n <= 102
 #define TZ_NCH 8      // chunks of the t range (deterministic two-level summation)
@@ -125,14 +119,6 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
   const int lcol = lane & 15, lq = lane >> 4;
   unsigned long long* dbg = uni(A.debug);
   unsigned long long t_prev = 0;
-#define STAMP(ph)                                                   \
-  do {                                                              \
-    if (dbg && tid == 0) {                                          \
-      unsigned long long t_now = __builtin_amdgcn_s_memtime();      \
-      atomicAdd(dbg + (ph), t_now - t_prev);                        \
-      t_prev = t_now;                                               \
-    }                                                               \
-  } while (0)
 
   {
     const int n = uni(A.ncol[f]);
@@ -144,7 +130,6 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     const int nb = TW ? T : nt;                        // tile columns of the basis chunk
     const int ldx = (nb << 4) + ((nb & 1) ? 0 : 16);  // ≡ 16 (mod 32): MFMA operand reads hit disjoint bank halves
     const int npair = T * (T + 1) / 2;
-    const int ntiles = nt * (nt + 1) / 2;
     const int is = 2 * Kc - 16 * (nt - 1);  // position of the signal column inside the last tile row (2,6,10,14)
     const double f0 = uni(A.f0_stale);
     const int* mycols = uni(A.cols) + (size_t)f * uni(A.Kmax);
@@ -160,7 +145,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     __syncthreads();
     int* gappy = (int*)(masks + (size_t)52 * CI_NCH);   // [52] flags
     prepare_slots<CI_STRIDE, TL_WAVES>(A, Qs, Rs, Npad, ci, masks, gappy, mycols, n, N, mid, c, wl, seeds, lane, wave, CI_NCH);
-    STAMP(0);
+    LS_STAMP(0);
 
     // system tiles of this wave
     // Three real products per complex one need a third accumulator per tile: the first NM3 tiles of a wave.  Register
@@ -199,7 +184,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       const int x = wave + 8 * sl;
       glive[sl] = TW && x < npair;
       int I = 0, J = 0;
-      if (glive[sl]) sys_tile_of(x, I, J);
+      if (glive[sl]) tile_of(x, I, J);
       gI[sl] = __builtin_amdgcn_readfirstlane(I);
       gJ[sl] = __builtin_amdgcn_readfirstlane(J);
 #pragma unroll
@@ -291,9 +276,9 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           if (d > mid || t < 0) { Xre[row * ldx + col] = 0.0; Xim[row * ldx + col] = 0.0; }
         }
       }
-      STAMP(12);
+      LS_STAMP(12);
       __syncthreads();
-      STAMP(1);
+      LS_STAMP(1);
       const int pcs = (npairs - d0 < PE) ? (npairs - d0) : PE;   // sample pairs in this chunk
       const int ksl = (pcs + 1) >> 1;                             // k-steps (4 rows each) that hold samples
       if constexpr (TW > 0) {
@@ -378,7 +363,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         }
       }
       __syncthreads();
-      STAMP(2);
+      LS_STAMP(2);
     }
     if constexpr (TW == 0 && NM3 > 0) {   // Re = P1 + P2,  Im = aR bI - aI bR = P3 + P1 - P2
 #pragma unroll
@@ -432,7 +417,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           accR[sl][r] = vr; accI[sl][r] = vi;
         }
       }
-      STAMP(2);
+      LS_STAMP(2);
     }
 
     {
@@ -496,7 +481,6 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           mine = true;
         }
         // real unknowns: every position but, in the last tile, the signal column `is` and the padding behind it
-#ifndef EAQHM_EXPERIMENT_NODIAG   /* (timing experiment: what a frame costs without the diagonal steps; wrong results) */
         if (mine) {
           unsigned long long td0 = 0;
           unsigned long long* tlast = (unsigned long long*)(dflag + 2);   // (diagnostics: end of the previous diag_D)
@@ -511,10 +495,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             *tlast = td1;
           }
         }
-#else
-        if (mine) asm volatile("" ::"v"(Rt[0]), "v"(It[0]));
-#endif
-        STAMP(10);
+        LS_STAMP(10);
         if (jb > 0) {
 #pragma unroll
           for (int sl = 0; sl < NS; ++sl) {
@@ -522,16 +503,14 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             TRAILING_UPDATE(sl)
           }
         }
-        STAMP(8);
-#ifndef EAQHM_EXPERIMENT_NODIAG
+        LS_STAMP(8);
         // The helper wave builds the inverse (eaqhm_ls_tilemap.h) — AFTER its own trailing tiles: diag_D's posts wait for
         // it in LDS and it runs through them without the owner's pace, so its tiles are not what the stage ends on.
         if (!mine && wave == (int)TL_HELP[nt][jb])
           diag_Z(post, dflag, 16 * jb, zs, WtR + jb * TL_TILE, WtI + jb * TL_TILE, dorig + 16 * jb,
                  (jb == nt - 1) ? is : 16, uni(A.fault));
-#endif
         __syncthreads();  // (A) inverse of the diagonal tile published; every read of panel jb-1 done
-        STAMP(6);
+        LS_STAMP(6);
         // ---- panel tiles (P > jb, Q == jb): X = T W^H, published as Pan[P][k][row]
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
@@ -565,12 +544,12 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             ti[lcol * TL_LD + lq + 4 * r] = xi[r];
           }
         }
-        STAMP(7);
+        LS_STAMP(7);
         __syncthreads();  // (C) panel jb published
       }
 #undef TRAILING_UPDATE
       __syncthreads();  // end of factorisation
-      STAMP(3);
+      LS_STAMP(3);
 
       // ============ back substitution  L^H x = y,  y = conj(row `is` of the last tile row) ============
 #pragma unroll
@@ -631,11 +610,11 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         }
         __syncthreads();
       }
-      STAMP(4);
+      LS_STAMP(4);
     }
 
     write_record(A, xs, sh, mycols, f, n, inst, c, f0, seeds);
-    STAMP(5);
+    LS_STAMP(5);
   }
 }
 
