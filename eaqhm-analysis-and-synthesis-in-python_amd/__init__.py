@@ -7,4 +7,5 @@ from .functions import (eaQHMAnalysisAndSynthesis, eaQHMAnalysisAndSynthesisBatc
                         iqhmLS_complexamps, phase_integr_interpolation)
 from .hip import HipUnavailable, load_library  # noqa: F401
 from .structs import Deterministic, Frame  # noqa: F401
-from .model import SCALE_RANGE, contour_time_map, eaQHMSynthesis, scale_contour, unpack_model  # noqa: F401
+from .model import (SCALE_RANGE, contour_time_map, eaQHMSynthesis, model_envelope, scale_contour,  # noqa: F401
+                    unpack_model)

@@ -6,7 +6,9 @@ prints the per-adaptation SRER lines in the reference's format (functions.py:391
 `<name>_reconstructed.wav` as float32 next to the input (main.py:72).  With --time-scale / --pitch-scale it also
 resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wav` (float32).  --time-scale-curve /
 --pitch-scale-curve FILE take a breakpoint curve instead (two whitespace-separated columns, seconds and value; lines
-starting with # are comments), turned into a per-instant contour with model.scale_contour."""
+starting with # are comments), turned into a per-instant contour with model.scale_contour.  --formant-scale A /
+--formant-scale-curve FILE move the spectral envelope by A; they need the envelope, so either one with
+--no-envelope is an error."""
 import argparse
 
 import numpy as np
@@ -38,16 +40,26 @@ def main(argv=None):
     ps.add_argument("--pitch-scale", type=float, default=None, help="also write <name>_modified.wav: pitch x B")
     ps.add_argument("--pitch-scale-curve", default=None, metavar="FILE",
                     help="like --pitch-scale, with a curve: lines 'seconds value' (# comments)")
+    fs_ = ap.add_mutually_exclusive_group()
+    fs_.add_argument("--formant-scale", type=float, default=None,
+                     help="also write <name>_modified.wav: spectral envelope (formants) x A")
+    fs_.add_argument("--formant-scale-curve", default=None, metavar="FILE",
+                     help="like --formant-scale, with a curve: lines 'seconds value' (# comments)")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
     a = ap.parse_args(argv)
-    modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve))
+    if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None):
+        ap.error("--formant-scale / --formant-scale-curve scale the spectral envelope: not with --no-envelope")
+    modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
+                                         a.formant_scale, a.formant_scale_curve))
     curves = {}
     if modify:   # reject bad scales and curves before the analysis runs
         from .model import _scale
         _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
         _scale(1.0 if a.pitch_scale is None else a.pitch_scale, "--pitch-scale")
-        for key, path in (("time", a.time_scale_curve), ("pitch", a.pitch_scale_curve)):
+        _scale(1.0 if a.formant_scale is None else a.formant_scale, "--formant-scale")
+        for key, path in (("time", a.time_scale_curve), ("pitch", a.pitch_scale_curve),
+                          ("formant", a.formant_scale_curve)):
             if path is not None:
                 curves[key] = read_scale_curve(path, "--%s-scale-curve %s" % (key, path))
     gender = a.gender
@@ -72,8 +84,11 @@ def main(argv=None):
                 rho = scale_contour(det, fs, *curves["time"])
             if "pitch" in curves:
                 beta = scale_contour(det, fs, *curves["pitch"])
+            alpha = 1.0 if a.formant_scale is None else a.formant_scale
+            if "formant" in curves:
+                alpha = scale_contour(det, fs, *curves["formant"])
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
-                                   preserve_envelope=not a.no_envelope)
+                                   preserve_envelope=not a.no_envelope, formant_scale=alpha)
             out = a.wav[:len(a.wav) - 4] + "_modified.wav"
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)

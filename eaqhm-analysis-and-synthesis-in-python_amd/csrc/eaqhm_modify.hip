@@ -15,6 +15,9 @@
 // Time and pitch scale contours use eaqhm_modify_prep_curve_kernel (the prep body with beta per
 // instant and the phase increments weighted by g_j), the same scan and carry kernels, and
 // eaqhm_modify_eval_curve_kernel (the eval body with the cumulative time map C in place of tau = n'/rho).
+// A formant scale alpha uses eaqhm_modify_prep_formant_kernel / eaqhm_modify_prep_formant_curve_kernel
+// (the prep body with alpha per instant and the envelope nodes ordered in LDS by a rank count over LDS) ahead of the
+// same scan, carry and eval kernels; eaqhm_model_envelope_kernel reads the envelope itself out on a frequency grid.
 #include "eaqhm_common.h"
 #include "eaqhm_pieces.h"
 
@@ -82,6 +85,100 @@ __device__ inline void interval_close(const SlotT& S, const FmPiece& P, int j, i
 //   P0[i][k]  ph_i at the first knot of a run (code != 0, previous instant inactive), else 0.
 // The body is in eaqhm_modify_body.inc (compiled below once per variant).
 #define PREP_WAVES 4
+
+// ------------------------------------------------------------------------------------------------
+// Envelope nodes in LDS (the formant prep kernels and eaqhm_model_envelope_kernel).  One wave per
+// instant; the calls are wave-uniform and separated by a barrier:
+//   env_compact  the instant's active slots (am != 0, f > 0) in slot order: their frequencies to sf[0, nn)
+//   env_rank     rank of each active slot in (f, k) order, counted over sf (LDS reads only; slot order is compacted
+//                order, so k breaks ties as it does in eaqhm_modify_prep_kernel): nf[rank] = f, nv[rank] = ln am
+//   env_at       E(q) on the sorted nodes: flat outside, the first of tied nodes at a node's own frequency, linear
+//                between (the expression of eaqhm_modify_prep_kernel's lookup)
+__device__ inline int env_compact(const double* row, int K, int lane, double* sf) {
+  int base = 0;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane;
+    const bool act = k < K && row[k] != 0.0 && row[K + k] > 0.0;
+    const unsigned long long m = __ballot(act);
+    if (act) sf[base + __popcll(m & ((1ull << lane) - 1ull))] = row[K + k];
+    base += __popcll(m);
+  }
+  return base;
+}
+
+__device__ inline void env_rank(const double* row, int K, int lane, const double* sf, int nn, double* nf,
+                                double* nv) {
+  int base = 0;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane;
+    const bool act = k < K && row[k] != 0.0 && row[K + k] > 0.0;
+    const unsigned long long m = __ballot(act);
+    if (act) {
+      const int p = base + __popcll(m & ((1ull << lane) - 1ull));
+      const double fk = sf[p];
+      int rank = 0;
+      for (int q = 0; q < nn; ++q) {   // every lane reads the same sf[q]: an LDS broadcast
+        const double fq = sf[q];
+        rank += (fq < fk || (fq == fk && q < p)) ? 1 : 0;
+      }
+      nf[rank] = fk;
+      nv[rank] = log(row[k]);
+    }
+    base += __popcll(m);
+  }
+}
+
+__device__ inline double env_at(const double* nf, const double* nv, int nn, double q) {
+  int lo = 0, hi = nn;   // first node with f >= q
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (nf[mid] < q) lo = mid + 1; else hi = mid;
+  }
+  double E;
+  if (lo < nn && nf[lo] == q) E = nv[lo];
+  else if (lo == 0) E = nv[0];
+  else if (lo == nn) E = nv[nn - 1];
+  else E = nv[lo - 1] + (nv[lo] - nv[lo - 1]) * ((q - nf[lo - 1]) / (nf[lo] - nf[lo - 1]));
+  return E;
+}
+
+// ---- the formant prep kernels: the prep body alone, scalar beta and beta / gain per instant.
+// They and the envelope kernel come ahead of the scan kernel, so that in the device assembly every kernel that existed
+// before them keeps its neighbours (tools/isa_diff.py compares each function with the text up to the next one).
+#define EAQHM_MODIFY_FORMANT 1
+#define EAQHM_MODIFY_CURVE 0
+#include "eaqhm_modify_body.inc"
+#undef EAQHM_MODIFY_CURVE
+#define EAQHM_MODIFY_CURVE 1
+#include "eaqhm_modify_body.inc"
+#undef EAQHM_MODIFY_CURVE
+#undef EAQHM_MODIFY_FORMANT
+
+// ------------------------------------------------------------------------------------------------
+// Envelope readout: one wave per instant i (four per block), the nodes ordered as in the formant prep,
+// lanes over the frequency grid: out[i][t] = E_i(freqs[t] / alpha_i), natural-log amplitude, not muted; -inf for an
+// instant without active slots.
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_model_envelope_kernel(const double* __restrict__ records, int No_ti, int K, const double* __restrict__ alphav,
+                                const double* __restrict__ freqs, int F, double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * PREP_WAVES + w;
+  double* sf = lds + (size_t)w * 3 * K;
+  double* nf = sf + K;
+  double* nv = nf + K;
+  const bool live = i < No_ti;
+  const double* row = records + (size_t)(live ? i : 0) * (3 * K + 1);
+  int nn = 0;
+  if (live) nn = env_compact(row, K, lane, sf);
+  __syncthreads();
+  if (live) env_rank(row, K, lane, sf, nn, nf, nv);
+  __syncthreads();
+  if (!live) return;
+  const double alpha = alphav[i];
+  for (int t = lane; t < F; t += 64)
+    out[(size_t)i * F + t] = (nn > 0) ? env_at(nf, nv, nn, freqs[t] / alpha) : -INFINITY;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Segmented scan of dR along the instants, per slot.  A segment starts at every knot whose interval to the previous
@@ -235,6 +332,7 @@ struct CurveMap {
 
 
 // ---- the scalar kernels: tau = n'/rho, phase weight beta rho
+#define EAQHM_MODIFY_FORMANT 0
 #define EAQHM_MODIFY_CURVE 0
 #define MAP_INIT
 #define MAP_LOCATE(n, j, r) locate(n, E.rho, D, j, r)
@@ -293,6 +391,7 @@ struct CurveMap {
 #undef MAP_ISO_RANGE
 #undef MAP_ISO_AT
 #undef MAP_TAU
+#undef EAQHM_MODIFY_FORMANT
 }  // namespace eaqhm
 
 using namespace eaqhm;
@@ -428,6 +527,66 @@ extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, c
                                    (int)lds_bytes));
   hipLaunchKernelGGL(eaqhm_modify_eval_curve_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu,
                      TBS, NR);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+// ---- formant scale: alpha[No_ti] per instant, the envelope nodes ordered in LDS
+// LDS of the formant prep and envelope kernels: staged frequencies, sorted frequencies and log amplitudes per wave
+static size_t formant_lds_bytes(int Kmax) { return (size_t)PREP_WAVES * 3 * Kmax * sizeof(double); }
+static const size_t FORMANT_LDS_MAX = 160 * 1024;
+
+extern "C" int eaqhm_modify_prep_formant(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                         int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta,
+                                         const double* alpha, double* amp, double* R, double* ph0) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !code || !mom || !alpha || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 ||
+      !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: bad argument");
+  if (!finite_pos(beta)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: beta must be finite and > 0");
+  const size_t lds = formant_lds_bytes(Kmax);
+  if (lds > FORMANT_LDS_MAX)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: Kmax too large for the envelope nodes");
+  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_formant_kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(eaqhm_modify_prep_formant_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, alpha, amp, R, ph0);
+  HIP_TRY(ctx, hipGetLastError());
+  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
+}
+
+extern "C" int eaqhm_modify_prep_formant_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
+                                               const double* mom, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
+                                               const double* beta, const double* gain, const double* alpha, double* amp,
+                                               double* R, double* ph0) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !code || !mom || !beta || !gain || !alpha || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 ||
+      step <= 0 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant_curve: bad argument");
+  const size_t lds = formant_lds_bytes(Kmax);
+  if (lds > FORMANT_LDS_MAX)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant_curve: Kmax too large for the envelope nodes");
+  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_formant_curve_kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(eaqhm_modify_prep_formant_curve_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, gain, alpha, amp, R, ph0);
+  HIP_TRY(ctx, hipGetLastError());
+  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
+}
+
+extern "C" int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax,
+                                    const double* alpha, const double* freqs, int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !alpha || !freqs || !out || No_ti < 4 || Kmax <= 0 || F <= 0)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope: bad argument");
+  const size_t lds = formant_lds_bytes(Kmax);
+  if (lds > FORMANT_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope: Kmax too large for the envelope nodes");
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_envelope_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_model_envelope_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, alpha, freqs, (int)F, out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -40,6 +40,9 @@ SYMBOLS = (
     ("eaqhm_modify_prep_curve", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P]),
     ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
                                             _I64, _I64, _P]),
+    ("eaqhm_modify_prep_formant", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P]),
+    ("eaqhm_modify_prep_formant_curve", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P]),
+    ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
 )
 
 
@@ -198,6 +201,19 @@ class Context:
         self._ck(self.lib.eaqhm_modify_synth_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
                                                    _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C), _ptr(rate),
                                                    _ptr(gain), float(rate_min), L_out, t_lo, t_hi, _ptr(out)))
+
+    def modify_prep_formant(self, records, code, mom, No_ti, Kmax, step, fs, beta, alpha, amp, R, ph0):
+        self._ck(self.lib.eaqhm_modify_prep_formant(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step,
+                                                    float(fs), float(beta), _ptr(alpha), _ptr(amp), _ptr(R), _ptr(ph0)))
+
+    def modify_prep_formant_curve(self, records, code, mom, No_ti, Kmax, step, fs, beta, gain, alpha, amp, R, ph0):
+        self._ck(self.lib.eaqhm_modify_prep_formant_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax,
+                                                          step, float(fs), _ptr(beta), _ptr(gain), _ptr(alpha),
+                                                          _ptr(amp), _ptr(R), _ptr(ph0)))
+
+    def model_envelope(self, records, No_ti, Kmax, alpha, freqs, F, out):
+        self._ck(self.lib.eaqhm_model_envelope(self.h, _ptr(records), No_ti, Kmax, _ptr(alpha), _ptr(freqs), F,
+                                               _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

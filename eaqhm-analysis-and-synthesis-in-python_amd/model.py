@@ -2,15 +2,18 @@
 
     unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
     eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   *, device_index=0) -> float64[L_out]
+                   formant_scale=1.0, *, device_index=0) -> float64[L_out]
+    model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[No_ti, len(freqs)]
     scale_contour(DetComponents, fs, times_s, values) -> float64[No_ti]
     contour_time_map(rho, beta, step, length) -> dict(rate, gain, C, L_out, rate_min)
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
-also be a contour, one value per analysis instant (§9.1).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
-eaqhm_modify_prep / eaqhm_modify_synth, or their _curve variants for contours); there is no CPU path.
+also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
+(§9.2).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep / eaqhm_modify_synth, or their _curve
+variants for contours, eaqhm_modify_prep_formant[_curve] for a formant scale, eaqhm_model_envelope); there is no CPU
+path.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -210,6 +213,11 @@ def check_arguments(model, fs, length, time_scale, pitch_scale):
     length = int(length)
     if length < int(model["ti"][-1]) + 1:
         raise ValueError("length (%d) must be >= the last instant + 1 (%d)" % (length, int(model["ti"][-1]) + 1))
+    _check_records(model)
+    return rho, beta, fs, length
+
+
+def _check_records(model):
     rec = model["records"]
     if len(rec) < 4:
         raise ValueError("the model needs at least 4 analysis instants (the cubic interpolation of the tracks)")
@@ -217,7 +225,6 @@ def check_arguments(model, fs, length, time_scale, pitch_scale):
         raise ValueError("the model holds non-finite values")
     if np.any(rec[:, :model["Kmax"]] < 0):
         raise ValueError("amplitudes must be >= 0 (the model holds |a_k|)")
-    return rho, beta, fs, length
 
 
 def check_contour_arguments(model, fs, length, time_scale, pitch_scale):
@@ -230,8 +237,22 @@ def check_contour_arguments(model, fs, length, time_scale, pitch_scale):
     return rho, beta, fs, length
 
 
-def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True, *,
-                   device_index=0, _ranges=None):
+def check_formant_scale(model, formant_scale, preserve_envelope):
+    """Validates a formant scale (no device work): returns alpha as a float, or as float64[No_ti] for a contour.
+    formant_scale != 1 needs the envelope it scales (preserve_envelope=True)."""
+    if _is_contour(formant_scale):
+        alpha = _contour(formant_scale, "formant_scale", len(model["ti"]))
+        scaled = bool(np.any(alpha != 1.0))
+    else:
+        alpha = _scale(formant_scale, "formant_scale")
+        scaled = alpha != 1.0
+    if scaled and not preserve_envelope:
+        raise ValueError("formant_scale != 1 needs preserve_envelope=True: there is no envelope to scale")
+    return alpha
+
+
+def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
+                   formant_scale=1.0, *, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -243,14 +264,23 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     (§9.1): interval j between two instants is stretched by the mean of their time scales and its frequencies are
     multiplied by the mean of their pitch scales; the length is contour_time_map(...)["L_out"].
 
+    `formant_scale` (alpha, in [0.25, 4]; a number or a contour like the others) multiplies the frequencies of the
+    spectral envelope: a formant at F in the model sits at alpha * F in the output, whatever the pitch does (§9.2).
+    Each partial's amplitude is read off its instant's envelope at (pitch_scale * f) / alpha; phases, durations and
+    the length do not change.  It needs preserve_envelope=True.  A formant contour runs the contour path; the number 1
+    leaves the result exactly as it is without a formant scale.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     model = unpack_model(DetComponents)
-    contour = _is_contour(time_scale) or _is_contour(pitch_scale)
+    contour = _is_contour(time_scale) or _is_contour(pitch_scale) or _is_contour(formant_scale)
     if contour:
         rho, beta, fs, length = check_contour_arguments(model, fs, length, time_scale, pitch_scale)
     else:
         rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
+    alpha = check_formant_scale(model, formant_scale, preserve_envelope)
+    # the formant prep runs for a formant contour or a number != 1; without the envelope alpha is 1 throughout
+    formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
@@ -277,12 +307,66 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     if contour:
         beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
                                        for x in (beta, tm["gain"], tm["C"], tm["rate"]))
-        c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, preserve_envelope, amp, R, ph0)
+        if formant:
+            alpha_d = torch.as_tensor(np.array(np.broadcast_to(alpha, (n,)), dtype=np.float64), device=dev)
+            c.modify_prep_formant_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, alpha_d, amp, R, ph0)
+        else:
+            c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, preserve_envelope, amp, R, ph0)
         for t_lo, t_hi in ranges:
             c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"], L_out,
                                  t_lo, t_hi, out)
     else:
-        c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
+        if formant:
+            alpha_d = torch.full((n,), alpha, dtype=torch.float64, device=dev)
+            c.modify_prep_formant(rec, code, mom, n, K, D, fs, beta, alpha_d, amp, R, ph0)
+        else:
+            c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
         for t_lo, t_hi in ranges:
             c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
+    return out.cpu().numpy()
+
+
+def check_envelope_arguments(model, fs, freqs, formant_scale):
+    """Validates everything model_envelope gets (no device work): returns (alpha float64[No_ti], freqs float64[F])."""
+    try:
+        fs = float(fs)
+    except (TypeError, ValueError):
+        raise ValueError("fs must be a number") from None
+    if not np.isfinite(fs) or fs <= 0:
+        raise ValueError("fs must be finite and > 0")
+    f = _numeric_1d(freqs, "freqs")
+    if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
+        raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
+    if len(model["records"]) < 4:
+        raise ValueError("the model needs at least 4 analysis instants")
+    _check_records(model)
+    alpha = check_formant_scale(model, formant_scale, True)
+    return np.array(np.broadcast_to(alpha, (len(model["ti"]),)), dtype=np.float64), f
+
+
+def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0):
+    """The log-amplitude envelope of every analysis instant on a frequency grid: out[i, t] = E_i(freqs[t] / alpha_i)
+    (DESIGN.md §9.2), the natural log of the amplitude |a|, not muted at Nyquist.  E_i interpolates ln |a| linearly
+    between the instant's active partials ordered by frequency and is flat outside them; rows of instants without
+    active partials are -inf.  With formant_scale = alpha (a number or one value per instant, in [0.25, 4]) it is the
+    envelope eaQHMSynthesis reads the amplitudes from at that formant scale.  `freqs` (Hz) is 1-D, finite and >= 0.
+
+    The result takes No_ti * len(freqs) * 8 bytes, once on the device and once on the host (61 MB for a 60 s model at
+    16 kHz, step 15, 64 000 instants, on a 120-point grid).  Returns float64[No_ti, len(freqs)]."""
+    model = unpack_model(DetComponents)
+    alpha, f = check_envelope_arguments(model, fs, freqs, formant_scale)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    rec_h = model["records"]
+    n, K = rec_h.shape[0], model["Kmax"]
+    if K == 0:                                   # no slot at all: one empty slot, every row -inf
+        rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
+        K = 1
+    rec = torch.as_tensor(np.ascontiguousarray(rec_h), device=dev)
+    alpha_d = torch.as_tensor(np.ascontiguousarray(alpha), device=dev)
+    f_d = torch.as_tensor(np.ascontiguousarray(f), device=dev)
+    out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)
+    c.model_envelope(rec, n, K, alpha_d, f_d, len(f), out)
     return out.cpu().numpy()

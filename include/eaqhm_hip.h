@@ -216,6 +216,31 @@ int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_
                              int32_t step, double fs, const double* C, const double* rate, const double* gain,
                              double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
 
+/* formant scale: alpha_i per analysis instant moves the spectral envelope (additive to ABI 3) ----------------------
+ * The definition is DESIGN.md §9.2.  E_i is the piecewise-linear envelope of ln |a| over the instant's active slots
+ * sorted by (f, k) (flat outside the end nodes, the first of tied nodes at a node's own frequency); a feature at F in
+ * the model sits at alpha_i F after the scale.  The nodes are ordered in LDS (3 * Kmax doubles per instant, four
+ * instants per block).  alpha is a device array of No_ti values, each finite and > 0 (the caller's).
+ * eaqhm_modify_prep_formant: as eaqhm_modify_prep with the envelope always on and
+ *   amp        beta == 1 and alpha_i == 1: |a|; otherwise exp(E_i((beta * f) / alpha_i)), zero where beta*f >= fs/2
+ *              (the output frequency; alpha plays no part) or the slot is inactive.  R and ph0 as eaqhm_modify_prep.
+ *   The synthesis is eaqhm_modify_synth's.
+ * eaqhm_modify_prep_formant_curve: the same with beta[No_ti] and gain[No_ti-1] as eaqhm_modify_prep_curve; the
+ *   synthesis is eaqhm_modify_synth_curve's.
+ * eaqhm_model_envelope (kernel: one wave per instant, lanes over the grid)
+ *   out        double[No_ti][F]  E_i(freqs[t] / alpha_i), the natural-log amplitude, not muted; -inf on the rows of
+ *                                instants without active slots.  freqs[F] is the caller's grid (device, finite, >= 0).
+ * EAQHM_EINVAL for null pointers, No_ti < 4, beta <= 0 or not finite, F <= 0, and Kmax beyond the LDS budget
+ * (Kmax > 1706).                                                                                                   */
+int eaqhm_modify_prep_formant(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                              int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta, const double* alpha,
+                              double* amp, double* R, double* ph0);
+int eaqhm_modify_prep_formant_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                    int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
+                                    const double* gain, const double* alpha, double* amp, double* R, double* ph0);
+int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* alpha,
+                         const double* freqs, int32_t F, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,16 @@
 """Resynthesis from the model: device time of eaqhm_modify_prep (prep + scan) and eaqhm_modify_synth against
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
-    python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--out FILE]
+    python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
+                                          [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour kernels (eaqhm_modify_prep_curve / _synth_curve,
 DESIGN.md §9.1): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with beta ramping 0.85 -> 1.2,
-and both varying; eval_ms_per_msample normalises the eval time by the output length.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
+and both varying; eval_ms_per_msample normalises the eval time by the output length.  --formant adds the formant
+prep kernels (eaqhm_modify_prep_formant / _curve) at rho = 1: alpha in {0.85, 1.2} x beta in {1, 1.25}
+with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with eaqhm_modify_synth_curve; ratio_to_scalar compares each
+with the scalar path at the same beta (envelope on).  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
 import json
@@ -54,11 +58,11 @@ def timed(torch, fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def probe(workload, reps, contours=False):
-    import torch
+def prepare(torch, det, fs, L, reps):
+    """Device state of one model: records, codes and moments, the prep outputs, and the time of eaqhm_eval_synth on the
+    same records (synthesis + SRER, no track output: what the analysis's last pass runs)."""
     from eaqhm_amd.functions import _ctx
     from eaqhm_amd.model import unpack_model
-    fs, L, det, arrays, t_pack = analyse(workload)
     t = time.perf_counter()
     m = unpack_model(det)
     t_unpack = time.perf_counter() - t
@@ -71,7 +75,6 @@ def probe(workload, reps, contours=False):
     mom = torch.empty(n * (K + 1), dtype=torch.float64, device=dev)
     amp, R, ph0 = (torch.empty(n * K, dtype=torch.float64, device=dev) for _ in range(3))
     c.spline_solve(rec, n, K, D, code, mom)
-    # eaqhm_eval_synth on the same records: synthesis + SRER, no track output (what the analysis's last pass runs)
     target = torch.zeros(L, dtype=torch.float64, device=dev)
     s_hat = torch.empty(L, dtype=torch.float64, device=dev)
     ph_knot = torch.empty(n * K, dtype=torch.float64, device=dev)
@@ -79,6 +82,17 @@ def probe(workload, reps, contours=False):
     sums = torch.empty(16, dtype=torch.float64, device=dev)
     t_eval = timed(torch, lambda: c.eval_synth(rec, code, mom, n, K, D, fs, L, 0, L, 0, L, target, 1.0, None, None, 0, 0,
                                                ph_knot, s_hat, partials, sums), reps)
+    return dict(c=c, rec=rec, code=code, mom=mom, amp=amp, R=R, ph0=ph0, n=n, K=K, D=D, fs=fs, L=L, t_eval=t_eval,
+                t_unpack=t_unpack)
+
+
+def probe(workload, reps, contours=False, formant=False):
+    import torch
+    fs, L, det, arrays, t_pack = analyse(workload)
+    st = prepare(torch, det, fs, L, reps)
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, t_eval, t_unpack = st["n"], st["K"], st["D"], st["t_eval"], st["t_unpack"]
+    dev = c.device
     rows = []
     for beta in (1.0, 1.25):
         t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0), reps)
@@ -96,7 +110,52 @@ def probe(workload, reps, contours=False):
                pack_results_s=round(t_pack, 3), unpack_model_s=round(t_unpack, 3), settings=rows)
     if contours:
         res["contours"] = probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval, reps)
+    if formant:
+        res["formant"] = formant_rows(torch, st, reps)
     return res
+
+
+def formant_rows(torch, st, reps):
+    """rho = 1: the scalar path (alpha = 1, envelope on) and the formant path at alpha in {0.85, 1.2} for beta in
+    {1, 1.25}, and an alpha ramp 0.85 -> 1.2 through the contour kernels (rho = beta = 1)."""
+    from eaqhm_amd.model import contour_time_map
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, fs, L, t_eval = st["n"], st["K"], st["D"], st["fs"], st["L"], st["t_eval"]
+    dev = c.device
+    out = torch.empty(L, dtype=torch.float64, device=dev)
+    rows = []
+
+    def row(setting, t_prep, t_syn, t_scalar):
+        total = t_prep + t_syn
+        return dict(setting=setting, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3), total_ms=round(total, 3),
+                    ratio_to_eval_synth=round(total / t_eval, 3), ratio_to_scalar=round(total / t_scalar, 3))
+
+    for beta in (1.0, 1.25):
+        t_sp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0), reps)
+        t_syn = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 1.0, beta, L, 0, L, out),
+                      reps)
+        t_scalar = t_sp + t_syn
+        rows.append(row("scalar_beta%g" % beta, t_sp, t_syn, t_scalar))
+        for alpha in (0.85, 1.2):
+            alpha_d = torch.full((n,), alpha, dtype=torch.float64, device=dev)
+            t_fp = timed(torch, lambda: c.modify_prep_formant(rec, code, mom, n, K, D, fs, beta, alpha_d, amp, R, ph0),
+                         reps)
+            t_fs = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 1.0, beta, L, 0, L,
+                                                       out), reps)
+            rows.append(row("alpha%g_beta%g" % (alpha, beta), t_fp, t_fs, t_scalar))
+    t = np.arange(n) * D / fs
+    one = np.ones(n)
+    ramp = np.interp(t, [0.0, t[-1]], [0.85, 1.2])
+    tm = contour_time_map(one, one, D, L)
+    one_d, gain_d, C_d, rate_d, alpha_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                                           for x in (one, tm["gain"], tm["C"], tm["rate"], ramp))
+    outc = torch.empty(tm["L_out"], dtype=torch.float64, device=dev)
+    t_fp = timed(torch, lambda: c.modify_prep_formant_curve(rec, code, mom, n, K, D, fs, one_d, gain_d, alpha_d, amp, R,
+                                                            ph0), reps)
+    t_fs = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
+                                                     tm["rate_min"], tm["L_out"], 0, tm["L_out"], outc), reps)
+    rows.append(row("alpha_ramp_contour", t_fp, t_fs, rows[0]["total_ms"]))
+    return rows
 
 
 def probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval, reps):
@@ -131,9 +190,10 @@ def main():
     ap.add_argument("--workloads", default="synth16k_60s,synth48k_60s")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--contours", action="store_true", help="also time the contour kernels")
+    ap.add_argument("--formant", action="store_true", help="also time the formant prep kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps, a.contours) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours, a.formant) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
