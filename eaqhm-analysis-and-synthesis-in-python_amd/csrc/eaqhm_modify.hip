@@ -2,9 +2,11 @@
 // gfx950 (MI355X) only, FP64.  The definition is in DESIGN.md ("Resynthesis from the model"); at rho = beta = 1 it
 // reproduces eaqhm_eval_kernel's synthesis (functions.py:337-385, :537-575) of the same records.
 //
-//   eaqhm_modify_prep_kernel   one wave per instant: the pitch-scaled knot amplitudes A' (log-amplitude envelope of
-//                              the instant's active slots, sorted in LDS, one binary search per slot) and the
-//                              unwrapped phase increment Delta of every in-run interval that starts at the instant.
+//   eaqhm_modify_prep_kernel   one wave per instant: the knot amplitudes A' (log-amplitude envelope of the instant's
+//                              active slots, ordered in LDS, read at beta f / alpha with one binary search per slot)
+//                              and the unwrapped phase increment Delta of every in-run interval that starts at the
+//                              instant.  beta is per instant; the gain g_j of the contours and the
+//                              formant scale alpha (§9.2) are optional.
 //   eaqhm_modify_scan_kernel   segmented prefix sum of Delta along the instants of each slot (chunks of SCAN_CH
 //                              instants: pass 0 chunk aggregates, pass 1 applies the carries), giving the unwrapped
 //                              knot phase R and the phase of each run's first knot.
@@ -12,12 +14,9 @@
 //   eaqhm_modify_eval_kernel   blocks of output samples: the touched intervals are integrated once into LDS (as
 //                              stage 1 of eaqhm_eval_kernel), then per (sample, slot) A * cos(phase), per sample the
 //                              a0 spline and the sum over slots in slot order.
-// Time and pitch scale contours use eaqhm_modify_prep_curve_kernel (the prep body with beta per
-// instant and the phase increments weighted by g_j), the same scan and carry kernels, and
-// eaqhm_modify_eval_curve_kernel (the eval body with the cumulative time map C in place of tau = n'/rho).
-// A formant scale alpha uses eaqhm_modify_prep_formant_kernel / eaqhm_modify_prep_formant_curve_kernel
-// (the prep body with alpha per instant and the envelope nodes ordered in LDS by a rank count over LDS) ahead of the
-// same scan, carry and eval kernels; eaqhm_model_envelope_kernel reads the envelope itself out on a frequency grid.
+//   eaqhm_modify_eval_curve_kernel  the eval body with the cumulative time map C of the contours in place of
+//                              tau = n'/rho (eaqhm_modify_body.inc holds the body of both).
+//   eaqhm_model_envelope_kernel  reads the envelope itself out on a frequency grid.
 #include "eaqhm_common.h"
 #include "eaqhm_pieces.h"
 
@@ -76,24 +75,16 @@ __device__ inline void interval_close(const SlotT& S, const FmPiece& P, int j, i
   emis = e - 2.0 * M_PI * Mr;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Prep: one wave per instant i (four per block).
-//   A'[i][k]  beta == 1: am.  Otherwise, with the envelope, exp(E_i(beta f)) where E_i interpolates ln am linearly over
-//             the instant's active slots sorted by (f, k) (flat outside, the first of tied nodes at a node's own
-//             frequency), without it am; both muted where beta f >= fs/2.
-//   dR[i+1][k] Delta of the interval (i, i+1) when it is in a run: (ph_{i+1} - ph_i) + 2 pi Mr.  Other rows 0.
-//   P0[i][k]  ph_i at the first knot of a run (code != 0, previous instant inactive), else 0.
-// The body is in eaqhm_modify_body.inc (compiled below once per variant).
 #define PREP_WAVES 4
 
 // ------------------------------------------------------------------------------------------------
-// Envelope nodes in LDS (the formant prep kernels and eaqhm_model_envelope_kernel).  One wave per
+// Envelope nodes in LDS (eaqhm_modify_prep_kernel and eaqhm_model_envelope_kernel).  One wave per
 // instant; the calls are wave-uniform and separated by a barrier:
 //   env_compact  the instant's active slots (am != 0, f > 0) in slot order: their frequencies to sf[0, nn)
 //   env_rank     rank of each active slot in (f, k) order, counted over sf (LDS reads only; slot order is compacted
-//                order, so k breaks ties as it does in eaqhm_modify_prep_kernel): nf[rank] = f, nv[rank] = ln am
+//                order, so k breaks ties): nf[rank] = f, nv[rank] = ln am
 //   env_at       E(q) on the sorted nodes: flat outside, the first of tied nodes at a node's own frequency, linear
-//                between (the expression of eaqhm_modify_prep_kernel's lookup)
+//                between
 __device__ inline int env_compact(const double* row, int K, int lane, double* sf) {
   int base = 0;
   for (int k0 = 0; k0 < K; k0 += 64) {
@@ -142,20 +133,8 @@ __device__ inline double env_at(const double* nf, const double* nv, int nn, doub
   return E;
 }
 
-// ---- the formant prep kernels: the prep body alone, scalar beta and beta / gain per instant.
-// They and the envelope kernel come ahead of the scan kernel, so that in the device assembly every kernel that existed
-// before them keeps its neighbours (tools/isa_diff.py compares each function with the text up to the next one).
-#define EAQHM_MODIFY_FORMANT 1
-#define EAQHM_MODIFY_CURVE 0
-#include "eaqhm_modify_body.inc"
-#undef EAQHM_MODIFY_CURVE
-#define EAQHM_MODIFY_CURVE 1
-#include "eaqhm_modify_body.inc"
-#undef EAQHM_MODIFY_CURVE
-#undef EAQHM_MODIFY_FORMANT
-
 // ------------------------------------------------------------------------------------------------
-// Envelope readout: one wave per instant i (four per block), the nodes ordered as in the formant prep,
+// Envelope readout: one wave per instant i (four per block), the nodes ordered as in the prep kernel,
 // lanes over the frequency grid: out[i][t] = E_i(freqs[t] / alpha_i), natural-log amplitude, not muted; -inf for an
 // instant without active slots.
 extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
@@ -263,6 +242,80 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_carry_kernel(int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Prep: one wave per instant i (PREP_WAVES per block), 3 Kmax doubles of LDS per wave.  beta: [No_ti]; gain: [No_ti-1]
+// g_j of interval j, or null (Delta unweighted); alphav: [No_ti], or null (alpha = 1).
+//   A'[i][k]  beta_i == 1 and alpha_i == 1: am.  Otherwise 0 for an inactive slot and, for an active one, with the
+//             envelope exp(E_i(beta_i f / alpha_i)) where E_i interpolates ln am linearly over the instant's active
+//             slots sorted by (f, k) (flat outside, the first of tied nodes at a node's own frequency), without it am;
+//             both muted where beta_i f >= fs/2.
+//   dR[i+1][k] Delta of the interval (i, i+1) when it is in a run: (ph_{i+1} - ph_i) + 2 pi Mr, times g_i when gain is
+//             given.  Other rows 0.
+//   P0[i][k]  ph_i at the first knot of a run (code != 0, previous instant inactive), else 0.
+// The nodes are built only where they are read; every wave of a block reaches both barriers.  The instant is a scalar
+// (beta, alpha and gain come through the scalar cache) and the Delta loop, which needs none of them but gain, runs
+// ahead of the barriers: the path that builds no envelope then pays for the two barriers alone.
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_modify_prep_kernel(ModArgs A, const double* __restrict__ betav, const double* __restrict__ gain,
+                             const double* __restrict__ alphav, int envelope, double* __restrict__ amp,
+                             double* __restrict__ dR, double* __restrict__ P0) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int K = A.Kmax, D = A.step, RS = 3 * K + 1;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * PREP_WAVES + w);   // one wave per instant: scalar
+  double* sf = lds + (size_t)w * 3 * K;   // active slots' frequencies in slot order [K], then the sorted nodes
+  double* nf = sf + K;
+  double* nv = nf + K;
+  const bool live = i < A.No_ti;
+  const double beta = betav[live ? i : 0];   // wave-uniform: one wave per instant
+  const double alpha = alphav ? alphav[live ? i : 0] : 1.0;
+  const double* row = A.records + (size_t)(live ? i : 0) * RS;
+  const bool unit = beta == 1.0 && alpha == 1.0;
+  const bool env = live && envelope && !unit;
+  if (live) {
+    // ---- Delta of the interval (i, i+1), first-knot phase
+    const double scale = 2.0 * M_PI / A.fs;
+    for (int k = lane; k < K; k += 64) {
+      GSlot S{A, k};
+      const int ci = S.code(i);
+      const bool head = ci != 0 && S.code(i - 1) == 0;
+      P0[(size_t)i * K + k] = (head && ci != 1) ? S.ph(i) : 0.0;
+      if (i == 0) dR[k] = 0.0;
+      if (i + 1 < A.No_ti) {
+        double d = 0.0;
+        if (ci != 0 && S.code(i + 1) != 0) {
+          const FmPiece P = make_piece(S, i, ci);
+          double w0, acc, emis, Mr;
+          interval_close(S, P, i, D, scale, w0, acc, emis, Mr);
+          d = (S.ph(i + 1) - S.ph(i)) + 2.0 * M_PI * Mr;
+          if (gain) d = gain[i] * d;
+        }
+        dR[(size_t)(i + 1) * K + k] = d;
+      }
+    }
+  }
+  int nn = 0;
+  if (env) nn = env_compact(row, K, lane, sf);
+  __syncthreads();
+  if (env) env_rank(row, K, lane, sf, nn, nf, nv);
+  __syncthreads();
+  if (!live) return;
+  // ---- A'
+  for (int k = lane; k < K; k += 64) {
+    const double ak = row[k], fk = row[K + k];
+    double a = ak;
+    if (!unit) {
+      a = 0.0;
+      if (ak != 0.0 && fk > 0.0) {
+        const double bf = beta * fk;   // the output frequency: it alone decides the muting
+        a = envelope ? exp(env_at(nf, nv, nn, bf / alpha)) : ak;
+        if (bf >= 0.5 * A.fs) a = 0.0;
+      }
+    }
+    amp[(size_t)i * K + k] = a;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Output sample n -> tau = n / rho, interval j = floor(tau / D) and r = tau - j D in [0, D) (the guards catch a quotient
 // that rounded across an integer)
 __device__ inline void locate(long long n, double rho, int D, int& j, double& r) {
@@ -332,7 +385,6 @@ struct CurveMap {
 
 
 // ---- the scalar kernels: tau = n'/rho, phase weight beta rho
-#define EAQHM_MODIFY_FORMANT 0
 #define EAQHM_MODIFY_CURVE 0
 #define MAP_INIT
 #define MAP_LOCATE(n, j, r) locate(n, E.rho, D, j, r)
@@ -391,7 +443,6 @@ struct CurveMap {
 #undef MAP_ISO_RANGE
 #undef MAP_ISO_AT
 #undef MAP_TAU
-#undef EAQHM_MODIFY_FORMANT
 }  // namespace eaqhm
 
 using namespace eaqhm;
@@ -399,19 +450,25 @@ using namespace eaqhm;
 static bool finite_pos(double x) { return std::isfinite(x) && x > 0.0; }
 static int modify_scan(eaqhm_ctx* ctx, const uint8_t* code, int32_t No_ti, int32_t Kmax, double* R, double* ph0);
 
+// LDS of the prep and envelope kernels: staged frequencies, sorted frequencies and log amplitudes per wave
+static size_t envelope_lds_bytes(int Kmax) { return (size_t)PREP_WAVES * 3 * Kmax * sizeof(double); }
+static const size_t ENVELOPE_LDS_MAX = 160 * 1024;
+
 extern "C" int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                 int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta,
-                                 int32_t preserve_envelope, double* amp, double* R, double* ph0) {
+                                 int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
+                                 const double* gain, const double* alpha, int32_t preserve_envelope, double* amp,
+                                 double* R, double* ph0) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 || !finite_pos(fs))
+  if (!records || !code || !mom || !beta || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 || !finite_pos(fs))
     return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep: bad argument");
-  if (!finite_pos(beta)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep: beta must be finite and > 0");
+  if (alpha && !preserve_envelope)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep: a formant scale needs the envelope (preserve_envelope != 0)");
+  const size_t lds = envelope_lds_bytes(Kmax);
+  if (lds > ENVELOPE_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep: Kmax too large for the envelope nodes");
   const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
-  const size_t lds = (size_t)PREP_WAVES * 2 * Kmax * sizeof(double);
-  if (lds > 64 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep: Kmax too large for the envelope nodes");
   HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(eaqhm_modify_prep_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)), dim3(64 * PREP_WAVES),
-                     lds, ctx->stream, A, beta, (int)(preserve_envelope != 0), amp, R, ph0);
+                     lds, ctx->stream, A, beta, gain, alpha, (int)(preserve_envelope != 0), amp, R, ph0);
   HIP_TRY(ctx, hipGetLastError());
   return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
 }
@@ -484,25 +541,6 @@ extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const u
 }
 
 // ---- time and pitch scale contours
-extern "C" int eaqhm_modify_prep_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                       int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
-                                       const double* gain, int32_t preserve_envelope, double* amp, double* R,
-                                       double* ph0) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !beta || !gain || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 ||
-      !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_curve: bad argument");
-  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
-  const size_t lds = (size_t)PREP_WAVES * 2 * Kmax * sizeof(double);
-  if (lds > 64 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_curve: Kmax too large for the envelope nodes");
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_curve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-  hipLaunchKernelGGL(eaqhm_modify_prep_curve_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
-                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, gain, (int)(preserve_envelope != 0), amp, R, ph0);
-  HIP_TRY(ctx, hipGetLastError());
-  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
-}
-
 extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                                         const double* amp, const double* R, const double* ph0, int32_t No_ti,
                                         int32_t Kmax, int32_t step, double fs, const double* C, const double* rate,
@@ -531,58 +569,14 @@ extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, c
   return EAQHM_OK;
 }
 
-// ---- formant scale: alpha[No_ti] per instant, the envelope nodes ordered in LDS
-// LDS of the formant prep and envelope kernels: staged frequencies, sorted frequencies and log amplitudes per wave
-static size_t formant_lds_bytes(int Kmax) { return (size_t)PREP_WAVES * 3 * Kmax * sizeof(double); }
-static const size_t FORMANT_LDS_MAX = 160 * 1024;
-
-extern "C" int eaqhm_modify_prep_formant(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                         int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta,
-                                         const double* alpha, double* amp, double* R, double* ph0) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !alpha || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 || step <= 0 ||
-      !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: bad argument");
-  if (!finite_pos(beta)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: beta must be finite and > 0");
-  const size_t lds = formant_lds_bytes(Kmax);
-  if (lds > FORMANT_LDS_MAX)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant: Kmax too large for the envelope nodes");
-  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_formant_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(eaqhm_modify_prep_formant_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
-                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, alpha, amp, R, ph0);
-  HIP_TRY(ctx, hipGetLastError());
-  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
-}
-
-extern "C" int eaqhm_modify_prep_formant_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
-                                               const double* mom, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
-                                               const double* beta, const double* gain, const double* alpha, double* amp,
-                                               double* R, double* ph0) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !beta || !gain || !alpha || !amp || !R || !ph0 || No_ti < 4 || Kmax <= 0 ||
-      step <= 0 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant_curve: bad argument");
-  const size_t lds = formant_lds_bytes(Kmax);
-  if (lds > FORMANT_LDS_MAX)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_prep_formant_curve: Kmax too large for the envelope nodes");
-  const ModArgs A{records, code, mom, No_ti, Kmax, step, fs};
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_prep_formant_curve_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(eaqhm_modify_prep_formant_curve_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
-                     dim3(64 * PREP_WAVES), lds, ctx->stream, A, beta, gain, alpha, amp, R, ph0);
-  HIP_TRY(ctx, hipGetLastError());
-  return modify_scan(ctx, code, No_ti, Kmax, R, ph0);
-}
-
+// ---- envelope readout
 extern "C" int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax,
                                     const double* alpha, const double* freqs, int32_t F, double* out) {
   if (!ctx) return EAQHM_EINVAL;
   if (!records || !alpha || !freqs || !out || No_ti < 4 || Kmax <= 0 || F <= 0)
     return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope: bad argument");
-  const size_t lds = formant_lds_bytes(Kmax);
-  if (lds > FORMANT_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope: Kmax too large for the envelope nodes");
+  const size_t lds = envelope_lds_bytes(Kmax);
+  if (lds > ENVELOPE_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope: Kmax too large for the envelope nodes");
   HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_envelope_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
   hipLaunchKernelGGL(eaqhm_model_envelope_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),

@@ -1,140 +1,9 @@
-// eaqhm_modify_body.inc — the prep and eval kernel bodies of eaqhm_modify.hip, compiled twice: EAQHM_MODIFY_CURVE 0
-// gives the scalar kernels (DESIGN.md §9), 1 the contour kernels (§9.1).  The time map enters the eval body through the
-// MAP_* macros that eaqhm_modify.hip defines for each variant.  The body is shared as text rather than as an inlined
-// device template because inlining reorders the scalar kernels' code; compiled from this text with the flag at 0,
-// their ISA is the one they had before the contour kernels existed.
-// EAQHM_MODIFY_FORMANT 1 compiles the prep body alone, as the formant prep kernels (§9.2): alpha per instant, the
-// envelope nodes ordered in LDS (env_compact / env_rank), A' = exp(E_i(beta f / alpha)) unless beta = alpha = 1.
+// eaqhm_modify_body.inc — the eval kernel body of eaqhm_modify.hip, compiled twice: EAQHM_MODIFY_CURVE 0 gives
+// eaqhm_modify_eval_kernel (DESIGN.md §9), 1 gives eaqhm_modify_eval_curve_kernel (§9.1).  The time map enters the body
+// through the MAP_* macros that eaqhm_modify.hip defines for each variant.  The body is shared as text rather than as an
+// inlined device template because inlining reorders the scalar kernel's code and costs it an occupancy step (§9.1).
 // No include guard: included once per variant.
 
-#if EAQHM_MODIFY_FORMANT && EAQHM_MODIFY_CURVE
-// beta: [No_ti] per instant; gain: [No_ti-1] g_j of interval j; alphav: [No_ti] formant scale per instant
-extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
-    eaqhm_modify_prep_formant_curve_kernel(ModArgs A, const double* __restrict__ betav, const double* __restrict__ gain,
-                                           const double* __restrict__ alphav, double* __restrict__ amp,
-                                           double* __restrict__ dR, double* __restrict__ P0) {
-#elif EAQHM_MODIFY_FORMANT
-extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
-    eaqhm_modify_prep_formant_kernel(ModArgs A, double beta, const double* __restrict__ alphav, double* __restrict__ amp,
-                                     double* __restrict__ dR, double* __restrict__ P0) {
-#elif EAQHM_MODIFY_CURVE
-// beta: [No_ti] per instant; gain: [No_ti-1] g_j of interval j
-extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
-    eaqhm_modify_prep_curve_kernel(ModArgs A, const double* __restrict__ betav, const double* __restrict__ gain,
-                                   int envelope, double* __restrict__ amp, double* __restrict__ dR,
-                                   double* __restrict__ P0) {
-#else
-extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
-    eaqhm_modify_prep_kernel(ModArgs A, double beta, int envelope, double* __restrict__ amp, double* __restrict__ dR,
-                             double* __restrict__ P0) {
-#endif
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int K = A.Kmax, D = A.step, RS = 3 * K + 1;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * PREP_WAVES + w;
-#if EAQHM_MODIFY_FORMANT
-  double* sf = lds + (size_t)w * 3 * K;   // active slots' frequencies in slot order [K], then the sorted nodes
-  double* nf = sf + K;
-#else
-  double* nf = lds + (size_t)w * 2 * K;   // sorted node frequencies [K] and log amplitudes [K] of this wave's instant
-#endif
-  double* nv = nf + K;
-  const bool live = i < A.No_ti;
-#if EAQHM_MODIFY_CURVE
-  const double beta = betav[live ? i : 0];   // wave-uniform: one wave per instant
-#endif
-  const double* row = A.records + (size_t)(live ? i : 0) * RS;
-#if EAQHM_MODIFY_FORMANT
-  const double alpha = alphav[live ? i : 0];
-  const bool env = live && !(beta == 1.0 && alpha == 1.0);
-  int nn = 0;
-  if (env) nn = env_compact(row, K, lane, sf);
-  __syncthreads();
-  if (env) env_rank(row, K, lane, sf, nn, nf, nv);
-#else
-  const bool env = live && beta != 1.0 && envelope;
-  int nn = 0;
-  if (env) {
-    // rank of every active slot in (f, k) order: slots are nearly sorted already, K is at most a few hundred
-    for (int k = lane; k < K; k += 64) {
-      const double ak = row[k], fk = row[K + k];
-      if (ak != 0.0 && fk > 0.0) {
-        int rank = 0;
-        for (int q = 0; q < K; ++q) {
-          const double aq = row[q], fq = row[K + q];
-          rank += (aq != 0.0 && fq > 0.0 && (fq < fk || (fq == fk && q < k))) ? 1 : 0;
-        }
-        nf[rank] = fk;
-        nv[rank] = log(ak);
-      }
-    }
-    for (int k = lane; k < K; k += 64) nn += (row[k] != 0.0 && row[K + k] > 0.0) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o);
-  }
-#endif
-  __syncthreads();
-  if (!live) return;
-  const double scale = 2.0 * M_PI / A.fs;
-  for (int k = lane; k < K; k += 64) {
-    // ---- A'
-    const double ak = row[k], fk = row[K + k];
-    double a = ak;
-#if EAQHM_MODIFY_FORMANT
-    if (env) {
-      a = 0.0;
-      if (ak != 0.0 && fk > 0.0) {
-        const double bf = beta * fk;   // the output frequency: it alone decides the muting
-        a = exp(env_at(nf, nv, nn, bf / alpha));
-        if (bf >= 0.5 * A.fs) a = 0.0;
-      }
-    }
-#else
-    if (beta != 1.0) {
-      a = 0.0;
-      if (ak != 0.0 && fk > 0.0) {
-        const double q = beta * fk;
-        a = ak;
-        if (envelope) {
-          int lo = 0, hi = nn;   // first node with f >= q
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (nf[mid] < q) lo = mid + 1; else hi = mid;
-          }
-          double E;
-          if (lo < nn && nf[lo] == q) E = nv[lo];
-          else if (lo == 0) E = nv[0];
-          else if (lo == nn) E = nv[nn - 1];
-          else E = nv[lo - 1] + (nv[lo] - nv[lo - 1]) * ((q - nf[lo - 1]) / (nf[lo] - nf[lo - 1]));
-          a = exp(E);
-        }
-        if (q >= 0.5 * A.fs) a = 0.0;
-      }
-    }
-#endif
-    amp[(size_t)i * K + k] = a;
-    // ---- Delta of the interval (i, i+1), first-knot phase
-    GSlot S{A, k};
-    const int ci = S.code(i);
-    const bool head = ci != 0 && S.code(i - 1) == 0;
-    P0[(size_t)i * K + k] = (head && ci != 1) ? S.ph(i) : 0.0;
-    if (i == 0) dR[k] = 0.0;
-    if (i + 1 < A.No_ti) {
-      double d = 0.0;
-      if (ci != 0 && S.code(i + 1) != 0) {
-        const FmPiece P = make_piece(S, i, ci);
-        double w0, acc, emis, Mr;
-        interval_close(S, P, i, D, scale, w0, acc, emis, Mr);
-        d = (S.ph(i + 1) - S.ph(i)) + 2.0 * M_PI * Mr;
-#if EAQHM_MODIFY_CURVE
-        d = gain[i] * d;
-#endif
-      }
-      dR[(size_t)(i + 1) * K + k] = d;
-    }
-  }
-}
-
-#if !EAQHM_MODIFY_FORMANT
 // ------------------------------------------------------------------------------------------------
 // Block of TBS consecutive output samples x all slots.
 //   stage 0  per sample: interval j and offset r (LDS).
@@ -285,4 +154,3 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEval
     E.out[n] = a0v + 2.0 * synth;
   }
 }
-#endif  // !EAQHM_MODIFY_FORMANT

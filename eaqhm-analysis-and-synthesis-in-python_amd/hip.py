@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("EAQHM_LIB") or os.path.join(_HERE, "csrc", "libeaqhm_
 # every symbol include/eaqhm_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
+# EAQHM_ABI_VERSION (csrc/eaqhm_common.h) this binding was written for: argument lists change under unchanged names
+ABI_VERSION = 4
 SYMBOLS = (
     ("eaqhm_ctx_create", C.c_int, [C.POINTER(_P), C.c_int]),
     ("eaqhm_ctx_destroy", C.c_int, [_P]),
@@ -34,14 +36,11 @@ SYMBOLS = (
     ("eaqhm_eval_synth", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _I64, _I64, _I64, _I64, _I64, _P, _F64,
                                     _P, _P, _I64, _I64, _P, _P, _P, _P]),
     ("eaqhm_eval_partials_len", _I64, [_I64, _I64, _I32]),
-    ("eaqhm_modify_prep", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _I32, _P, _P, _P]),
+    ("eaqhm_modify_prep", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _P, _P]),
     ("eaqhm_modify_synth", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64, _I64,
                                       _P]),
-    ("eaqhm_modify_prep_curve", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P]),
     ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
                                             _I64, _I64, _P]),
-    ("eaqhm_modify_prep_formant", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P]),
-    ("eaqhm_modify_prep_formant_curve", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P]),
     ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
 )
 
@@ -105,6 +104,10 @@ class Context:
         info = (_I32 * 4)()
         self._ck(self.lib.eaqhm_device_info(self.h, info))
         self.n_cu, self.lds_bytes, self.clock_khz, self.abi_version = [int(v) for v in info]
+        if self.abi_version != ABI_VERSION:
+            self.close()
+            raise HipUnavailable("%s has ABI version %d, this binding needs %d: stale build, rebuild"
+                                 % (LIB_PATH, self.abi_version, ABI_VERSION))
         v = os.environ.get("EAQHM_LS_VARIANT")          # A/B knob for measurements (include/eaqhm_hip.h)
         if v:
             self.set_option(1, int(v))
@@ -182,34 +185,22 @@ class Context:
                                            _ptr(am_out), _ptr(fm_out), track_t0, track_len, _ptr(ph_knot), _ptr(s_hat),
                                            _ptr(partials), _ptr(sums_out)))
 
-    def modify_prep(self, records, code, mom, No_ti, Kmax, step, fs, beta, preserve_envelope, amp, R, ph0):
+    def modify_prep(self, records, code, mom, No_ti, Kmax, step, fs, beta, gain, alpha, preserve_envelope, amp, R,
+                    ph0):
         self._ck(self.lib.eaqhm_modify_prep(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step, float(fs),
-                                            float(beta), int(bool(preserve_envelope)), _ptr(amp), _ptr(R), _ptr(ph0)))
+                                            _ptr(beta), _ptr(gain), _ptr(alpha), int(bool(preserve_envelope)),
+                                            _ptr(amp), _ptr(R), _ptr(ph0)))
 
     def modify_synth(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi, out):
         self._ck(self.lib.eaqhm_modify_synth(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R), _ptr(ph0),
                                              No_ti, Kmax, step, float(fs), float(rho), float(beta), L_out, t_lo, t_hi,
                                              _ptr(out)))
 
-    def modify_prep_curve(self, records, code, mom, No_ti, Kmax, step, fs, beta, gain, preserve_envelope, amp, R, ph0):
-        self._ck(self.lib.eaqhm_modify_prep_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step,
-                                                  float(fs), _ptr(beta), _ptr(gain), int(bool(preserve_envelope)),
-                                                  _ptr(amp), _ptr(R), _ptr(ph0)))
-
     def modify_synth_curve(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, C, rate, gain, rate_min, L_out,
                            t_lo, t_hi, out):
         self._ck(self.lib.eaqhm_modify_synth_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
                                                    _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C), _ptr(rate),
                                                    _ptr(gain), float(rate_min), L_out, t_lo, t_hi, _ptr(out)))
-
-    def modify_prep_formant(self, records, code, mom, No_ti, Kmax, step, fs, beta, alpha, amp, R, ph0):
-        self._ck(self.lib.eaqhm_modify_prep_formant(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax, step,
-                                                    float(fs), float(beta), _ptr(alpha), _ptr(amp), _ptr(R), _ptr(ph0)))
-
-    def modify_prep_formant_curve(self, records, code, mom, No_ti, Kmax, step, fs, beta, gain, alpha, amp, R, ph0):
-        self._ck(self.lib.eaqhm_modify_prep_formant_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), No_ti, Kmax,
-                                                          step, float(fs), _ptr(beta), _ptr(gain), _ptr(alpha),
-                                                          _ptr(amp), _ptr(R), _ptr(ph0)))
 
     def model_envelope(self, records, No_ti, Kmax, alpha, freqs, F, out):
         self._ck(self.lib.eaqhm_model_envelope(self.h, _ptr(records), No_ti, Kmax, _ptr(alpha), _ptr(freqs), F,

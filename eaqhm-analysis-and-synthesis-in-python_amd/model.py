@@ -11,9 +11,8 @@
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
 also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
-(§9.2).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep / eaqhm_modify_synth, or their _curve
-variants for contours, eaqhm_modify_prep_formant[_curve] for a formant scale, eaqhm_model_envelope); there is no CPU
-path.
+(§9.2).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep, eaqhm_modify_synth or
+eaqhm_modify_synth_curve for contours, eaqhm_model_envelope); there is no CPU path.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -119,6 +118,16 @@ def _scale(x, name):
     return v
 
 
+def _sample_rate(fs):
+    try:
+        fs = float(fs)
+    except (TypeError, ValueError):
+        raise ValueError("fs must be a number") from None
+    if not np.isfinite(fs) or fs <= 0:
+        raise ValueError("fs must be finite and > 0")
+    return fs
+
+
 def _is_contour(x):
     """True for an array-like scale (a contour); numbers and strings are scalars."""
     return not isinstance(x, (str, bytes)) and np.ndim(x) > 0
@@ -172,13 +181,7 @@ def scale_contour(DetComponents, fs, times_s, values):
     (times_s in seconds, values in SCALE_RANGE) interpolated linearly at every analysis instant ti / fs of the model,
     held flat before the first and after the last breakpoint.  Returns float64[No_ti]."""
     t, v = check_curve(times_s, values)
-    try:
-        fs = float(fs)
-    except (TypeError, ValueError):
-        raise ValueError("fs must be a number") from None
-    if not np.isfinite(fs) or fs <= 0:
-        raise ValueError("fs must be finite and > 0")
-    return np.interp(_model_instants(DetComponents) / fs, t, v)
+    return np.interp(_model_instants(DetComponents) / _sample_rate(fs), t, v)
 
 
 def contour_time_map(rho, beta, step, length):
@@ -202,12 +205,7 @@ def check_arguments(model, fs, length, time_scale, pitch_scale):
     """Validates everything eaQHMSynthesis gets (no device work): returns (rho, beta, fs, length)."""
     rho = _scale(time_scale, "time_scale")
     beta = _scale(pitch_scale, "pitch_scale")
-    try:
-        fs = float(fs)
-    except (TypeError, ValueError):
-        raise ValueError("fs must be a number") from None
-    if not np.isfinite(fs) or fs <= 0:
-        raise ValueError("fs must be finite and > 0")
+    fs = _sample_rate(fs)
     if isinstance(length, bool) or not float(length).is_integer():
         raise ValueError("length must be an integer number of samples")
     length = int(length)
@@ -251,6 +249,18 @@ def check_formant_scale(model, formant_scale, preserve_envelope):
     return alpha
 
 
+def _device_records(model, dev):
+    """The model's records on the device: (tensor, No_ti, Kmax).  A model without any slot keeps one empty slot, so that
+    the kernels still run (the a0 spline of the synthesis, the -inf rows of the envelope)."""
+    import torch
+    rec_h = model["records"]
+    n, K = rec_h.shape[0], model["Kmax"]
+    if K == 0:
+        rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
+        K = 1
+    return torch.as_tensor(np.ascontiguousarray(rec_h), device=dev), n, K
+
+
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
                    formant_scale=1.0, *, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
@@ -279,23 +289,19 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     else:
         rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
     alpha = check_formant_scale(model, formant_scale, preserve_envelope)
-    # the formant prep runs for a formant contour or a number != 1; without the envelope alpha is 1 throughout
+    # alpha reaches the prep for a formant contour or a number != 1; without the envelope alpha is 1 throughout
     formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
     dev = c.device
-    rec_h = model["records"]
-    n, K, D = rec_h.shape[0], model["Kmax"], model["step"]
+    rec, n, K = _device_records(model, dev)
+    D = model["step"]
     if contour:
         tm = contour_time_map(rho, beta, D, length)
         L_out = tm["L_out"]
     else:
         L_out = int(np.rint(rho * length))
-    if K == 0:                                   # no slot at all: keep one empty slot so the a0 spline still runs
-        rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
-        K = 1
-    rec = torch.as_tensor(np.ascontiguousarray(rec_h), device=dev)
     code = torch.empty(n * K, dtype=torch.uint8, device=dev)
     mom = torch.empty(n * (K + 1), dtype=torch.float64, device=dev)
     amp = torch.empty(n * K, dtype=torch.float64, device=dev)
@@ -304,23 +310,19 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     out = torch.empty(L_out, dtype=torch.float64, device=dev)
     ranges = [(0, L_out)] if _ranges is None else [(int(a), int(b)) for a, b in _ranges]
     c.spline_solve(rec, n, K, D, code, mom)
+
+    def dv(x):   # float64 on the device; a number becomes one value per instant
+        return torch.as_tensor(np.full(n, x) if np.ndim(x) == 0 else np.ascontiguousarray(x), device=dev)
+
+    gain_d = dv(tm["gain"]) if contour else None      # without it Delta stays unweighted: the scalar synthesis
+    c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta), gain_d, dv(alpha) if formant else None,
+                  preserve_envelope, amp, R, ph0)
     if contour:
-        beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
-                                       for x in (beta, tm["gain"], tm["C"], tm["rate"]))
-        if formant:
-            alpha_d = torch.as_tensor(np.array(np.broadcast_to(alpha, (n,)), dtype=np.float64), device=dev)
-            c.modify_prep_formant_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, alpha_d, amp, R, ph0)
-        else:
-            c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, preserve_envelope, amp, R, ph0)
+        C_d, rate_d = dv(tm["C"]), dv(tm["rate"])
         for t_lo, t_hi in ranges:
             c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"], L_out,
                                  t_lo, t_hi, out)
     else:
-        if formant:
-            alpha_d = torch.full((n,), alpha, dtype=torch.float64, device=dev)
-            c.modify_prep_formant(rec, code, mom, n, K, D, fs, beta, alpha_d, amp, R, ph0)
-        else:
-            c.modify_prep(rec, code, mom, n, K, D, fs, beta, preserve_envelope, amp, R, ph0)
         for t_lo, t_hi in ranges:
             c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
     return out.cpu().numpy()
@@ -328,12 +330,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
 
 def check_envelope_arguments(model, fs, freqs, formant_scale):
     """Validates everything model_envelope gets (no device work): returns (alpha float64[No_ti], freqs float64[F])."""
-    try:
-        fs = float(fs)
-    except (TypeError, ValueError):
-        raise ValueError("fs must be a number") from None
-    if not np.isfinite(fs) or fs <= 0:
-        raise ValueError("fs must be finite and > 0")
+    _sample_rate(fs)
     f = _numeric_1d(freqs, "freqs")
     if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
         raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
@@ -359,12 +356,7 @@ def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=
     from .functions import _ctx
     c = _ctx(device_index)
     dev = c.device
-    rec_h = model["records"]
-    n, K = rec_h.shape[0], model["Kmax"]
-    if K == 0:                                   # no slot at all: one empty slot, every row -inf
-        rec_h = np.concatenate((np.zeros((n, 3)), rec_h), axis=1)
-        K = 1
-    rec = torch.as_tensor(np.ascontiguousarray(rec_h), device=dev)
+    rec, n, K = _device_records(model, dev)
     alpha_d = torch.as_tensor(np.ascontiguousarray(alpha), device=dev)
     f_d = torch.as_tensor(np.ascontiguousarray(f), device=dev)
     out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)

@@ -176,68 +176,55 @@ int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
 /* number of 8-byte words `partials` must hold for a given range */
 int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step);
 
-/* resynthesis from the model with a time scale rho and a pitch scale beta (additive to ABI 3) --------------------
+/* resynthesis from the model with a time scale rho, a pitch scale beta and a formant scale alpha (ABI 4) ----------
  * Generalises functions.py:337-385 (track interpolation and additive synthesis) and :537-575 (phase integration) from
- * the analysed timeline to output samples n' = rho * tau; the definition is DESIGN.md "Resynthesis from the model".
- * Both calls take the records of an analysed (possibly edited) model and the code / mom that eaqhm_spline_solve
- * produced from them; at rho = beta = 1 the synthesis is eaqhm_eval_synth's s_hat of the same records.
- * eaqhm_modify_prep (kernels: prep, segmented scan of the phase increments)
- *   amp        double[No_ti][Kmax]  knot amplitudes A' after the pitch scale: beta == 1: |a|; otherwise, with
- *                                   preserve_envelope, exp of the instant's piecewise-linear log-amplitude envelope at
- *                                   beta*f, without it |a|; zero where beta*f >= fs/2 (or the slot is inactive)
+ * the analysed timeline to output samples n' = rho * tau; the definition is DESIGN.md "Resynthesis from the model"
+ * (§9), §9.1 for scales per analysis instant (contours) and §9.2 for the formant scale.  All calls take the records
+ * of an analysed (possibly edited) model and the code / mom that eaqhm_spline_solve produced from them; at
+ * rho = beta = 1 the synthesis is eaqhm_eval_synth's s_hat of the same records.
+ * eaqhm_modify_prep (kernels: prep, segmented scan of the phase increments) serves every synthesis:
+ *   beta       double[No_ti]    pitch scale per instant (the scalar synthesis passes No_ti equal values)
+ *   gain       double[No_ti-1]  g_j of eaqhm_modify_synth_curve, or NULL: Delta unweighted (eaqhm_modify_synth)
+ *   alpha      double[No_ti]    formant scale per instant, each finite and > 0, or NULL: no formant scale; it needs
+ *                               preserve_envelope != 0
+ *   amp        double[No_ti][Kmax]  knot amplitudes A': beta_i == 1 and alpha_i == 1: |a|; otherwise, with
+ *                                   preserve_envelope, exp(E_i((beta_i * f) / alpha_i)), without it |a|; zero where
+ *                                   beta_i * f >= fs/2 (the output frequency; alpha plays no part) or the slot is
+ *                                   inactive.  E_i is the piecewise-linear envelope of ln |a| over the instant's
+ *                                   active slots sorted by (f, k) (flat outside the end nodes, the first of tied nodes
+ *                                   at a node's own frequency); a feature at F in the model sits at alpha_i F after
+ *                                   the scale.  The nodes are ordered in LDS (3 * Kmax doubles per instant, four
+ *                                   instants per block).
  *   R          double[No_ti][Kmax]  unwrapped knot phase along each run of consecutive active instants (0 at the run's
- *                                   first knot, R_{j+1} = R_j + (ph_{j+1} - ph_j) + 2 pi M_j); 0 outside runs
+ *                                   first knot, R_{j+1} = R_j + (ph_{j+1} - ph_j) + 2 pi M_j); 0 outside runs.  With
+ *                                   gain it is the weighted knot phase G, G_{j+1} = G_j + g_j ((ph_{j+1} - ph_j) +
+ *                                   2 pi M_j).
  *   ph0        double[No_ti][Kmax]  phase of the first knot of the run each knot belongs to; 0 outside runs
- * eaqhm_modify_synth writes out[t_lo, t_hi) of the L_out-sample signal (out is double[L_out]).
- * EAQHM_EINVAL for rho or beta <= 0 or not finite, and for a range outside [0, L_out).                           */
+ * eaqhm_modify_synth writes out[t_lo, t_hi) of the L_out-sample signal (out is double[L_out]) from the outputs of a
+ *   prep without gain; beta is the number the prep's beta array holds.
+ * eaqhm_modify_synth_curve does so from the outputs of a prep with gain.  Per interval j:
+ *   r_j = (rho_j + rho_{j+1}) / 2, b_j = (beta_j + beta_{j+1}) / 2, g_j = r_j b_j; output knots C_0 = 0,
+ *   C_{j+1} = C_j + r_j step (the caller computes them in double, in this order);
+ *   L_out = rint(C_{n-1} + rho_{n-1} (L - c_{n-1})).  C[No_ti] output knot positions, rate[No_ti] = r_j with
+ *   rate[No_ti-1] = rho_{n-1} (past the last knot), gain[No_ti-1] = g_j, rate_min = the smallest entry of rate (sizes
+ *   the staged rows).
+ * eaqhm_model_envelope (kernel: one wave per instant, lanes over the grid)
+ *   out        double[No_ti][F]  E_i(freqs[t] / alpha_i), the natural-log amplitude, not muted; -inf on the rows of
+ *                                instants without active slots.  freqs[F] is the caller's grid (device, finite, >= 0).
+ * Device arrays are the caller's: every beta, alpha and rate must be finite and > 0 and C strictly increasing.
+ * EAQHM_EINVAL for null pointers (other than gain and alpha of the prep), No_ti < 4, alpha without preserve_envelope,
+ * rho, beta or rate_min <= 0 or not finite, a range outside [0, L_out), F <= 0, and Kmax beyond the LDS budget of the
+ * envelope nodes (Kmax > 1706).                                                                                     */
 int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, int32_t No_ti,
-                      int32_t Kmax, int32_t step, double fs, double beta, int32_t preserve_envelope, double* amp,
-                      double* R, double* ph0);
+                      int32_t Kmax, int32_t step, double fs, const double* beta, const double* gain,
+                      const double* alpha, int32_t preserve_envelope, double* amp, double* R, double* ph0);
 int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, const double* amp,
                        const double* R, const double* ph0, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
                        double rho, double beta, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
-
-/* time and pitch scale contours: rho_i and beta_i per analysis instant (additive to ABI 3) ---------------------------
- * The definition is DESIGN.md §9.1; with constant contours it is §9.  Per interval j: r_j = (rho_j + rho_{j+1}) / 2,
- * b_j = (beta_j + beta_{j+1}) / 2, g_j = r_j b_j; output knots C_0 = 0, C_{j+1} = C_j + r_j step (the caller computes
- * them in double, in this order); L_out = rint(C_{n-1} + rho_{n-1} (L - c_{n-1})).
- * eaqhm_modify_prep_curve: as eaqhm_modify_prep with beta[No_ti] per instant (A' uses beta_i) and gain[No_ti-1] = g_j;
- *   R holds the weighted knot phase G (0 at a run's first knot, G_{j+1} = G_j + g_j ((ph_{j+1} - ph_j) + 2 pi M_j)).
- * eaqhm_modify_synth_curve: writes out[t_lo, t_hi) of the L_out-sample signal from the prep_curve outputs.
- *   C[No_ti] output knot positions, rate[No_ti] = r_j with rate[No_ti-1] = rho_{n-1} (past the last knot),
- *   gain[No_ti-1] = g_j, rate_min = the smallest entry of rate (sizes the staged rows).
- * Device arrays are the caller's: every rate must be finite and > 0 and C strictly increasing.  EAQHM_EINVAL for null
- * pointers, rate_min <= 0 or not finite, and a range outside [0, L_out).                                            */
-int eaqhm_modify_prep_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                            int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
-                            const double* gain, int32_t preserve_envelope, double* amp, double* R, double* ph0);
 int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                              const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
                              int32_t step, double fs, const double* C, const double* rate, const double* gain,
                              double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
-
-/* formant scale: alpha_i per analysis instant moves the spectral envelope (additive to ABI 3) ----------------------
- * The definition is DESIGN.md §9.2.  E_i is the piecewise-linear envelope of ln |a| over the instant's active slots
- * sorted by (f, k) (flat outside the end nodes, the first of tied nodes at a node's own frequency); a feature at F in
- * the model sits at alpha_i F after the scale.  The nodes are ordered in LDS (3 * Kmax doubles per instant, four
- * instants per block).  alpha is a device array of No_ti values, each finite and > 0 (the caller's).
- * eaqhm_modify_prep_formant: as eaqhm_modify_prep with the envelope always on and
- *   amp        beta == 1 and alpha_i == 1: |a|; otherwise exp(E_i((beta * f) / alpha_i)), zero where beta*f >= fs/2
- *              (the output frequency; alpha plays no part) or the slot is inactive.  R and ph0 as eaqhm_modify_prep.
- *   The synthesis is eaqhm_modify_synth's.
- * eaqhm_modify_prep_formant_curve: the same with beta[No_ti] and gain[No_ti-1] as eaqhm_modify_prep_curve; the
- *   synthesis is eaqhm_modify_synth_curve's.
- * eaqhm_model_envelope (kernel: one wave per instant, lanes over the grid)
- *   out        double[No_ti][F]  E_i(freqs[t] / alpha_i), the natural-log amplitude, not muted; -inf on the rows of
- *                                instants without active slots.  freqs[F] is the caller's grid (device, finite, >= 0).
- * EAQHM_EINVAL for null pointers, No_ti < 4, beta <= 0 or not finite, F <= 0, and Kmax beyond the LDS budget
- * (Kmax > 1706).                                                                                                   */
-int eaqhm_modify_prep_formant(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                              int32_t No_ti, int32_t Kmax, int32_t step, double fs, double beta, const double* alpha,
-                              double* amp, double* R, double* ph0);
-int eaqhm_modify_prep_formant_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                    int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* beta,
-                                    const double* gain, const double* alpha, double* amp, double* R, double* ph0);
 int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* alpha,
                          const double* freqs, int32_t F, double* out);
 

@@ -1,7 +1,10 @@
-"""The formant scale on the MI355X (eaQHMSynthesis(formant_scale=...) -> eaqhm_modify_prep_formant[_curve], and
-model_envelope -> eaqhm_model_envelope): bit-identity with today's paths at alpha = 1 (the node ordering in LDS),
+"""The formant scale on the MI355X (eaQHMSynthesis(formant_scale=...) -> eaqhm_modify_prep with alpha, and
+model_envelope -> eaqhm_model_envelope): bit-identity with the four prep kernels the one prep kernel replaced and with
+the synthesis as it was then (digests recorded on the MI355X at that commit, tests/golden/modify_parent_digests.json),
 agreement with the NumPy model of DESIGN.md §9.2 (tests/model_formant_ref.py), the envelope readout, a hand-built
 model whose formant moves where the definition says, the CLI and the probe's numbers."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -48,9 +51,8 @@ def models(synth16k_fresh, synth48k_fresh):
             ("synth48k_0p6s", a48, 48000, len(s48))]
 
 
-def _prep_outputs(amd, det, fs, beta, alpha=None, gain=None):
-    """amp, R, ph0 of one prep call: today's (alpha None) or the formant one; beta / gain arrays take the contour
-    kernels."""
+def _prep_outputs(amd, det, fs, beta, alpha=None, gain=None, envelope=True):
+    """amp, R, ph0 of one prep call: beta a number or one value per instant, gain (contours) and alpha optional."""
     import torch
     from eaqhm_amd.functions import _ctx
     from eaqhm_amd.model import unpack_model
@@ -64,38 +66,86 @@ def _prep_outputs(amd, det, fs, beta, alpha=None, gain=None):
     mom = torch.empty(n * (K + 1), dtype=torch.float64, device=dev)
     amp, R, ph0 = (torch.empty(n * K, dtype=torch.float64, device=dev) for _ in range(3))
     c.spline_solve(rec, n, K, D, code, mom)
-    dv = lambda x: torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)   # noqa: E731
-    if gain is None:
-        if alpha is None:
-            c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0)
-        else:
-            c.modify_prep_formant(rec, code, mom, n, K, D, fs, beta, dv(alpha), amp, R, ph0)
-    else:
-        if alpha is None:
-            c.modify_prep_curve(rec, code, mom, n, K, D, fs, dv(beta), dv(gain), True, amp, R, ph0)
-        else:
-            c.modify_prep_formant_curve(rec, code, mom, n, K, D, fs, dv(beta), dv(gain), dv(alpha), amp, R, ph0)
+
+    def dv(x):
+        return None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
+
+    beta_n = beta if np.ndim(beta) else np.full(n, beta)
+    c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta_n), dv(gain), dv(alpha), envelope, amp, R, ph0)
     return [x.cpu().numpy().reshape(n, K) for x in (amp, R, ph0)]
 
 
-def test_unit_alpha_prep_is_todays_prep_bit_for_bit(amd, models):
-    """The formant kernels at alpha = 1 against eaqhm_modify_prep / _curve: amp, R and ph0 bit for bit (the LDS rank
-    count orders the nodes exactly as the global-memory count does)."""
+def _parent_digests():
+    with open(os.path.join(GOLDEN, "modify_parent_digests.json")) as f:
+        return json.load(f)
+
+
+def _digest(a):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return dict(shape=list(a.shape), sha256=hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def _sa19_contours(n):
+    """The rho / beta contour of the recorded contour cases and the alpha ramp 0.9 -> 1.2."""
+    x = np.arange(n) / (n - 1)
+    return 1.1 + 0.5 * np.sin(2 * np.pi * 3 * x), 0.8 + 0.5 * x, 0.9 + 0.3 * x
+
+
+def test_unit_alpha_prep_is_todays_prep_bit_for_bit(amd):
+    """eaqhm_modify_prep against amp, R and ph0 of the four entry points it replaced (eaqhm_modify_prep, _prep_curve,
+    _prep_formant, _prep_formant_curve), recorded on the MI355X at the commit the fixture names, on the committed SA19
+    model.  Cases that had no alpha are called both without one and with alpha = 1 per instant: the envelope nodes
+    ordered in LDS and read at (beta f) / 1 give the bits of the global-memory count and its own lookup."""
     from eaqhm_amd.model import contour_time_map
-    for label, det, fs, L in models:
-        n = len(det["ti"])
-        for beta in (1.0, 0.8, 1.25, 1.9):
-            a = _prep_outputs(amd, det, fs, beta)
-            b = _prep_outputs(amd, det, fs, beta, alpha=np.ones(n))
-            for x, y, name in zip(a, b, ("amp", "R", "ph0")):
-                assert np.array_equal(x, y), (label, beta, name)
-        x = np.arange(n) / (n - 1)
-        rho, beta = 1.1 + 0.5 * np.sin(2 * np.pi * 3 * x), 0.8 + 0.5 * x
-        gain = contour_time_map(rho, beta, int(det["ti"][1] - det["ti"][0]), L)["gain"]
-        a = _prep_outputs(amd, det, fs, beta, gain=gain)
-        b = _prep_outputs(amd, det, fs, beta, alpha=np.ones(n), gain=gain)
-        for x, y, name in zip(a, b, ("amp", "R", "ph0")):
-            assert np.array_equal(x, y), (label, "contour", name)
+    g, det = reference_model()
+    fs, L = 16000, len(g["s_recon"])
+    n = len(det["ti"])
+    want = _parent_digests()
+    assert (want["fs"], want["length"], want["No_ti"]) == (fs, L, n)
+    rho_c, beta_c, alpha_c = _sa19_contours(n)
+    gain_c = contour_time_map(rho_c, beta_c, int(det["ti"][1] - det["ti"][0]), L)["gain"]
+    cases = [("scalar_beta%g_env1" % b, dict(beta=b)) for b in (1.0, 0.8, 1.25, 1.9)]
+    cases += [("scalar_beta%g_env0" % b, dict(beta=b, envelope=False)) for b in (1.0, 1.25)]
+    cases += [("contour_env1", dict(beta=beta_c, gain=gain_c))]
+    cases += [("formant_beta%g_alpha%g" % (b, a), dict(beta=b, alpha=np.full(n, a)))
+              for a in (0.8, 1.25) for b in (1.0, 1.25)]
+    cases += [("formant_contour", dict(beta=beta_c, gain=gain_c, alpha=alpha_c))]
+    assert {k for k, _ in cases} == set(want["prep"])
+    for key, kw in cases:
+        forms = [("as recorded", kw)]
+        if "alpha" not in kw and kw.get("envelope", True):      # alpha needs the envelope (EAQHM_EINVAL without)
+            forms.append(("alpha = 1", dict(kw, alpha=np.ones(n))))
+        for form, kw2 in forms:
+            for x, name in zip(_prep_outputs(amd, det, fs, **kw2), ("amp", "R", "ph0")):
+                assert _digest(x) == want["prep"][key][name], (key, form, name)
+
+
+def test_synthesis_is_the_parents_bit_for_bit(amd):
+    """eaQHMSynthesis and model_envelope on the committed SA19 model against the digests recorded on the MI355X before
+    the four prep kernels became one: scalar (rho, beta, envelope), the three contour pairs of the test below, the
+    formant SETTINGS, a formant contour, and the envelope readout on a 120-point grid."""
+    g, det = reference_model()
+    fs, L = 16000, len(g["s_recon"])
+    n = len(det["ti"])
+    want = _parent_digests()["synthesis"]
+    x = np.arange(n) / (n - 1)
+    rho_c, beta_c, alpha_c = _sa19_contours(n)
+    cases = [("scalar_rho%g_beta%g_env%d" % (rho, b, env),
+              dict(time_scale=rho, pitch_scale=b, preserve_envelope=env))
+             for rho in (0.5, 1.0, 1.5) for b in (1.0, 0.8, 1.25) for env in (True, False)]
+    cases += [("contour_rho_sinus", dict(time_scale=1.1 + 0.5 * np.sin(2 * np.pi * 3 * x), pitch_scale=np.ones(n))),
+              ("contour_beta_ramp", dict(time_scale=np.ones(n), pitch_scale=0.8 + 0.5 * x)),
+              ("contour_both", dict(time_scale=0.9 + 0.4 * x, pitch_scale=1.3 - 0.5 * x))]
+    cases += [("formant_rho%g_beta%g_alpha%g" % (rho, b, a), dict(time_scale=rho, pitch_scale=b, formant_scale=a))
+              for rho, b, a in SETTINGS]
+    cases += [("formant_contour", dict(time_scale=rho_c, pitch_scale=beta_c, formant_scale=alpha_c))]
+    got = {key: _digest(amd.eaQHMSynthesis(det, fs, L, **kw)) for key, kw in cases}
+    grid = np.linspace(0.0, fs / 2, 120)
+    for a in (1.0, 1.25):
+        got["envelope_alpha%g" % a] = _digest(amd.model_envelope(det, fs, grid, formant_scale=a))
+    assert set(got) == set(want)
+    for key in sorted(want):
+        assert got[key] == want[key], key
 
 
 def test_unit_alpha_contour_is_todays_contour_path_bit_for_bit(amd, models):

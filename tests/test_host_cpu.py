@@ -14,8 +14,10 @@ from conftest import GOLDEN, ROOT, load_golden
 
 def test_library_exports_every_header_symbol():
     import eaqhm_amd  # noqa: F401
-    from eaqhm_amd.hip import SYMBOLS, load_library
+    from eaqhm_amd.hip import ABI_VERSION, SYMBOLS, load_library
     lib = load_library()
+    common = open(os.path.join(ROOT, "eaqhm-analysis-and-synthesis-in-python_amd", "csrc", "eaqhm_common.h")).read()
+    assert ABI_VERSION == int(re.search(r"^#define\s+EAQHM_ABI_VERSION\s+(\d+)", common, re.M).group(1))
     header = open(os.path.join(ROOT, "include", "eaqhm_hip.h")).read()
     declared = set(re.findall(r"\b(eaqhm_[a-z_0-9]+)\s*\(", header))
     declared.discard("eaqhm_ctx")

@@ -5,12 +5,13 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
                                           [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
-{0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour kernels (eaqhm_modify_prep_curve / _synth_curve,
-DESIGN.md §9.1): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with beta ramping 0.85 -> 1.2,
-and both varying; eval_ms_per_msample normalises the eval time by the output length.  --formant adds the formant
-prep kernels (eaqhm_modify_prep_formant / _curve, DESIGN.md §9.2) at rho = 1: alpha in {0.85, 1.2} x beta in {1, 1.25}
-with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with eaqhm_modify_synth_curve; ratio_to_scalar compares each
-with the scalar path at the same beta (envelope on).  Device times are warmed HIP-event windows around synchronised launches; per-kernel
+{0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
+eaqhm_modify_synth_curve): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with
+beta ramping 0.85 -> 1.2, and both varying; eval_ms_per_msample normalises the eval time by the output length.
+--formant adds the formant scale (eaqhm_modify_prep with alpha) at rho = 1: alpha in {0.85, 1.2} x
+beta in {1, 1.25} with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with eaqhm_modify_synth_curve;
+ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  EAQHM_LIB selects another build of
+the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
 import json
@@ -95,7 +96,9 @@ def probe(workload, reps, contours=False, formant=False):
     dev = c.device
     rows = []
     for beta in (1.0, 1.25):
-        t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0), reps)
+        beta_d = torch.full((n,), beta, dtype=torch.float64, device=dev)
+        t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, True, amp, R, ph0),
+                       reps)
         for rho in (0.5, 1.0, 2.0):
             Lo = int(np.rint(rho * L))
             out = torch.empty(Lo, dtype=torch.float64, device=dev)
@@ -131,15 +134,17 @@ def formant_rows(torch, st, reps):
                     ratio_to_eval_synth=round(total / t_eval, 3), ratio_to_scalar=round(total / t_scalar, 3))
 
     for beta in (1.0, 1.25):
-        t_sp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta, True, amp, R, ph0), reps)
+        beta_d = torch.full((n,), beta, dtype=torch.float64, device=dev)
+        t_sp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, True, amp, R, ph0),
+                     reps)
         t_syn = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 1.0, beta, L, 0, L, out),
                       reps)
         t_scalar = t_sp + t_syn
         rows.append(row("scalar_beta%g" % beta, t_sp, t_syn, t_scalar))
         for alpha in (0.85, 1.2):
             alpha_d = torch.full((n,), alpha, dtype=torch.float64, device=dev)
-            t_fp = timed(torch, lambda: c.modify_prep_formant(rec, code, mom, n, K, D, fs, beta, alpha_d, amp, R, ph0),
-                         reps)
+            t_fp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, alpha_d, True, amp, R,
+                                                      ph0), reps)
             t_fs = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 1.0, beta, L, 0, L,
                                                        out), reps)
             rows.append(row("alpha%g_beta%g" % (alpha, beta), t_fp, t_fs, t_scalar))
@@ -150,8 +155,8 @@ def formant_rows(torch, st, reps):
     one_d, gain_d, C_d, rate_d, alpha_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
                                            for x in (one, tm["gain"], tm["C"], tm["rate"], ramp))
     outc = torch.empty(tm["L_out"], dtype=torch.float64, device=dev)
-    t_fp = timed(torch, lambda: c.modify_prep_formant_curve(rec, code, mom, n, K, D, fs, one_d, gain_d, alpha_d, amp, R,
-                                                            ph0), reps)
+    t_fp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, one_d, gain_d, alpha_d, True, amp, R, ph0),
+                 reps)
     t_fs = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
                                                      tm["rate_min"], tm["L_out"], 0, tm["L_out"], outc), reps)
     rows.append(row("alpha_ramp_contour", t_fp, t_fs, rows[0]["total_ms"]))
@@ -173,8 +178,8 @@ def probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval
         beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
                                        for x in (beta, tm["gain"], tm["C"], tm["rate"]))
         out = torch.empty(Lo, dtype=torch.float64, device=dev)
-        t_prep = timed(torch, lambda: c.modify_prep_curve(rec, code, mom, n, K, D, fs, beta_d, gain_d, True, amp, R,
-                                                          ph0), reps)
+        t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, gain_d, None, True, amp, R,
+                                                    ph0), reps)
         t_syn = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
                                                           tm["rate_min"], Lo, 0, Lo, out), reps)
         rows.append(dict(contour=label, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3),
