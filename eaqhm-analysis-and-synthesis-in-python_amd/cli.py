@@ -8,7 +8,9 @@ resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wa
 --pitch-scale-curve FILE take a breakpoint curve instead (two whitespace-separated columns, seconds and value; lines
 starting with # are comments), turned into a per-instant contour with model.scale_contour.  --formant-scale A /
 --formant-scale-curve FILE move the spectral envelope by A; they need the envelope, so either one with
---no-envelope is an error."""
+--no-envelope is an error.  --noise (with --noise-seed N) models the residual input - reconstruction
+(model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
+writes `<name>_resynthesis.wav`: model + noise at unit scales."""
 import argparse
 
 import numpy as np
@@ -17,7 +19,7 @@ from scipy.io import wavfile
 from .functions import eaQHMAnalysisAndSynthesis
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="eaqhm_amd", description="eaQHM analysis/resynthesis on MI355X")
     ap.add_argument("wav")
     ap.add_argument("--gender", default="other", help="male | female | child | other | fmin,fmax")
@@ -47,7 +49,21 @@ def main(argv=None):
                      help="like --formant-scale, with a curve: lines 'seconds value' (# comments)")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
+    ap.add_argument("--noise", action="store_true",
+                    help="model the residual as filtered noise and add it to <name>_modified.wav; without a scale flag "
+                         "write <name>_resynthesis.wav (model + noise)")
+    ap.add_argument("--noise-seed", type=int, default=None, metavar="N", help="with --noise: seed of the excitation (0)")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     a = ap.parse_args(argv)
+    if a.noise_seed is not None and not a.noise:
+        ap.error("--noise-seed needs --noise")
+    if a.noise:
+        from .model import _seed
+        _seed(0 if a.noise_seed is None else a.noise_seed)
     if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None):
         ap.error("--formant-scale / --formant-scale-curve scale the spectral envelope: not with --no-envelope")
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
@@ -76,8 +92,8 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
-        if modify:
-            from .model import eaQHMSynthesis, scale_contour
+        if modify or a.noise:
+            from .model import eaQHMNoiseAnalysis, eaQHMSynthesis, scale_contour
             rho = 1.0 if a.time_scale is None else a.time_scale
             beta = 1.0 if a.pitch_scale is None else a.pitch_scale
             if "time" in curves:
@@ -87,9 +103,14 @@ def main(argv=None):
             alpha = 1.0 if a.formant_scale is None else a.formant_scale
             if "formant" in curves:
                 alpha = scale_contour(det, fs, *curves["formant"])
+            nz = None
+            if a.noise:
+                from .prologue import read_signal
+                nz = eaQHMNoiseAnalysis(read_signal(a.wav, a.fc)[1], s_recon, fs)
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
-                                   preserve_envelope=not a.no_envelope, formant_scale=alpha)
-            out = a.wav[:len(a.wav) - 4] + "_modified.wav"
+                                   preserve_envelope=not a.no_envelope, formant_scale=alpha, noise=nz,
+                                   noise_seed=a.noise_seed or 0)
+            out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)
     return 0

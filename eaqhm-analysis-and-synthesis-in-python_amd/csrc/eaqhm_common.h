@@ -8,7 +8,7 @@
 
 #include "../../include/eaqhm_hip.h"
 
-#define EAQHM_ABI_VERSION 4
+#define EAQHM_ABI_VERSION 5
 
 struct eaqhm_ctx {
   int device = 0;

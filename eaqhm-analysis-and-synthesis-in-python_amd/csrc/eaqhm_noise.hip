@@ -1,0 +1,200 @@
+// eaqhm_noise.hip — the stochastic component: an all-pole (LPC) envelope and a gain per short frame of
+// the residual s - s_recon, and its resynthesis as filtered white noise under a time map.  Not in the reference.
+//   eaqhm_noise_analyse_kernel   one wave per frame: windowed frame in LDS, lane l owns lag l, Levinson-Durbin in the wave
+//   eaqhm_noise_filter_kernel    one lane per output frame: the all-pole lattice, state and coefficients in LDS
+//   eaqhm_noise_combine_kernel   one thread per output sample: cross-fade of the two frames that cover it
+#include "eaqhm_common.h"
+
+// The synthesis follows the NumPy model of the definition operation by operation (no fused multiply-add), so the two
+// differ only where a library function does (cos); the autocorrelation sums ask for their FMAs by name.
+#pragma clang fp contract(off)
+
+namespace eaqhm {
+
+constexpr int NA_WAVES = 4;   // frames (waves) per block of the analysis kernel
+constexpr int NA_PAD = 64;    // zeros in front of each wave's frame: x[v - l] for v < l reads them (l <= 63)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// LDS: NA_WAVES x (NA_PAD + 4 hop) doubles
+extern "C" __global__ void __launch_bounds__(64 * NA_WAVES)
+    eaqhm_noise_analyse_kernel(const double* __restrict__ e, long long L, int H, int p, int Nf,
+                               double* __restrict__ sigma, double* __restrict__ refl) {
+  extern __shared__ double na_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int W = 4 * H;
+  double* x = na_lds + (size_t)wave * (NA_PAD + W);
+  const int m = blockIdx.x * NA_WAVES + wave;
+  const bool live = m < Nf;
+  const long long base = (long long)m * H - 2 * H;
+  x[lane] = 0.0;
+  double sw2 = 0.0;
+  for (int v = lane; v < W; v += 64) {
+    const double w = 0.5 - 0.5 * cospi((double)(2 * v + 1) / (double)W);
+    const long long t = base + v;
+    const double ev = (live && t >= 0 && t < L) ? e[t] : 0.0;
+    x[NA_PAD + v] = w * ev;
+    sw2 += w * w;
+  }
+  __syncthreads();
+  if (!live) return;
+
+  // r[l] on lane l: x[v] is one address for the wave, x[v - l] consecutive addresses across lanes
+  const double* xv = x + NA_PAD;
+  const double* xl = x + NA_PAD - lane;
+  double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
+  for (int v = 0; v < W; v += 4) {
+    r0 = fma(xv[v], xl[v], r0);
+    r1 = fma(xv[v + 1], xl[v + 1], r1);
+    r2 = fma(xv[v + 2], xl[v + 2], r2);
+    r3 = fma(xv[v + 3], xl[v + 3], r3);
+  }
+  double r = (r0 + r1) + (r2 + r3);
+  sw2 = wave_sum(sw2);
+
+  // Levinson-Durbin: a_j on lane j (a_0 = 1), the reversed vectors by a cross-lane read, the sum by a wave reduction
+  const double r00 = __shfl(r, 0, 64);
+  double kk = 0.0, E = 0.0;
+  if (r00 > 0.0) {
+    if (lane == 0) r *= (1.0 + 1e-9);
+    E = __shfl(r, 0, 64);
+    double a = lane == 0 ? 1.0 : 0.0;
+    for (int i = 1; i <= p; ++i) {
+      const int src = (i - lane) & 63;
+      const double rr = __shfl(r, src, 64);
+      const double acc = __shfl(wave_sum(lane < i ? a * rr : 0.0), 0, 64);
+      const double k = -acc / E;
+      if (!(fabs(k) < 1.0)) break;
+      const double ar = __shfl(a, src, 64);
+      if (lane >= 1 && lane <= i) a += k * ar;      // lane i: 0 + k a_0
+      if (lane == i) kk = k;
+      E *= (1.0 - k * k);
+    }
+  }
+  if (lane == 0) sigma[m] = r00 > 0.0 ? sqrt(E / sw2) : 0.0;
+  if (lane >= 1 && lane <= p) refl[(size_t)m * p + (lane - 1)] = kk;
+}
+
+// the white excitation: a pure function of (seed, n), exact in integers (splitmix64), uniform with unit variance
+__device__ __forceinline__ double white(unsigned long long seed, long long n) {
+  unsigned long long z = seed + ((unsigned long long)n + 1ull) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return ((double)(z >> 11) * 0x1p-53 - 0.5) * 3.4641016151377544;
+}
+
+// Output frames [q_lo, q_lo + nq): lane = frame.  LDS [stage][lane]: k_1..k_p, then b_0..b_{p-1} (b_p is never read).
+// Y[u][frame], u = 0..2H-1: the 2H samples the frame keeps, n' = qH - H + u.
+extern "C" __global__ void __launch_bounds__(64)
+    eaqhm_noise_filter_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int H, int p,
+                              const double* __restrict__ tau, unsigned long long seed, int q_lo, int nq,
+                              double* __restrict__ Y) {
+  extern __shared__ double ns_lds[];
+  const int lane = threadIdx.x;
+  const int qi = blockIdx.x * 64 + lane;
+  if (qi >= nq) return;
+  double* kq = ns_lds + lane;
+  double* b = ns_lds + (size_t)p * 64 + lane;
+  const long long q = (long long)q_lo + qi;
+  const double mu = tau[q] / (double)H;
+  long long m0 = (long long)floor(mu);
+  m0 = m0 < 0 ? 0 : (m0 > Nf - 1 ? Nf - 1 : m0);        // tau is the caller's: never index outside the model
+  const long long m1 = m0 + 1 > Nf - 1 ? Nf - 1 : m0 + 1;
+  const double fr = fmin(mu - (double)m0, 1.0);
+  const double w0 = 1.0 - fr;
+  const double sg = w0 * sigma[m0] + fr * sigma[m1];
+  for (int i = 0; i < p; ++i) {
+    kq[i * 64] = w0 * refl[m0 * p + i] + fr * refl[m1 * p + i];
+    b[i * 64] = 0.0;
+  }
+  const long long n0 = q * H - 3 * H;
+  for (int t = 0; t < 4 * H; ++t) {
+    const long long n = n0 + t;
+    double f = n >= 0 ? sg * white(seed, n) : 0.0;
+    f = f - kq[(p - 1) * 64] * b[(p - 1) * 64];
+#pragma unroll 4
+    for (int i = p - 1; i >= 1; --i) {
+      const double k = kq[(i - 1) * 64], bp = b[(i - 1) * 64];
+      f = f - k * bp;
+      b[i * 64] = bp + k * f;
+    }
+    b[0] = f;
+    if (t >= 2 * H) Y[(size_t)(t - 2 * H) * nq + qi] = f;
+  }
+}
+
+__device__ __forceinline__ double fade(int u, int H) { return 0.5 - 0.5 * cos(2.0 * M_PI * (double)u / (double)(2 * H)); }
+
+extern "C" __global__ void __launch_bounds__(256)
+    eaqhm_noise_combine_kernel(const double* __restrict__ Y, int H, int q_lo, int nq, int Nq, long long t_lo,
+                               long long t_hi, double* __restrict__ out, int accumulate) {
+  const long long n = t_lo + (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= t_hi) return;
+  const long long q = n / H;
+  const int j = (int)(n - q * H);
+  const int qi = (int)(q - q_lo);
+  double val = fade(H + j, H) * Y[(size_t)(H + j) * nq + qi];
+  if (q + 1 < Nq) val = val + fade(j, H) * Y[(size_t)j * nq + qi + 1];
+  out[n] = accumulate ? out[n] + val : val;
+}
+
+}  // namespace eaqhm
+
+using namespace eaqhm;
+
+static bool noise_shape_ok(int32_t hop, int32_t order) {
+  return hop >= 1 && hop <= 1024 && order >= 1 && order <= 63 && order < 4 * hop;
+}
+
+extern "C" int eaqhm_noise_analyse(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, int32_t order, double* sigma,
+                                   double* refl) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!e || !sigma || !refl || L < 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_analyse: bad argument");
+  if (!noise_shape_ok(hop, order))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_analyse: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop");
+  const int64_t Nf = (L - 1) / hop + 1;
+  if (Nf > INT32_MAX - NA_WAVES) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_analyse: too many frames");
+  const size_t lds = (size_t)NA_WAVES * (NA_PAD + 4 * (size_t)hop) * sizeof(double);
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_noise_analyse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_noise_analyse_kernel, dim3((unsigned)((Nf + NA_WAVES - 1) / NA_WAVES)), dim3(64 * NA_WAVES), lds,
+                     ctx->stream, e, (long long)L, (int)hop, (int)order, (int)Nf, sigma, refl);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
+                                 int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
+                                 int64_t t_hi, double* out, int32_t accumulate) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !tau || !out || Nf < 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: bad argument");
+  if (!noise_shape_ok(hop, order))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop");
+  if (L_out <= 0 || (L_out - 1) / hop + 1 != (int64_t)Nq)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: Nq must be (L_out - 1) / hop + 1");
+  if (t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: [t_lo, t_hi) outside [0, L_out)");
+  // the frames that cover [t_lo, t_hi): sample n' lies in frames n' / hop and n' / hop + 1
+  const int64_t q_lo = t_lo / hop;
+  int64_t q_hi = (t_hi - 1) / hop + 1;
+  if (q_hi > Nq - 1) q_hi = Nq - 1;
+  const int nq = (int)(q_hi - q_lo + 1);
+  if (int rc = ctx->reserve((size_t)nq * 2 * hop * sizeof(double))) return rc;
+  double* Y = (double*)ctx->scratch;
+  const size_t lds = (size_t)2 * order * 64 * sizeof(double);
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_noise_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_noise_filter_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64), lds, ctx->stream, sigma, refl,
+                     (int)Nf, (int)hop, (int)order, tau, (unsigned long long)seed, (int)q_lo, nq, Y);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(eaqhm_noise_combine_kernel, dim3((unsigned)((t_hi - t_lo + 255) / 256)), dim3(256), 0, ctx->stream,
+                     (const double*)Y, (int)hop, (int)q_lo, nq, (int)Nq, (long long)t_lo, (long long)t_hi, out,
+                     (int)(accumulate != 0));
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}

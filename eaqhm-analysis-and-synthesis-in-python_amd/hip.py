@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("EAQHM_LIB") or os.path.join(_HERE, "csrc", "libeaqhm_
 _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
 # EAQHM_ABI_VERSION (csrc/eaqhm_common.h) this binding was written for: argument lists change under unchanged names
-ABI_VERSION = 4
+ABI_VERSION = 5
 SYMBOLS = (
     ("eaqhm_ctx_create", C.c_int, [C.POINTER(_P), C.c_int]),
     ("eaqhm_ctx_destroy", C.c_int, [_P]),
@@ -42,6 +42,8 @@ SYMBOLS = (
     ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
                                             _I64, _I64, _P]),
     ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
+    ("eaqhm_noise_analyse", C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
+    ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32]),
 )
 
 
@@ -205,6 +207,13 @@ class Context:
     def model_envelope(self, records, No_ti, Kmax, alpha, freqs, F, out):
         self._ck(self.lib.eaqhm_model_envelope(self.h, _ptr(records), No_ti, Kmax, _ptr(alpha), _ptr(freqs), F,
                                                _ptr(out)))
+
+    def noise_analyse(self, e, L, hop, order, sigma, refl):
+        self._ck(self.lib.eaqhm_noise_analyse(self.h, _ptr(e), L, hop, order, _ptr(sigma), _ptr(refl)))
+
+    def noise_synth(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, accumulate=False):
+        self._ck(self.lib.eaqhm_noise_synth(self.h, _ptr(sigma), _ptr(refl), Nf, hop, order, _ptr(tau), Nq, seed, L_out,
+                                            t_lo, t_hi, _ptr(out), int(bool(accumulate))))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

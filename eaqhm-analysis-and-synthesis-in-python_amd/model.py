@@ -6,13 +6,18 @@
     model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[No_ti, len(freqs)]
     scale_contour(DetComponents, fs, times_s, values) -> float64[No_ti]
     contour_time_map(rho, beta, step, length) -> dict(rate, gain, C, L_out, rate_min)
+    eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
+    eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0) -> float64[L_out]
+    noise_time_map(hop, L_out, rho) / noise_time_map_contour(hop, tm, step) -> float64[Nq]
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
 also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
-(§9.2).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve, eaqhm_modify_prep, eaqhm_modify_synth or
-eaqhm_modify_synth_curve for contours, eaqhm_model_envelope); there is no CPU path.
+(§9.2).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
+filtered white noise under the same time map (§10).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
+eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours, eaqhm_model_envelope,
+eaqhm_noise_analyse, eaqhm_noise_synth); there is no CPU path.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -20,6 +25,8 @@ from operator import itemgetter
 import numpy as np
 
 SCALE_RANGE = (0.25, 4.0)
+NOISE_MAX_HOP = 1024     # the analysis kernel keeps one 4-hop frame per wave in LDS
+NOISE_MAX_ORDER = 63     # lane l of a wave owns lag l
 
 
 def _cells(rows, mask=None):
@@ -262,7 +269,7 @@ def _device_records(model, dev):
 
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, device_index=0, _ranges=None):
+                   formant_scale=1.0, *, noise=None, noise_seed=0, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -280,6 +287,12 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     the length do not change.  It needs preserve_envelope=True.  A formant contour runs the contour path; the number 1
     leaves the result exactly as it is without a formant scale.
 
+    `noise` (a model from eaQHMNoiseAnalysis of the same signal: its fs and length must be this call's) adds the
+    stochastic component (§10): the LPC model of the residual resynthesised as filtered white noise, seeded by
+    `noise_seed`, under this call's time map, so it is stretched with the sinusoids.  `pitch_scale` and `formant_scale`
+    do not touch the noise.  The result is the sum of the synthesis without `noise` and eaQHMNoiseSynthesis at
+    noise_time_map(...) (noise_time_map_contour for contours), bit for bit.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     model = unpack_model(DetComponents)
@@ -291,6 +304,12 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     alpha = check_formant_scale(model, formant_scale, preserve_envelope)
     # alpha reaches the prep for a formant contour or a number != 1; without the envelope alpha is 1 throughout
     formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
+    if noise is not None:
+        nz = check_noise_model(noise)
+        seed = _seed(noise_seed)
+        if nz["fs"] != fs or nz["length"] != length:
+            raise ValueError("the noise model is of another signal: fs %g, length %d; this call: fs %g, length %d"
+                             % (nz["fs"], nz["length"], fs, length))
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
@@ -325,6 +344,13 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     else:
         for t_lo, t_hi in ranges:
             c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
+    if noise is not None:
+        H = nz["hop"]
+        tau = noise_time_map_contour(H, tm, D) if contour else noise_time_map(H, L_out, rho)
+        sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
+        for t_lo, t_hi in ranges:
+            c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo, t_hi,
+                          out, accumulate=True)
     return out.cpu().numpy()
 
 
@@ -361,4 +387,149 @@ def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=
     f_d = torch.as_tensor(np.ascontiguousarray(f), device=dev)
     out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)
     c.model_envelope(rec, n, K, alpha_d, f_d, len(f), out)
+    return out.cpu().numpy()
+
+
+# ---- the stochastic component
+def _integer(x, name):
+    if isinstance(x, (bool, np.bool_)):
+        raise ValueError("%s must be an integer" % name)
+    try:
+        ok = float(x).is_integer()
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be an integer, got %r" % (name, x))
+    return int(x)
+
+
+def _seed(seed):
+    seed = _integer(seed, "seed")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2**64)")
+    return seed
+
+
+def _noise_shape(hop, order):
+    if not 1 <= hop <= NOISE_MAX_HOP:
+        raise ValueError("hop must be in [1, %d], got %d" % (NOISE_MAX_HOP, hop))
+    if not 1 <= order <= NOISE_MAX_ORDER or order >= 4 * hop:
+        raise ValueError("order must be in [1, %d] and < 4 * hop (%d), got %d" % (NOISE_MAX_ORDER, 4 * hop, order))
+
+
+def check_noise_analysis_arguments(s, s_recon, fs, order=None, hop=None):
+    """Validates everything eaQHMNoiseAnalysis gets (no device work): returns (e, fs, hop, order) with the residual
+    e = s - s_recon as float64.  hop defaults to round(0.005 fs), order to min(63, 2 + round(fs / 1000))."""
+    fs = _sample_rate(fs)
+    a = _numeric_1d(s, "s")
+    b = _numeric_1d(s_recon, "s_recon")
+    if len(a) == 0 or len(a) != len(b):
+        raise ValueError("s and s_recon must be non-empty and of the same length, got %d and %d" % (len(a), len(b)))
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
+        raise ValueError("s and s_recon must be finite")
+    hop = int(round(0.005 * fs)) if hop is None else _integer(hop, "hop")
+    order = min(NOISE_MAX_ORDER, 2 + int(round(fs / 1000.0))) if order is None else _integer(order, "order")
+    _noise_shape(hop, order)
+    return a - b, fs, hop, order
+
+
+def check_noise_model(noise):
+    """Validates a noise model (no device work): returns it with sigma float64[Nf] (finite, >= 0), refl
+    float64[Nf, order] (|k| < 1) contiguous, hop, order and length ints, fs a float, Nf = (length - 1) // hop + 1."""
+    if not isinstance(noise, dict) or not all(k in noise for k in ("sigma", "refl", "hop", "order", "fs", "length")):
+        raise ValueError("a noise model is the dict eaQHMNoiseAnalysis returns: sigma, refl, hop, order, fs, length")
+    hop, order, length = (_integer(noise[k], k) for k in ("hop", "order", "length"))
+    _noise_shape(hop, order)
+    fs = _sample_rate(noise["fs"])
+    sigma = _numeric_1d(noise["sigma"], "sigma")
+    refl = np.asarray(noise["refl"])
+    if refl.dtype.kind not in "iuf" or refl.ndim != 2:
+        raise ValueError("refl must be a 2-D array of numbers")
+    refl = np.ascontiguousarray(refl, dtype=np.float64)
+    if length < 1 or len(sigma) != (length - 1) // hop + 1 or refl.shape != (len(sigma), order):
+        raise ValueError("a noise model of %d samples at hop %d has %d frames: sigma must be (Nf,), refl (Nf, %d)"
+                         % (length, hop, (max(length, 1) - 1) // hop + 1, order))
+    if not np.all(np.isfinite(sigma)) or np.any(sigma < 0):
+        raise ValueError("sigma must be finite and >= 0")
+    if not np.all(np.abs(refl) < 1):     # also rejects NaN
+        raise ValueError("reflection coefficients must lie inside (-1, 1)")
+    return dict(sigma=np.ascontiguousarray(sigma), refl=refl, hop=hop, order=order, fs=fs, length=length)
+
+
+def check_noise_synthesis_arguments(noise, tau, L_out, seed=0):
+    """Validates everything eaQHMNoiseSynthesis gets (no device work): returns (model, tau, L_out, seed); tau is
+    float64[(L_out - 1) // hop + 1], finite and >= 0."""
+    nz = check_noise_model(noise)
+    L_out = _integer(L_out, "L_out")
+    if L_out < 1:
+        raise ValueError("L_out must be >= 1")
+    tau = _numeric_1d(tau, "tau")
+    Nq = (L_out - 1) // nz["hop"] + 1
+    if len(tau) != Nq:
+        raise ValueError("tau must have one value per output frame ((L_out - 1) // hop + 1 = %d), got %d"
+                         % (Nq, len(tau)))
+    if not np.all(np.isfinite(tau)) or np.any(tau < 0):
+        raise ValueError("tau must be finite and >= 0")
+    return nz, np.ascontiguousarray(tau), L_out, _seed(seed)
+
+
+def noise_time_map(hop, L_out, rho):
+    """tau of eaQHMNoiseSynthesis for a time scale rho: output frame centre q hop lies at (q hop) / rho of the analysed
+    signal.  Returns float64[(L_out - 1) // hop + 1]."""
+    return (np.arange((int(L_out) - 1) // int(hop) + 1, dtype=np.float64) * float(hop)) / float(rho)
+
+
+def noise_time_map_contour(hop, tm, step):
+    """tau of eaQHMNoiseSynthesis for a contour: the inverse of contour_time_map's map (`tm`) at the output frame
+    centres x = q hop.  With j the last knot at or before x (C_j <= x), tau = j step + (x - C_j) / rate_j; past the
+    last knot rate is rho_{n-1}, as contour_time_map stores it."""
+    x = np.arange((int(tm["L_out"]) - 1) // int(hop) + 1, dtype=np.float64) * float(hop)
+    C = np.asarray(tm["C"], dtype=np.float64)
+    j = np.clip(np.searchsorted(C, x, side="right") - 1, 0, len(C) - 1)
+    return j * float(step) + (x - C[j]) / np.asarray(tm["rate"], dtype=np.float64)[j]
+
+
+def eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0):
+    """The stochastic component of a signal: an all-pole (LPC) envelope and a gain for every frame of
+    the residual e = s - s_recon.  `s` is the signal the analysis saw (read_signal(wav, fc)[1]), `s_recon` what
+    eaQHMAnalysisAndSynthesis returned for it.  Frames are `hop` samples apart (default round(0.005 fs): 5 ms) and
+    4 hop long (Hann); `order` (default min(63, 2 + round(fs / 1000))) is at most 63 and below 4 hop.
+
+    Returns dict(sigma=float64[Nf] the standard deviation of the white excitation (0: a silent frame),
+    refl=float64[Nf, order] the reflection coefficients k_1..k_p, hop, order, fs, length), Nf = (len(s) - 1) // hop + 1.
+    Reflection coefficients, not the polynomial, are the stored form: a blend of two stable sets is stable."""
+    e, fs, hop, order = check_noise_analysis_arguments(s, s_recon, fs, order, hop)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    L = len(e)
+    Nf = (L - 1) // hop + 1
+    e_d = torch.as_tensor(np.ascontiguousarray(e), device=dev)
+    sigma = torch.empty(Nf, dtype=torch.float64, device=dev)
+    refl = torch.empty((Nf, order), dtype=torch.float64, device=dev)
+    c.noise_analyse(e_d, L, hop, order, sigma, refl)
+    return dict(sigma=sigma.cpu().numpy(), refl=refl.cpu().numpy(), hop=hop, order=order, fs=fs, length=L)
+
+
+def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0, _ranges=None):
+    """Synthesises L_out samples of noise from a model of eaQHMNoiseAnalysis: white noise, a pure
+    function of `seed` (0 <= seed < 2**64) and the sample index, through the all-pole lattice of each output frame and
+    cross-faded between frames.  `tau[q]`, one value per output frame q = 0 .. (L_out - 1) // hop, is the position (in
+    samples of the analysed signal, finite and >= 0) the output sample q hop maps back to: noise_time_map(hop, L_out,
+    rho) for a time scale, noise_time_map_contour for a contour; sigma and the reflection coefficients are interpolated
+    linearly between the model's frames there.
+
+    `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
+    Returns float64[L_out]."""
+    nz, tau, L_out, seed = check_noise_synthesis_arguments(noise, tau, L_out, seed)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
+    out = torch.empty(L_out, dtype=torch.float64, device=dev)
+    for t_lo, t_hi in ([(0, L_out)] if _ranges is None else _ranges):
+        c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
+                      int(t_lo), int(t_hi), out)
     return out.cpu().numpy()

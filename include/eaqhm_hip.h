@@ -228,6 +228,28 @@ int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_
 int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* alpha,
                          const double* freqs, int32_t F, double* out);
 
+/* the stochastic component: an LPC model of the residual and its resynthesis as filtered noise (ABI 5) -----------------
+ * Not in the reference; the definition is DESIGN.md "The stochastic component" (§10).  hop = H, order = p,
+ * 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop.
+ * eaqhm_noise_analyse (kernel: one wave per frame, the windowed frame in LDS, lane l owns lag l, Levinson-Durbin in the
+ *   wave) models e = s - s_recon (double[L]) in frames m = 0 .. Nf-1, Nf = (L-1)/hop + 1, centred at m hop, 4 hop long:
+ *   sigma      double[Nf]         standard deviation of the white excitation; 0 for a silent frame
+ *   refl       double[Nf][order]  reflection coefficients k_1..k_p of A(z); zeros from the first |k_i| >= 1 on
+ * eaqhm_noise_synth (kernels: all-pole lattice, one lane per output frame; cross-fade of the two frames covering a
+ *   sample) writes out[t_lo, t_hi) of the L_out-sample noise signal (out is double[L_out]); accumulate != 0 adds it to
+ *   what out holds instead.  The excitation is a pure function of (seed, sample index), so the result does not depend
+ *   on how [0, L_out) is split into ranges.
+ *   tau        double[Nq]         Nq = (L_out-1)/hop + 1: the position, in samples of the analysed signal, that output
+ *                                 frame centre q hop maps back to (finite, >= 0); sigma and refl are interpolated
+ *                                 linearly between frames floor(tau/hop) and the next, held past the last frame
+ * EAQHM_EINVAL for null pointers, L < 1, Nf < 1, hop or order outside the limits above, Nq != (L_out-1)/hop + 1 and a
+ * range outside [0, L_out).                                                                                          */
+int eaqhm_noise_analyse(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, int32_t order, double* sigma,
+                        double* refl);
+int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop, int32_t order,
+                      const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo, int64_t t_hi,
+                      double* out, int32_t accumulate);
+
 #ifdef __cplusplus
 }
 #endif

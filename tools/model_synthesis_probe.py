@@ -2,7 +2,7 @@
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
-                                          [--out FILE]
+                                          [--noise] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -10,7 +10,10 @@ eaqhm_modify_synth_curve): unit contours, rho a 0.5 Hz sinusoid
 beta ramping 0.85 -> 1.2, and both varying; eval_ms_per_msample normalises the eval time by the output length.
 --formant adds the formant scale (eaqhm_modify_prep with alpha) at rho = 1: alpha in {0.85, 1.2} x
 beta in {1, 1.25} with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with eaqhm_modify_synth_curve;
-ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  EAQHM_LIB selects another build of
+ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  --noise adds the stochastic
+component on the workload's own residual: eaqhm_noise_analyse, and eaqhm_noise_synth at rho in
+{0.5, 1, 2} beside the deterministic prep + eval of the same session at the same rho (beta = 1); every time there is
+the median of three windows of 20 launches, with the max - min of the three.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -37,14 +40,15 @@ def analyse(workload):
     grid = np.load(os.path.join(GOLDEN, fix))[key]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, workload + ".wav")
-        wavfile.write(path, fs, synth_speech_int16(60.0, fs))
+        x = synth_speech_int16(60.0, fs)
+        wavfile.write(path, fs, x)
         s_recon, _, _, _, eng = eaqhm_amd.eaQHMAnalysisAndSynthesis(path, "female", maxAdpt=adpt, printPrompts=False,
                                                                     pitch_track=grid, _return_engine=True)
     fin = eng.final_arrays()
     t = time.perf_counter()
     det = pack_results(eng.plan, fin)
     t_pack = time.perf_counter() - t
-    return fs, len(s_recon), det, pack_arrays(eng.plan, fin), t_pack
+    return fs, len(s_recon), det, pack_arrays(eng.plan, fin), t_pack, x / 32768.0 - s_recon
 
 
 def timed(torch, fn, reps):
@@ -87,9 +91,9 @@ def prepare(torch, det, fs, L, reps):
                 t_unpack=t_unpack)
 
 
-def probe(workload, reps, contours=False, formant=False):
+def probe(workload, reps, contours=False, formant=False, noise=False):
     import torch
-    fs, L, det, arrays, t_pack = analyse(workload)
+    fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
     c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
     n, K, D, t_eval, t_unpack = st["n"], st["K"], st["D"], st["t_eval"], st["t_unpack"]
@@ -115,7 +119,44 @@ def probe(workload, reps, contours=False, formant=False):
         res["contours"] = probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval, reps)
     if formant:
         res["formant"] = formant_rows(torch, st, reps)
+    if noise:
+        res["noise"] = noise_rows(torch, st, residual)
     return res
+
+
+def noise_rows(torch, st, residual, reps=20, runs=3):
+    """The stochastic component on `residual` (the workload's s - s_recon, default hop and order): device time of
+    eaqhm_noise_analyse, and of eaqhm_noise_synth (lattice + cross-fade) at rho in {0.5, 1, 2} beside the deterministic
+    eaqhm_modify_prep + eaqhm_modify_synth at the same rho and beta = 1.  Each time: median of `runs` windows of `reps`
+    launches, and their max - min."""
+    from eaqhm_amd.model import check_noise_analysis_arguments, noise_time_map
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, fs, L = st["n"], st["K"], st["D"], st["fs"], st["L"]
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    e, _, H, p = check_noise_analysis_arguments(residual, np.zeros(len(residual)), fs)
+    Nf = (L - 1) // H + 1
+    e_d = torch.as_tensor(e, device=dev)
+    sigma = torch.empty(Nf, dtype=torch.float64, device=dev)
+    refl = torch.empty((Nf, p), dtype=torch.float64, device=dev)
+    t_an, s_an = med(lambda: c.noise_analyse(e_d, L, H, p, sigma, refl))
+    one_d = torch.ones(n, dtype=torch.float64, device=dev)
+    t_prep, _ = med(lambda: c.modify_prep(rec, code, mom, n, K, D, fs, one_d, None, None, True, amp, R, ph0))
+    rows = [dict(setting="analysis", hop=H, order=p, frames=Nf, analyse_ms=t_an, analyse_spread_ms=s_an)]
+    for rho in (0.5, 1.0, 2.0):
+        Lo = int(np.rint(rho * L))
+        tau = torch.as_tensor(noise_time_map(H, Lo, rho), device=dev)
+        out = torch.empty(Lo, dtype=torch.float64, device=dev)
+        t_ns, s_ns = med(lambda: c.noise_synth(sigma, refl, Nf, H, p, tau, len(tau), 0, Lo, 0, Lo, out))
+        t_det, s_det = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, 1.0, Lo, 0, Lo, out))
+        rows.append(dict(setting="rho%g" % rho, out_frames=len(tau), noise_synth_ms=t_ns, noise_synth_spread_ms=s_ns,
+                         det_eval_ms=t_det, det_eval_spread_ms=s_det, det_total_ms=round(t_prep + t_det, 4),
+                         noise_to_det_eval=round(t_ns / t_det, 3)))
+    return rows
 
 
 def formant_rows(torch, st, reps):
@@ -196,9 +237,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--contours", action="store_true", help="also time the contour kernels")
     ap.add_argument("--formant", action="store_true", help="also time the formant prep kernels")
+    ap.add_argument("--noise", action="store_true", help="also time the noise analysis and synthesis kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps, a.contours, a.formant) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours, a.formant, a.noise) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
