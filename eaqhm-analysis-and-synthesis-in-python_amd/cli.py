@@ -8,7 +8,7 @@ resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wa
 --pitch-scale-curve FILE take a breakpoint curve instead (two whitespace-separated columns, seconds and value; lines
 starting with # are comments), turned into a per-instant contour with model.scale_contour.  --formant-scale A /
 --formant-scale-curve FILE move the spectral envelope by A; they need the envelope, so either one with
---no-envelope is an error.  --noise (with --noise-seed N) models the residual input - reconstruction
+--no-envelope is an error.  --phase shape keeps the waveform shape under those scales.  --noise (with --noise-seed N) models the residual input - reconstruction
 (model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
 writes `<name>_resynthesis.wav`: model + noise at unit scales."""
 import argparse
@@ -49,6 +49,9 @@ def parser():
                      help="like --formant-scale, with a curve: lines 'seconds value' (# comments)")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
+    ap.add_argument("--phase", choices=("independent", "shape"), default="independent",
+                    help="with a scale flag: 'shape' keeps the harmonics' phases relative to the fundamental (the "
+                         "waveform shape of a pitch period) at every scale; 'independent' scales each partial's own")
     ap.add_argument("--noise", action="store_true",
                     help="model the residual as filtered noise and add it to <name>_modified.wav; without a scale flag "
                          "write <name>_resynthesis.wav (model + noise)")
@@ -108,8 +111,8 @@ def main(argv=None):
                 from .prologue import read_signal
                 nz = eaQHMNoiseAnalysis(read_signal(a.wav, a.fc)[1], s_recon, fs)
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
-                                   preserve_envelope=not a.no_envelope, formant_scale=alpha, noise=nz,
-                                   noise_seed=a.noise_seed or 0)
+                                   preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
+                                   noise=nz, noise_seed=a.noise_seed or 0)
             out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)

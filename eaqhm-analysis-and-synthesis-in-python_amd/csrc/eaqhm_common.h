@@ -29,6 +29,11 @@ struct eaqhm_ctx {
     snprintf(err, sizeof(err), "%s", msg);
     return code;
   }
+  // fmt holds one %s: the entry point's name (entry points that share their checks)
+  int failf(int code, const char* fmt, const char* who) {
+    snprintf(err, sizeof(err), fmt, who);
+    return code;
+  }
   // grow-only scratch; growing synchronises the stream first (never happens in steady state)
   int reserve(size_t bytes) {
     if (bytes <= scratch_bytes) return EAQHM_OK;

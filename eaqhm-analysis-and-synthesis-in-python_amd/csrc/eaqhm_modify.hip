@@ -16,6 +16,9 @@
 //                              a0 spline and the sum over slots in slot order.
 //   eaqhm_modify_eval_curve_kernel  the eval body with the cumulative time map C of the contours in place of
 //                              tau = n'/rho (eaqhm_modify_body.inc holds the body of both).
+//   eaqhm_modify_eval_shape_kernel, eaqhm_modify_eval_curve_shape_kernel  the two eval bodies once more with the
+//                              shape-invariant phase of DESIGN.md §11: Psi unweighted plus (k+1) times the phase
+//                              advance of the fundamental, from the per-instant tracks f0 and S.
 //   eaqhm_model_envelope_kernel  reads the envelope itself out on a frequency grid.
 #include "eaqhm_common.h"
 #include "eaqhm_pieces.h"
@@ -384,13 +387,34 @@ struct CurveMap {
 };
 
 
+// The shape-invariant phase mode of DESIGN.md §11: the fundamental track f0_i (Hz) and its phase advance S_i (cycles,
+// in [0, 1)) per instant.  Inside interval j <= No_ti - 2 at offset r the advance is s = S_j + (g_j - 1) (f0_j r +
+// (f0_{j+1} - f0_j) r^2 / (2 D)) / fs, the same for every slot: stage 0 forms it once per sample, as S_j + r (c1 + r c2),
+// and stage 2 adds 2 pi (k+1) s to the phase of each slot before the cosines.  Past the last knot no slot is in a run: S_{n-1} serves.
+struct MShape { const double* f0; const double* S; };
+
+__device__ inline double shape_advance(const MShape& Sh, int j, double r, double gm1, int D, double fs) {
+  const double sf = Sh.f0[j], sgm = gm1 / fs;
+  return Sh.S[j] + r * (sgm * sf + r * (sgm * (Sh.f0[j + 1] - sf) / (2.0 * (double)D)));
+}
+
+// ---- the phase term of the shape kernels (§11): Psi weighs 1 and stage 2 adds 2 pi (k+1) s to each phase; s of the
+// block's samples [TBS] follows the time-map rows in LDS (MAP_CROW doubles per row).  Without it every macro is empty.
+#define EAQHM_MODIFY_SHAPE 0
+#define SHAPE_WEIGHT(g) g
+#define SHAPE_INIT
+#define SHAPE_ADD
+#define SHAPE_SAMPLE
+
 // ---- the scalar kernels: tau = n'/rho, phase weight beta rho
 #define EAQHM_MODIFY_CURVE 0
+#define MAP_CROW 0
+#define MAP_G E.beta * E.rho
 #define MAP_INIT
 #define MAP_LOCATE(n, j, r) locate(n, E.rho, D, j, r)
 #define MAP_BOUND
 #define MAP_STAGE
-#define MAP_BLOCK_WEIGHT const double br = E.beta * E.rho;
+#define MAP_BLOCK_WEIGHT const double br = SHAPE_WEIGHT(E.beta * E.rho);
 #define MAP_INTERVAL_WEIGHT
 #define MAP_PSI(loc) Rj + (loc)
 #define MAP_OFF ph0
@@ -401,7 +425,10 @@ struct CurveMap {
 #define MAP_ISO_AT(i) (long long)rint(E.rho * ((double)i * (double)D)) == n
 #define MAP_TAU (double)n / E.rho
 #include "eaqhm_modify_body.inc"
+#include "eaqhm_modify_shape.inc"   // the same map with the shape term: eaqhm_modify_eval_shape_kernel
 #undef EAQHM_MODIFY_CURVE
+#undef MAP_CROW
+#undef MAP_G
 #undef MAP_INIT
 #undef MAP_LOCATE
 #undef MAP_BOUND
@@ -417,12 +444,14 @@ struct CurveMap {
 // ---- the contour kernels: R holds the weighted phase G, the phase weight g_j is per interval, and
 // the staged rows [NR][3] (C_j, r_j, g_j) follow the codes
 #define EAQHM_MODIFY_CURVE 1
+#define MAP_CROW 3
+#define MAP_G Cu.gain[j]
 #define MAP_INIT CurveMap Mp{Cu, A.No_ti - 1, D, 0, A.No_ti - 2, nullptr, 0, -1};
 #define MAP_LOCATE(n, j, r) Mp.locate(n, D, j, r)
 #define MAP_BOUND Mp.bound(jfirst, jlast, A.No_ti);
 #define MAP_STAGE Mp.stage((double*)(ccode + (((size_t)NR * K + 7) & ~(size_t)7)), C.r0, C.r1, tid, blockDim.x);
 #define MAP_BLOCK_WEIGHT
-#define MAP_INTERVAL_WEIGHT const double br = Mp.gv(j), o = ph0 + Rj;
+#define MAP_INTERVAL_WEIGHT const double br = SHAPE_WEIGHT(Mp.gv(j)), o = ph0 + Rj;
 #define MAP_PSI(loc) (loc)
 #define MAP_OFF o
 #define MAP_ISO_RANGE                                                                                               \
@@ -431,7 +460,10 @@ struct CurveMap {
 #define MAP_ISO_AT(i) (long long)rint(Mp.Cv(i)) == n
 #define MAP_TAU Mp.tau(sj[s], sr[s])
 #include "eaqhm_modify_body.inc"
+#include "eaqhm_modify_shape.inc"   // eaqhm_modify_eval_curve_shape_kernel
 #undef EAQHM_MODIFY_CURVE
+#undef MAP_CROW
+#undef MAP_G
 #undef MAP_INIT
 #undef MAP_LOCATE
 #undef MAP_BOUND
@@ -494,19 +526,20 @@ static int modify_scan(eaqhm_ctx* ctx, const uint8_t* code, int32_t No_ti, int32
 
 // samples per block of eaqhm_modify_eval_kernel and staged rows: the largest of 64/32/16 whose tables fit; the staged
 // rows follow the block's tau-span (TBS / rho samples), capped by the LDS budget (rows beyond it are read from memory).
-// The contour kernel's staged rows also hold C_j, r_j, g_j (crow = 3 doubles per row; 0 for the scalar kernel).
-static size_t modify_lds_bytes(int K, int step, int tbs, int nr, int crow) {
+// The contour kernel's staged rows also hold C_j, r_j, g_j (crow = 3 doubles per row; 0 for the scalar kernel); the
+// shape kernels keep one more double per sample (shape = 1).
+static size_t modify_lds_bytes(int K, int step, int tbs, int nr, int crow, int shape) {
   return (((size_t)step + 2) & ~(size_t)1) * 8 + (size_t)K * (tbs + 1) * 8 + (size_t)tbs * 8 +
          (size_t)nr * ((3 * (size_t)K + 1) + (K + 1)) * 8 + (((size_t)tbs + 1) & ~(size_t)1) * 4 +
-         (((size_t)nr * K + 7) & ~(size_t)7) + (size_t)nr * crow * 8;
+         (((size_t)nr * K + 7) & ~(size_t)7) + (size_t)nr * crow * 8 + (size_t)tbs * shape * 8;
 }
 
 // rho: the smallest rate of the time map (the contour's fewest output samples per knot interval)
-static int modify_block_samples(int Kmax, int step, double rho, int crow, size_t* lds_bytes, int* nr) {
+static int modify_block_samples(int Kmax, int step, double rho, int crow, int shape, size_t* lds_bytes, int* nr) {
   for (int tbs = 64; tbs >= 16; tbs >>= 1) {
     int NR = (int)ceil((double)(tbs - 1) / (rho * (double)step)) + 6;
-    while (NR > 4 && modify_lds_bytes(Kmax, step, tbs, NR, crow) > 78 * 1024) --NR;
-    const size_t bytes = modify_lds_bytes(Kmax, step, tbs, NR, crow);
+    while (NR > 4 && modify_lds_bytes(Kmax, step, tbs, NR, crow, shape) > 78 * 1024) --NR;
+    const size_t bytes = modify_lds_bytes(Kmax, step, tbs, NR, crow, shape);
     if (bytes <= 78 * 1024 || tbs == 16) {
       *lds_bytes = bytes; *nr = NR;
       return tbs;
@@ -515,58 +548,112 @@ static int modify_block_samples(int Kmax, int step, double rho, int crow, size_t
   return 16;
 }
 
-extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                  const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
-                                  int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
-                                  int64_t t_hi, double* out) {
+// the scalar eval launch: eaqhm_modify_eval_kernel, or eaqhm_modify_eval_shape_kernel when sh is given
+static int modify_synth_launch(eaqhm_ctx* ctx, const char* who, const double* records, const uint8_t* code,
+                               const double* mom, const double* amp, const double* R, const double* ph0, int32_t No_ti,
+                               int32_t Kmax, int32_t step, double fs, double rho, double beta, int64_t L_out,
+                               int64_t t_lo, int64_t t_hi, double* out, const MShape* sh) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !amp || !R || !ph0 || !out || No_ti < 4 || Kmax <= 0 || step <= 0 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: bad argument");
+  if (!records || !code || !mom || !amp || !R || !ph0 || !out || No_ti < 4 || Kmax <= 0 || step <= 0 ||
+      !finite_pos(fs) || (sh && (!sh->f0 || !sh->S)))
+    return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
   if (!finite_pos(rho) || !finite_pos(beta))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: rho and beta must be finite and > 0");
+    return ctx->failf(EAQHM_EINVAL, "%s: rho and beta must be finite and > 0", who);
   if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: [t_lo, t_hi) outside [0, L_out)");
+    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
   size_t lds_bytes = 0;
   int NR = 0;
-  const int TBS = modify_block_samples(Kmax, step, rho, 0, &lds_bytes, &NR);
-  if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: Kmax too large for the LDS tables");
+  const int TBS = modify_block_samples(Kmax, step, rho, 0, sh ? 1 : 0, &lds_bytes, &NR);
+  if (lds_bytes > 160 * 1024) return ctx->failf(EAQHM_EINVAL, "%s: Kmax too large for the LDS tables", who);
   const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, rho, beta, (long long)t_lo,
                     (long long)t_hi, out};
   const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_bytes));
-  hipLaunchKernelGGL(eaqhm_modify_eval_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, TBS, NR);
+  if (sh) {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_shape_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(eaqhm_modify_eval_shape_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, *sh,
+                       TBS, NR);
+  } else {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds_bytes));
+    hipLaunchKernelGGL(eaqhm_modify_eval_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, TBS, NR);
+  }
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
 
-// ---- time and pitch scale contours
+extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                  const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
+                                  int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
+                                  int64_t t_hi, double* out) {
+  return modify_synth_launch(ctx, "eaqhm_modify_synth", records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta,
+                             L_out, t_lo, t_hi, out, nullptr);
+}
+
+// ---- shape-invariant phase: the prep ran without gain
+extern "C" int eaqhm_modify_synth_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                        const double* amp, const double* R, const double* ph0, int32_t No_ti,
+                                        int32_t Kmax, int32_t step, double fs, double rho, double beta, int64_t L_out,
+                                        int64_t t_lo, int64_t t_hi, double* out, const double* f0, const double* S) {
+  const MShape sh{f0, S};
+  return modify_synth_launch(ctx, "eaqhm_modify_synth_shape", records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho,
+                             beta, L_out, t_lo, t_hi, out, &sh);
+}
+
+// ---- time and pitch scale contours; with sh the shape kernel (§11)
+static int modify_synth_curve_launch(eaqhm_ctx* ctx, const char* who, const double* records, const uint8_t* code,
+                                     const double* mom, const double* amp, const double* R, const double* ph0,
+                                     int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* C,
+                                     const double* rate, const double* gain, double rate_min, int64_t L_out,
+                                     int64_t t_lo, int64_t t_hi, double* out, const MShape* sh) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !code || !mom || !amp || !R || !ph0 || !C || !rate || !gain || !out || No_ti < 4 || Kmax <= 0 ||
+      step <= 0 || !finite_pos(fs) || (sh && (!sh->f0 || !sh->S)))
+    return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
+  if (!finite_pos(rate_min)) return ctx->failf(EAQHM_EINVAL, "%s: rate_min must be finite and > 0", who);
+  if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
+    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
+  size_t lds_bytes = 0;
+  int NR = 0;
+  const int TBS = modify_block_samples(Kmax, step, rate_min, 3, sh ? 1 : 0, &lds_bytes, &NR);
+  if (lds_bytes > 160 * 1024) return ctx->failf(EAQHM_EINVAL, "%s: Kmax too large for the LDS tables", who);
+  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, 0.0, 0.0, (long long)t_lo,
+                    (long long)t_hi, out};
+  const MCurve Cu{C, rate, gain};
+  const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
+  if (sh) {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_shape_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(eaqhm_modify_eval_curve_shape_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E,
+                       Cu, *sh, TBS, NR);
+  } else {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(eaqhm_modify_eval_curve_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu,
+                       TBS, NR);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
 extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                                         const double* amp, const double* R, const double* ph0, int32_t No_ti,
                                         int32_t Kmax, int32_t step, double fs, const double* C, const double* rate,
                                         const double* gain, double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi,
                                         double* out) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !amp || !R || !ph0 || !C || !rate || !gain || !out || No_ti < 4 || Kmax <= 0 ||
-      step <= 0 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: bad argument");
-  if (!finite_pos(rate_min)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: rate_min must be finite and > 0");
-  if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: [t_lo, t_hi) outside [0, L_out)");
-  size_t lds_bytes = 0;
-  int NR = 0;
-  const int TBS = modify_block_samples(Kmax, step, rate_min, 3, &lds_bytes, &NR);
-  if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth_curve: Kmax too large for the LDS tables");
-  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, 0.0, 0.0, (long long)t_lo,
-                    (long long)t_hi, out};
-  const MCurve Cu{C, rate, gain};
-  const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_bytes));
-  hipLaunchKernelGGL(eaqhm_modify_eval_curve_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu,
-                     TBS, NR);
-  HIP_TRY(ctx, hipGetLastError());
-  return EAQHM_OK;
+  return modify_synth_curve_launch(ctx, "eaqhm_modify_synth_curve", records, code, mom, amp, R, ph0, No_ti, Kmax, step,
+                                   fs, C, rate, gain, rate_min, L_out, t_lo, t_hi, out, nullptr);
+}
+
+extern "C" int eaqhm_modify_synth_curve_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
+                                              const double* mom, const double* amp, const double* R, const double* ph0,
+                                              int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* C,
+                                              const double* rate, const double* gain, double rate_min, int64_t L_out,
+                                              int64_t t_lo, int64_t t_hi, double* out, const double* f0,
+                                              const double* S) {
+  const MShape sh{f0, S};
+  return modify_synth_curve_launch(ctx, "eaqhm_modify_synth_curve_shape", records, code, mom, amp, R, ph0, No_ti, Kmax,
+                                   step, fs, C, rate, gain, rate_min, L_out, t_lo, t_hi, out, &sh);
 }
 
 // ---- envelope readout

@@ -1,19 +1,29 @@
-// eaqhm_modify_body.inc — the eval kernel body of eaqhm_modify.hip, compiled twice: EAQHM_MODIFY_CURVE 0 gives
-// eaqhm_modify_eval_kernel (DESIGN.md §9), 1 gives eaqhm_modify_eval_curve_kernel (§9.1).  The time map enters the body
-// through the MAP_* macros that eaqhm_modify.hip defines for each variant.  The body is shared as text rather than as an
-// inlined device template because inlining reorders the scalar kernel's code and costs it an occupancy step (§9.1).
+// eaqhm_modify_body.inc — the eval kernel body of eaqhm_modify.hip, compiled four times: EAQHM_MODIFY_CURVE 0 gives
+// eaqhm_modify_eval_kernel (DESIGN.md §9), 1 gives eaqhm_modify_eval_curve_kernel (§9.1); with EAQHM_MODIFY_SHAPE 1
+// they become eaqhm_modify_eval_shape_kernel and eaqhm_modify_eval_curve_shape_kernel (§11).  The time map enters the
+// body through the MAP_* macros and the shape-invariant phase term through the SHAPE_* macros (empty without it) that
+// eaqhm_modify.hip defines for each variant.  The body is shared as text rather than as an inlined device template
+// because inlining reorders the scalar kernel's code and costs it an occupancy step (§9.1).
 // No include guard: included once per variant.
 
 // ------------------------------------------------------------------------------------------------
 // Block of TBS consecutive output samples x all slots.
-//   stage 0  per sample: interval j and offset r (LDS).
+//   stage 0  per sample: interval j and offset r (LDS); the shape kernels also the fundamental's phase advance s(n') in
+//            cycles (§11).
 //   stage 1  one thread per (interval, slot) touching the block: the interval's local phase
 //            Psi(u) = R_j + sum_{v=1..u} w(v) - sum_{v=0..u} sin(pi v/D) er, u = 0..D, in the eval kernel's summation
 //            order; at each of the block's samples in the interval the phase P0 + beta rho ((1-fr) Psi(u0) + fr Psi(u0+1))
-//            goes to X[k][s].  A run's last knot (tau = c_b) is the end u = D of its last interval.
-//   stage 2  one thread per (sample, slot group): amplitude, A cos(phase), isolated knots; then one thread per sample
-//            adds the slots in slot order and the a0 spline.
-#if EAQHM_MODIFY_CURVE
+//            goes to X[k][s].  A run's last knot (tau = c_b) is the end u = D of its last interval.  The shape kernels
+//            weigh Psi by 1 (§11).
+//   stage 2  one thread per (sample, slot group): amplitude, A cos(phase), isolated knots (the shape kernels first add
+//            2 pi (k+1) s(n') to the phases of their cells); then one thread per sample adds the slots in slot order
+//            and the a0 spline.
+#if EAQHM_MODIFY_CURVE && EAQHM_MODIFY_SHAPE
+extern "C" __global__ void __launch_bounds__(256)
+    eaqhm_modify_eval_curve_shape_kernel(MEvalArgs E, MCurve Cu, MShape Sh, int TBS, int NR) {
+#elif EAQHM_MODIFY_SHAPE
+extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_shape_kernel(MEvalArgs E, MShape Sh, int TBS, int NR) {
+#elif EAQHM_MODIFY_CURVE
 extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_curve_kernel(MEvalArgs E, MCurve Cu, int TBS, int NR) {
 #else
 extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEvalArgs E, int TBS, int NR) {
@@ -33,6 +43,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEval
   const long long t1 = (t0 + TBS < E.t_hi) ? (t0 + TBS) : E.t_hi;
   const int ns = (int)(t1 - t0);
   MAP_INIT
+  SHAPE_INIT
   int jfirst, jlast;
   double rdummy;
   MAP_LOCATE(t0, jfirst, rdummy);
@@ -58,6 +69,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEval
     int j; double r;
     MAP_LOCATE(t0 + s, j, r);
     sj[s] = j; sr[s] = r;
+    SHAPE_SAMPLE
   }
   __syncthreads();
   MAP_BLOCK_WEIGHT
@@ -118,6 +130,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEval
     const int j = sj[s];
     const double r = sr[s];
     MAP_ISO_RANGE
+    SHAPE_ADD
     for (int k = g; k < K; k += G) {
       CSlot Sl{A, C, k};
       auto inrun = [&](int q) { return q >= 0 && q <= A.No_ti - 2 && Sl.code(q) != 0 && Sl.code(q + 1) != 0; };

@@ -41,6 +41,10 @@ SYMBOLS = (
                                       _P]),
     ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
                                             _I64, _I64, _P]),
+    ("eaqhm_modify_synth_shape", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64,
+                                            _I64, _P, _P, _P]),
+    ("eaqhm_modify_synth_curve_shape", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64,
+                                                  _I64, _I64, _I64, _P, _P, _P]),
     ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
     ("eaqhm_noise_analyse", C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
     ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32]),
@@ -203,6 +207,19 @@ class Context:
         self._ck(self.lib.eaqhm_modify_synth_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
                                                    _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C), _ptr(rate),
                                                    _ptr(gain), float(rate_min), L_out, t_lo, t_hi, _ptr(out)))
+
+    def modify_synth_shape(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi,
+                           out, f0, S):
+        self._ck(self.lib.eaqhm_modify_synth_shape(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
+                                                   _ptr(ph0), No_ti, Kmax, step, float(fs), float(rho), float(beta),
+                                                   L_out, t_lo, t_hi, _ptr(out), _ptr(f0), _ptr(S)))
+
+    def modify_synth_curve_shape(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, C, rate, gain, rate_min,
+                                 L_out, t_lo, t_hi, out, f0, S):
+        self._ck(self.lib.eaqhm_modify_synth_curve_shape(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp),
+                                                         _ptr(R), _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C),
+                                                         _ptr(rate), _ptr(gain), float(rate_min), L_out, t_lo, t_hi,
+                                                         _ptr(out), _ptr(f0), _ptr(S)))
 
     def model_envelope(self, records, No_ti, Kmax, alpha, freqs, F, out):
         self._ck(self.lib.eaqhm_model_envelope(self.h, _ptr(records), No_ti, Kmax, _ptr(alpha), _ptr(freqs), F,

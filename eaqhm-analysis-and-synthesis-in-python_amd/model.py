@@ -2,7 +2,8 @@
 
     unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
     eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, device_index=0) -> float64[L_out]
+                   formant_scale=1.0, *, phase="independent", f0=None, device_index=0) -> float64[L_out]
+    model_f0(DetComponents, fs) -> float64[No_ti]
     model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[No_ti, len(freqs)]
     scale_contour(DetComponents, fs, times_s, values) -> float64[No_ti]
     contour_time_map(rho, beta, step, length) -> dict(rate, gain, C, L_out, rate_min)
@@ -15,8 +16,10 @@ the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
 also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
 (§9.2).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
-filtered white noise under the same time map (§10).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
-eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours, eaqhm_model_envelope,
+filtered white noise under the same time map (§10).  phase="shape" keeps the phases of the harmonics relative to the
+fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
+eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours (eaqhm_modify_synth_shape and
+eaqhm_modify_synth_curve_shape for phase="shape"), eaqhm_model_envelope,
 eaqhm_noise_analyse, eaqhm_noise_synth); there is no CPU path.
 """
 from itertools import chain, compress, repeat
@@ -256,6 +259,73 @@ def check_formant_scale(model, formant_scale, preserve_envelope):
     return alpha
 
 
+PHASE_MODES = ("independent", "shape")
+
+
+def _records_f0(rec, K):
+    """The fundamental track of DESIGN.md §11 from records: per instant the a^2-weighted mean of f_k / (k+1) over the
+    active slots; an instant without one takes the nearest earlier instant's value that has one, else the nearest
+    later one's; 0 everywhere for a model without any active slot."""
+    am, fm = rec[:, :K], rec[:, K:2 * K]
+    w = np.where((am != 0) & (fm > 0), am * am, 0.0)
+    # sums in slot order (cumsum is sequential): trailing empty slots, which det_format="arrays" keeps and "structs"
+    # drops, add exact zeros and leave f0 as it is
+    den = np.cumsum(w, axis=1)[:, -1] if K else np.zeros(len(rec))
+    has = den > 0
+    n = len(rec)
+    if not has.any():
+        return np.zeros(n)
+    num = np.cumsum(w * (fm / np.arange(1, K + 1)), axis=1)[:, -1]
+    f0 = np.where(has, num / np.where(has, den, 1.0), 0.0)
+    idx = np.where(has, np.arange(n), -1)
+    src = np.maximum.accumulate(idx)                 # the nearest earlier instant with an active slot
+    src[src < 0] = int(np.flatnonzero(has)[0])       # none earlier: the nearest later one
+    return f0[src]
+
+
+def model_f0(DetComponents, fs):
+    """The fundamental frequency the model itself holds, in Hz per analysis instant: the a^2-weighted
+    mean of f_k / (k+1) over the instant's active partials (slot k holds harmonic k+1), held over instants without any.
+    It is what eaQHMSynthesis(..., phase="shape") advances, and what drives a pitch contour to a target:
+    pitch_scale = target_hz / model_f0(det, fs).  Returns float64[No_ti]."""
+    _sample_rate(fs)
+    model = unpack_model(DetComponents)
+    return _records_f0(model["records"], model["Kmax"])
+
+
+def check_phase_arguments(model, phase, f0):
+    """Validates the phase mode and the fundamental track (no device work): returns (shape: bool, f0: float64[No_ti]
+    or None).  f0 is only allowed with phase="shape"; it must be finite and > 0 at every instant."""
+    if phase not in PHASE_MODES:
+        raise ValueError("phase must be one of %s, got %r" % (", ".join(map(repr, PHASE_MODES)), phase))
+    shape = phase == "shape"
+    if f0 is None:
+        return shape, (_records_f0(model["records"], model["Kmax"]) if shape else None)
+    if not shape:
+        raise ValueError("f0 is the fundamental track of phase='shape'; it has no meaning with phase=%r" % phase)
+    v = _numeric_1d(f0, "f0")
+    if len(v) != len(model["ti"]):
+        raise ValueError("f0 must have one value per analysis instant (%d), got %d" % (len(model["ti"]), len(v)))
+    if not np.all(np.isfinite(v)) or np.any(v <= 0):
+        raise ValueError("f0 must be finite and > 0 (Hz)")
+    return shape, v
+
+
+def fundamental_advance(f0, gain, step, fs):
+    """S of DESIGN.md §11: the phase advance of the fundamental in cycles at every instant, S_0 = 0,
+    S_{j+1} = frac(S_j + (g_j - 1) (step / fs) (f0_j + f0_{j+1}) / 2), in float64 in this order.  `gain` is g_j per
+    interval (float64[n-1]).  frac keeps (k+1) S small whatever the length of the file.  Returns float64[n] in [0, 1)."""
+    f0 = np.asarray(f0, dtype=np.float64)
+    inc = (np.asarray(gain, dtype=np.float64) - 1.0) * (float(step) / float(fs)) * (f0[:-1] + f0[1:]) / 2
+    S = np.zeros(len(f0))
+    acc = 0.0
+    for j, d in enumerate(inc.tolist()):
+        acc += d
+        acc -= np.floor(acc)
+        S[j + 1] = acc
+    return S
+
+
 def _device_records(model, dev):
     """The model's records on the device: (tensor, No_ti, Kmax).  A model without any slot keeps one empty slot, so that
     the kernels still run (the a0 spline of the synthesis, the -inf rows of the envelope)."""
@@ -269,7 +339,8 @@ def _device_records(model, dev):
 
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, noise=None, noise_seed=0, device_index=0, _ranges=None):
+                   formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, device_index=0,
+                   _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -287,6 +358,12 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     the length do not change.  It needs preserve_envelope=True.  A formant contour runs the contour path; the number 1
     leaves the result exactly as it is without a formant scale.
 
+    `phase` is "independent" (the default: the unwrapped phase of every partial is scaled on its own, §9) or "shape"
+    (§11): the phase of harmonic k+1 relative to the fundamental, which fixes the waveform shape of a pitch period,
+    stays the model's at every scale, and only the fundamental's phase advances at the new rate; stretched voiced speech
+    keeps its pulse shape instead of turning reverberant.  The fundamental is model_f0(DetComponents, fs), or `f0` (Hz
+    per analysis instant, finite and > 0; only with phase="shape").  At unit scales both modes give the same samples.
+
     `noise` (a model from eaQHMNoiseAnalysis of the same signal: its fs and length must be this call's) adds the
     stochastic component (§10): the LPC model of the residual resynthesised as filtered white noise, seeded by
     `noise_seed`, under this call's time map, so it is stretched with the sinusoids.  `pitch_scale` and `formant_scale`
@@ -302,6 +379,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     else:
         rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
     alpha = check_formant_scale(model, formant_scale, preserve_envelope)
+    shape, f0 = check_phase_arguments(model, phase, f0)
     # alpha reaches the prep for a formant contour or a number != 1; without the envelope alpha is 1 throughout
     formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
     if noise is not None:
@@ -334,16 +412,28 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         return torch.as_tensor(np.full(n, x) if np.ndim(x) == 0 else np.ascontiguousarray(x), device=dev)
 
     gain_d = dv(tm["gain"]) if contour else None      # without it Delta stays unweighted: the scalar synthesis
-    c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta), gain_d, dv(alpha) if formant else None,
+    # phase="shape" leaves Delta unweighted on either path: the weight moves to the fundamental's advance S
+    c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta), None if shape else gain_d, dv(alpha) if formant else None,
                   preserve_envelope, amp, R, ph0)
+    if shape:
+        f0_d = dv(f0)
+        S_d = dv(fundamental_advance(f0, tm["gain"] if contour else np.full(n - 1, beta * rho), D, fs))
     if contour:
         C_d, rate_d = dv(tm["C"]), dv(tm["rate"])
         for t_lo, t_hi in ranges:
-            c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"], L_out,
-                                 t_lo, t_hi, out)
+            if shape:
+                c.modify_synth_curve_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
+                                           tm["rate_min"], L_out, t_lo, t_hi, out, f0_d, S_d)
+            else:
+                c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"],
+                                     L_out, t_lo, t_hi, out)
     else:
         for t_lo, t_hi in ranges:
-            c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
+            if shape:
+                c.modify_synth_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out, f0_d,
+                                     S_d)
+            else:
+                c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
     if noise is not None:
         H = nz["hop"]
         tau = noise_time_map_contour(H, tm, D) if contour else noise_time_map(H, L_out, rho)

@@ -228,6 +228,27 @@ int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_
 int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* alpha,
                          const double* freqs, int32_t F, double* out);
 
+/* shape-invariant phase for the two syntheses above (new entry points; no existing argument list changes) ----------
+ * The definition is DESIGN.md "Shape-invariant phase" (§11).  Both take the argument list of their counterpart plus
+ *   f0         double[No_ti]    the fundamental track in Hz (finite, >= 0), linear between instants
+ *   S          double[No_ti]    the fundamental's phase advance in cycles at each instant, in [0, 1): S_0 = 0,
+ *                               S_{j+1} = frac(S_j + (g_j - 1) (step / fs) (f0_j + f0_{j+1}) / 2), computed by the caller
+ *                               in double in this order; g_j = beta rho for eaqhm_modify_synth_shape, gain[j] for
+ *                               eaqhm_modify_synth_curve_shape
+ * and the outputs of a prep WITHOUT gain (R unweighted) in both cases.  The phase of slot k at an output sample in
+ * interval j at offset r is ph0 + R_j + Psi_j(r) + 2 pi (k+1) (S_j + (g_j - 1) (f0_j r + (f0_{j+1} - f0_j) r^2 /
+ * (2 step)) / fs); amplitudes, isolated knots and a0 are those of the counterpart.  With every g_j = 1 and S = 0 the
+ * result is the counterpart's.  EAQHM_EINVAL as for the counterpart, and for a null f0 or S.                          */
+int eaqhm_modify_synth_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                             const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
+                             int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
+                             int64_t t_hi, double* out, const double* f0, const double* S);
+int eaqhm_modify_synth_curve_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
+                                   const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
+                                   int32_t step, double fs, const double* C, const double* rate, const double* gain,
+                                   double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out,
+                                   const double* f0, const double* S);
+
 /* the stochastic component: an LPC model of the residual and its resynthesis as filtered noise (ABI 5) -----------------
  * Not in the reference; the definition is DESIGN.md "The stochastic component" (§10).  hop = H, order = p,
  * 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop.

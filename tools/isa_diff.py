@@ -6,8 +6,10 @@ Builds the gfx950 device assembly of every source in csrc/Makefile's SRC, from t
 HEAD, extracted with git archive), with the Makefile's flags plus --offload-device-only -S and the -D flags given (to
 both builds).  Each .s is normalised: comments, blank lines, .file / .loc / .ident directives and the __hip_cuid_*
 symbol (it differs between two builds of the same source) are dropped, and the local labels (.LBB*, .Ltmp*,
-.Lfunc_end*) are renumbered in order of appearance within each function.  Reports every function (kernels and
-non-inlined device functions): identical, or differs with its VGPR / AGPR / SGPR counts and scratch / LDS bytes before
+.Lfunc_end*) are renumbered in order of appearance within each function.  A function's text runs from the directives
+that open it (.text / .protected / .globl / .p2align ahead of its .type) to those of the next one, or to the padding
+that closes the text section, so that a function added next to it leaves it identical.  Reports every function (kernels
+and non-inlined device functions): identical, or differs with its VGPR / AGPR / SGPR counts and scratch / LDS bytes before
 -> after.  Exit status 0 when every function and everything outside them compares equal.
 """
 import argparse
@@ -25,6 +27,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fno-strict-aliasing", "--offload-arch=gfx950", "--offload-device-only", "-S"]
 
 LABEL = re.compile(r"\.(LBB\d+_\d+|Ltmp\d+|Lfunc_end\d+)\b")
+OPENERS = (".text", ".protected", ".globl", ".p2align", ".weak")
 FUNC = re.compile(r"^\s*\.type\s+([^,\s]+),@function")
 KD_FIELDS = {  # .amdhsa_* directive of the kernel descriptor -> column of the report
     "next_free_vgpr": "vgpr", "accum_offset": "agpr_off", "next_free_sgpr": "sgpr",
@@ -66,9 +69,12 @@ def split(path):
             if not s or s.startswith(("//", ".file", ".loc", ".ident")) or "__hip_cuid_" in s:
                 continue
             m = FUNC.match(line)
-            if m or s.startswith(".amdgpu_metadata"):
+            if m or s.startswith((".amdgpu_metadata", ".p2alignl")):
+                head = []   # what opens the next function (or the closing padding) is not the one before's
+                while (m or s.startswith(".p2alignl")) and cur and cur[-1].split()[0] in OPENERS:
+                    head.insert(0, cur.pop())
                 parts.setdefault(name, []).extend(cur)
-                cur, name = [], (m.group(1) if m else "<outside functions>")
+                cur, name = head, (m.group(1) if m else "<outside functions>")
             cur.append(line)
     parts.setdefault(name, []).extend(cur)
     for k, lines in parts.items():

@@ -2,7 +2,7 @@
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
-                                          [--noise] [--out FILE]
+                                          [--noise] [--shape] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -13,7 +13,10 @@ beta in {1, 1.25} with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with ea
 ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  --noise adds the stochastic
 component on the workload's own residual: eaqhm_noise_analyse, and eaqhm_noise_synth at rho in
 {0.5, 1, 2} beside the deterministic prep + eval of the same session at the same rho (beta = 1); every time there is
-the median of three windows of 20 launches, with the max - min of the three.  EAQHM_LIB selects another build of
+the median of three windows of 20 launches, with the max - min of the three.  --shape adds the shape-invariant phase
+mode: eaqhm_modify_synth_shape next to eaqhm_modify_synth at rho in {0.5, 1, 2} x beta in {1, 1.25}, and
+eaqhm_modify_synth_curve_shape next to eaqhm_modify_synth_curve on the four contour settings, each the median of three
+windows of 20 launches with the max - min of the existing kernel's three (the margin).  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -91,7 +94,7 @@ def prepare(torch, det, fs, L, reps):
                 t_unpack=t_unpack)
 
 
-def probe(workload, reps, contours=False, formant=False, noise=False):
+def probe(workload, reps, contours=False, formant=False, noise=False, shape=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -121,6 +124,8 @@ def probe(workload, reps, contours=False, formant=False, noise=False):
         res["formant"] = formant_rows(torch, st, reps)
     if noise:
         res["noise"] = noise_rows(torch, st, residual)
+    if shape:
+        res["shape"] = shape_rows(torch, st)
     return res
 
 
@@ -156,6 +161,60 @@ def noise_rows(torch, st, residual, reps=20, runs=3):
         rows.append(dict(setting="rho%g" % rho, out_frames=len(tau), noise_synth_ms=t_ns, noise_synth_spread_ms=s_ns,
                          det_eval_ms=t_det, det_eval_spread_ms=s_det, det_total_ms=round(t_prep + t_det, 4),
                          noise_to_det_eval=round(t_ns / t_det, 3)))
+    return rows
+
+
+def shape_rows(torch, st, reps=20, runs=3):
+    """The shape-invariant phase mode: device time of the shape eval kernels next to the existing ones,
+    same session, same prepared model.  Each time: median of `runs` windows of `reps` launches; margin_ms = max - min of
+    the existing kernel's windows."""
+    from eaqhm_amd.model import _records_f0, contour_time_map, fundamental_advance
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, fs, L = st["n"], st["K"], st["D"], st["fs"], st["L"]
+    dev = c.device
+    f0 = _records_f0(rec.cpu().numpy(), K)
+    f0_d = torch.as_tensor(f0, device=dev)
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    def row(setting, Lo, base, new):
+        return dict(setting=setting, out_samples=Lo, eval_ms=round(base[0], 4), margin_ms=round(base[1], 4),
+                    shape_eval_ms=round(new[0], 4), shape_spread_ms=round(new[1], 4),
+                    shape_minus_eval_ms=round(new[0] - base[0], 4), ratio=round(new[0] / base[0], 4))
+
+    rows = []
+    for beta in (1.0, 1.25):
+        beta_d = torch.full((n,), beta, dtype=torch.float64, device=dev)
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, True, amp, R, ph0)
+        for rho in (0.5, 1.0, 2.0):
+            Lo = int(np.rint(rho * L))
+            out = torch.empty(Lo, dtype=torch.float64, device=dev)
+            S_d = torch.as_tensor(fundamental_advance(f0, np.full(n - 1, beta * rho), D, fs), device=dev)
+            base = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo, out))
+            new = med(lambda: c.modify_synth_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo, out,
+                                                   f0_d, S_d))
+            rows.append(row("rho%g_beta%g" % (rho, beta), Lo, base, new))
+    t = np.arange(n) * D / fs
+    one = np.ones(n)
+    sinus = 1.05 + 0.35 * np.sin(2 * np.pi * 0.5 * t)
+    ramp = np.interp(t, [0.0, t[-1]], [0.85, 1.2])
+    for label, rho, beta in (("unit", one, one), ("rho_sinus", sinus, one), ("beta_ramp", one, ramp),
+                             ("both", sinus, ramp)):
+        tm = contour_time_map(rho, beta, D, L)
+        Lo = tm["L_out"]
+        beta_d, gain_d, C_d, rate_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                                       for x in (beta, tm["gain"], tm["C"], tm["rate"]))
+        S_d = torch.as_tensor(fundamental_advance(f0, tm["gain"], D, fs), device=dev)
+        out = torch.empty(Lo, dtype=torch.float64, device=dev)
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, gain_d, None, True, amp, R, ph0)
+        base = med(lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
+                                                tm["rate_min"], Lo, 0, Lo, out))
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, True, amp, R, ph0)   # the shape mode's prep
+        new = med(lambda: c.modify_synth_curve_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
+                                                     tm["rate_min"], Lo, 0, Lo, out, f0_d, S_d))
+        rows.append(row("contour_" + label, Lo, base, new))
     return rows
 
 
@@ -238,9 +297,10 @@ def main():
     ap.add_argument("--contours", action="store_true", help="also time the contour kernels")
     ap.add_argument("--formant", action="store_true", help="also time the formant prep kernels")
     ap.add_argument("--noise", action="store_true", help="also time the noise analysis and synthesis kernels")
+    ap.add_argument("--shape", action="store_true", help="also time the shape-invariant phase kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps, a.contours, a.formant, a.noise) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
