@@ -8,6 +8,6 @@ from .functions import (eaQHMAnalysisAndSynthesis, eaQHMAnalysisAndSynthesisBatc
 from .hip import HipUnavailable, load_library  # noqa: F401
 from .structs import Deterministic, Frame  # noqa: F401
 from .model import (SCALE_RANGE, contour_time_map, eaQHMNoiseAnalysis, eaQHMNoiseSynthesis,  # noqa: F401
-                    eaQHMSynthesis, model_envelope, model_f0, noise_time_map, noise_time_map_contour, scale_contour,
-                    unpack_model)
+                    eaQHMNoiseWarp, eaQHMSynthesis, model_envelope, model_f0, noise_envelope, noise_formant_contour,
+                    noise_time_map, noise_time_map_contour, scale_contour, unpack_model)
 from .prologue import read_signal  # noqa: F401

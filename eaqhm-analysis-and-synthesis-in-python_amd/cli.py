@@ -10,7 +10,8 @@ starting with # are comments), turned into a per-instant contour with model.scal
 --formant-scale-curve FILE move the spectral envelope by A; they need the envelope, so either one with
 --no-envelope is an error.  --phase shape keeps the waveform shape under those scales.  --noise (with --noise-seed N) models the residual input - reconstruction
 (model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
-writes `<name>_resynthesis.wav`: model + noise at unit scales."""
+writes `<name>_resynthesis.wav`: model + noise at unit scales.  --noise-formant (with --noise and a formant scale flag) lets the
+noise's envelope follow the formant scale (eaQHMSynthesis(noise_formant=True))."""
 import argparse
 
 import numpy as np
@@ -56,6 +57,9 @@ def parser():
                     help="model the residual as filtered noise and add it to <name>_modified.wav; without a scale flag "
                          "write <name>_resynthesis.wav (model + noise)")
     ap.add_argument("--noise-seed", type=int, default=None, metavar="N", help="with --noise: seed of the excitation (0)")
+    ap.add_argument("--noise-formant", action="store_true",
+                    help="with --noise and --formant-scale / --formant-scale-curve: the noise's spectral envelope "
+                         "follows the formant scale")
     return ap
 
 
@@ -64,6 +68,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.noise_seed is not None and not a.noise:
         ap.error("--noise-seed needs --noise")
+    if a.noise_formant and not a.noise:
+        ap.error("--noise-formant needs --noise")
+    if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None:
+        ap.error("--noise-formant needs --formant-scale or --formant-scale-curve")
     if a.noise:
         from .model import _seed
         _seed(0 if a.noise_seed is None else a.noise_seed)
@@ -112,7 +120,7 @@ def main(argv=None):
                 nz = eaQHMNoiseAnalysis(read_signal(a.wav, a.fc)[1], s_recon, fs)
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
-                                   noise=nz, noise_seed=a.noise_seed or 0)
+                                   noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant)
             out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)

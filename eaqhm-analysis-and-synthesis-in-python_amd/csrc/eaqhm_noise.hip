@@ -3,6 +3,9 @@
 //   eaqhm_noise_analyse_kernel   one wave per frame: windowed frame in LDS, lane l owns lag l, Levinson-Durbin in the wave
 //   eaqhm_noise_filter_kernel    one lane per output frame: the all-pole lattice, state and coefficients in LDS
 //   eaqhm_noise_combine_kernel   one thread per output sample: cross-fade of the two frames that cover it
+//   eaqhm_noise_warp_kernel      one wave per frame: the frame's spectrum warped by alpha on a grid in LDS, lane l owns
+//                                lag l of its autocorrelation, Levinson-Durbin in the wave
+//   eaqhm_noise_envelope_kernel  one wave per frame, lanes over the frequency grid: the warped log power spectrum
 #include "eaqhm_common.h"
 
 // The synthesis follows the NumPy model of the definition operation by operation (no fused multiply-add), so the two
@@ -143,6 +146,139 @@ extern "C" __global__ void __launch_bounds__(256)
   out[n] = accumulate ? out[n] + val : val;
 }
 
+// ---- the formant warp of the model (tests/noise_warp_ref.py)
+constexpr int NW_M = 1024;    // grid intervals on [0, pi] (M of the definition)
+constexpr int NW_WAVES = 8;   // frames (waves) per block of the warp kernel
+constexpr int NE_WAVES = 4;   // frames (waves) per block of the envelope kernel
+
+// The Levinson-Durbin recursion of eaqhm_noise_analyse_kernel on r[l] of lane l (r[0] > 0), a second copy: calling one
+// function from both changed the analysis kernel's machine code (tools/isa_diff.py).  Leaves k_lane in kk (lanes 1..p;
+// 0 from the stage it stopped at) and returns E.
+__device__ __forceinline__ double levinson_lanes(double r, int p, int lane, double& kk) {
+  if (lane == 0) r *= (1.0 + 1e-9);
+  double E = __shfl(r, 0, 64);
+  double a = lane == 0 ? 1.0 : 0.0;
+  for (int i = 1; i <= p; ++i) {
+    const int src = (i - lane) & 63;
+    const double rr = __shfl(r, src, 64);
+    const double acc = __shfl(wave_sum(lane < i ? a * rr : 0.0), 0, 64);
+    const double k = -acc / E;
+    if (!(fabs(k) < 1.0)) break;
+    const double ar = __shfl(a, src, 64);
+    if (lane >= 1 && lane <= i) a += k * ar;      // lane i: 0 + k a_0
+    if (lane == i) kk = k;
+    E *= (1.0 - k * k);
+  }
+  return E;
+}
+
+// A(z) of reflection coefficients: lane i holds k_i in kk (lanes 1..p); a_j comes back on lane j (a_0 = 1).  The
+// model's step-up operation by operation: a_j += k_i a_{i-j}, j = 1..i, from the old values.
+__device__ __forceinline__ double stepup_lanes(double kk, int p, int lane) {
+  double a = lane == 0 ? 1.0 : 0.0;
+  for (int i = 1; i <= p; ++i) {
+    const double k = __shfl(kk, i, 64);
+    const double ar = __shfl(a, (i - lane) & 63, 64);
+    if (lane >= 1 && lane <= i) a += k * ar;
+  }
+  return a;
+}
+
+// |A(e^{jw})|^2, a[0..p] in LDS (one address for the wave).  One sincos, then e^{jiw} by rotation: its error grows like
+// i ulp, the size of the rounding of the product i w in the model.
+__device__ __forceinline__ double poly_power(const double* a, int p, double w) {
+  double s, c;
+  sincos(w, &s, &c);
+  double re = 1.0, im = 0.0, ci = c, si = s;
+  for (int i = 1; i <= p; ++i) {
+    const double ai = a[i];
+    re = fma(ai, ci, re);
+    im = fma(ai, si, im);
+    const double cn = fma(ci, c, -(si * s));
+    si = fma(si, c, ci * s);
+    ci = cn;
+  }
+  return re * re + im * im;
+}
+
+// LDS (static): the cosine table cos(pi j / M), j = 0..M (shared by the block), and per wave P'[0..M] and a[0..63]
+extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+    eaqhm_noise_warp_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
+                            const double* __restrict__ alpha, double* __restrict__ sigma_out,
+                            double* __restrict__ refl_out) {
+  __shared__ double tab[NW_M + 1];
+  __shared__ double Pw[NW_WAVES][NW_M + 2];
+  __shared__ double aw[NW_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NW_WAVES + wave;
+  const bool live = m < Nf;
+  for (int j = threadIdx.x; j <= NW_M; j += 64 * NW_WAVES) tab[j] = cospi((double)j / (double)NW_M);
+  const double sg = live ? sigma[m] : 0.0;
+  const double al = live ? alpha[m] : 1.0;
+  const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
+  const bool work = live && al != 1.0 && sg > 0.0;     // uniform over the wave
+  if (work) aw[wave][lane] = stepup_lanes(kin, p, lane);
+  __syncthreads();
+  double* P = Pw[wave];
+  if (work) {
+    for (int t = lane; t <= NW_M; t += 64) {
+      const double w = fmin(M_PI * (double)t / (double)NW_M / al, M_PI);
+      P[t] = sg * sg / poly_power(aw[wave], p, w);
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (!work) {   // alpha == 1: the frame bit for bit; otherwise a silent frame
+    if (lane == 0) sigma_out[m] = al == 1.0 ? sg : 0.0;
+    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = al == 1.0 ? kin : 0.0;
+    return;
+  }
+
+  // r'[l] on lane l: P'[t] is one address for the wave; the table index (l t) mod 2M folds onto [0, M]
+  auto ct = [&](int t) {
+    const int idx = (lane * t) & (2 * NW_M - 1);
+    return tab[idx > NW_M ? 2 * NW_M - idx : idx];
+  };
+  double r0 = 0.5 * P[0], r1 = 0.0, r2 = 0.0, r3 = ((lane & 1) ? -0.5 : 0.5) * P[NW_M];
+  for (int t = 1; t + 3 < NW_M; t += 4) {
+    r0 = fma(P[t], ct(t), r0);
+    r1 = fma(P[t + 1], ct(t + 1), r1);
+    r2 = fma(P[t + 2], ct(t + 2), r2);
+    r3 = fma(P[t + 3], ct(t + 3), r3);
+  }
+  r0 = fma(P[NW_M - 3], ct(NW_M - 3), r0);
+  r1 = fma(P[NW_M - 2], ct(NW_M - 2), r1);
+  r2 = fma(P[NW_M - 1], ct(NW_M - 1), r2);
+  const double r = ((r0 + r1) + (r2 + r3)) / (double)NW_M;
+
+  double kk = 0.0;
+  const double E = levinson_lanes(r, p, lane, kk);
+  if (lane == 0) sigma_out[m] = sqrt(E);
+  if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = kk;
+}
+
+// out[m][t] = 2 ln sigma_m - ln |A_m(e^{jw})|^2 at w = 2 pi min(fnorm[t] / alpha_m, 1/2); -inf rows for silent frames
+extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
+    eaqhm_noise_envelope_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
+                                const double* __restrict__ alpha, const double* __restrict__ fnorm, int F,
+                                double* __restrict__ out) {
+  __shared__ double aw[NE_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NE_WAVES + wave;
+  const bool live = m < Nf;
+  const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
+  aw[wave][lane] = stepup_lanes(kin, p, lane);
+  __syncthreads();
+  if (!live) return;
+  const double sg = sigma[m], al = alpha[m];
+  const double ls = 2.0 * log(sg);
+  double* row = out + (size_t)m * F;
+  for (int t = lane; t < F; t += 64) {
+    const double w = (2.0 * M_PI) * fmin(fnorm[t] / al, 0.5);
+    row[t] = sg > 0.0 ? ls - log(poly_power(aw[wave], p, w)) : -INFINITY;
+  }
+}
+
 }  // namespace eaqhm
 
 using namespace eaqhm;
@@ -195,6 +331,30 @@ extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const doub
   hipLaunchKernelGGL(eaqhm_noise_combine_kernel, dim3((unsigned)((t_hi - t_lo + 255) / 256)), dim3(256), 0, ctx->stream,
                      (const double*)Y, (int)hop, (int)q_lo, nq, (int)Nq, (long long)t_lo, (long long)t_hi, out,
                      (int)(accumulate != 0));
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_warp(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                                const double* alpha, double* sigma_out, double* refl_out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !alpha || !sigma_out || !refl_out || Nf < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_warp: bad argument");
+  if (order < 1 || order > 63) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_warp: need 1 <= order <= 63");
+  hipLaunchKernelGGL(eaqhm_noise_warp_kernel, dim3((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)),
+                     dim3(64 * NW_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, alpha, sigma_out, refl_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_envelope(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                                    const double* alpha, const double* fnorm, int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !alpha || !fnorm || !out || Nf < 1 || F < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope: bad argument");
+  if (order < 1 || order > 63) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope: need 1 <= order <= 63");
+  hipLaunchKernelGGL(eaqhm_noise_envelope_kernel, dim3((unsigned)(((int64_t)Nf + NE_WAVES - 1) / NE_WAVES)),
+                     dim3(64 * NE_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, alpha, fnorm, (int)F, out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -48,6 +48,8 @@ SYMBOLS = (
     ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
     ("eaqhm_noise_analyse", C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
     ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32]),
+    ("eaqhm_noise_warp", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    ("eaqhm_noise_envelope", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P]),
 )
 
 
@@ -231,6 +233,14 @@ class Context:
     def noise_synth(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, accumulate=False):
         self._ck(self.lib.eaqhm_noise_synth(self.h, _ptr(sigma), _ptr(refl), Nf, hop, order, _ptr(tau), Nq, seed, L_out,
                                             t_lo, t_hi, _ptr(out), int(bool(accumulate))))
+
+    def noise_warp(self, sigma, refl, Nf, order, alpha, sigma_out, refl_out):
+        self._ck(self.lib.eaqhm_noise_warp(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(alpha), _ptr(sigma_out),
+                                           _ptr(refl_out)))
+
+    def noise_envelope(self, sigma, refl, Nf, order, alpha, fnorm, F, out):
+        self._ck(self.lib.eaqhm_noise_envelope(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(alpha), _ptr(fnorm), F,
+                                               _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

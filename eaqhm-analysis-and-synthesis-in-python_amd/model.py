@@ -10,17 +10,20 @@
     eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
     eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0) -> float64[L_out]
     noise_time_map(hop, L_out, rho) / noise_time_map_contour(hop, tm, step) -> float64[Nq]
+    eaQHMNoiseWarp(noise, formant_scale, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
+    noise_formant_contour(noise, DetComponents, formant_scale) -> float64[Nf]
+    noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[Nf, len(freqs)]
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
 also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
 (§9.2).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
-filtered white noise under the same time map (§10).  phase="shape" keeps the phases of the harmonics relative to the
+filtered white noise under the same time map (§10); its envelope follows a formant scale on request (§10.1).  phase="shape" keeps the phases of the harmonics relative to the
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
 eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours (eaqhm_modify_synth_shape and
 eaqhm_modify_synth_curve_shape for phase="shape"), eaqhm_model_envelope,
-eaqhm_noise_analyse, eaqhm_noise_synth); there is no CPU path.
+eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp, eaqhm_noise_envelope); there is no CPU path.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -339,8 +342,8 @@ def _device_records(model, dev):
 
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, device_index=0,
-                   _ranges=None):
+                   formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, noise_formant=False,
+                   device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -366,9 +369,14 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
 
     `noise` (a model from eaQHMNoiseAnalysis of the same signal: its fs and length must be this call's) adds the
     stochastic component (§10): the LPC model of the residual resynthesised as filtered white noise, seeded by
-    `noise_seed`, under this call's time map, so it is stretched with the sinusoids.  `pitch_scale` and `formant_scale`
-    do not touch the noise.  The result is the sum of the synthesis without `noise` and eaQHMNoiseSynthesis at
-    noise_time_map(...) (noise_time_map_contour for contours), bit for bit.
+    `noise_seed`, under this call's time map, so it is stretched with the sinusoids.  `pitch_scale` does not touch the
+    noise, and neither does `formant_scale` by default.  The result is the sum of the synthesis without `noise` and
+    eaQHMNoiseSynthesis at noise_time_map(...) (noise_time_map_contour for contours), bit for bit.
+
+    `noise_formant=True` (it needs `noise` and preserve_envelope=True) lets the noise follow the formant scale (§10.1):
+    the noise is synthesised from eaQHMNoiseWarp(noise, noise_formant_contour(noise, DetComponents, formant_scale)),
+    the model whose all-pole envelope is moved up in frequency by alpha, so the result is bit for bit that of passing
+    that warped model as `noise`.  The default leaves the noise's envelope where the analysis found it.
 
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
@@ -388,6 +396,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         if nz["fs"] != fs or nz["length"] != length:
             raise ValueError("the noise model is of another signal: fs %g, length %d; this call: fs %g, length %d"
                              % (nz["fs"], nz["length"], fs, length))
+    warp = check_noise_formant(noise_formant, noise, preserve_envelope)
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
@@ -438,6 +447,9 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         H = nz["hop"]
         tau = noise_time_map_contour(H, tm, D) if contour else noise_time_map(H, L_out, rho)
         sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
+        if warp:
+            sigma_d, refl_d = _device_noise_warp(c, sigma_d, refl_d, nz["order"],
+                                                 _frame_alpha(nz, model["ti"], np.broadcast_to(alpha, (n,))))
         for t_lo, t_hi in ranges:
             c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo, t_hi,
                           out, accumulate=True)
@@ -622,4 +634,106 @@ def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0, _ranges=No
     for t_lo, t_hi in ([(0, L_out)] if _ranges is None else _ranges):
         c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
                       int(t_lo), int(t_hi), out)
+    return out.cpu().numpy()
+
+
+# ---- the formant warp of the noise model
+def check_noise_formant(noise_formant, noise, preserve_envelope):
+    """Validates eaQHMSynthesis's noise_formant (no device work): a bool; True needs a noise model and the envelope."""
+    if not isinstance(noise_formant, (bool, np.bool_)):
+        raise ValueError("noise_formant must be True or False, got %r" % (noise_formant,))
+    if noise_formant and noise is None:
+        raise ValueError("noise_formant=True needs noise=: there is no noise model to warp")
+    if noise_formant and not preserve_envelope:
+        raise ValueError("noise_formant=True needs preserve_envelope=True, as formant_scale does")
+    return bool(noise_formant)
+
+
+def _frame_alpha(nz, ti, alpha):
+    """alpha per noise frame from alpha per analysis instant: linear at sample m hop over the instants ti, flat
+    outside them."""
+    Nf = len(nz["sigma"])
+    return np.interp(np.arange(Nf, dtype=np.float64) * float(nz["hop"]), np.asarray(ti, dtype=np.float64), alpha)
+
+
+def noise_formant_contour(noise, DetComponents, formant_scale):
+    """The formant scale of every frame of a noise model, for eaQHMNoiseWarp (host only): `formant_scale` is a number
+    or one value per analysis instant of the model (what eaQHMSynthesis takes); frame m takes the linear interpolation
+    at sample m hop over the instants' sample positions unpack_model(...)["ti"], flat before the first and after the
+    last.  Returns float64[Nf]."""
+    nz = check_noise_model(noise)
+    ti = unpack_model(DetComponents)["ti"]
+    return _frame_alpha(nz, ti, _contour(formant_scale, "formant_scale", len(ti)))
+
+
+def check_noise_warp_arguments(noise, formant_scale):
+    """Validates everything eaQHMNoiseWarp gets (no device work): returns (model, alpha float64[Nf]); formant_scale is
+    a number or one value per noise frame, finite and in SCALE_RANGE."""
+    nz = check_noise_model(noise)
+    Nf = len(nz["sigma"])
+    if not _is_contour(formant_scale):
+        return nz, np.full(Nf, _scale(formant_scale, "formant_scale"))
+    v = _numeric_1d(formant_scale, "formant_scale")
+    if len(v) != Nf:
+        raise ValueError("formant_scale must have one value per noise frame (%d), got %d" % (Nf, len(v)))
+    return nz, np.ascontiguousarray(_in_range(v, "formant_scale"))
+
+
+def check_noise_envelope_arguments(noise, fs, freqs, formant_scale):
+    """Validates everything noise_envelope gets (no device work): returns (model, alpha float64[Nf], fnorm float64[F])
+    with fnorm = freqs / fs.  fs must be the model's."""
+    fs = _sample_rate(fs)
+    f = _numeric_1d(freqs, "freqs")
+    if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
+        raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
+    nz, alpha = check_noise_warp_arguments(noise, formant_scale)
+    if nz["fs"] != fs:
+        raise ValueError("the noise model has fs %g, this call %g" % (nz["fs"], fs))
+    return nz, alpha, np.ascontiguousarray(f / fs)
+
+
+def _device_noise_warp(c, sigma_d, refl_d, order, alpha):
+    """eaqhm_noise_warp on device tensors: (sigma', refl') as new tensors."""
+    import torch
+    alpha_d = torch.as_tensor(np.ascontiguousarray(alpha, dtype=np.float64), device=c.device)
+    sigma_o, refl_o = torch.empty_like(sigma_d), torch.empty_like(refl_d)
+    c.noise_warp(sigma_d, refl_d, sigma_d.shape[0], order, alpha_d, sigma_o, refl_o)
+    return sigma_o, refl_o
+
+
+def eaQHMNoiseWarp(noise, formant_scale, *, device_index=0):
+    """The noise model whose spectral envelope is `noise`'s moved up in frequency by `formant_scale` (alpha; DESIGN.md
+    §10.1): a feature at F sits at alpha F.  Each frame's all-pole power spectrum sigma^2 / |A|^2 is read at w / alpha on
+    a 1025-point grid (held at its Nyquist value above alpha pi), turned into an autocorrelation and re-fitted with the
+    analysis's Levinson-Durbin recursion at the same order.  `formant_scale` is a number or one value per noise frame
+    (noise_formant_contour gives them from a per-instant contour), finite and in [0.25, 4].  A frame with alpha == 1
+    comes back bit for bit, a silent frame silent.  The total power is not renormalised.
+
+    Returns a new dict(sigma, refl, hop, order, fs, length) of the same layout."""
+    nz, alpha = check_noise_warp_arguments(noise, formant_scale)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    sigma_d, refl_d = (torch.as_tensor(x, device=c.device) for x in (nz["sigma"], nz["refl"]))
+    sigma_o, refl_o = _device_noise_warp(c, sigma_d, refl_d, nz["order"], alpha)
+    return dict(nz, sigma=sigma_o.cpu().numpy(), refl=refl_o.cpu().numpy())
+
+
+def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0):
+    """The log power spectrum of every frame of a noise model on a frequency grid, read at the formant scale alpha
+    (DESIGN.md §10.1): out[m, t] = 2 ln sigma_m - 2 ln |A_m(e^{jw})| at w = 2 pi min(freqs[t] / alpha_m, fs / 2) / fs,
+    the natural log of the power; rows of silent frames are -inf.  It is the exact warped spectrum, the one
+    eaQHMNoiseWarp's refit approximates; the counterpart of model_envelope for the noise.  `freqs` (Hz) is 1-D, finite
+    and >= 0; `formant_scale` a number or one value per noise frame in [0.25, 4]; `fs` must be the model's.
+
+    Returns float64[Nf, len(freqs)]."""
+    nz, alpha, fnorm = check_noise_envelope_arguments(noise, fs, freqs, formant_scale)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    sigma_d, refl_d, alpha_d, f_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], alpha, fnorm))
+    Nf = len(nz["sigma"])
+    out = torch.empty((Nf, len(fnorm)), dtype=torch.float64, device=dev)
+    c.noise_envelope(sigma_d, refl_d, Nf, nz["order"], alpha_d, f_d, len(fnorm), out)
     return out.cpu().numpy()

@@ -271,6 +271,22 @@ int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, i
                       const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo, int64_t t_hi,
                       double* out, int32_t accumulate);
 
+/* the formant warp of the noise model (additions under ABI 5) ----------------------------------------
+ * A frame (sigma, k_1..k_p) is the power spectrum P(w) = sigma^2 / |A(e^{jw})|^2, A the step-up of k.
+ * eaqhm_noise_warp (kernel: one wave per frame; the spectrum at min(w_t / alpha, pi) on the grid w_t = pi t / 1024,
+ *   t = 0..1024, in LDS; lane l owns lag l of its autocorrelation; the Levinson-Durbin recursion of the analysis) gives
+ *   the model whose spectrum is the frame's moved up in frequency by alpha[m]:
+ *   sigma_out  double[Nf]         sqrt(E) of the refit; a frame with alpha == 1 is copied bit for bit, a silent frame
+ *   refl_out   double[Nf][order]  (sigma == 0) gives sigma_out = 0 and zeros
+ * eaqhm_noise_envelope (kernel: one wave per frame, lanes over the grid) reads the warped spectrum itself:
+ *   out        double[Nf][F]      2 ln sigma_m - 2 ln |A_m(e^{jw})| at w = 2 pi min(fnorm[t] / alpha[m], 1/2), fnorm =
+ *                                 f / fs (device, finite, >= 0); -inf on the rows of silent frames
+ * alpha[Nf] is the caller's: finite and > 0.  EAQHM_EINVAL for null pointers, Nf < 1, F < 1, order outside [1, 63].    */
+int eaqhm_noise_warp(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                     const double* alpha, double* sigma_out, double* refl_out);
+int eaqhm_noise_envelope(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                         const double* alpha, const double* fnorm, int32_t F, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
-                                          [--noise] [--shape] [--out FILE]
+                                          [--noise] [--noise-formant] [--shape] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -13,7 +13,10 @@ beta in {1, 1.25} with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with ea
 ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  --noise adds the stochastic
 component on the workload's own residual: eaqhm_noise_analyse, and eaqhm_noise_synth at rho in
 {0.5, 1, 2} beside the deterministic prep + eval of the same session at the same rho (beta = 1); every time there is
-the median of three windows of 20 launches, with the max - min of the three.  --shape adds the shape-invariant phase
+the median of three windows of 20 launches, with the max - min of the three.  --noise-formant adds the formant warp of
+the noise model on the same residual's model: eaqhm_noise_warp and eaqhm_noise_envelope (a 129-point
+grid) at alpha in {0.85, 1.2} and a ramp between them, beside eaqhm_noise_synth of the warped model at rho = 1 in the
+same session, with the same windows.  --shape adds the shape-invariant phase
 mode: eaqhm_modify_synth_shape next to eaqhm_modify_synth at rho in {0.5, 1, 2} x beta in {1, 1.25}, and
 eaqhm_modify_synth_curve_shape next to eaqhm_modify_synth_curve on the four contour settings, each the median of three
 windows of 20 launches with the max - min of the existing kernel's three (the margin).  EAQHM_LIB selects another build of
@@ -94,7 +97,7 @@ def prepare(torch, det, fs, L, reps):
                 t_unpack=t_unpack)
 
 
-def probe(workload, reps, contours=False, formant=False, noise=False, shape=False):
+def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -126,7 +129,45 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
         res["noise"] = noise_rows(torch, st, residual)
     if shape:
         res["shape"] = shape_rows(torch, st)
+    if noise_formant:
+        import eaqhm_amd
+        res["noise_formant"] = noise_formant_rows(torch, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     return res
+
+
+def noise_formant_rows(torch, nz, reps=20, runs=3, grid=129):
+    """The formant warp of a noise model `nz` (from eaQHMNoiseAnalysis): device time of eaqhm_noise_warp and of
+    eaqhm_noise_envelope on `grid` frequencies in [0, fs/2] at alpha 0.85, 1.2 and a ramp 0.85 -> 1.2 over the frames,
+    beside eaqhm_noise_synth of the warped model at rho = 1.  Each time: median of `runs` windows of `reps` launches,
+    and their max - min."""
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.model import noise_time_map
+    c = _ctx(0)
+    dev = c.device
+    H, p, L = nz["hop"], nz["order"], nz["length"]
+    Nf = len(nz["sigma"])
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    sigma, refl, tau = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                        for x in (nz["sigma"], nz["refl"], noise_time_map(H, L, 1.0)))
+    sigma_w, refl_w = torch.empty_like(sigma), torch.empty_like(refl)
+    fnorm = torch.as_tensor(np.linspace(0.0, 0.5, grid), device=dev)
+    env = torch.empty((Nf, grid), dtype=torch.float64, device=dev)
+    out = torch.empty(L, dtype=torch.float64, device=dev)
+    rows = []
+    for setting, alpha in (("alpha0.85", np.full(Nf, 0.85)), ("alpha1.2", np.full(Nf, 1.2)),
+                           ("alpha_ramp", np.linspace(0.85, 1.2, Nf))):
+        alpha_d = torch.as_tensor(alpha, device=dev)
+        t_w, s_w = med(lambda: c.noise_warp(sigma, refl, Nf, p, alpha_d, sigma_w, refl_w))
+        t_e, s_e = med(lambda: c.noise_envelope(sigma, refl, Nf, p, alpha_d, fnorm, grid, env))
+        t_ns, s_ns = med(lambda: c.noise_synth(sigma_w, refl_w, Nf, H, p, tau, len(tau), 0, L, 0, L, out))
+        rows.append(dict(setting=setting, hop=H, order=p, frames=Nf, warp_ms=t_w, warp_spread_ms=s_w, envelope_ms=t_e,
+                         envelope_spread_ms=s_e, envelope_grid=grid, noise_synth_ms=t_ns, noise_synth_spread_ms=s_ns,
+                         warp_to_noise_synth=round(t_w / t_ns, 3)))
+    return rows
 
 
 def noise_rows(torch, st, residual, reps=20, runs=3):
@@ -297,10 +338,11 @@ def main():
     ap.add_argument("--contours", action="store_true", help="also time the contour kernels")
     ap.add_argument("--formant", action="store_true", help="also time the formant prep kernels")
     ap.add_argument("--noise", action="store_true", help="also time the noise analysis and synthesis kernels")
+    ap.add_argument("--noise-formant", action="store_true", help="also time the noise warp and envelope kernels")
     ap.add_argument("--shape", action="store_true", help="also time the shape-invariant phase kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
