@@ -11,7 +11,8 @@ starting with # are comments), turned into a per-instant contour with model.scal
 --no-envelope is an error.  --phase shape keeps the waveform shape under those scales.  --noise (with --noise-seed N) models the residual input - reconstruction
 (model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
 writes `<name>_resynthesis.wav`: model + noise at unit scales.  --noise-formant (with --noise and a formant scale flag) lets the
-noise's envelope follow the formant scale (eaQHMSynthesis(noise_formant=True))."""
+noise's envelope follow the formant scale (eaQHMSynthesis(noise_formant=True)).  --noise-modulation [M]
+(with --noise; M harmonics, default 2) modulates the noise pitch-synchronously (model.eaQHMNoiseModulation)."""
 import argparse
 
 import numpy as np
@@ -60,6 +61,8 @@ def parser():
     ap.add_argument("--noise-formant", action="store_true",
                     help="with --noise and --formant-scale / --formant-scale-curve: the noise's spectral envelope "
                          "follows the formant scale")
+    ap.add_argument("--noise-modulation", type=int, nargs="?", const=2, default=None, metavar="M",
+                    help="with --noise: modulate the noise pitch-synchronously, M harmonics of the envelope (2)")
     return ap
 
 
@@ -72,9 +75,13 @@ def main(argv=None):
         ap.error("--noise-formant needs --noise")
     if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None:
         ap.error("--noise-formant needs --formant-scale or --formant-scale-curve")
+    if a.noise_modulation is not None and not a.noise:
+        ap.error("--noise-modulation needs --noise")
     if a.noise:
-        from .model import _seed
+        from .model import _mod_harmonics, _seed
         _seed(0 if a.noise_seed is None else a.noise_seed)
+        if a.noise_modulation is not None:
+            _mod_harmonics(a.noise_modulation, "--noise-modulation")
     if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None):
         ap.error("--formant-scale / --formant-scale-curve scale the spectral envelope: not with --no-envelope")
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
@@ -104,7 +111,7 @@ def main(argv=None):
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
         if modify or a.noise:
-            from .model import eaQHMNoiseAnalysis, eaQHMSynthesis, scale_contour
+            from .model import eaQHMNoiseAnalysis, eaQHMNoiseModulation, eaQHMSynthesis, scale_contour
             rho = 1.0 if a.time_scale is None else a.time_scale
             beta = 1.0 if a.pitch_scale is None else a.pitch_scale
             if "time" in curves:
@@ -117,10 +124,14 @@ def main(argv=None):
             nz = None
             if a.noise:
                 from .prologue import read_signal
-                nz = eaQHMNoiseAnalysis(read_signal(a.wav, a.fc)[1], s_recon, fs)
+                sig = read_signal(a.wav, a.fc)[1]
+                nz = eaQHMNoiseAnalysis(sig, s_recon, fs)
+                if a.noise_modulation is not None:
+                    nz = eaQHMNoiseModulation(sig, s_recon, nz, det, a.noise_modulation)
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
-                                   noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant)
+                                   noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
+                                   noise_modulation=a.noise_modulation is not None)
             out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)

@@ -6,6 +6,9 @@
 //   eaqhm_noise_warp_kernel      one wave per frame: the frame's spectrum warped by alpha on a grid in LDS, lane l owns
 //                                lag l of its autocorrelation, Levinson-Durbin in the wave
 //   eaqhm_noise_envelope_kernel  one wave per frame, lanes over the frequency grid: the warped log power spectrum
+//   eaqhm_noise_modulation_kernel   one wave per frame, lanes over the frame's samples: the Fourier coefficients of the
+//                                   residual's power over the fundamental's phase
+//   eaqhm_noise_combine_mod_kernel  the combine kernel with each frame's pitch-synchronous gain g_q(n')
 #include "eaqhm_common.h"
 
 // The synthesis follows the NumPy model of the definition operation by operation (no fused multiply-add), so the two
@@ -279,6 +282,114 @@ extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
   }
 }
 
+// ---- pitch-synchronous modulation of the noise (tests/noise_modulation_ref.py)
+constexpr int NM_WAVES = 4;   // frames (waves) per block of the modulation kernel
+constexpr int NM_MAX = 8;     // harmonics of the envelope (M of the definition) at most
+
+// i of the definition: the instant nearest to input position x
+__device__ __forceinline__ int nearest_instant(double x, double ti0, double D, int n) {
+  const double r = rint((x - ti0) / D);
+  return r < 0.0 ? 0 : (r > (double)(n - 1) ? n - 1 : (int)r);
+}
+
+// mod[m][2j], mod[m][2j+1] = Re, Im of c_{j+1} = sum_v u[v] exp(-2 pi i (j+1) Theta(mH - 2H + v)) / sum_v u[v],
+// u = (w e)^2.  Order of the sums: lane l adds its samples v = l, l + 64, .. in increasing v, then the butterfly of
+// wave_sum (partner lane ^ 32, 16, .. 1).  All NM_MAX harmonics are summed (registers, no indexing by M); M are stored.
+extern "C" __global__ void __launch_bounds__(64 * NM_WAVES)
+    eaqhm_noise_modulation_kernel(const double* __restrict__ e, long long L, int H, int Nf,
+                                  const double* __restrict__ theta, const double* __restrict__ f0,
+                                  const unsigned char* __restrict__ voiced, int n, double ti0, double D, double fs, int M,
+                                  double* __restrict__ mod) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NM_WAVES + wave;
+  if (m >= Nf) return;
+  double* row = mod + (size_t)m * 2 * M;
+  const int W = 4 * H;
+  const long long base = (long long)m * H - 2 * H;
+  if (!voiced[nearest_instant((double)((long long)m * H), ti0, D, n)]) {   // uniform over the wave
+    if (lane < 2 * M) row[lane] = 0.0;
+    return;
+  }
+  double P = 0.0, re[NM_MAX], im[NM_MAX];
+#pragma unroll
+  for (int j = 0; j < NM_MAX; ++j) re[j] = im[j] = 0.0;
+  for (int v = lane; v < W; v += 64) {
+    const double w = 0.5 - 0.5 * cospi((double)(2 * v + 1) / (double)W);
+    const long long t = base + v;
+    const double x = w * ((t >= 0 && t < L) ? e[t] : 0.0);
+    const double u = x * x;
+    const double pos = (double)t;
+    const int i = nearest_instant(pos, ti0, D, n);
+    double th = theta[i] + f0[i] * (pos - (ti0 + (double)i * D)) / fs;
+    th = th - floor(th);
+    double s1, c1;
+    sincos((2.0 * M_PI) * th, &s1, &c1);
+    P = P + u;
+    double cj = c1, sj = s1;
+#pragma unroll
+    for (int j = 0; j < NM_MAX; ++j) {
+      re[j] = re[j] + u * cj;
+      im[j] = im[j] - u * sj;
+      const double cn = cj * c1 - sj * s1;
+      sj = sj * c1 + cj * s1;
+      cj = cn;
+    }
+  }
+  P = wave_sum(P);
+  const bool some = P > 0.0;
+#pragma unroll
+  for (int j = 0; j < NM_MAX; ++j) {
+    const double cr = wave_sum(re[j]), ci = wave_sum(im[j]);
+    if (j < M && lane == 2 * j) row[lane] = some ? cr / P : 0.0;
+    if (j < M && lane == 2 * j + 1) row[lane] = some ? ci / P : 0.0;
+  }
+}
+
+// g_q(n'), d = n' - qH: the coefficients blended between the model's frames as the filter kernel blends sigma and k;
+// one sincos of the reduced phase, e^{2 pi i j phi} by rotation, as the model has it
+__device__ __forceinline__ double mod_gain(const double* __restrict__ mod, int M, int Nf, int H, double tauq, double thq,
+                                           double nuq, double d) {
+  const double mu = tauq / (double)H;
+  long long m0 = (long long)floor(mu);
+  m0 = m0 < 0 ? 0 : (m0 > Nf - 1 ? Nf - 1 : m0);
+  const long long m1 = m0 + 1 > Nf - 1 ? Nf - 1 : m0 + 1;
+  const double fr = fmin(mu - (double)m0, 1.0);
+  const double w0 = 1.0 - fr;
+  const double* a = mod + (size_t)m0 * 2 * M;
+  const double* b = mod + (size_t)m1 * 2 * M;
+  double ph = thq + nuq * d;
+  ph = ph - floor(ph);
+  double s1, c1;
+  sincos((2.0 * M_PI) * ph, &s1, &c1);
+  double cj = c1, sj = s1, acc = 0.0;
+  for (int j = 0; j < M; ++j) {
+    const double cr = w0 * a[2 * j] + fr * b[2 * j];
+    const double ci = w0 * a[2 * j + 1] + fr * b[2 * j + 1];
+    acc = acc + (cr * cj - ci * sj);
+    const double cn = cj * c1 - sj * s1;
+    sj = sj * c1 + cj * s1;
+    cj = cn;
+  }
+  return sqrt(fmax(0.01, 1.0 + 2.0 * acc));
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+    eaqhm_noise_combine_mod_kernel(const double* __restrict__ Y, int H, int q_lo, int nq, int Nq, long long t_lo,
+                                   long long t_hi, double* __restrict__ out, int accumulate,
+                                   const double* __restrict__ mod, int M, int Nf, const double* __restrict__ tau,
+                                   const double* __restrict__ theta, const double* __restrict__ nu) {
+  const long long n = t_lo + (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= t_hi) return;
+  const long long q = n / H;
+  const int j = (int)(n - q * H);
+  const int qi = (int)(q - q_lo);
+  double val = (fade(H + j, H) * mod_gain(mod, M, Nf, H, tau[q], theta[q], nu[q], (double)j)) * Y[(size_t)(H + j) * nq + qi];
+  if (q + 1 < Nq)
+    val = val + (fade(j, H) * mod_gain(mod, M, Nf, H, tau[q + 1], theta[q + 1], nu[q + 1], (double)(j - H))) *
+                    Y[(size_t)j * nq + qi + 1];
+  out[n] = accumulate ? out[n] + val : val;
+}
+
 }  // namespace eaqhm
 
 using namespace eaqhm;
@@ -304,17 +415,18 @@ extern "C" int eaqhm_noise_analyse(eaqhm_ctx* ctx, const double* e, int64_t L, i
   return EAQHM_OK;
 }
 
-extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
-                                 int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
-                                 int64_t t_hi, double* out, int32_t accumulate) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!sigma || !refl || !tau || !out || Nf < 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: bad argument");
+// eaqhm_noise_synth and eaqhm_noise_synth_mod: the same checks and lattice; mod != nullptr selects the modulated cross-fade
+static int noise_synth_run(eaqhm_ctx* ctx, const char* who, const double* sigma, const double* refl, int32_t Nf,
+                           int32_t hop, int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out,
+                           int64_t t_lo, int64_t t_hi, double* out, int32_t accumulate, const double* mod,
+                           int32_t harmonics, const double* theta, const double* nu) {
+  if (!sigma || !refl || !tau || !out || Nf < 1) return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
   if (!noise_shape_ok(hop, order))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop");
+    return ctx->failf(EAQHM_EINVAL, "%s: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop", who);
   if (L_out <= 0 || (L_out - 1) / hop + 1 != (int64_t)Nq)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: Nq must be (L_out - 1) / hop + 1");
+    return ctx->failf(EAQHM_EINVAL, "%s: Nq must be (L_out - 1) / hop + 1", who);
   if (t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: [t_lo, t_hi) outside [0, L_out)");
+    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
   // the frames that cover [t_lo, t_hi): sample n' lies in frames n' / hop and n' / hop + 1
   const int64_t q_lo = t_lo / hop;
   int64_t q_hi = (t_hi - 1) / hop + 1;
@@ -328,9 +440,51 @@ extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const doub
   hipLaunchKernelGGL(eaqhm_noise_filter_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(64), lds, ctx->stream, sigma, refl,
                      (int)Nf, (int)hop, (int)order, tau, (unsigned long long)seed, (int)q_lo, nq, Y);
   HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(eaqhm_noise_combine_kernel, dim3((unsigned)((t_hi - t_lo + 255) / 256)), dim3(256), 0, ctx->stream,
-                     (const double*)Y, (int)hop, (int)q_lo, nq, (int)Nq, (long long)t_lo, (long long)t_hi, out,
-                     (int)(accumulate != 0));
+  const dim3 grid((unsigned)((t_hi - t_lo + 255) / 256));
+  if (mod)
+    hipLaunchKernelGGL(eaqhm_noise_combine_mod_kernel, grid, dim3(256), 0, ctx->stream, (const double*)Y, (int)hop,
+                       (int)q_lo, nq, (int)Nq, (long long)t_lo, (long long)t_hi, out, (int)(accumulate != 0), mod,
+                       (int)harmonics, (int)Nf, tau, theta, nu);
+  else
+    hipLaunchKernelGGL(eaqhm_noise_combine_kernel, grid, dim3(256), 0, ctx->stream, (const double*)Y, (int)hop, (int)q_lo,
+                       nq, (int)Nq, (long long)t_lo, (long long)t_hi, out, (int)(accumulate != 0));
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
+                                 int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
+                                 int64_t t_hi, double* out, int32_t accumulate) {
+  if (!ctx) return EAQHM_EINVAL;
+  return noise_synth_run(ctx, "eaqhm_noise_synth", sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out,
+                         accumulate, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int eaqhm_noise_synth_mod(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
+                                     int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out,
+                                     int64_t t_lo, int64_t t_hi, double* out, int32_t accumulate, const double* mod,
+                                     int32_t harmonics, const double* theta, const double* nu) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!mod || !theta || !nu) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth_mod: bad argument");
+  if (harmonics < 1 || harmonics > NM_MAX)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth_mod: need 1 <= harmonics <= 8");
+  return noise_synth_run(ctx, "eaqhm_noise_synth_mod", sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi,
+                         out, accumulate, mod, harmonics, theta, nu);
+}
+
+extern "C" int eaqhm_noise_modulation(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, const double* theta,
+                                      const double* f0, const uint8_t* voiced, int32_t No_ti, double ti0, double step,
+                                      double fs, int32_t harmonics, double* mod) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!e || !theta || !f0 || !voiced || !mod || L < 1 || No_ti < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_modulation: bad argument");
+  if (hop < 1 || hop > 1024 || harmonics < 1 || harmonics > NM_MAX || !(step > 0.0) || !(fs > 0.0))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_modulation: need 1 <= hop <= 1024, 1 <= harmonics <= 8, step > 0, fs > 0");
+  const int64_t Nf = (L - 1) / hop + 1;
+  if (Nf > INT32_MAX - NM_WAVES) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_modulation: too many frames");
+  hipLaunchKernelGGL(eaqhm_noise_modulation_kernel, dim3((unsigned)((Nf + NM_WAVES - 1) / NM_WAVES)), dim3(64 * NM_WAVES),
+                     0, ctx->stream, e, (long long)L, (int)hop, (int)Nf, theta, f0, (const unsigned char*)voiced,
+                     (int)No_ti, ti0, step, fs, (int)harmonics, mod);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

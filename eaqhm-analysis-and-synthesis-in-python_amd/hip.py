@@ -50,6 +50,9 @@ SYMBOLS = (
     ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32]),
     ("eaqhm_noise_warp", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     ("eaqhm_noise_envelope", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P]),
+    ("eaqhm_noise_modulation", C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _F64, _F64, _F64, _I32, _P]),
+    ("eaqhm_noise_synth_mod", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32,
+                                         _P, _I32, _P, _P]),
 )
 
 
@@ -241,6 +244,16 @@ class Context:
     def noise_envelope(self, sigma, refl, Nf, order, alpha, fnorm, F, out):
         self._ck(self.lib.eaqhm_noise_envelope(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(alpha), _ptr(fnorm), F,
                                                _ptr(out)))
+
+    def noise_modulation(self, e, L, hop, theta, f0, voiced, No_ti, ti0, step, fs, harmonics, mod):
+        self._ck(self.lib.eaqhm_noise_modulation(self.h, _ptr(e), L, hop, _ptr(theta), _ptr(f0), _ptr(voiced), No_ti,
+                                                 float(ti0), float(step), float(fs), harmonics, _ptr(mod)))
+
+    def noise_synth_mod(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, mod, harmonics, theta,
+                        nu, accumulate=False):
+        self._ck(self.lib.eaqhm_noise_synth_mod(self.h, _ptr(sigma), _ptr(refl), Nf, hop, order, _ptr(tau), Nq, seed,
+                                                L_out, t_lo, t_hi, _ptr(out), int(bool(accumulate)), _ptr(mod),
+                                                harmonics, _ptr(theta), _ptr(nu)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

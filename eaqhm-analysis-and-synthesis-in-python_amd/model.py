@@ -13,6 +13,9 @@
     eaQHMNoiseWarp(noise, formant_scale, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
     noise_formant_contour(noise, DetComponents, formant_scale) -> float64[Nf]
     noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[Nf, len(freqs)]
+    model_phase(DetComponents, fs, f0=None) -> float64[No_ti]
+    eaQHMNoiseModulation(s, s_recon, noise, DetComponents, harmonics=2, f0=None, *, device_index=0) -> noise + mod
+    noise_fundamental(DetComponents, fs, tau, time_map=None, time_scale=1.0, pitch_scale=1.0, f0=None) -> (theta, nu)
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
@@ -23,7 +26,10 @@ filtered white noise under the same time map (§10); its envelope follows a form
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
 eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours (eaqhm_modify_synth_shape and
 eaqhm_modify_synth_curve_shape for phase="shape"), eaqhm_model_envelope,
-eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp, eaqhm_noise_envelope); there is no CPU path.
+eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp, eaqhm_noise_envelope, eaqhm_noise_modulation,
+eaqhm_noise_synth_mod); there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
+(§10.2): eaQHMNoiseModulation adds the Fourier coefficients of the residual's power over the fundamental's phase to the
+noise model, and the synthesis plays that envelope at the output's fundamental.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -33,6 +39,7 @@ import numpy as np
 SCALE_RANGE = (0.25, 4.0)
 NOISE_MAX_HOP = 1024     # the analysis kernel keeps one 4-hop frame per wave in LDS
 NOISE_MAX_ORDER = 63     # lane l of a wave owns lag l
+NOISE_MOD_MAX = 8        # harmonics of the pitch-synchronous envelope of the noise at most
 
 
 def _cells(rows, mask=None):
@@ -343,7 +350,7 @@ def _device_records(model, dev):
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
                    formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, noise_formant=False,
-                   device_index=0, _ranges=None):
+                   noise_modulation=False, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -378,6 +385,11 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     the model whose all-pole envelope is moved up in frequency by alpha, so the result is bit for bit that of passing
     that warped model as `noise`.  The default leaves the noise's envelope where the analysis found it.
 
+    `noise_modulation=True` (it needs `noise` with the `mod` of eaQHMNoiseModulation) modulates the noise
+    pitch-synchronously (§10.2): the bursts of the analysed noise follow the fundamental this call plays, at every
+    scale and in both phase modes.  The result is bit for bit the synthesis without noise plus eaQHMNoiseSynthesis(noise,
+    tau, L_out, noise_seed, fundamental=noise_fundamental(DetComponents, fs, tau, ...)).  The default ignores `mod`.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     model = unpack_model(DetComponents)
@@ -397,6 +409,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
             raise ValueError("the noise model is of another signal: fs %g, length %d; this call: fs %g, length %d"
                              % (nz["fs"], nz["length"], fs, length))
     warp = check_noise_formant(noise_formant, noise, preserve_envelope)
+    modulate = check_noise_modulation(noise_modulation, nz if noise is not None else None)
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
@@ -450,9 +463,18 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         if warp:
             sigma_d, refl_d = _device_noise_warp(c, sigma_d, refl_d, nz["order"],
                                                  _frame_alpha(nz, model["ti"], np.broadcast_to(alpha, (n,))))
+        if modulate:
+            f0m = f0 if f0 is not None else _records_f0(model["records"], model["Kmax"])
+            path = (tm["gain"], tm["rate"], tm["rate"][-1] * beta[-1]) if contour else _scalar_path(n, rho, beta)
+            mod_d, th_d, nu_d = (torch.as_tensor(x, device=dev)
+                                 for x in (nz["mod"],) + _fundamental_at(model, fs, tau, f0m, *path))
         for t_lo, t_hi in ranges:
-            c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo, t_hi,
-                          out, accumulate=True)
+            if modulate:
+                c.noise_synth_mod(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo,
+                                  t_hi, out, mod_d, nz["mod_harmonics"], th_d, nu_d, accumulate=True)
+            else:
+                c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo,
+                              t_hi, out, accumulate=True)
     return out.cpu().numpy()
 
 
@@ -537,7 +559,9 @@ def check_noise_analysis_arguments(s, s_recon, fs, order=None, hop=None):
 
 def check_noise_model(noise):
     """Validates a noise model (no device work): returns it with sigma float64[Nf] (finite, >= 0), refl
-    float64[Nf, order] (|k| < 1) contiguous, hop, order and length ints, fs a float, Nf = (length - 1) // hop + 1."""
+    float64[Nf, order] (|k| < 1) contiguous, hop, order and length ints, fs a float, Nf = (length - 1) // hop + 1.
+    A model with the modulation of eaQHMNoiseModulation also returns mod float64[Nf, 2 M] (finite,
+    contiguous) and mod_harmonics = M in [1, 8]; the two keys come together or not at all."""
     if not isinstance(noise, dict) or not all(k in noise for k in ("sigma", "refl", "hop", "order", "fs", "length")):
         raise ValueError("a noise model is the dict eaQHMNoiseAnalysis returns: sigma, refl, hop, order, fs, length")
     hop, order, length = (_integer(noise[k], k) for k in ("hop", "order", "length"))
@@ -555,7 +579,19 @@ def check_noise_model(noise):
         raise ValueError("sigma must be finite and >= 0")
     if not np.all(np.abs(refl) < 1):     # also rejects NaN
         raise ValueError("reflection coefficients must lie inside (-1, 1)")
-    return dict(sigma=np.ascontiguousarray(sigma), refl=refl, hop=hop, order=order, fs=fs, length=length)
+    out = dict(sigma=np.ascontiguousarray(sigma), refl=refl, hop=hop, order=order, fs=fs, length=length)
+    if "mod" in noise or "mod_harmonics" in noise:
+        if not ("mod" in noise and "mod_harmonics" in noise):
+            raise ValueError("a modulated noise model holds both mod and mod_harmonics")
+        M = _mod_harmonics(noise["mod_harmonics"], "mod_harmonics")
+        mod = np.asarray(noise["mod"])
+        if mod.dtype.kind not in "iuf" or mod.shape != (len(sigma), 2 * M):
+            raise ValueError("mod must be a (Nf, 2 mod_harmonics) = (%d, %d) array of numbers" % (len(sigma), 2 * M))
+        mod = np.ascontiguousarray(mod, dtype=np.float64)
+        if not np.all(np.isfinite(mod)):
+            raise ValueError("mod must be finite")
+        out.update(mod=mod, mod_harmonics=M)
+    return out
 
 
 def check_noise_synthesis_arguments(noise, tau, L_out, seed=0):
@@ -614,7 +650,7 @@ def eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0):
     return dict(sigma=sigma.cpu().numpy(), refl=refl.cpu().numpy(), hop=hop, order=order, fs=fs, length=L)
 
 
-def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0, _ranges=None):
+def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, fundamental=None, *, device_index=0, _ranges=None):
     """Synthesises L_out samples of noise from a model of eaQHMNoiseAnalysis: white noise, a pure
     function of `seed` (0 <= seed < 2**64) and the sample index, through the all-pole lattice of each output frame and
     cross-faded between frames.  `tau[q]`, one value per output frame q = 0 .. (L_out - 1) // hop, is the position (in
@@ -622,18 +658,31 @@ def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0, _ranges=No
     rho) for a time scale, noise_time_map_contour for a contour; sigma and the reflection coefficients are interpolated
     linearly between the model's frames there.
 
+    `fundamental=(theta, nu)`, one value each per output frame (noise_fundamental gives them), turns the
+    pitch-synchronous modulation on: theta[q] is the phase of the output's fundamental in cycles at
+    sample q hop, nu[q] its advance in cycles per sample; frame q's samples are multiplied by
+    g_q(n') = sqrt(max(0.01, 1 + 2 Re sum_j c_{q,j} exp(2 pi i j (theta[q] + nu[q] (n' - q hop))))).  It needs a model
+    with `mod` (eaQHMNoiseModulation).  Without it nothing changes, whatever the model holds.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     nz, tau, L_out, seed = check_noise_synthesis_arguments(noise, tau, L_out, seed)
+    fund = check_noise_fundamental(nz, fundamental, len(tau))
     import torch
     from .functions import _ctx
     c = _ctx(device_index)
     dev = c.device
     sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
     out = torch.empty(L_out, dtype=torch.float64, device=dev)
+    if fund is not None:
+        mod_d, th_d, nu_d = (torch.as_tensor(x, device=dev) for x in (nz["mod"],) + fund)
     for t_lo, t_hi in ([(0, L_out)] if _ranges is None else _ranges):
-        c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
-                      int(t_lo), int(t_hi), out)
+        if fund is not None:
+            c.noise_synth_mod(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
+                              int(t_lo), int(t_hi), out, mod_d, nz["mod_harmonics"], th_d, nu_d)
+        else:
+            c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
+                          int(t_lo), int(t_hi), out)
     return out.cpu().numpy()
 
 
@@ -737,3 +786,195 @@ def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0):
     out = torch.empty((Nf, len(fnorm)), dtype=torch.float64, device=dev)
     c.noise_envelope(sigma_d, refl_d, Nf, nz["order"], alpha_d, f_d, len(fnorm), out)
     return out.cpu().numpy()
+
+
+# ---- pitch-synchronous modulation of the noise
+def _mod_harmonics(M, name="harmonics"):
+    M = _integer(M, name)
+    if not 1 <= M <= NOISE_MOD_MAX:
+        raise ValueError("%s must be in [1, %d], got %d" % (name, NOISE_MOD_MAX, M))
+    return M
+
+
+def _frac(x):
+    """x - floor(x), in [0, 1): a negative x so small that the difference rounds to 1 gives 0."""
+    y = x - np.floor(x)
+    return np.where(y >= 1.0, 0.0, y)
+
+
+def _records_phase(rec, K, f0, step, fs):
+    """Theta of DESIGN.md §10.2 from records: frac(ph / 2 pi) of slot 0 where it is active (an anchored instant); the
+    others by Theta_i = frac(Theta_{i-1} + (step / fs) (f0_{i-1} + f0_i) / 2) in increasing i, those ahead of the first
+    anchored instant by the same step backwards from it; from Theta_0 = 0 without any anchored instant."""
+    n = len(rec)
+    anchored = (rec[:, 0] != 0) & (rec[:, K] > 0) if K else np.zeros(n, dtype=bool)
+    th = np.zeros(n)
+    if K:
+        th[anchored] = _frac(rec[anchored, 2 * K] / (2 * np.pi))
+    inc = ((float(step) / float(fs)) * (f0[:-1] + f0[1:]) / 2).tolist()
+    first = int(np.flatnonzero(anchored)[0]) if anchored.any() else 0
+    v = th.tolist()
+    for i in range(first + 1, n):
+        if not anchored[i]:
+            v[i] = float(_frac(v[i - 1] + inc[i - 1]))
+    for i in range(first - 1, -1, -1):
+        v[i] = float(_frac(v[i + 1] - inc[i]))
+    return np.array(v)
+
+
+def model_phase(DetComponents, fs, f0=None):
+    """The phase of the model's fundamental in cycles, in [0, 1), per analysis instant: the analysed
+    phase of slot 0 (harmonic 1) where that slot is active, carried over the other instants by the integral of the
+    fundamental `f0` (model_f0(DetComponents, fs), or Hz per instant, finite and > 0 as for phase="shape").  It is what
+    the pitch-synchronous envelope of the noise is measured against.  Returns float64[No_ti]."""
+    fs = _sample_rate(fs)
+    model = unpack_model(DetComponents)
+    _, f0 = check_phase_arguments(model, "shape", f0)
+    return _records_phase(model["records"], model["Kmax"], f0, model["step"], fs)
+
+
+def _phase_at(x, theta, f0, ti0, step, fs):
+    """Theta(x) = Theta_i + f0_i (x - ti_i) / fs at the instant i nearest to x (rint, clipped to the model)."""
+    i = np.clip(np.rint((x - float(ti0)) / float(step)), 0, len(theta) - 1).astype(np.int64)
+    return theta[i] + f0[i] * (x - (float(ti0) + i * float(step))) / fs
+
+
+def _scalar_path(n, rho, beta):
+    """(gain, rate, g past the last knot) of the scalar path, in the form of the contour path's."""
+    return np.full(n - 1, beta * rho), np.full(n, rho), beta * rho
+
+
+def _fundamental_at(model, fs, tau, f0, gain, rate, g_last):
+    """(theta, nu) of DESIGN.md §10.2 at the input positions tau: tau lies in interval j = min(floor(tau / D), n-1) of
+    the instants at offset r = tau - j D; s is §11's advance there (f0 and the rate held past the last instant);
+    theta = frac(Theta(tau) + s), nu = (g_j / rho_j) F(tau) / fs with F the linear interpolation of f0."""
+    rec, K, D, ti = model["records"], model["Kmax"], float(model["step"]), model["ti"]
+    n = len(ti)
+    tau = np.asarray(tau, dtype=np.float64)
+    S = fundamental_advance(f0, gain, D, fs)
+    j = np.clip(np.floor(tau / D).astype(np.int64), 0, n - 1)
+    r = tau - j * D
+    inside = j <= n - 2
+    jc = np.minimum(j, n - 2)
+    fa = f0[j]
+    fb = np.where(inside, f0[jc + 1], f0[n - 1])
+    g = np.where(inside, np.asarray(gain, dtype=np.float64)[jc], g_last)
+    s = S[j] + (g - 1.0) * (fa * r + (fb - fa) * r * r / (2.0 * D)) / fs
+    Theta = _phase_at(tau, _records_phase(rec, K, f0, D, fs), f0, ti[0], D, fs)
+    F = np.interp(tau, ti.astype(np.float64), f0)
+    return np.ascontiguousarray(_frac(Theta + s)), np.ascontiguousarray((g / np.asarray(rate, dtype=np.float64)[j]) * F / fs)
+
+
+def _tau(tau):
+    tau = _numeric_1d(tau, "tau")
+    if len(tau) == 0 or not np.all(np.isfinite(tau)) or np.any(tau < 0):
+        raise ValueError("tau must be non-empty, finite and >= 0")
+    return tau
+
+
+def noise_fundamental(DetComponents, fs, tau, time_map=None, time_scale=1.0, pitch_scale=1.0, f0=None):
+    """The fundamental the synthesis plays at the output frames of the noise (host only): for
+    `tau` (noise_time_map / noise_time_map_contour) returns (theta, nu), float64 per output frame: the phase of the
+    fundamental in cycles, in [0, 1), at the frame's centre and its advance in cycles per output sample.  It is the
+    fundamental of phase="shape" (§11): the model's phase at tau plus the advance s.  The scalar path takes the numbers
+    `time_scale` and `pitch_scale`; the contour path takes `time_map` = contour_time_map(rho, beta, step, length) and
+    `pitch_scale` = beta (its value at the last instant holds past it; `time_scale` is in the map).  `f0` as for
+    phase="shape"; default model_f0.  This is eaQHMNoiseSynthesis's `fundamental`."""
+    fs = _sample_rate(fs)
+    model = unpack_model(DetComponents)
+    _check_records(model)
+    _, f0 = check_phase_arguments(model, "shape", f0)
+    tau = _tau(tau)
+    n = len(model["ti"])
+    if time_map is None:
+        path = _scalar_path(n, _scale(time_scale, "time_scale"), _scale(pitch_scale, "pitch_scale"))
+    else:
+        try:
+            gain, rate = _numeric_1d(time_map["gain"], "time_map gain"), _numeric_1d(time_map["rate"], "time_map rate")
+        except (TypeError, KeyError, IndexError):
+            raise ValueError("time_map is the dict contour_time_map returns") from None
+        if len(gain) != n - 1 or len(rate) != n or not np.all(np.isfinite(gain)) or not np.all(rate > 0):
+            raise ValueError("time_map is of another model: gain must have %d values and rate %d (> 0)" % (n - 1, n))
+        path = (gain, rate, rate[-1] * _contour(pitch_scale, "pitch_scale", n)[-1])
+    return _fundamental_at(model, fs, tau, f0, *path)
+
+
+def check_noise_fundamental(nz, fundamental, Nq):
+    """Validates eaQHMNoiseSynthesis's `fundamental` (no device work): None, or (theta, nu) as two contiguous
+    float64[Nq], finite; it needs a checked model `nz` with mod."""
+    if fundamental is None:
+        return None
+    if "mod" not in nz:
+        raise ValueError("fundamental= needs a noise model with mod (eaQHMNoiseModulation)")
+    try:
+        theta, nu = fundamental
+    except (TypeError, ValueError):
+        raise ValueError("fundamental must be the pair (theta, nu) of noise_fundamental") from None
+    theta, nu = _numeric_1d(theta, "theta"), _numeric_1d(nu, "nu")
+    if len(theta) != Nq or len(nu) != Nq:
+        raise ValueError("theta and nu must have one value per output frame (%d), got %d and %d"
+                         % (Nq, len(theta), len(nu)))
+    if not (np.all(np.isfinite(theta)) and np.all(np.isfinite(nu))):
+        raise ValueError("theta and nu must be finite")
+    return np.ascontiguousarray(theta), np.ascontiguousarray(nu)
+
+
+def check_noise_modulation(noise_modulation, nz):
+    """Validates eaQHMSynthesis's noise_modulation (no device work): a bool; True needs a noise model with mod."""
+    if not isinstance(noise_modulation, (bool, np.bool_)):
+        raise ValueError("noise_modulation must be True or False, got %r" % (noise_modulation,))
+    if noise_modulation and nz is None:
+        raise ValueError("noise_modulation=True needs noise=: there is no noise to modulate")
+    if noise_modulation and "mod" not in nz:
+        raise ValueError("noise_modulation=True needs a noise model with mod (eaQHMNoiseModulation)")
+    return bool(noise_modulation)
+
+
+def check_noise_modulation_arguments(s, s_recon, noise, DetComponents, harmonics=2, f0=None):
+    """Validates everything eaQHMNoiseModulation gets (no device work): returns (e, model of the noise, unpacked model,
+    M, f0).  The noise model and the deterministic model must be of this signal: the length is s's, and no instant lies
+    past it."""
+    nz = check_noise_model(noise)
+    a = _numeric_1d(s, "s")
+    b = _numeric_1d(s_recon, "s_recon")
+    if len(a) == 0 or len(a) != len(b):
+        raise ValueError("s and s_recon must be non-empty and of the same length, got %d and %d" % (len(a), len(b)))
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
+        raise ValueError("s and s_recon must be finite")
+    if len(a) != nz["length"]:
+        raise ValueError("the noise model is of another signal: length %d, s has %d" % (nz["length"], len(a)))
+    M = _mod_harmonics(harmonics)
+    model = unpack_model(DetComponents)
+    if int(model["ti"][-1]) >= len(a):
+        raise ValueError("the model is of another signal: its last instant (%d) lies past s (%d samples)"
+                         % (int(model["ti"][-1]), len(a)))
+    if not np.all(np.isfinite(model["records"])):
+        raise ValueError("the model holds non-finite values")
+    _, f0 = check_phase_arguments(model, "shape", f0)
+    return a - b, nz, model, M, f0
+
+
+def eaQHMNoiseModulation(s, s_recon, noise, DetComponents, harmonics=2, f0=None, *, device_index=0):
+    """The pitch-synchronous modulation of the noise.  In voiced speech the noise comes in bursts
+    locked to the glottal cycle; per frame of `noise` (eaQHMNoiseAnalysis of the same `s`, `s_recon`) this measures the
+    power of the windowed residual over the phase Theta of the model's fundamental (model_phase(DetComponents, fs, f0))
+    as Fourier coefficients c_j = sum u exp(-2 pi i j Theta) / sum u, u = (w e)^2, j = 1..`harmonics` (1 to 8).  They
+    stand for the power envelope g^2(theta) = 1 + 2 Re sum_j c_j exp(2 pi i j theta) over one pitch period.  A frame
+    without power, and a frame whose nearest analysis instant has no active partial (unvoiced), gets c = 0 exactly.
+
+    Returns a copy of `noise` with mod=float64[Nf, 2 harmonics] (Re c_1, Im c_1, ..) and mod_harmonics=harmonics, which
+    eaQHMNoiseSynthesis(fundamental=) and eaQHMSynthesis(noise_modulation=True) play; eaQHMNoiseWarp carries them
+    through."""
+    e, nz, model, M, f0 = check_noise_modulation_arguments(s, s_recon, noise, DetComponents, harmonics, f0)
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    dev = c.device
+    rec, K, D, ti = model["records"], model["Kmax"], model["step"], model["ti"]
+    theta = _records_phase(rec, K, f0, D, nz["fs"])
+    voiced = np.ascontiguousarray((rec[:, :K] != 0).any(axis=1), dtype=np.uint8)
+    e_d, th_d, f0_d, v_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev) for x in (e, theta, f0, voiced))
+    Nf = len(nz["sigma"])
+    mod = torch.empty((Nf, 2 * M), dtype=torch.float64, device=dev)
+    c.noise_modulation(e_d, len(e), nz["hop"], th_d, f0_d, v_d, len(ti), float(ti[0]), float(D), nz["fs"], M, mod)
+    return dict(nz, mod=mod.cpu().numpy(), mod_harmonics=M)

@@ -287,6 +287,28 @@ int eaqhm_noise_warp(eaqhm_ctx* ctx, const double* sigma, const double* refl, in
 int eaqhm_noise_envelope(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
                          const double* alpha, const double* fnorm, int32_t F, double* out);
 
+/* pitch-synchronous modulation of the noise (additions under ABI 5) ----------------------------------
+ * The noise of voiced speech comes in bursts locked to the glottal cycle.  Per noise frame the power envelope over the
+ * fundamental's phase theta (cycles) is g^2(theta) = 1 + 2 Re sum_j c_j exp(2 pi i j theta), j = 1..harmonics <= 8.
+ * eaqhm_noise_modulation (kernel: one wave per frame, lanes over the frame's 4 hop samples) analyses e = s - s_recon
+ *   (double[L]) on the frames of eaqhm_noise_analyse: c_j = sum_v u[v] exp(-2 pi i j Theta(m hop - 2 hop + v)) / sum_v u[v],
+ *   u = (w e)^2, Theta(x) = theta[i] + f0[i] (x - ti0 - i step) / fs at the instant i nearest to x.
+ *   theta, f0  double[No_ti]      the fundamental's phase (cycles, [0, 1)) and frequency (Hz) at every instant
+ *   voiced     uint8[No_ti]       0: a frame whose nearest instant is this one gets c = 0
+ *   mod        double[Nf][2 harmonics]  Re c_1, Im c_1, .. ; zeros where the frame's power is not > 0
+ * eaqhm_noise_synth_mod is eaqhm_noise_synth with the gain g_q(n') = sqrt(max(0.01, g^2(theta[q] + nu[q] (n' - q hop))))
+ *   on frame q's samples in the cross-fade, the coefficients blended between the model's frames at tau[q] as sigma is;
+ *   theta, nu  double[Nq]         the output fundamental's phase (cycles) at frame centre q hop and its advance per sample
+ *   A mod of zeros gives eaqhm_noise_synth's samples bit for bit.
+ * EAQHM_EINVAL as for their counterparts, and for null pointers, harmonics outside [1, 8], step or fs not > 0.        */
+int eaqhm_noise_modulation(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, const double* theta,
+                           const double* f0, const uint8_t* voiced, int32_t No_ti, double ti0, double step, double fs,
+                           int32_t harmonics, double* mod);
+int eaqhm_noise_synth_mod(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
+                          int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
+                          int64_t t_hi, double* out, int32_t accumulate, const double* mod, int32_t harmonics,
+                          const double* theta, const double* nu);
+
 #ifdef __cplusplus
 }
 #endif

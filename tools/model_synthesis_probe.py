@@ -2,7 +2,7 @@
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
-                                          [--noise] [--noise-formant] [--shape] [--out FILE]
+                                          [--noise] [--noise-formant] [--noise-modulation] [--shape] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -16,7 +16,9 @@ component on the workload's own residual: eaqhm_noise_analyse, 
 the median of three windows of 20 launches, with the max - min of the three.  --noise-formant adds the formant warp of
 the noise model on the same residual's model: eaqhm_noise_warp and eaqhm_noise_envelope (a 129-point
 grid) at alpha in {0.85, 1.2} and a ramp between them, beside eaqhm_noise_synth of the warped model at rho = 1 in the
-same session, with the same windows.  --shape adds the shape-invariant phase
+same session, with the same windows.  --noise-modulation adds the pitch-synchronous modulation of the noise (DESIGN.md
+§10.2): eaqhm_noise_modulation (2 harmonics) next to eaqhm_noise_analyse, and eaqhm_noise_synth_mod next to
+eaqhm_noise_synth at rho in {0.5, 1, 2}, with the same windows.  --shape adds the shape-invariant phase
 mode: eaqhm_modify_synth_shape next to eaqhm_modify_synth at rho in {0.5, 1, 2} x beta in {1, 1.25}, and
 eaqhm_modify_synth_curve_shape next to eaqhm_modify_synth_curve on the four contour settings, each the median of three
 windows of 20 launches with the max - min of the existing kernel's three (the margin).  EAQHM_LIB selects another build of
@@ -97,7 +99,8 @@ def prepare(torch, det, fs, L, reps):
                 t_unpack=t_unpack)
 
 
-def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False):
+def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
+          noise_modulation=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -132,7 +135,55 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
     if noise_formant:
         import eaqhm_amd
         res["noise_formant"] = noise_formant_rows(torch, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
+    if noise_modulation:
+        res["noise_modulation"] = noise_modulation_rows(torch, st, residual)
     return res
+
+
+def noise_modulation_rows(torch, st, residual, harmonics=2, reps=20, runs=3):
+    """The pitch-synchronous modulation of the noise on `residual` with the model of `st`: device time
+    of eaqhm_noise_modulation next to eaqhm_noise_analyse, and of eaqhm_noise_synth_mod next to eaqhm_noise_synth at
+    rho in {0.5, 1, 2} (beta = 1) with the analysed coefficients.  Each time: median of `runs` windows of `reps`
+    launches, and their max - min."""
+    from eaqhm_amd.model import (_fundamental_at, _records_f0, _records_phase, _scalar_path,
+                                 check_noise_analysis_arguments, noise_time_map)
+    c, K, D, fs, L, n = (st[k] for k in ("c", "K", "D", "fs", "L", "n"))
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rec = st["rec"].cpu().numpy()
+    model = dict(records=rec, Kmax=K, step=D, ti=np.arange(n, dtype=np.int64) * D)
+    f0 = _records_f0(rec, K)
+    e, _, H, p = check_noise_analysis_arguments(residual, np.zeros(len(residual)), fs)
+    Nf = (L - 1) // H + 1
+    e_d, th_d, f0_d, v_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                            for x in (e, _records_phase(rec, K, f0, D, fs), f0,
+                                      (rec[:, :K] != 0).any(axis=1).astype(np.uint8)))
+    sigma = torch.empty(Nf, dtype=torch.float64, device=dev)
+    refl = torch.empty((Nf, p), dtype=torch.float64, device=dev)
+    mod = torch.empty((Nf, 2 * harmonics), dtype=torch.float64, device=dev)
+    t_an, s_an = med(lambda: c.noise_analyse(e_d, L, H, p, sigma, refl))
+    t_mo, s_mo = med(lambda: c.noise_modulation(e_d, L, H, th_d, f0_d, v_d, n, 0.0, float(D), fs, harmonics, mod))
+    rows = [dict(setting="analysis", hop=H, order=p, frames=Nf, harmonics=harmonics, analyse_ms=t_an,
+                 analyse_spread_ms=s_an, modulation_ms=t_mo, modulation_spread_ms=s_mo,
+                 modulation_to_analyse=round(t_mo / t_an, 3),
+                 mean_abs_c1=round(float(torch.hypot(mod[:, 0], mod[:, 1]).mean()), 4))]
+    for rho in (0.5, 1.0, 2.0):
+        Lo = int(np.rint(rho * L))
+        tau = noise_time_map(H, Lo, rho)
+        theta, nu = _fundamental_at(model, fs, tau, f0, *_scalar_path(n, rho, 1.0))
+        tau_d, theta_d, nu_d = (torch.as_tensor(x, device=dev) for x in (tau, theta, nu))
+        out = torch.empty(Lo, dtype=torch.float64, device=dev)
+        t_ns, s_ns = med(lambda: c.noise_synth(sigma, refl, Nf, H, p, tau_d, len(tau), 0, Lo, 0, Lo, out))
+        t_nm, s_nm = med(lambda: c.noise_synth_mod(sigma, refl, Nf, H, p, tau_d, len(tau), 0, Lo, 0, Lo, out, mod,
+                                                   harmonics, theta_d, nu_d))
+        rows.append(dict(setting="rho%g" % rho, out_frames=len(tau), noise_synth_ms=t_ns, noise_synth_spread_ms=s_ns,
+                         noise_synth_mod_ms=t_nm, noise_synth_mod_spread_ms=s_nm,
+                         mod_minus_plain_ms=round(t_nm - t_ns, 4), mod_to_plain=round(t_nm / t_ns, 3)))
+    return rows
 
 
 def noise_formant_rows(torch, nz, reps=20, runs=3, grid=129):
@@ -339,10 +390,13 @@ def main():
     ap.add_argument("--formant", action="store_true", help="also time the formant prep kernels")
     ap.add_argument("--noise", action="store_true", help="also time the noise analysis and synthesis kernels")
     ap.add_argument("--noise-formant", action="store_true", help="also time the noise warp and envelope kernels")
+    ap.add_argument("--noise-modulation", action="store_true",
+                    help="also time the modulation analysis and the modulated noise synthesis")
     ap.add_argument("--shape", action="store_true", help="also time the shape-invariant phase kernels")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant) for w in a.workloads.split(",")]
+    res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
+                 a.noise_modulation) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
