@@ -138,6 +138,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_spline_edge_kernel(const
 struct EvalArgs {
   const double* records; const unsigned char* code; const double* mom;
   int No_ti; int Kmax; int step; double fs; long long L; long long t_lo; long long t_hi; long long s_lo; long long s_hi;
+  int eshift;   // error_sum_shift(std_det)
   // am_out / fm_out: biased by -track_t0, rows of Lt samples (only samples [t_lo, t_hi) are written); NULL: no track
   // output.  s_hat NULL: no synthesis, no phase rows, no error sums (a pass that only regenerates tracks).
   const double* target; double* am_out; double* fm_out; long long Lt; double* ph_knot; double* s_hat; long long* partials;
@@ -147,17 +148,32 @@ struct EvalArgs {
 // SRER (functions.py:388) needs sum d and sum d^2 over the whole file, d = target - s_hat.  They are collected per
 // block, per rank and (long files) per time block; a floating-point sum would make the last digits of the SRER — and
 // with them the stop rule `SRER[a] <= SRER[a-1]` — depend on that grouping.  So every sample is turned into fixed
-// point, three signed 64-bit limbs in base 2^32 (d * 2^60 and d^2 * 2^64, truncated: 2^-60 / 2^-64 absolute), and the
-// limbs are added as integers: exact, associative, identical for every block size, world size and streaming block.
-// |d| < 2^20 is required (anything larger, and NaN / Inf, is counted in limb 6 and reported by the host).
-#define ES_LIMBS 8   // {d: l0, l1, l2,  d^2: l0, l1, l2,  non-finite or huge samples, -}
+// point and the limbs are added as integers: exact, associative, identical for every block size, world size and
+// streaming block.  The resolution follows the signal: with std_det = m * 2^e, 0.5 <= m < 1 (frexp), the shift is
+// s = 10 - e (0 for a std_det that is zero or not finite, clamped to +-ES_SHIFT_MAX), which puts std_det * 2^s into
+// [2^9, 2^10), and d' = d * 2^s (exact) is what is summed: rint(d' * 2^60) and rint(d'^2 * 2^64), to nearest, ties to
+// even, three signed 64-bit limbs in base 2^32 each.  |d'| < 2^30 is required (anything larger — an error a million
+// times the signal's own level — and NaN / Inf is counted in limb 6 and reported by the host); the squared error is
+// resolved to 2^-84 of the squared level, which keeps the SRER to 1e-7 dB up to 180 dB.  The top limb of one sample
+// stays below 2^60; what bounds the int64 sums is the sum itself, sum d'^2 < 2^63 (include/eaqhm_hip.h).  The shift travels in limb 7:
+// the words say at which scale they were taken, and s = 0 is the plain d * 2^60, d^2 * 2^64.
+#define ES_LIMBS 8   // {d': l0, l1, l2,  d'^2: l0, l1, l2,  non-finite or huge samples, the shift s}
+#define ES_SHIFT_MAX 900
+__host__ __device__ inline int error_sum_shift(double std_det) {
+  if (!(std_det > 0.0) || std_det > 1.7e308) return 0;
+  int e;
+  frexp(std_det, &e);
+  const int s = 10 - e;
+  return s > ES_SHIFT_MAX ? ES_SHIFT_MAX : (s < -ES_SHIFT_MAX ? -ES_SHIFT_MAX : s);
+}
 __device__ inline void fixed_limbs(double x, long long& l0, long long& l1, long long& l2) {
-  // x already scaled by a power of two (exact); |x| < 2^104
+  // x already scaled by a power of two (exact); |x| < 2^126
+  x = rint(x);                                // to nearest; from here on every step is exact
   const double h2 = trunc(x * 0x1p-64);
   const double r1 = x - h2 * 0x1p64;          // exact: the low bits of x
   const double h1 = trunc(r1 * 0x1p-32);
   const double r0 = r1 - h1 * 0x1p32;         // exact
-  l2 = (long long)h2; l1 = (long long)h1; l0 = (long long)trunc(r0);
+  l2 = (long long)h2; l1 = (long long)h1; l0 = (long long)r0;
 }
 
 // Rows [r0, r1] of records / code / mom staged in LDS by the block (eaqhm_eval_kernel); anything outside (only the
@@ -349,8 +365,8 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
     const double sh = a0v + 2.0 * synth;
     A.s_hat[t] = sh;
     if (t >= A.s_lo && t < A.s_hi) {
-      const double d = A.target[t] - sh;
-      if (fabs(d) < 0x1p20) {   // (false for NaN)
+      const double d = scalbn(A.target[t] - sh, A.eshift);
+      if (fabs(d) < 0x1p30) {   // (false for NaN)
         fixed_limbs(d * 0x1p60, e[0], e[1], e[2]);
         fixed_limbs((d * d) * 0x1p64, e[3], e[4], e[5]);
       } else {
@@ -371,7 +387,8 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
 //   sums_out[0..3]  sum d, sum d^2, n, SRER in dB — doubles, a convenience for C callers; the Python host derives the
 //                   SRER itself from the limbs (one formula for every world size and block count)
 //   sums_out[4..6]  LS breakdowns / stalled diagonal pipelines / dropped frames since the last read (counters are cleared)
-//   sums_out[8..15] the limbs as int64 bit patterns: what ranks and time blocks add up
+//   sums_out[8..15] the limbs as int64 bit patterns: what ranks and time blocks add up (the last one is the shift, the
+//                   same on every rank: it is not added)
 extern "C" __global__ void __launch_bounds__(1024) eaqhm_srer_kernel(const long long* partials, long long nblocks, double n,
                                                                     double std_det, double* sums_out, int* faults) {
   __shared__ long long red[16][ES_LIMBS];
@@ -392,13 +409,15 @@ extern "C" __global__ void __launch_bounds__(1024) eaqhm_srer_kernel(const long 
       for (int w = 0; w < (int)(blockDim.x >> 6); ++w) e[q] += red[w][q];
       lim[q] = e[q];
     }
-    lim[ES_LIMBS - 1] = 0;
+    const int sh = error_sum_shift(std_det);
+    lim[ES_LIMBS - 1] = sh;
+    // the sums of d' and d'^2; the SRER is a ratio, so it is taken in the scaled domain (std_det * 2^s is in [2^9, 2^10))
     const double a = ((double)e[2] * 0x1p64 + (double)e[1] * 0x1p32 + (double)e[0]) * 0x1p-60;
     const double b = ((double)e[5] * 0x1p64 + (double)e[4] * 0x1p32 + (double)e[3]) * 0x1p-64;
     const double mean = a / n;
     const double var = b / n - mean * mean;
-    sums_out[0] = a; sums_out[1] = b; sums_out[2] = n;
-    sums_out[3] = e[6] ? __builtin_nan("") : 20.0 * log10(std_det / sqrt(var));
+    sums_out[0] = scalbn(a, -sh); sums_out[1] = scalbn(scalbn(b, -sh), -sh); sums_out[2] = n;
+    sums_out[3] = e[6] ? __builtin_nan("") : 20.0 * log10(scalbn(std_det, sh) / sqrt(var));
     sums_out[4] = (double)faults[0];   // LS systems whose factorisation broke down in this adaptation (eaqhm_ls_faults)
     sums_out[5] = (double)faults[1];   // diagonal pipelines that timed out (a bug of the library if ever nonzero)
     sums_out[6] = (double)faults[2];   // frames dropped because their window lay outside the resident track window
@@ -510,7 +529,7 @@ extern "C" int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uin
     return ctx->fail(EAQHM_EINVAL, "eaqhm_eval_synth: [t_lo, t_hi) outside the track window");
   if ((int64_t)(No_ti - 1) * step >= L) return ctx->fail(EAQHM_EINVAL, "eaqhm_eval_synth: instants beyond the signal");
   EvalArgs A{records, code, mom, No_ti, Kmax, step, fs, (long long)L, (long long)t_lo, (long long)t_hi,
-             (long long)s_lo, (long long)s_hi, target, tracks ? am_out - track_t0 : nullptr,
+             (long long)s_lo, (long long)s_hi, error_sum_shift(std_det), target, tracks ? am_out - track_t0 : nullptr,
              tracks ? fm_out - track_t0 : nullptr, (long long)track_len, ph_knot, s_hat, (long long*)partials};
   size_t lds_bytes = 0;
   int NK = 0, NR = 0;

@@ -28,6 +28,10 @@ class FramePlan:
 
     def __init__(self, length, fs, f0_grid, frames, frame_step, step, pitch_periods, analysis_window, partials):
         f0_grid = np.asarray(f0_grid, dtype=np.float64)
+        if analysis_window < 3:
+            # instants 0, 1 and No_ti-1 must stay unanalysed: the reference's run finder (functions.py:352) mispairs
+            # runs that touch them, and the pad knots of short runs sit on instants 0 and 1
+            raise ValueError("analysisWindow must be at least 3")
         self.L, self.fs, self.step = int(length), fs, int(step)
         self.Fmax = int(fs / 2 - 200)                                            # functions.py:115
         self.Kmax = int(partials) if partials > 0 else int(round(self.Fmax / np.min(f0_grid[:, 1])) + 10)
@@ -164,21 +168,37 @@ class StalledPipeline(RuntimeError):
     a defect of the library, never a property of the input — reported apart from singular systems."""
 
 
+ES_SHIFT_MAX = 900
+
+
+def error_sum_shift(std_det):
+    """The power of two s the error is scaled by before eaqhm_eval_synth sums it (include/eaqhm_hip.h): 10 - e of
+    std_det = m 2^e, 0.5 <= m < 1, so that std_det 2^s lies in [2^9, 2^10); 0 for a std_det that is zero or not finite.
+    std_det is the same on every rank, so the shift is too.  The library writes it into the eighth word of the sums;
+    this is the same rule for a host that wants to know it beforehand."""
+    s = float(std_det)
+    if not (s > 0.0) or not np.isfinite(s):
+        return 0
+    return int(min(max(10 - int(np.frexp(s)[1]), -ES_SHIFT_MAX), ES_SHIFT_MAX))
+
+
 def srer_from_limbs(limbs, n, std_det):
     """SRER in dB (functions.py:388: 20 log10(std(target) / std(target - s_recon)), population std) from the
-    fixed-point error sums of eaqhm_eval_synth (include/eaqhm_hip.h): three base-2^32 limbs of sum(d * 2^60), three of
-    sum(d^2 * 2^64), the count of non-finite (or absurdly large) samples.  Integer sums: the same value whatever
-    the number of ranks, blocks or time blocks that contributed.  NumPy semantics for the degenerate cases like the
-    reference's: a non-finite reconstruction gives nan, a perfect one +inf, a silent target -inf or nan."""
+    fixed-point error sums of eaqhm_eval_synth (include/eaqhm_hip.h): with d' = d 2^s, three base-2^32 limbs of
+    sum rint(d' 2^60), three of sum rint(d'^2 2^64), the count of non-finite (or absurdly large) samples, and s, the
+    shift the sums were taken at (the same on every rank: it is not added up with the rest).  Integer sums: the same
+    value whatever the number of ranks, blocks or time blocks that contributed.  NumPy semantics for the degenerate cases like the reference's: a non-finite reconstruction gives nan,
+    a perfect one +inf, a silent target -inf or nan."""
     v = [int(x) for x in limbs]
     if v[6]:
         return np.float64(np.nan)
     tot = (v[0] + (v[1] << 32) + (v[2] << 64)) / (1 << 60)          # int / int: correctly rounded
     tot2 = (v[3] + (v[4] << 32) + (v[5] << 64)) / (1 << 64)
     with np.errstate(all="ignore"):
+        # a ratio: taken in the scaled domain, where std_det 2^s is in [2^9, 2^10) and nothing under- or overflows
         mean = np.float64(tot) / np.float64(n)
         var = np.float64(tot2) / np.float64(n) - mean * mean
-        return np.float64(20.0) * np.log10(np.float64(std_det) / np.sqrt(var))
+        return np.float64(20.0) * np.log10(np.ldexp(np.float64(std_det), v[7]) / np.sqrt(var))
 
 
 def auto_track_budget(resident_bytes, free_bytes):
@@ -444,11 +464,15 @@ class DeviceAnalysis:
         aborts with numpy.linalg.LinAlgError."""
         p, sh = self.plan, self.shard
         words = self.sums.view(self.torch.int64)[8:16].clone()
+        # the eighth word is the shift the sums were taken at, the same on every rank that summed anything: it is added
+        # up next to the number of such ranks and divided again (a rank without samples of its own has all zeros)
+        shift = words[7:8].clone()
         words[7] = 0
         counts = self.sums[4:7].to(self.torch.int64)
-        red = self.torch.cat((words, counts))
+        red = self.torch.cat((words, counts, shift, self.torch.full_like(shift, int(self.s_hi > self.s_lo))))
         sh.all_reduce_sum(red)
         red = red.cpu().numpy()
+        red[7] = red[11] // max(int(red[12]), 1)
         faults, stalled, dropped = int(red[8]), int(red[9]), int(red[10])
         if dropped > 0:
             raise ValueError("%d frame(s) had their analysis window outside the resident track window (engine defect or a "

@@ -163,11 +163,26 @@ int eaqhm_spline_solve_range(eaqhm_ctx* ctx, const double* records, int32_t No_t
  *   partials         8-byte words, eaqhm_eval_partials_len of them: per-block error sums
  *   sums_out         double[16]: {sum d, sum d^2, n, SRER dB, LS breakdowns, stalled pipelines and dropped frames since the
  *                    last read (see eaqhm_ls_faults), -, then eight int64 bit patterns} with d = target - s_hat over
- *                    [s_lo,s_hi).  The int64 words are the same sums in fixed point — three base-2^32 limbs of
- *                    d*2^60, three of d^2*2^64, the number of samples with |d| >= 2^20 or non-finite, 0 — which add
- *                    up exactly over blocks, ranks and time blocks, so the SRER (functions.py:388, the input of the
- *                    stop rule :394) does not depend on how the file was split; sums_out[3] is that SRER for this
- *                    call's range alone (std_det: functions.py:161).                                  */
+ *                    [s_lo,s_hi).  The int64 words are the same sums in fixed point, which add up exactly over blocks,
+ *                    ranks and time blocks, so the SRER (functions.py:388, the input of the stop rule :394) does not
+ *                    depend on how the file was split; sums_out[3] is that SRER for this call's range alone.
+ *                    The fixed point follows the level of the signal.  std_det (functions.py:161, the same number on
+ *                    every rank) = m 2^e with 0.5 <= m < 1 gives the shift s = 10 - e (0 when std_det is zero or not
+ *                    finite; clamped to +-900), so that std_det 2^s lies in [2^9, 2^10), and d' = d 2^s is what is
+ *                    summed:
+ *                      words 0..2  three signed base-2^32 limbs of sum rint(d' 2^60)
+ *                      words 3..5  three of sum rint(d'^2 2^64), d'^2 rounded to double first
+ *                      word  6     the number of samples with |d'| >= 2^30 or d not finite; they enter no sum, and
+ *                                  the SRER is NaN when there is one
+ *                      word  7     s: the words say at which scale they were taken (s = 0: plain d 2^60, d^2 2^64).
+ *                                  Every call writes it; a host that adds the words of several ranks leaves it out
+ *                                  of the sum and keeps one copy
+ *                    rint is to nearest, ties to even.  Representable: a single error up to 2^20 times the signal's
+ *                    own level (a click 120 dB above it) in steps of 2^-70 of that level, its square in steps of
+ *                    2^-84 of the squared level: an SRER of 180 dB is still resolved to 1e-7 dB.  The top limb of one
+ *                    sample is below 2^60; the int64 sums hold sum d'^2 < 2^63, that is n x (mean square error /
+ *                    std_det^2) < 2^43: 2^23 samples at an SRER of -60 dB, 2^43 at 0 dB.
+ *                    sum d = (w0 + w1 2^32 + w2 2^64) 2^-60 2^-s, sum d^2 = (w3 + w4 2^32 + w5 2^64) 2^-64 2^-2s.    */
 int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                      int32_t No_ti, int32_t Kmax, int32_t step, double fs, int64_t L, int64_t t_lo, int64_t t_hi,
                      int64_t s_lo, int64_t s_hi, const double* target, double std_det, double* am_out,

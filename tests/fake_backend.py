@@ -111,12 +111,17 @@ class OracleBackend:
         so = sums_out.numpy()
         so[:] = 0
         so[0], so[1], so[2] = d.sum(), (d * d).sum(), n
-        # the fixed-point error sums of include/eaqhm_hip.h: sum of trunc(d * 2^60) and of trunc(d^2 * 2^64) as exact
-        # integers, cut into base-2^32 limbs (any cut that adds up to the same integer serves the host's recombination)
-        tot = sum(int(v) for v in np.trunc(d * 2.0 ** 60).astype(object))
-        tot2 = sum(int(v) for v in np.trunc((d * d) * 2.0 ** 64).astype(object))
+        # the fixed-point error sums of include/eaqhm_hip.h: with d' = d 2^s, s from std_det, the sums of rint(d' 2^60)
+        # and of rint(d'^2 2^64) as exact integers, cut into base-2^32 limbs (any cut that adds up to the same integer
+        # serves the host's recombination); the eighth word is the shift
+        from eaqhm_amd.engine import error_sum_shift
+        sh = error_sum_shift(std_det)
+        dp = np.ldexp(d, sh)
+        tot = sum(int(v) for v in np.rint(np.ldexp(dp, 60)))
+        tot2 = sum(int(v) for v in np.rint(np.ldexp(dp * dp, 64)))
         limbs = so.view(np.int64)[8:16]
         for j, v in ((0, tot), (3, tot2)):
             limbs[j], limbs[j + 1], limbs[j + 2] = v & 0xffffffff, (v >> 32) & 0xffffffff, v >> 64
+        limbs[7] = sh
         mean = so[0] / n
         so[3] = 20 * np.log10(std_det / np.sqrt(so[1] / n - mean * mean))
