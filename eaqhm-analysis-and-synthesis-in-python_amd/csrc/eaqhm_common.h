@@ -8,7 +8,7 @@
 
 #include "../../include/eaqhm_hip.h"
 
-#define EAQHM_ABI_VERSION 5
+#define EAQHM_ABI_VERSION 6
 
 struct eaqhm_ctx {
   int device = 0;
@@ -27,11 +27,6 @@ struct eaqhm_ctx {
 
   int fail(int code, const char* msg) {
     snprintf(err, sizeof(err), "%s", msg);
-    return code;
-  }
-  // fmt holds one %s: the entry point's name (entry points that share their checks)
-  int failf(int code, const char* fmt, const char* who) {
-    snprintf(err, sizeof(err), fmt, who);
     return code;
   }
   // grow-only scratch; growing synchronises the stream first (never happens in steady state)

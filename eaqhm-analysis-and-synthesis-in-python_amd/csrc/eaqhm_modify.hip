@@ -548,112 +548,51 @@ static int modify_block_samples(int Kmax, int step, double rho, int crow, int sh
   return 16;
 }
 
-// the scalar eval launch: eaqhm_modify_eval_kernel, or eaqhm_modify_eval_shape_kernel when sh is given
-static int modify_synth_launch(eaqhm_ctx* ctx, const char* who, const double* records, const uint8_t* code,
-                               const double* mom, const double* amp, const double* R, const double* ph0, int32_t No_ti,
-                               int32_t Kmax, int32_t step, double fs, double rho, double beta, int64_t L_out,
-                               int64_t t_lo, int64_t t_hi, double* out, const MShape* sh) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !amp || !R || !ph0 || !out || No_ti < 4 || Kmax <= 0 || step <= 0 ||
-      !finite_pos(fs) || (sh && (!sh->f0 || !sh->S)))
-    return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
-  if (!finite_pos(rho) || !finite_pos(beta))
-    return ctx->failf(EAQHM_EINVAL, "%s: rho and beta must be finite and > 0", who);
-  if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
-  size_t lds_bytes = 0;
-  int NR = 0;
-  const int TBS = modify_block_samples(Kmax, step, rho, 0, sh ? 1 : 0, &lds_bytes, &NR);
-  if (lds_bytes > 160 * 1024) return ctx->failf(EAQHM_EINVAL, "%s: Kmax too large for the LDS tables", who);
-  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, rho, beta, (long long)t_lo,
-                    (long long)t_hi, out};
-  const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  if (sh) {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_shape_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(eaqhm_modify_eval_shape_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, *sh,
-                       TBS, NR);
-  } else {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes));
-    hipLaunchKernelGGL(eaqhm_modify_eval_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, TBS, NR);
-  }
+// one eval launch: the kernel's LDS limit, the launch, the error check.  P is deduced from the kernel and from the
+// arguments alike, so each argument must have exactly its parameter's type: nothing is converted at the launch.
+template <class... P>
+static int modify_eval_launch(eaqhm_ctx* ctx, void (*kernel)(P...), long long nblocks, size_t lds_bytes, P... args) {
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, args...);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
 
+// The time map is the contours'  when C, rate and gain are given, else tau = n'/rho; the phase is the
+// shape-invariant one (§11; the prep ran without gain) when f0 and S are given, else each slot's own.  Two groups, four
+// kernels.
 extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                                   const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
                                   int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
-                                  int64_t t_hi, double* out) {
-  return modify_synth_launch(ctx, "eaqhm_modify_synth", records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta,
-                             L_out, t_lo, t_hi, out, nullptr);
-}
-
-// ---- shape-invariant phase: the prep ran without gain
-extern "C" int eaqhm_modify_synth_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                        const double* amp, const double* R, const double* ph0, int32_t No_ti,
-                                        int32_t Kmax, int32_t step, double fs, double rho, double beta, int64_t L_out,
-                                        int64_t t_lo, int64_t t_hi, double* out, const double* f0, const double* S) {
-  const MShape sh{f0, S};
-  return modify_synth_launch(ctx, "eaqhm_modify_synth_shape", records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho,
-                             beta, L_out, t_lo, t_hi, out, &sh);
-}
-
-// ---- time and pitch scale contours; with sh the shape kernel (§11)
-static int modify_synth_curve_launch(eaqhm_ctx* ctx, const char* who, const double* records, const uint8_t* code,
-                                     const double* mom, const double* amp, const double* R, const double* ph0,
-                                     int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* C,
-                                     const double* rate, const double* gain, double rate_min, int64_t L_out,
-                                     int64_t t_lo, int64_t t_hi, double* out, const MShape* sh) {
+                                  int64_t t_hi, double* out, const double* C, const double* rate, const double* gain,
+                                  double rate_min, const double* f0, const double* S) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!records || !code || !mom || !amp || !R || !ph0 || !C || !rate || !gain || !out || No_ti < 4 || Kmax <= 0 ||
-      step <= 0 || !finite_pos(fs) || (sh && (!sh->f0 || !sh->S)))
-    return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
-  if (!finite_pos(rate_min)) return ctx->failf(EAQHM_EINVAL, "%s: rate_min must be finite and > 0", who);
+  const bool curve = C && rate && gain, shape = f0 && S;
+  if (!records || !code || !mom || !amp || !R || !ph0 || !out || No_ti < 4 || Kmax <= 0 || step <= 0 ||
+      !finite_pos(fs) || (!curve && (C || rate || gain)) || (!shape && (f0 || S)))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: bad argument");
+  if (curve) {   // rho and beta are not read: the kernel gets 0, 0
+    if (!finite_pos(rate_min)) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: rate_min must be finite and > 0");
+    rho = beta = 0.0;
+  } else if (!finite_pos(rho) || !finite_pos(beta)) {
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: rho and beta must be finite and > 0");
+  }
   if (L_out <= 0 || t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: [t_lo, t_hi) outside [0, L_out)");
   size_t lds_bytes = 0;
   int NR = 0;
-  const int TBS = modify_block_samples(Kmax, step, rate_min, 3, sh ? 1 : 0, &lds_bytes, &NR);
-  if (lds_bytes > 160 * 1024) return ctx->failf(EAQHM_EINVAL, "%s: Kmax too large for the LDS tables", who);
-  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, 0.0, 0.0, (long long)t_lo,
+  const int TBS = modify_block_samples(Kmax, step, curve ? rate_min : rho, curve ? 3 : 0, shape ? 1 : 0, &lds_bytes, &NR);
+  if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_synth: Kmax too large for the LDS tables");
+  const MEvalArgs E{ModArgs{records, code, mom, No_ti, Kmax, step, fs}, amp, R, ph0, rho, beta, (long long)t_lo,
                     (long long)t_hi, out};
   const MCurve Cu{C, rate, gain};
+  const MShape Sh{f0, S};
   const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  if (sh) {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_shape_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(eaqhm_modify_eval_curve_shape_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E,
-                       Cu, *sh, TBS, NR);
-  } else {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_eval_curve_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(eaqhm_modify_eval_curve_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu,
-                       TBS, NR);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return EAQHM_OK;
-}
-
-extern "C" int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                        const double* amp, const double* R, const double* ph0, int32_t No_ti,
-                                        int32_t Kmax, int32_t step, double fs, const double* C, const double* rate,
-                                        const double* gain, double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi,
-                                        double* out) {
-  return modify_synth_curve_launch(ctx, "eaqhm_modify_synth_curve", records, code, mom, amp, R, ph0, No_ti, Kmax, step,
-                                   fs, C, rate, gain, rate_min, L_out, t_lo, t_hi, out, nullptr);
-}
-
-extern "C" int eaqhm_modify_synth_curve_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
-                                              const double* mom, const double* amp, const double* R, const double* ph0,
-                                              int32_t No_ti, int32_t Kmax, int32_t step, double fs, const double* C,
-                                              const double* rate, const double* gain, double rate_min, int64_t L_out,
-                                              int64_t t_lo, int64_t t_hi, double* out, const double* f0,
-                                              const double* S) {
-  const MShape sh{f0, S};
-  return modify_synth_curve_launch(ctx, "eaqhm_modify_synth_curve_shape", records, code, mom, amp, R, ph0, No_ti, Kmax,
-                                   step, fs, C, rate, gain, rate_min, L_out, t_lo, t_hi, out, &sh);
+  if (curve)
+    return shape ? modify_eval_launch(ctx, eaqhm_modify_eval_curve_shape_kernel, nblocks, lds_bytes, E, Cu, Sh, TBS, NR)
+                 : modify_eval_launch(ctx, eaqhm_modify_eval_curve_kernel, nblocks, lds_bytes, E, Cu, TBS, NR);
+  return shape ? modify_eval_launch(ctx, eaqhm_modify_eval_shape_kernel, nblocks, lds_bytes, E, Sh, TBS, NR)
+               : modify_eval_launch(ctx, eaqhm_modify_eval_kernel, nblocks, lds_bytes, E, TBS, NR);
 }
 
 // ---- envelope readout

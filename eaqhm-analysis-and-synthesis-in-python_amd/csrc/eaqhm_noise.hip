@@ -415,18 +415,22 @@ extern "C" int eaqhm_noise_analyse(eaqhm_ctx* ctx, const double* e, int64_t L, i
   return EAQHM_OK;
 }
 
-// eaqhm_noise_synth and eaqhm_noise_synth_mod: the same checks and lattice; mod != nullptr selects the modulated cross-fade
-static int noise_synth_run(eaqhm_ctx* ctx, const char* who, const double* sigma, const double* refl, int32_t Nf,
-                           int32_t hop, int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out,
-                           int64_t t_lo, int64_t t_hi, double* out, int32_t accumulate, const double* mod,
-                           int32_t harmonics, const double* theta, const double* nu) {
-  if (!sigma || !refl || !tau || !out || Nf < 1) return ctx->failf(EAQHM_EINVAL, "%s: bad argument", who);
+// mod, theta and nu given: the modulated cross-fade; none of them: the plain one, harmonics not read
+extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
+                                 int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
+                                 int64_t t_hi, double* out, int32_t accumulate, const double* mod, int32_t harmonics,
+                                 const double* theta, const double* nu) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !tau || !out || Nf < 1 || ((mod || theta || nu) && !(mod && theta && nu)))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: bad argument");
+  if (mod && (harmonics < 1 || harmonics > NM_MAX))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: need 1 <= harmonics <= 8");
   if (!noise_shape_ok(hop, order))
-    return ctx->failf(EAQHM_EINVAL, "%s: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop", who);
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: need 1 <= hop <= 1024, 1 <= order <= 63, order < 4 hop");
   if (L_out <= 0 || (L_out - 1) / hop + 1 != (int64_t)Nq)
-    return ctx->failf(EAQHM_EINVAL, "%s: Nq must be (L_out - 1) / hop + 1", who);
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: Nq must be (L_out - 1) / hop + 1");
   if (t_lo < 0 || t_hi > L_out || t_lo >= t_hi)
-    return ctx->failf(EAQHM_EINVAL, "%s: [t_lo, t_hi) outside [0, L_out)", who);
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth: [t_lo, t_hi) outside [0, L_out)");
   // the frames that cover [t_lo, t_hi): sample n' lies in frames n' / hop and n' / hop + 1
   const int64_t q_lo = t_lo / hop;
   int64_t q_hi = (t_hi - 1) / hop + 1;
@@ -450,26 +454,6 @@ static int noise_synth_run(eaqhm_ctx* ctx, const char* who, const double* sigma,
                        nq, (int)Nq, (long long)t_lo, (long long)t_hi, out, (int)(accumulate != 0));
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
-}
-
-extern "C" int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
-                                 int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
-                                 int64_t t_hi, double* out, int32_t accumulate) {
-  if (!ctx) return EAQHM_EINVAL;
-  return noise_synth_run(ctx, "eaqhm_noise_synth", sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out,
-                         accumulate, nullptr, 0, nullptr, nullptr);
-}
-
-extern "C" int eaqhm_noise_synth_mod(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
-                                     int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out,
-                                     int64_t t_lo, int64_t t_hi, double* out, int32_t accumulate, const double* mod,
-                                     int32_t harmonics, const double* theta, const double* nu) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!mod || !theta || !nu) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth_mod: bad argument");
-  if (harmonics < 1 || harmonics > NM_MAX)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_synth_mod: need 1 <= harmonics <= 8");
-  return noise_synth_run(ctx, "eaqhm_noise_synth_mod", sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi,
-                         out, accumulate, mod, harmonics, theta, nu);
 }
 
 extern "C" int eaqhm_noise_modulation(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, const double* theta,

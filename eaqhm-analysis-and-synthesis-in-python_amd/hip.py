@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("EAQHM_LIB") or os.path.join(_HERE, "csrc", "libeaqhm_
 _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
 # EAQHM_ABI_VERSION (csrc/eaqhm_common.h) this binding was written for: argument lists change under unchanged names
-ABI_VERSION = 5
+ABI_VERSION = 6
 SYMBOLS = (
     ("eaqhm_ctx_create", C.c_int, [C.POINTER(_P), C.c_int]),
     ("eaqhm_ctx_destroy", C.c_int, [_P]),
@@ -38,21 +38,14 @@ SYMBOLS = (
     ("eaqhm_eval_partials_len", _I64, [_I64, _I64, _I32]),
     ("eaqhm_modify_prep", C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _P, _P]),
     ("eaqhm_modify_synth", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64, _I64,
-                                      _P]),
-    ("eaqhm_modify_synth_curve", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64, _I64,
-                                            _I64, _I64, _P]),
-    ("eaqhm_modify_synth_shape", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _F64, _F64, _I64, _I64,
-                                            _I64, _P, _P, _P]),
-    ("eaqhm_modify_synth_curve_shape", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _F64,
-                                                  _I64, _I64, _I64, _P, _P, _P]),
+                                      _P, _P, _P, _P, _F64, _P, _P]),
     ("eaqhm_model_envelope", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P]),
     ("eaqhm_noise_analyse", C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
-    ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32]),
+    ("eaqhm_noise_synth", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32,
+                                     _P, _I32, _P, _P]),
     ("eaqhm_noise_warp", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     ("eaqhm_noise_envelope", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P]),
     ("eaqhm_noise_modulation", C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _F64, _F64, _F64, _I32, _P]),
-    ("eaqhm_noise_synth_mod", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_uint64, _I64, _I64, _I64, _P, _I32,
-                                         _P, _I32, _P, _P]),
 )
 
 
@@ -202,29 +195,15 @@ class Context:
                                             _ptr(beta), _ptr(gain), _ptr(alpha), int(bool(preserve_envelope)),
                                             _ptr(amp), _ptr(R), _ptr(ph0)))
 
-    def modify_synth(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi, out):
+    def modify_synth(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi, out,
+                     curve=None, shape=None):
+        """curve = (C, rate, gain, rate_min): the contour map (rho, beta not read); shape = (f0, S): the shape phase."""
+        C_, rate, gain, rate_min = curve or (None, None, None, 0.0)
+        f0, S = shape or (None, None)
         self._ck(self.lib.eaqhm_modify_synth(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R), _ptr(ph0),
                                              No_ti, Kmax, step, float(fs), float(rho), float(beta), L_out, t_lo, t_hi,
-                                             _ptr(out)))
-
-    def modify_synth_curve(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, C, rate, gain, rate_min, L_out,
-                           t_lo, t_hi, out):
-        self._ck(self.lib.eaqhm_modify_synth_curve(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
-                                                   _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C), _ptr(rate),
-                                                   _ptr(gain), float(rate_min), L_out, t_lo, t_hi, _ptr(out)))
-
-    def modify_synth_shape(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, rho, beta, L_out, t_lo, t_hi,
-                           out, f0, S):
-        self._ck(self.lib.eaqhm_modify_synth_shape(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp), _ptr(R),
-                                                   _ptr(ph0), No_ti, Kmax, step, float(fs), float(rho), float(beta),
-                                                   L_out, t_lo, t_hi, _ptr(out), _ptr(f0), _ptr(S)))
-
-    def modify_synth_curve_shape(self, records, code, mom, amp, R, ph0, No_ti, Kmax, step, fs, C, rate, gain, rate_min,
-                                 L_out, t_lo, t_hi, out, f0, S):
-        self._ck(self.lib.eaqhm_modify_synth_curve_shape(self.h, _ptr(records), _ptr(code), _ptr(mom), _ptr(amp),
-                                                         _ptr(R), _ptr(ph0), No_ti, Kmax, step, float(fs), _ptr(C),
-                                                         _ptr(rate), _ptr(gain), float(rate_min), L_out, t_lo, t_hi,
-                                                         _ptr(out), _ptr(f0), _ptr(S)))
+                                             _ptr(out), _ptr(C_), _ptr(rate), _ptr(gain), float(rate_min), _ptr(f0),
+                                             _ptr(S)))
 
     def model_envelope(self, records, No_ti, Kmax, alpha, freqs, F, out):
         self._ck(self.lib.eaqhm_model_envelope(self.h, _ptr(records), No_ti, Kmax, _ptr(alpha), _ptr(freqs), F,
@@ -233,9 +212,13 @@ class Context:
     def noise_analyse(self, e, L, hop, order, sigma, refl):
         self._ck(self.lib.eaqhm_noise_analyse(self.h, _ptr(e), L, hop, order, _ptr(sigma), _ptr(refl)))
 
-    def noise_synth(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, accumulate=False):
+    def noise_synth(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, accumulate=False,
+                    mod=None):
+        """mod = (mod, harmonics, theta, nu): the pitch-synchronous modulation."""
+        mod_, harmonics, theta, nu = mod or (None, 0, None, None)
         self._ck(self.lib.eaqhm_noise_synth(self.h, _ptr(sigma), _ptr(refl), Nf, hop, order, _ptr(tau), Nq, seed, L_out,
-                                            t_lo, t_hi, _ptr(out), int(bool(accumulate))))
+                                            t_lo, t_hi, _ptr(out), int(bool(accumulate)), _ptr(mod_), harmonics,
+                                            _ptr(theta), _ptr(nu)))
 
     def noise_warp(self, sigma, refl, Nf, order, alpha, sigma_out, refl_out):
         self._ck(self.lib.eaqhm_noise_warp(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(alpha), _ptr(sigma_out),
@@ -248,12 +231,6 @@ class Context:
     def noise_modulation(self, e, L, hop, theta, f0, voiced, No_ti, ti0, step, fs, harmonics, mod):
         self._ck(self.lib.eaqhm_noise_modulation(self.h, _ptr(e), L, hop, _ptr(theta), _ptr(f0), _ptr(voiced), No_ti,
                                                  float(ti0), float(step), float(fs), harmonics, _ptr(mod)))
-
-    def noise_synth_mod(self, sigma, refl, Nf, hop, order, tau, Nq, seed, L_out, t_lo, t_hi, out, mod, harmonics, theta,
-                        nu, accumulate=False):
-        self._ck(self.lib.eaqhm_noise_synth_mod(self.h, _ptr(sigma), _ptr(refl), Nf, hop, order, _ptr(tau), Nq, seed,
-                                                L_out, t_lo, t_hi, _ptr(out), int(bool(accumulate)), _ptr(mod),
-                                                harmonics, _ptr(theta), _ptr(nu)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

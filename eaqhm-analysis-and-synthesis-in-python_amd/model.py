@@ -24,10 +24,8 @@ also be a contour, one value per analysis instant (§9.1).  A formant scale move
 (§9.2).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
 filtered white noise under the same time map (§10); its envelope follows a formant scale on request (§10.1).  phase="shape" keeps the phases of the harmonics relative to the
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
-eaqhm_modify_prep, eaqhm_modify_synth or eaqhm_modify_synth_curve for contours (eaqhm_modify_synth_shape and
-eaqhm_modify_synth_curve_shape for phase="shape"), eaqhm_model_envelope,
-eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp, eaqhm_noise_envelope, eaqhm_noise_modulation,
-eaqhm_noise_synth_mod); there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
+eaqhm_modify_prep, eaqhm_modify_synth, eaqhm_model_envelope, eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp,
+eaqhm_noise_envelope, eaqhm_noise_modulation); there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
 (§10.2): eaQHMNoiseModulation adds the Fourier coefficients of the residual's power over the fundamental's phase to the
 noise model, and the synthesis plays that envelope at the output's fundamental.
 """
@@ -336,6 +334,14 @@ def fundamental_advance(f0, gain, step, fs):
     return S
 
 
+def _device(device_index):
+    """(torch, the library context of the device bound to torch's current stream, its torch.device)."""
+    import torch
+    from .functions import _ctx
+    c = _ctx(device_index)
+    return torch, c, c.device
+
+
 def _device_records(model, dev):
     """The model's records on the device: (tensor, No_ti, Kmax).  A model without any slot keeps one empty slot, so that
     the kernels still run (the a0 spline of the synthesis, the -inf rows of the envelope)."""
@@ -410,10 +416,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
                              % (nz["fs"], nz["length"], fs, length))
     warp = check_noise_formant(noise_formant, noise, preserve_envelope)
     modulate = check_noise_modulation(noise_modulation, nz if noise is not None else None)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     rec, n, K = _device_records(model, dev)
     D = model["step"]
     if contour:
@@ -437,25 +440,14 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     # phase="shape" leaves Delta unweighted on either path: the weight moves to the fundamental's advance S
     c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta), None if shape else gain_d, dv(alpha) if formant else None,
                   preserve_envelope, amp, R, ph0)
+    # the two optional groups of eaqhm_modify_synth; the contour map holds rho and beta, which are then not read
+    curve_d = (dv(tm["C"]), dv(tm["rate"]), gain_d, tm["rate_min"]) if contour else None
+    shape_d = None
     if shape:
-        f0_d = dv(f0)
-        S_d = dv(fundamental_advance(f0, tm["gain"] if contour else np.full(n - 1, beta * rho), D, fs))
-    if contour:
-        C_d, rate_d = dv(tm["C"]), dv(tm["rate"])
-        for t_lo, t_hi in ranges:
-            if shape:
-                c.modify_synth_curve_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
-                                           tm["rate_min"], L_out, t_lo, t_hi, out, f0_d, S_d)
-            else:
-                c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d, tm["rate_min"],
-                                     L_out, t_lo, t_hi, out)
-    else:
-        for t_lo, t_hi in ranges:
-            if shape:
-                c.modify_synth_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out, f0_d,
-                                     S_d)
-            else:
-                c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, L_out, t_lo, t_hi, out)
+        shape_d = (dv(f0), dv(fundamental_advance(f0, tm["gain"] if contour else np.full(n - 1, beta * rho), D, fs)))
+    rho_s, beta_s = (0.0, 0.0) if contour else (rho, beta)
+    for t_lo, t_hi in ranges:
+        c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho_s, beta_s, L_out, t_lo, t_hi, out, curve_d, shape_d)
     if noise is not None:
         H = nz["hop"]
         tau = noise_time_map_contour(H, tm, D) if contour else noise_time_map(H, L_out, rho)
@@ -463,27 +455,29 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         if warp:
             sigma_d, refl_d = _device_noise_warp(c, sigma_d, refl_d, nz["order"],
                                                  _frame_alpha(nz, model["ti"], np.broadcast_to(alpha, (n,))))
+        mod_d = None
         if modulate:
             f0m = f0 if f0 is not None else _records_f0(model["records"], model["Kmax"])
             path = (tm["gain"], tm["rate"], tm["rate"][-1] * beta[-1]) if contour else _scalar_path(n, rho, beta)
-            mod_d, th_d, nu_d = (torch.as_tensor(x, device=dev)
-                                 for x in (nz["mod"],) + _fundamental_at(model, fs, tau, f0m, *path))
+            theta, nu = _fundamental_at(model, fs, tau, f0m, *path)
+            mod_d = _device_mod(torch, dev, nz, theta, nu)
         for t_lo, t_hi in ranges:
-            if modulate:
-                c.noise_synth_mod(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo,
-                                  t_hi, out, mod_d, nz["mod_harmonics"], th_d, nu_d, accumulate=True)
-            else:
-                c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo,
-                              t_hi, out, accumulate=True)
+            c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), H, nz["order"], tau_d, len(tau), seed, L_out, t_lo, t_hi, out,
+                          accumulate=True, mod=mod_d)
     return out.cpu().numpy()
+
+
+def _freq_grid(freqs):
+    f = _numeric_1d(freqs, "freqs")
+    if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
+        raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
+    return f
 
 
 def check_envelope_arguments(model, fs, freqs, formant_scale):
     """Validates everything model_envelope gets (no device work): returns (alpha float64[No_ti], freqs float64[F])."""
     _sample_rate(fs)
-    f = _numeric_1d(freqs, "freqs")
-    if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
-        raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
+    f = _freq_grid(freqs)
     if len(model["records"]) < 4:
         raise ValueError("the model needs at least 4 analysis instants")
     _check_records(model)
@@ -502,10 +496,7 @@ def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=
     16 kHz, step 15, 64 000 instants, on a 120-point grid).  Returns float64[No_ti, len(freqs)]."""
     model = unpack_model(DetComponents)
     alpha, f = check_envelope_arguments(model, fs, freqs, formant_scale)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     rec, n, K = _device_records(model, dev)
     alpha_d = torch.as_tensor(np.ascontiguousarray(alpha), device=dev)
     f_d = torch.as_tensor(np.ascontiguousarray(f), device=dev)
@@ -541,16 +532,21 @@ def _noise_shape(hop, order):
         raise ValueError("order must be in [1, %d] and < 4 * hop (%d), got %d" % (NOISE_MAX_ORDER, 4 * hop, order))
 
 
-def check_noise_analysis_arguments(s, s_recon, fs, order=None, hop=None):
-    """Validates everything eaQHMNoiseAnalysis gets (no device work): returns (e, fs, hop, order) with the residual
-    e = s - s_recon as float64.  hop defaults to round(0.005 fs), order to min(63, 2 + round(fs / 1000))."""
-    fs = _sample_rate(fs)
+def _signal_pair(s, s_recon):
     a = _numeric_1d(s, "s")
     b = _numeric_1d(s_recon, "s_recon")
     if len(a) == 0 or len(a) != len(b):
         raise ValueError("s and s_recon must be non-empty and of the same length, got %d and %d" % (len(a), len(b)))
     if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
         raise ValueError("s and s_recon must be finite")
+    return a, b
+
+
+def check_noise_analysis_arguments(s, s_recon, fs, order=None, hop=None):
+    """Validates everything eaQHMNoiseAnalysis gets (no device work): returns (e, fs, hop, order) with the residual
+    e = s - s_recon as float64.  hop defaults to round(0.005 fs), order to min(63, 2 + round(fs / 1000))."""
+    fs = _sample_rate(fs)
+    a, b = _signal_pair(s, s_recon)
     hop = int(round(0.005 * fs)) if hop is None else _integer(hop, "hop")
     order = min(NOISE_MAX_ORDER, 2 + int(round(fs / 1000.0))) if order is None else _integer(order, "order")
     _noise_shape(hop, order)
@@ -637,10 +633,7 @@ def eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0):
     refl=float64[Nf, order] the reflection coefficients k_1..k_p, hop, order, fs, length), Nf = (len(s) - 1) // hop + 1.
     Reflection coefficients, not the polynomial, are the stored form: a blend of two stable sets is stable."""
     e, fs, hop, order = check_noise_analysis_arguments(s, s_recon, fs, order, hop)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     L = len(e)
     Nf = (L - 1) // hop + 1
     e_d = torch.as_tensor(np.ascontiguousarray(e), device=dev)
@@ -648,6 +641,12 @@ def eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0):
     refl = torch.empty((Nf, order), dtype=torch.float64, device=dev)
     c.noise_analyse(e_d, L, hop, order, sigma, refl)
     return dict(sigma=sigma.cpu().numpy(), refl=refl.cpu().numpy(), hop=hop, order=order, fs=fs, length=L)
+
+
+def _device_mod(torch, dev, nz, theta, nu):
+    """The optional group of eaqhm_noise_synth on the device: (mod, harmonics, theta, nu)."""
+    mod_d, th_d, nu_d = (torch.as_tensor(x, device=dev) for x in (nz["mod"], theta, nu))
+    return mod_d, nz["mod_harmonics"], th_d, nu_d
 
 
 def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, fundamental=None, *, device_index=0, _ranges=None):
@@ -668,21 +667,13 @@ def eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, fundamental=None, *, device_i
     Returns float64[L_out]."""
     nz, tau, L_out, seed = check_noise_synthesis_arguments(noise, tau, L_out, seed)
     fund = check_noise_fundamental(nz, fundamental, len(tau))
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
     out = torch.empty(L_out, dtype=torch.float64, device=dev)
-    if fund is not None:
-        mod_d, th_d, nu_d = (torch.as_tensor(x, device=dev) for x in (nz["mod"],) + fund)
+    mod_d = None if fund is None else _device_mod(torch, dev, nz, *fund)
     for t_lo, t_hi in ([(0, L_out)] if _ranges is None else _ranges):
-        if fund is not None:
-            c.noise_synth_mod(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
-                              int(t_lo), int(t_hi), out, mod_d, nz["mod_harmonics"], th_d, nu_d)
-        else:
-            c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
-                          int(t_lo), int(t_hi), out)
+        c.noise_synth(sigma_d, refl_d, len(nz["sigma"]), nz["hop"], nz["order"], tau_d, len(tau), seed, L_out,
+                      int(t_lo), int(t_hi), out, mod=mod_d)
     return out.cpu().numpy()
 
 
@@ -732,9 +723,7 @@ def check_noise_envelope_arguments(noise, fs, freqs, formant_scale):
     """Validates everything noise_envelope gets (no device work): returns (model, alpha float64[Nf], fnorm float64[F])
     with fnorm = freqs / fs.  fs must be the model's."""
     fs = _sample_rate(fs)
-    f = _numeric_1d(freqs, "freqs")
-    if len(f) == 0 or len(f) > 2 ** 31 - 1 or not np.all(np.isfinite(f)) or np.any(f < 0):
-        raise ValueError("freqs must be a non-empty 1-D array of finite frequencies >= 0 (Hz)")
+    f = _freq_grid(freqs)
     nz, alpha = check_noise_warp_arguments(noise, formant_scale)
     if nz["fs"] != fs:
         raise ValueError("the noise model has fs %g, this call %g" % (nz["fs"], fs))
@@ -760,10 +749,8 @@ def eaQHMNoiseWarp(noise, formant_scale, *, device_index=0):
 
     Returns a new dict(sigma, refl, hop, order, fs, length) of the same layout."""
     nz, alpha = check_noise_warp_arguments(noise, formant_scale)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    sigma_d, refl_d = (torch.as_tensor(x, device=c.device) for x in (nz["sigma"], nz["refl"]))
+    torch, c, dev = _device(device_index)
+    sigma_d, refl_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"]))
     sigma_o, refl_o = _device_noise_warp(c, sigma_d, refl_d, nz["order"], alpha)
     return dict(nz, sigma=sigma_o.cpu().numpy(), refl=refl_o.cpu().numpy())
 
@@ -777,10 +764,7 @@ def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0):
 
     Returns float64[Nf, len(freqs)]."""
     nz, alpha, fnorm = check_noise_envelope_arguments(noise, fs, freqs, formant_scale)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     sigma_d, refl_d, alpha_d, f_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], alpha, fnorm))
     Nf = len(nz["sigma"])
     out = torch.empty((Nf, len(fnorm)), dtype=torch.float64, device=dev)
@@ -935,12 +919,7 @@ def check_noise_modulation_arguments(s, s_recon, noise, DetComponents, harmonics
     M, f0).  The noise model and the deterministic model must be of this signal: the length is s's, and no instant lies
     past it."""
     nz = check_noise_model(noise)
-    a = _numeric_1d(s, "s")
-    b = _numeric_1d(s_recon, "s_recon")
-    if len(a) == 0 or len(a) != len(b):
-        raise ValueError("s and s_recon must be non-empty and of the same length, got %d and %d" % (len(a), len(b)))
-    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
-        raise ValueError("s and s_recon must be finite")
+    a, b = _signal_pair(s, s_recon)
     if len(a) != nz["length"]:
         raise ValueError("the noise model is of another signal: length %d, s has %d" % (nz["length"], len(a)))
     M = _mod_harmonics(harmonics)
@@ -966,10 +945,7 @@ def eaQHMNoiseModulation(s, s_recon, noise, DetComponents, harmonics=2, f0=None,
     eaQHMNoiseSynthesis(fundamental=) and eaQHMSynthesis(noise_modulation=True) play; eaQHMNoiseWarp carries them
     through."""
     e, nz, model, M, f0 = check_noise_modulation_arguments(s, s_recon, noise, DetComponents, harmonics, f0)
-    import torch
-    from .functions import _ctx
-    c = _ctx(device_index)
-    dev = c.device
+    torch, c, dev = _device(device_index)
     rec, K, D, ti = model["records"], model["Kmax"], model["step"], model["ti"]
     theta = _records_phase(rec, K, f0, D, nz["fs"])
     voiced = np.ascontiguousarray((rec[:, :K] != 0).any(axis=1), dtype=np.uint8)

@@ -194,12 +194,14 @@ int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step);
 /* resynthesis from the model with a time scale rho, a pitch scale beta and a formant scale alpha (ABI 4) ----------
  * Generalises functions.py:337-385 (track interpolation and additive synthesis) and :537-575 (phase integration) from
  * the analysed timeline to output samples n' = rho * tau; the definition is DESIGN.md "Resynthesis from the model"
- * (§9), §9.1 for scales per analysis instant (contours) and §9.2 for the formant scale.  All calls take the records
+ * (§9), §9.1 for scales per analysis instant (contours), §9.2 for the formant scale and §11 for the
+ * shape-invariant phase.  All calls take the records
  * of an analysed (possibly edited) model and the code / mom that eaqhm_spline_solve produced from them; at
  * rho = beta = 1 the synthesis is eaqhm_eval_synth's s_hat of the same records.
  * eaqhm_modify_prep (kernels: prep, segmented scan of the phase increments) serves every synthesis:
  *   beta       double[No_ti]    pitch scale per instant (the scalar synthesis passes No_ti equal values)
- *   gain       double[No_ti-1]  g_j of eaqhm_modify_synth_curve, or NULL: Delta unweighted (eaqhm_modify_synth)
+ *   gain       double[No_ti-1]  g_j of the contour map below, or NULL: Delta unweighted (the scalar map, and the shape
+ *                               phase on either map)
  *   alpha      double[No_ti]    formant scale per instant, each finite and > 0, or NULL: no formant scale; it needs
  *                               preserve_envelope != 0
  *   amp        double[No_ti][Kmax]  knot amplitudes A': beta_i == 1 and alpha_i == 1: |a|; otherwise, with
@@ -215,54 +217,44 @@ int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step);
  *                                   gain it is the weighted knot phase G, G_{j+1} = G_j + g_j ((ph_{j+1} - ph_j) +
  *                                   2 pi M_j).
  *   ph0        double[No_ti][Kmax]  phase of the first knot of the run each knot belongs to; 0 outside runs
- * eaqhm_modify_synth writes out[t_lo, t_hi) of the L_out-sample signal (out is double[L_out]) from the outputs of a
- *   prep without gain; beta is the number the prep's beta array holds.
- * eaqhm_modify_synth_curve does so from the outputs of a prep with gain.  Per interval j:
- *   r_j = (rho_j + rho_{j+1}) / 2, b_j = (beta_j + beta_{j+1}) / 2, g_j = r_j b_j; output knots C_0 = 0,
- *   C_{j+1} = C_j + r_j step (the caller computes them in double, in this order);
- *   L_out = rint(C_{n-1} + rho_{n-1} (L - c_{n-1})).  C[No_ti] output knot positions, rate[No_ti] = r_j with
- *   rate[No_ti-1] = rho_{n-1} (past the last knot), gain[No_ti-1] = g_j, rate_min = the smallest entry of rate (sizes
- *   the staged rows).
+ * eaqhm_modify_synth (kernels: one eval kernel per combination of the two groups below) writes out[t_lo, t_hi) of the
+ *   L_out-sample signal (out is double[L_out]) from the outputs of a prep.  Two optional groups of arguments, each
+ *   given whole or not at all (NULL pointers), select the time map and the phase:
+ *   C, rate, gain, rate_min   all NULL: the scalar map tau = n'/rho with phase weight beta rho, from a prep without
+ *                             gain; rho is the time scale, beta the number the prep's beta array holds; rate_min is not
+ *                             read.  All given: the contour map of §9.1, and rho, beta are not read.  Per interval j:
+ *                             r_j = (rho_j + rho_{j+1}) / 2, b_j = (beta_j + beta_{j+1}) / 2, g_j = r_j b_j; output
+ *                             knots C_0 = 0, C_{j+1} = C_j + r_j step (the caller computes them in double, in this
+ *                             order); L_out = rint(C_{n-1} + rho_{n-1} (L - c_{n-1})).  C[No_ti] output knot positions,
+ *                             rate[No_ti] = r_j with rate[No_ti-1] = rho_{n-1} (past the last knot), gain[No_ti-1] =
+ *                             g_j, rate_min = the smallest entry of rate (sizes the staged rows).  The prep ran with
+ *                             this gain, unless f0, S are given.
+ *   f0, S                     both NULL: every slot's phase is scaled on its own.  Both given: the shape-invariant
+ *                             phase of §11, from a prep WITHOUT gain (R unweighted) on either map.
+ *                             f0[No_ti] is the fundamental track in Hz (finite, >= 0), linear between instants;
+ *                             S[No_ti] the fundamental's phase advance in cycles at each instant, in [0, 1): S_0 = 0,
+ *                             S_{j+1} = frac(S_j + (g_j - 1) (step / fs) (f0_j + f0_{j+1}) / 2), computed by the caller
+ *                             in double in this order, g_j = beta rho on the scalar map and gain[j] on the contour map.
+ *                             The phase of slot k at an output sample in interval j at offset r is ph0 + R_j + Psi_j(r)
+ *                             + 2 pi (k+1) (S_j + (g_j - 1) (f0_j r + (f0_{j+1} - f0_j) r^2 / (2 step)) / fs);
+ *                             amplitudes, isolated knots and a0 are those of the independent phases.  With every
+ *                             g_j = 1 and S = 0 the result is that of the same map without f0, S.
  * eaqhm_model_envelope (kernel: one wave per instant, lanes over the grid)
  *   out        double[No_ti][F]  E_i(freqs[t] / alpha_i), the natural-log amplitude, not muted; -inf on the rows of
  *                                instants without active slots.  freqs[F] is the caller's grid (device, finite, >= 0).
  * Device arrays are the caller's: every beta, alpha and rate must be finite and > 0 and C strictly increasing.
- * EAQHM_EINVAL for null pointers (other than gain and alpha of the prep), No_ti < 4, alpha without preserve_envelope,
- * rho, beta or rate_min <= 0 or not finite, a range outside [0, L_out), F <= 0, and Kmax beyond the LDS budget of the
- * envelope nodes (Kmax > 1706).                                                                                     */
+ * EAQHM_EINVAL for null pointers (other than gain and alpha of the prep and the two groups of the synthesis), a group
+ * given in part, No_ti < 4, alpha without preserve_envelope, rho or beta (scalar map) or rate_min (contour map) <= 0 or
+ * not finite, a range outside [0, L_out), F <= 0, and Kmax beyond the LDS budget of the envelope nodes (Kmax > 1706). */
 int eaqhm_modify_prep(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, int32_t No_ti,
                       int32_t Kmax, int32_t step, double fs, const double* beta, const double* gain,
                       const double* alpha, int32_t preserve_envelope, double* amp, double* R, double* ph0);
 int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom, const double* amp,
                        const double* R, const double* ph0, int32_t No_ti, int32_t Kmax, int32_t step, double fs,
-                       double rho, double beta, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
-int eaqhm_modify_synth_curve(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                             const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
-                             int32_t step, double fs, const double* C, const double* rate, const double* gain,
-                             double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out);
+                       double rho, double beta, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out, const double* C,
+                       const double* rate, const double* gain, double rate_min, const double* f0, const double* S);
 int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* alpha,
                          const double* freqs, int32_t F, double* out);
-
-/* shape-invariant phase for the two syntheses above (new entry points; no existing argument list changes) ----------
- * The definition is DESIGN.md "Shape-invariant phase" (§11).  Both take the argument list of their counterpart plus
- *   f0         double[No_ti]    the fundamental track in Hz (finite, >= 0), linear between instants
- *   S          double[No_ti]    the fundamental's phase advance in cycles at each instant, in [0, 1): S_0 = 0,
- *                               S_{j+1} = frac(S_j + (g_j - 1) (step / fs) (f0_j + f0_{j+1}) / 2), computed by the caller
- *                               in double in this order; g_j = beta rho for eaqhm_modify_synth_shape, gain[j] for
- *                               eaqhm_modify_synth_curve_shape
- * and the outputs of a prep WITHOUT gain (R unweighted) in both cases.  The phase of slot k at an output sample in
- * interval j at offset r is ph0 + R_j + Psi_j(r) + 2 pi (k+1) (S_j + (g_j - 1) (f0_j r + (f0_{j+1} - f0_j) r^2 /
- * (2 step)) / fs); amplitudes, isolated knots and a0 are those of the counterpart.  With every g_j = 1 and S = 0 the
- * result is the counterpart's.  EAQHM_EINVAL as for the counterpart, and for a null f0 or S.                          */
-int eaqhm_modify_synth_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                             const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
-                             int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
-                             int64_t t_hi, double* out, const double* f0, const double* S);
-int eaqhm_modify_synth_curve_shape(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
-                                   const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
-                                   int32_t step, double fs, const double* C, const double* rate, const double* gain,
-                                   double rate_min, int64_t L_out, int64_t t_lo, int64_t t_hi, double* out,
-                                   const double* f0, const double* S);
 
 /* the stochastic component: an LPC model of the residual and its resynthesis as filtered noise (ABI 5) -----------------
  * Not in the reference; the definition is DESIGN.md "The stochastic component" (§10).  hop = H, order = p,
@@ -278,13 +270,16 @@ int eaqhm_modify_synth_curve_shape(eaqhm_ctx* ctx, const double* records, const 
  *   tau        double[Nq]         Nq = (L_out-1)/hop + 1: the position, in samples of the analysed signal, that output
  *                                 frame centre q hop maps back to (finite, >= 0); sigma and refl are interpolated
  *                                 linearly between frames floor(tau/hop) and the next, held past the last frame
- * EAQHM_EINVAL for null pointers, L < 1, Nf < 1, hop or order outside the limits above, Nq != (L_out-1)/hop + 1 and a
- * range outside [0, L_out).                                                                                          */
+ *   mod, harmonics, theta, nu     an optional group (ABI 6): the three pointers all NULL give the plain cross-fade, and
+ *                                 harmonics is not read; all given, the pitch-synchronous modulation of §10.2 (below)
+ * EAQHM_EINVAL for null pointers (other than that group), the group given in part, harmonics outside [1, 8] with it,
+ * L < 1, Nf < 1, hop or order outside the limits above, Nq != (L_out-1)/hop + 1 and a range outside [0, L_out).      */
 int eaqhm_noise_analyse(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, int32_t order, double* sigma,
                         double* refl);
 int eaqhm_noise_synth(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop, int32_t order,
                       const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo, int64_t t_hi,
-                      double* out, int32_t accumulate);
+                      double* out, int32_t accumulate, const double* mod, int32_t harmonics, const double* theta,
+                      const double* nu);
 
 /* the formant warp of the noise model (additions under ABI 5) ----------------------------------------
  * A frame (sigma, k_1..k_p) is the power spectrum P(w) = sigma^2 / |A(e^{jw})|^2, A the step-up of k.
@@ -311,18 +306,15 @@ int eaqhm_noise_envelope(eaqhm_ctx* ctx, const double* sigma, const double* refl
  *   theta, f0  double[No_ti]      the fundamental's phase (cycles, [0, 1)) and frequency (Hz) at every instant
  *   voiced     uint8[No_ti]       0: a frame whose nearest instant is this one gets c = 0
  *   mod        double[Nf][2 harmonics]  Re c_1, Im c_1, .. ; zeros where the frame's power is not > 0
- * eaqhm_noise_synth_mod is eaqhm_noise_synth with the gain g_q(n') = sqrt(max(0.01, g^2(theta[q] + nu[q] (n' - q hop))))
- *   on frame q's samples in the cross-fade, the coefficients blended between the model's frames at tau[q] as sigma is;
+ * eaqhm_noise_synth with mod, harmonics, theta, nu applies the gain g_q(n') = sqrt(max(0.01, g^2(theta[q] + nu[q] (n' -
+ *   q hop)))) on frame q's samples in the cross-fade, the coefficients (mod, double[Nf][2 harmonics]) blended between
+ *   the model's frames at tau[q] as sigma is;
  *   theta, nu  double[Nq]         the output fundamental's phase (cycles) at frame centre q hop and its advance per sample
- *   A mod of zeros gives eaqhm_noise_synth's samples bit for bit.
- * EAQHM_EINVAL as for their counterparts, and for null pointers, harmonics outside [1, 8], step or fs not > 0.        */
+ *   A mod of zeros gives the plain cross-fade's samples bit for bit.
+ * EAQHM_EINVAL for null pointers, L < 1, No_ti < 1, hop outside [1, 1024], harmonics outside [1, 8], step or fs not > 0. */
 int eaqhm_noise_modulation(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t hop, const double* theta,
                            const double* f0, const uint8_t* voiced, int32_t No_ti, double ti0, double step, double fs,
                            int32_t harmonics, double* mod);
-int eaqhm_noise_synth_mod(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t hop,
-                          int32_t order, const double* tau, int32_t Nq, uint64_t seed, int64_t L_out, int64_t t_lo,
-                          int64_t t_hi, double* out, int32_t accumulate, const double* mod, int32_t harmonics,
-                          const double* theta, const double* nu);
 
 #ifdef __cplusplus
 }

@@ -456,4 +456,4 @@ def test_argument_checks(ctx):
         ctx.eval_synth(z(T, 3 * big + 1), z(T, big, dtype=torch.uint8), z(T, big + 1), T, big, D, fs, L, 0, L, 0, L,
                        st.target, st.std_det, amb, z(big, L), 0, L, phb, sh, part, sums)
     ctx.sync()
-    assert ctx.abi_version == 5
+    assert ctx.abi_version == 6

@@ -1,5 +1,5 @@
-"""Time and pitch scale contours on the MI355X (model.eaQHMSynthesis with array scales -> eaqhm_modify_prep_curve /
-eaqhm_modify_synth_curve): constant contours against the scalar path, agreement with the NumPy model of DESIGN.md §9.1
+"""Time and pitch scale contours on the MI355X (model.eaQHMSynthesis with array scales -> eaqhm_modify_prep with gain,
+eaqhm_modify_synth with the contour map): constant contours against the scalar path, agreement with the NumPy model of DESIGN.md §9.1
 (tests/model_contour_ref.py), pitch and duration, locality, split ranges, additivity over slots and the CLI."""
 import os
 

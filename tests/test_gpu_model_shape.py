@@ -1,5 +1,5 @@
-"""The shape-invariant phase mode on the MI355X (model.eaQHMSynthesis with phase="shape" -> eaqhm_modify_synth_shape /
-eaqhm_modify_synth_curve_shape): agreement with the NumPy model of DESIGN.md §11 (tests/model_shape_ref.py), unit
+"""The shape-invariant phase mode on the MI355X (model.eaQHMSynthesis with phase="shape" -> eaqhm_modify_synth with
+f0 and S, on either time map): agreement with the NumPy model of DESIGN.md §11 (tests/model_shape_ref.py), unit
 scales against the default mode and s_recon, a constructed model with a closed-form answer, locality, noise and the
 CLI."""
 import os

@@ -237,7 +237,7 @@ def test_entry_points_reject_bad_shapes(amd):
             c.noise_synth(sigma, refl, Nf, H, p, tau, Nf, 0, L, t_lo, t_hi, out)
     with pytest.raises(RuntimeError, match="error -1"):
         c.noise_analyse(e, 0, H, p, sigma, refl)
-    assert c.abi_version == 5
+    assert c.abi_version == 6
 
 
 def test_cli_noise_writes_resynthesis_and_modified(amd, tmp_path):

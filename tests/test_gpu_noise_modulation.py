@@ -1,5 +1,5 @@
 """Pitch-synchronous modulation of the noise on the MI355X (eaQHMNoiseModulation -> eaqhm_noise_modulation,
-eaQHMNoiseSynthesis(fundamental=) and eaQHMSynthesis(noise_modulation=True) -> eaqhm_noise_synth_mod) against the NumPy
+eaQHMNoiseSynthesis(fundamental=) and eaQHMSynthesis(noise_modulation=True) -> eaqhm_noise_synth with mod) against the NumPy
 model of DESIGN.md §10.2 (tests/noise_modulation_ref.py).
 
 Bars: §10's rule for reductions, 100 x the largest deviation between the model run in float64 and in np.longdouble on
@@ -173,8 +173,8 @@ def test_zero_mod_ranges_and_accumulate_bit_for_bit(amd):
     dv = [torch.as_tensor(np.ascontiguousarray(x), device=c.device)
           for x in (nz["sigma"], nz["refl"], tau, nz["mod"], fund[0], fund[1])]
     for t_lo, t_hi in ((0, 20000), (20000, L_out)):
-        c.noise_synth_mod(dv[0], dv[1], Nf, H, p, dv[2], len(tau), 5, L_out, t_lo, t_hi, buf, dv[3], 3, dv[4], dv[5],
-                          accumulate=True)
+        c.noise_synth(dv[0], dv[1], Nf, H, p, dv[2], len(tau), 5, L_out, t_lo, t_hi, buf, accumulate=True,
+                      mod=(dv[3], 3, dv[4], dv[5]))
     assert np.array_equal(buf.cpu().numpy(), base + a)
     # the floor: coefficients that drive g^2 negative, against the model (cos, sin and sqrt apart: 1e-12 of the maximum)
     deep = dict(nz, mod=np.tile([0.9, 0.0, 0.0, 0.0, 0.0, 0.0], (Nf, 1)))
@@ -280,13 +280,13 @@ def test_entry_points_reject_bad_arguments(amd):
     e, sigma, refl, tau, out, mod, th, f0 = z(L), z(Nf), z(Nf, p), z(Nf), z(L), z(Nf, 16), z(n), z(n)
     vo = z(n, dtype=torch.uint8)
     c.noise_modulation(e, L, H, th, f0, vo, n, 0.0, 15.0, 16000.0, 8, mod)          # the good calls
-    c.noise_synth_mod(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod, 8, tau, tau)
+    c.noise_synth(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod=(mod, 8, tau, tau))
     c.sync()
     for M in (0, 9, -1):
         with pytest.raises(RuntimeError, match="error -1"):
             c.noise_modulation(e, L, H, th, f0, vo, n, 0.0, 15.0, 16000.0, M, mod)
         with pytest.raises(RuntimeError, match="error -1"):
-            c.noise_synth_mod(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod, M, tau, tau)
+            c.noise_synth(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod=(mod, M, tau, tau))
     for kw in (dict(hop=0), dict(hop=1025), dict(L=0), dict(n=0), dict(step=0.0), dict(fs=0.0)):
         a = dict(L=L, hop=H, n=n, step=15.0, fs=16000.0)
         a.update(kw)
@@ -296,11 +296,45 @@ def test_entry_points_reject_bad_arguments(amd):
         c.noise_modulation(e, L, H, None, f0, vo, n, 0.0, 15.0, 16000.0, 2, mod)
     for bad in ((None, tau, tau), (mod, None, tau), (mod, tau, None)):
         with pytest.raises(RuntimeError, match="error -1"):
-            c.noise_synth_mod(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, bad[0], 2, bad[1], bad[2])
+            c.noise_synth(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod=(bad[0], 2, bad[1], bad[2]))
     for Nq, t_lo, t_hi in ((Nf - 1, 0, L), (Nf, -1, L), (Nf, 0, L + 1), (Nf, 5, 5)):
         with pytest.raises(RuntimeError, match="error -1"):
-            c.noise_synth_mod(sigma, refl, Nf, H, p, tau, Nq, 0, L, t_lo, t_hi, out, mod, 2, tau, tau)
-    assert c.abi_version == 5
+            c.noise_synth(sigma, refl, Nf, H, p, tau, Nq, 0, L, t_lo, t_hi, out, mod=(mod, 2, tau, tau))
+    assert c.abi_version == 6
+
+
+def test_optional_groups_given_in_part_are_rejected(amd):
+    """A partial mod group of eaqhm_noise_synth, a partial curve group and a partial shape group of eaqhm_modify_synth:
+    EAQHM_EINVAL from the argument checks, which return before any launch, and `out` as it was."""
+    import torch
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+
+    def z(*shape, dtype=torch.float64):
+        return torch.zeros(shape, dtype=dtype, device=c.device)
+
+    def rejected(call):
+        out = torch.full((L,), 7.0, dtype=torch.float64, device=c.device)
+        with pytest.raises(RuntimeError, match="error -1: eaqhm_(noise|modify)_synth: bad argument"):
+            call(out)
+        c.sync()
+        assert bool((out == 7.0).all())
+
+    L, H, p, n, K, D = 1000, 8, 4, 67, 3, 15
+    Nf = (L - 1) // H + 1
+    sigma, refl, tau, mod = z(Nf), z(Nf, p), z(Nf), z(Nf, 4)
+    for m, th, nu in ((None, tau, tau), (mod, None, tau), (mod, tau, None), (mod, None, None), (None, None, tau)):
+        rejected(lambda out: c.noise_synth(sigma, refl, Nf, H, p, tau, Nf, 0, L, 0, L, out, mod=(m, 2, th, nu)))
+    rec, code, mom = z(n, 3 * K + 1), z(n * K, dtype=torch.uint8), z(n * (K + 1))
+    amp, R, ph0, v = z(n * K), z(n * K), z(n * K), z(n)
+    for C_, rate, gain in ((None, v, v), (v, None, v), (v, v, None), (v, None, None), (None, None, v)):
+        rejected(lambda out: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, 16000.0, 1.0, 1.0, L, 0, L, out,
+                                            curve=(C_, rate, gain, 1.0)))
+    for f0, S in ((v, None), (None, v)):
+        rejected(lambda out: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, 16000.0, 1.0, 1.0, L, 0, L, out,
+                                            shape=(f0, S)))
+        rejected(lambda out: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, 16000.0, 1.0, 1.0, L, 0, L, out,
+                                            curve=(v, v, v, 1.0), shape=(f0, S)))
 
 
 def test_cli_noise_modulation_writes_resynthesis(amd, tmp_path):
@@ -319,8 +353,8 @@ def test_cli_noise_modulation_writes_resynthesis(amd, tmp_path):
 
 
 def test_record_probe_numbers(amd, synth48k):
-    """Device times of the two new entry points beside their counterparts on the 0.6 s model at 48 kHz (evidence, not
-    assertions; the 60 s numbers come from tools/model_synthesis_probe.py --noise-modulation)."""
+    """Device times of the modulation analysis and the modulated synthesis beside the plain ones on the 0.6 s model at
+    48 kHz (evidence, not assertions; the 60 s numbers come from tools/model_synthesis_probe.py --noise-modulation)."""
     import sys
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tools"))

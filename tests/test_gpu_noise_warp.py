@@ -246,7 +246,7 @@ def test_entry_points_reject_bad_shapes(amd):
     for i in (0, 1, 4, 5, 7):
         with pytest.raises(RuntimeError, match="error -1"):
             c.noise_envelope(*[None if j == i else a for j, a in enumerate(args)])
-    assert c.abi_version == 5
+    assert c.abi_version == 6
 
 
 def test_cli_noise_formant_writes_modified(amd, tmp_path):

@@ -1,6 +1,8 @@
 """CPU tests (no GPU) of the shape-invariant phase mode on its NumPy model (tests/model_shape_ref.py):
 the relative phases of the harmonics are the model's own at every scale, model_f0, the argument checks of
 eaQHMSynthesis(phase=, f0=), the binding and the CLI flag."""
+import os
+
 import numpy as np
 import pytest
 
@@ -162,14 +164,22 @@ def test_good_phase_arguments_reach_the_backend(backend):
 def test_binding_exports_and_cli_flag():
     import eaqhm_amd
     from eaqhm_amd import cli, hip
-    names = {n for n, _, _ in hip.SYMBOLS}
-    assert {"eaqhm_modify_synth_shape", "eaqhm_modify_synth_curve_shape"} <= names
+    import ctypes as C
+    from conftest import ROOT
+    assert hip.ABI_VERSION == 6
     sig = {n: a for n, _, a in hip.SYMBOLS}
-    assert sig["eaqhm_modify_synth_shape"][:-2] == sig["eaqhm_modify_synth"]
-    assert sig["eaqhm_modify_synth_curve_shape"][:-2] == sig["eaqhm_modify_synth_curve"]
+    with open(os.path.join(ROOT, "include", "eaqhm_hip.h")) as fh:
+        header = fh.read()
+    # one entry point: the scalar list, then the optional groups (C, rate, gain, rate_min) and (f0, S)
+    P, I32, I64, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    plain = [P] * 7 + [I32] * 3 + [F64] * 3 + [I64] * 3 + [P]          # ctx .. fs, rho, beta, L_out, t_lo, t_hi, out
+    assert sig["eaqhm_modify_synth"] == plain + [P, P, P, F64] + [P, P]
+    assert "int eaqhm_modify_synth(" in header
+    for gone in ("synth_curve", "synth_shape", "synth_curve_shape"):
+        assert "eaqhm_modify_" + gone not in sig and "eaqhm_modify_" + gone not in header
+        assert not hasattr(hip.Context, "modify_" + gone)
     assert callable(eaqhm_amd.model_f0)
-    for name in ("modify_synth_shape", "modify_synth_curve_shape"):
-        assert callable(getattr(hip.Context, name))
+    assert callable(hip.Context.modify_synth)
     a = cli.parser().parse_args(["x.wav", "--phase", "shape", "--time-scale", "2"])
     assert a.phase == "shape" and cli.parser().parse_args(["x.wav"]).phase == "independent"
     with pytest.raises(SystemExit):

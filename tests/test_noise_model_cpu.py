@@ -216,7 +216,7 @@ def test_synthesis_rejects_a_bad_noise_seed(no_device):
 def test_binding_and_exports():
     import eaqhm_amd
     from eaqhm_amd import hip
-    assert hip.ABI_VERSION == 5
+    assert hip.ABI_VERSION == 6
     names = {n for n, _, _ in hip.SYMBOLS}
     assert {"eaqhm_noise_analyse", "eaqhm_noise_synth"} <= names
     for name in ("eaQHMNoiseAnalysis", "eaQHMNoiseSynthesis", "noise_time_map", "noise_time_map_contour", "read_signal"):

@@ -341,14 +341,20 @@ def test_binding_header_and_exports():
     import eaqhm_amd
     from eaqhm_amd import hip
     from conftest import ROOT
-    assert hip.ABI_VERSION == 5
+    assert hip.ABI_VERSION == 6
     sym = {n: a for n, _, a in hip.SYMBOLS}
     assert len(sym["eaqhm_noise_modulation"]) == 13
-    assert sym["eaqhm_noise_synth_mod"][:14] == sym["eaqhm_noise_synth"] and len(sym["eaqhm_noise_synth_mod"]) == 18
+    import ctypes as C
+    P, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
+    plain = [P, P, P, I32, I32, I32, P, I32, C.c_uint64, I64, I64, I64, P, I32]      # ctx .. out, accumulate
+    assert sym["eaqhm_noise_synth"] == plain + [P, I32, P, P] and len(sym["eaqhm_noise_synth"]) == 18
     with open(os.path.join(ROOT, "include", "eaqhm_hip.h")) as fh:
         header = fh.read()
-    assert "int eaqhm_noise_modulation(" in header and "int eaqhm_noise_synth_mod(" in header
-    assert callable(hip.Context.noise_modulation) and callable(hip.Context.noise_synth_mod)
+    assert "int eaqhm_noise_modulation(" in header and "int eaqhm_noise_synth(" in header
+    gone = "eaqhm_noise_synth" + "_mod"
+    assert gone not in sym and gone not in header
+    assert callable(hip.Context.noise_modulation) and callable(hip.Context.noise_synth)
+    assert not hasattr(hip.Context, "noise_synth_mod")
     for name in ("eaQHMNoiseModulation", "model_phase", "noise_fundamental"):
         assert callable(getattr(eaqhm_amd, name))
 

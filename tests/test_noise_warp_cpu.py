@@ -177,7 +177,7 @@ def test_synthesis_noise_formant_checks(no_device):
 def test_binding_and_exports():
     import eaqhm_amd
     from eaqhm_amd import hip
-    assert hip.ABI_VERSION == 5
+    assert hip.ABI_VERSION == 6
     sym = {n: a for n, _, a in hip.SYMBOLS}
     assert len(sym["eaqhm_noise_warp"]) == 8 and len(sym["eaqhm_noise_envelope"]) == 9
     for name in ("eaQHMNoiseWarp", "noise_formant_contour", "noise_envelope"):

@@ -6,10 +6,10 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
-eaqhm_modify_synth_curve): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with
+eaqhm_modify_synth with the curve group): unit contours, rho a 0.5 Hz sinusoid 0.7-1.4 with beta = 1, rho = 1 with
 beta ramping 0.85 -> 1.2, and both varying; eval_ms_per_msample normalises the eval time by the output length.
 --formant adds the formant scale (eaqhm_modify_prep with alpha) at rho = 1: alpha in {0.85, 1.2} x
-beta in {1, 1.25} with eaqhm_modify_synth, and alpha ramping 0.85 -> 1.2 with eaqhm_modify_synth_curve;
+beta in {1, 1.25} on the scalar map, and alpha ramping 0.85 -> 1.2 on the contour map;
 ratio_to_scalar compares each with the scalar path at the same beta (envelope on).  --noise adds the stochastic
 component on the workload's own residual: eaqhm_noise_analyse, and eaqhm_noise_synth at rho in
 {0.5, 1, 2} beside the deterministic prep + eval of the same session at the same rho (beta = 1); every time there is
@@ -17,10 +17,10 @@ the median of three windows of 20 launches, with the max - min of the three.  --
 the noise model on the same residual's model: eaqhm_noise_warp and eaqhm_noise_envelope (a 129-point
 grid) at alpha in {0.85, 1.2} and a ramp between them, beside eaqhm_noise_synth of the warped model at rho = 1 in the
 same session, with the same windows.  --noise-modulation adds the pitch-synchronous modulation of the noise (DESIGN.md
-§10.2): eaqhm_noise_modulation (2 harmonics) next to eaqhm_noise_analyse, and eaqhm_noise_synth_mod next to
-eaqhm_noise_synth at rho in {0.5, 1, 2}, with the same windows.  --shape adds the shape-invariant phase
-mode: eaqhm_modify_synth_shape next to eaqhm_modify_synth at rho in {0.5, 1, 2} x beta in {1, 1.25}, and
-eaqhm_modify_synth_curve_shape next to eaqhm_modify_synth_curve on the four contour settings, each the median of three
+§10.2): eaqhm_noise_modulation (2 harmonics) next to eaqhm_noise_analyse, and eaqhm_noise_synth with the mod group next to
+the plain one at rho in {0.5, 1, 2}, with the same windows.  --shape adds the shape-invariant phase
+mode (DESIGN.md §11): eaqhm_modify_synth with the shape group next to without at rho in {0.5, 1, 2} x beta in {1, 1.25}
+and on the four contour settings, each the median of three
 windows of 20 launches with the max - min of the existing kernel's three (the margin).  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -142,8 +142,8 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
 
 def noise_modulation_rows(torch, st, residual, harmonics=2, reps=20, runs=3):
     """The pitch-synchronous modulation of the noise on `residual` with the model of `st`: device time
-    of eaqhm_noise_modulation next to eaqhm_noise_analyse, and of eaqhm_noise_synth_mod next to eaqhm_noise_synth at
-    rho in {0.5, 1, 2} (beta = 1) with the analysed coefficients.  Each time: median of `runs` windows of `reps`
+    of eaqhm_noise_modulation next to eaqhm_noise_analyse, and of eaqhm_noise_synth with the mod group next to without
+    at rho in {0.5, 1, 2} (beta = 1) with the analysed coefficients.  Each time: median of `runs` windows of `reps`
     launches, and their max - min."""
     from eaqhm_amd.model import (_fundamental_at, _records_f0, _records_phase, _scalar_path,
                                  check_noise_analysis_arguments, noise_time_map)
@@ -178,8 +178,8 @@ def noise_modulation_rows(torch, st, residual, harmonics=2, reps=20, runs=3):
         tau_d, theta_d, nu_d = (torch.as_tensor(x, device=dev) for x in (tau, theta, nu))
         out = torch.empty(Lo, dtype=torch.float64, device=dev)
         t_ns, s_ns = med(lambda: c.noise_synth(sigma, refl, Nf, H, p, tau_d, len(tau), 0, Lo, 0, Lo, out))
-        t_nm, s_nm = med(lambda: c.noise_synth_mod(sigma, refl, Nf, H, p, tau_d, len(tau), 0, Lo, 0, Lo, out, mod,
-                                                   harmonics, theta_d, nu_d))
+        t_nm, s_nm = med(lambda: c.noise_synth(sigma, refl, Nf, H, p, tau_d, len(tau), 0, Lo, 0, Lo, out,
+                                               mod=(mod, harmonics, theta_d, nu_d)))
         rows.append(dict(setting="rho%g" % rho, out_frames=len(tau), noise_synth_ms=t_ns, noise_synth_spread_ms=s_ns,
                          noise_synth_mod_ms=t_nm, noise_synth_mod_spread_ms=s_nm,
                          mod_minus_plain_ms=round(t_nm - t_ns, 4), mod_to_plain=round(t_nm / t_ns, 3)))
@@ -285,8 +285,8 @@ def shape_rows(torch, st, reps=20, runs=3):
             out = torch.empty(Lo, dtype=torch.float64, device=dev)
             S_d = torch.as_tensor(fundamental_advance(f0, np.full(n - 1, beta * rho), D, fs), device=dev)
             base = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo, out))
-            new = med(lambda: c.modify_synth_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo, out,
-                                                   f0_d, S_d))
+            new = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, rho, beta, Lo, 0, Lo, out,
+                                             shape=(f0_d, S_d)))
             rows.append(row("rho%g_beta%g" % (rho, beta), Lo, base, new))
     t = np.arange(n) * D / fs
     one = np.ones(n)
@@ -301,11 +301,11 @@ def shape_rows(torch, st, reps=20, runs=3):
         S_d = torch.as_tensor(fundamental_advance(f0, tm["gain"], D, fs), device=dev)
         out = torch.empty(Lo, dtype=torch.float64, device=dev)
         c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, gain_d, None, True, amp, R, ph0)
-        base = med(lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
-                                                tm["rate_min"], Lo, 0, Lo, out))
+        curve = (C_d, rate_d, gain_d, tm["rate_min"])
+        base = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 0.0, 0.0, Lo, 0, Lo, out, curve))
         c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, True, amp, R, ph0)   # the shape mode's prep
-        new = med(lambda: c.modify_synth_curve_shape(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
-                                                     tm["rate_min"], Lo, 0, Lo, out, f0_d, S_d))
+        new = med(lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 0.0, 0.0, Lo, 0, Lo, out, curve,
+                                         (f0_d, S_d)))
         rows.append(row("contour_" + label, Lo, base, new))
     return rows
 
@@ -349,8 +349,8 @@ def formant_rows(torch, st, reps):
     outc = torch.empty(tm["L_out"], dtype=torch.float64, device=dev)
     t_fp = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, one_d, gain_d, alpha_d, True, amp, R, ph0),
                  reps)
-    t_fs = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
-                                                     tm["rate_min"], tm["L_out"], 0, tm["L_out"], outc), reps)
+    t_fs = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 0.0, 0.0, tm["L_out"], 0,
+                                               tm["L_out"], outc, (C_d, rate_d, gain_d, tm["rate_min"])), reps)
     rows.append(row("alpha_ramp_contour", t_fp, t_fs, rows[0]["total_ms"]))
     return rows
 
@@ -372,8 +372,8 @@ def probe_contours(torch, c, rec, code, mom, amp, R, ph0, n, K, D, fs, L, t_eval
         out = torch.empty(Lo, dtype=torch.float64, device=dev)
         t_prep = timed(torch, lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, gain_d, None, True, amp, R,
                                                     ph0), reps)
-        t_syn = timed(torch, lambda: c.modify_synth_curve(rec, code, mom, amp, R, ph0, n, K, D, fs, C_d, rate_d, gain_d,
-                                                          tm["rate_min"], Lo, 0, Lo, out), reps)
+        t_syn = timed(torch, lambda: c.modify_synth(rec, code, mom, amp, R, ph0, n, K, D, fs, 0.0, 0.0, Lo, 0, Lo, out,
+                                                    (C_d, rate_d, gain_d, tm["rate_min"])), reps)
         rows.append(dict(contour=label, prep_scan_ms=round(t_prep, 3), eval_ms=round(t_syn, 3),
                          total_ms=round(t_prep + t_syn, 3), out_samples=Lo,
                          eval_ms_per_msample=round(t_syn / (Lo / 1e6), 4),
