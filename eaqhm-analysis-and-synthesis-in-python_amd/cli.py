@@ -8,10 +8,12 @@ resynthesises the analysed model (model.eaQHMSynthesis) into `<name>_modified.wa
 --pitch-scale-curve FILE take a breakpoint curve instead (two whitespace-separated columns, seconds and value; lines
 starting with # are comments), turned into a per-instant contour with model.scale_contour.  --formant-scale A /
 --formant-scale-curve FILE move the spectral envelope by A; they need the envelope, so either one with
---no-envelope is an error.  --phase shape keeps the waveform shape under those scales.  --noise (with --noise-seed N) models the residual input - reconstruction
+--no-envelope is an error.  --formant-warp-curve FILE (two columns, Hz in the model and Hz in the output) and
+--formant-vtln ALPHA (with --formant-knee K, default 0.875) move it along a piecewise-linear map instead (DESIGN.md
+§9.4); the four formant flags exclude each other.  --phase shape keeps the waveform shape under those scales.  --noise (with --noise-seed N) models the residual input - reconstruction
 (model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
 writes `<name>_resynthesis.wav`: model + noise at unit scales.  --noise-formant (with --noise and a formant scale flag) lets the
-noise's envelope follow the formant scale (eaQHMSynthesis(noise_formant=True)).  --noise-modulation [M]
+noise's envelope follow the formant scale or warp (eaQHMSynthesis(noise_formant=True)).  --noise-modulation [M]
 (with --noise; M harmonics, default 2) modulates the noise pitch-synchronously (model.eaQHMNoiseModulation)."""
 import argparse
 
@@ -49,6 +51,14 @@ def parser():
                      help="also write <name>_modified.wav: spectral envelope (formants) x A")
     fs_.add_argument("--formant-scale-curve", default=None, metavar="FILE",
                      help="like --formant-scale, with a curve: lines 'seconds value' (# comments)")
+    fs_.add_argument("--formant-warp-curve", default=None, metavar="FILE",
+                     help="also write <name>_modified.wav: spectral envelope moved along a piecewise-linear map: lines "
+                          "'Hz_in Hz_out' (# comments), 1 to 16 of them, both columns increasing")
+    fs_.add_argument("--formant-vtln", type=float, default=None, metavar="ALPHA",
+                     help="like --formant-warp-curve, with the VTLN map: slope ALPHA up to the knee, then straight to "
+                          "(fs/2, fs/2)")
+    ap.add_argument("--formant-knee", type=float, default=None, metavar="K",
+                    help="with --formant-vtln: the knee as a fraction of fs/2 (0.875)")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
     ap.add_argument("--phase", choices=("independent", "shape"), default="independent",
@@ -59,8 +69,8 @@ def parser():
                          "write <name>_resynthesis.wav (model + noise)")
     ap.add_argument("--noise-seed", type=int, default=None, metavar="N", help="with --noise: seed of the excitation (0)")
     ap.add_argument("--noise-formant", action="store_true",
-                    help="with --noise and --formant-scale / --formant-scale-curve: the noise's spectral envelope "
-                         "follows the formant scale")
+                    help="with --noise and a formant flag (--formant-scale, --formant-scale-curve, --formant-warp-curve, "
+                         "--formant-vtln): the noise's spectral envelope follows it")
     ap.add_argument("--noise-modulation", type=int, nargs="?", const=2, default=None, metavar="M",
                     help="with --noise: modulate the noise pitch-synchronously, M harmonics of the envelope (2)")
     return ap
@@ -73,8 +83,11 @@ def main(argv=None):
         ap.error("--noise-seed needs --noise")
     if a.noise_formant and not a.noise:
         ap.error("--noise-formant needs --noise")
-    if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None:
-        ap.error("--noise-formant needs --formant-scale or --formant-scale-curve")
+    warped = a.formant_warp_curve is not None or a.formant_vtln is not None
+    if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None and not warped:
+        ap.error("--noise-formant needs --formant-scale, --formant-scale-curve, --formant-warp-curve or --formant-vtln")
+    if a.formant_knee is not None and a.formant_vtln is None:
+        ap.error("--formant-knee needs --formant-vtln")
     if a.noise_modulation is not None and not a.noise:
         ap.error("--noise-modulation needs --noise")
     if a.noise:
@@ -82,11 +95,12 @@ def main(argv=None):
         _seed(0 if a.noise_seed is None else a.noise_seed)
         if a.noise_modulation is not None:
             _mod_harmonics(a.noise_modulation, "--noise-modulation")
-    if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None):
-        ap.error("--formant-scale / --formant-scale-curve scale the spectral envelope: not with --no-envelope")
+    if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None or warped):
+        ap.error("the formant flags move the spectral envelope: not with --no-envelope")
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
-                                         a.formant_scale, a.formant_scale_curve))
+                                         a.formant_scale, a.formant_scale_curve)) or warped
     curves = {}
+    wmap = None
     if modify:   # reject bad scales and curves before the analysis runs
         from .model import _scale
         _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
@@ -96,6 +110,11 @@ def main(argv=None):
                           ("formant", a.formant_scale_curve)):
             if path is not None:
                 curves[key] = read_scale_curve(path, "--%s-scale-curve %s" % (key, path))
+        if a.formant_warp_curve is not None:
+            wmap = read_warp_curve(a.formant_warp_curve, "--formant-warp-curve %s" % a.formant_warp_curve)
+        if a.formant_vtln is not None:   # the map needs fs: the slopes are checked here, at the nominal fs = 2
+            from .model import formant_warp_vtln
+            formant_warp_vtln(2.0, a.formant_vtln, 0.875 if a.formant_knee is None else a.formant_knee)
     gender = a.gender
     if "," in gender:
         lo, hi = gender.split(",")
@@ -121,6 +140,9 @@ def main(argv=None):
             alpha = 1.0 if a.formant_scale is None else a.formant_scale
             if "formant" in curves:
                 alpha = scale_contour(det, fs, *curves["formant"])
+            if a.formant_vtln is not None:
+                from .model import formant_warp_vtln
+                wmap = formant_warp_vtln(fs, a.formant_vtln, 0.875 if a.formant_knee is None else a.formant_knee)
             nz = None
             if a.noise:
                 from .prologue import read_signal
@@ -131,20 +153,34 @@ def main(argv=None):
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
                                    noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
-                                   noise_modulation=a.noise_modulation is not None)
+                                   noise_modulation=a.noise_modulation is not None, formant_warp=wmap)
             out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)
     return 0
 
 
-def read_scale_curve(path, name):
-    """A breakpoint curve file: (times, values), validated as model.check_curve does."""
-    from .model import check_curve
+def _two_columns(path, name, what):
     try:
         xy = np.loadtxt(path, comments="#", ndmin=2)
     except (OSError, ValueError) as e:
         raise ValueError("%s: cannot read two numeric columns (%s)" % (name, e)) from None
     if xy.shape[1] != 2:
-        raise ValueError("%s: expected two columns (seconds, value), got %d" % (name, xy.shape[1]))
-    return check_curve(xy[:, 0], xy[:, 1], name)
+        raise ValueError("%s: expected two columns (%s), got %d" % (name, what, xy.shape[1]))
+    return xy[:, 0], xy[:, 1]
+
+
+def read_scale_curve(path, name):
+    """A breakpoint curve file: (times, values), validated as model.check_curve does."""
+    from .model import check_curve
+    return check_curve(*_two_columns(path, name, "seconds, value"), name)
+
+
+def read_warp_curve(path, name):
+    """A formant warp file, lines 'Hz_in Hz_out': (f_in, f_out), validated as model.check_formant_warp does."""
+    from .model import _warp_rows
+    try:
+        f_in, f_out = _warp_rows(_two_columns(path, name, "Hz in the model, Hz in the output"), 1, "file")
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e)) from None
+    return f_in, f_out[0]

@@ -20,8 +20,11 @@
 //                              shape-invariant phase of DESIGN.md §11: Psi unweighted plus (k+1) times the phase
 //                              advance of the fundamental, from the per-instant tracks f0 and S.
 //   eaqhm_model_envelope_kernel  reads the envelope itself out on a frequency grid.
+//   eaqhm_modify_amp_warp_kernel, eaqhm_model_envelope_warp_kernel  the amplitudes A' and the readout with the
+//                              piecewise-linear formant warp of DESIGN.md §9.4 (eaqhm_warp.h) in place of / alpha.
 #include "eaqhm_common.h"
 #include "eaqhm_pieces.h"
+#include "eaqhm_warp.h"
 
 namespace eaqhm {
 
@@ -160,6 +163,84 @@ extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
   const double alpha = alphav[i];
   for (int t = lane; t < F; t += 64)
     out[(size_t)i * F + t] = (nn > 0) ? env_at(nf, nv, nn, freqs[t] / alpha) : -INFINITY;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The formant warp.  Both kernels: one wave per instant i (PREP_WAVES per block), the envelope nodes
+// as above, then per wave its row of the map (eaqhm_warp.h: y_j and the slope ratios, 2 x WARP_BMAX doubles) and once
+// per block x.  LDS: PREP_WAVES x 3 K doubles, then PREP_WAVES x 2 x WARP_BMAX, then WARP_BMAX.
+__device__ inline WarpRow warp_row_lds(double* lds, int K, int w, int lane, bool live, const double* __restrict__ f_in,
+                                       const double* __restrict__ yrow, int B) {
+  double* wy = lds + (size_t)PREP_WAVES * 3 * K + (size_t)w * 2 * WARP_BMAX;
+  double* ws = wy + WARP_BMAX;
+  double* wx = lds + (size_t)PREP_WAVES * 3 * K + (size_t)PREP_WAVES * 2 * WARP_BMAX;
+  warp_stage_x(f_in, B, threadIdx.x, wx);
+  const bool ident = live ? warp_stage(f_in, yrow, B, lane, wy, ws) : true;
+  return WarpRow{wx, wy, ws, B, ident};
+}
+
+// A'[i][k] = exp(E_i(V_i(beta_i f_k))) for an active slot, 0 for an inactive one and where beta_i f_k >= fs/2; an
+// instant with an identity row and beta_i == 1 copies am (the prep's unit rule).  Overwrites the amp of a prep that ran
+// without the envelope.
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_modify_amp_warp_kernel(const double* __restrict__ records, int No_ti, int K, double fs,
+                                 const double* __restrict__ betav, const double* __restrict__ f_in,
+                                 const double* __restrict__ f_out, int B, double* __restrict__ amp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * PREP_WAVES + w);   // one wave per instant: scalar
+  double* sf = lds + (size_t)w * 3 * K;
+  double* nf = sf + K;
+  double* nv = nf + K;
+  const bool live = i < No_ti;
+  const double beta = betav[live ? i : 0];
+  const double* row = records + (size_t)(live ? i : 0) * (3 * K + 1);
+  const WarpRow W = warp_row_lds(lds, K, w, lane, live, f_in, f_out + (size_t)(live ? i : 0) * B, B);
+  const bool unit = beta == 1.0 && W.ident;
+  const bool env = live && !unit;
+  int nn = 0;
+  if (env) nn = env_compact(row, K, lane, sf);
+  __syncthreads();
+  if (env) env_rank(row, K, lane, sf, nn, nf, nv);
+  __syncthreads();
+  if (!live) return;
+  for (int k = lane; k < K; k += 64) {
+    const double ak = row[k], fk = row[K + k];
+    double a = ak;
+    if (!unit) {
+      a = 0.0;
+      if (ak != 0.0 && fk > 0.0) {
+        const double bf = beta * fk;   // the output frequency: it alone decides the muting
+        a = exp(env_at(nf, nv, nn, warp_inverse(W, bf)));
+        if (bf >= 0.5 * fs) a = 0.0;
+      }
+    }
+    amp[(size_t)i * K + k] = a;
+  }
+}
+
+// out[i][t] = E_i(V_i(freqs[t])), natural-log amplitude, not muted; -inf for an instant without active slots
+extern "C" __global__ void __launch_bounds__(64 * PREP_WAVES)
+    eaqhm_model_envelope_warp_kernel(const double* __restrict__ records, int No_ti, int K,
+                                     const double* __restrict__ f_in, const double* __restrict__ f_out, int B,
+                                     const double* __restrict__ freqs, int F, double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * PREP_WAVES + w);
+  double* sf = lds + (size_t)w * 3 * K;
+  double* nf = sf + K;
+  double* nv = nf + K;
+  const bool live = i < No_ti;
+  const double* row = records + (size_t)(live ? i : 0) * (3 * K + 1);
+  const WarpRow W = warp_row_lds(lds, K, w, lane, live, f_in, f_out + (size_t)(live ? i : 0) * B, B);
+  int nn = 0;
+  if (live) nn = env_compact(row, K, lane, sf);
+  __syncthreads();
+  if (live) env_rank(row, K, lane, sf, nn, nf, nv);
+  __syncthreads();
+  if (!live) return;
+  for (int t = lane; t < F; t += 64)
+    out[(size_t)i * F + t] = (nn > 0) ? env_at(nf, nv, nn, warp_inverse(W, freqs[t])) : -INFINITY;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -607,6 +688,48 @@ extern "C" int eaqhm_model_envelope(eaqhm_ctx* ctx, const double* records, int32
                                    (int)lds));
   hipLaunchKernelGGL(eaqhm_model_envelope_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
                      dim3(64 * PREP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, alpha, freqs, (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+// ---- the piecewise-linear formant warp: amplitudes after a prep without the envelope, and the readout
+static size_t warp_lds_bytes(int Kmax) {
+  return envelope_lds_bytes(Kmax) + ((size_t)PREP_WAVES * 2 * WARP_BMAX + WARP_BMAX) * sizeof(double);
+}
+
+extern "C" int eaqhm_modify_amp_warp(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                                     const double* beta, const double* f_in, const double* f_out, int32_t B,
+                                     double* amp) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !beta || !f_in || !f_out || !amp || No_ti < 4 || Kmax <= 0 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_warp: bad argument");
+  if (B < 1 || B > WARP_BMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_warp: need 1 <= B <= 16 breakpoints");
+  const size_t lds = warp_lds_bytes(Kmax);
+  if (lds > ENVELOPE_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_warp: Kmax too large for the envelope nodes");
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_modify_amp_warp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_modify_amp_warp_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs, beta, f_in, f_out,
+                     (int)B, amp);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_model_envelope_warp(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax,
+                                         const double* f_in, const double* f_out, int32_t B, const double* freqs,
+                                         int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !f_in || !f_out || !freqs || !out || No_ti < 4 || Kmax <= 0 || F <= 0)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope_warp: bad argument");
+  if (B < 1 || B > WARP_BMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope_warp: need 1 <= B <= 16 breakpoints");
+  const size_t lds = warp_lds_bytes(Kmax);
+  if (lds > ENVELOPE_LDS_MAX)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_envelope_warp: Kmax too large for the envelope nodes");
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_envelope_warp_kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(eaqhm_model_envelope_warp_kernel, dim3((unsigned)((No_ti + PREP_WAVES - 1) / PREP_WAVES)),
+                     dim3(64 * PREP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, f_in, f_out, (int)B, freqs,
+                     (int)F, out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -6,10 +6,13 @@
 //   eaqhm_noise_warp_kernel      one wave per frame: the frame's spectrum warped by alpha on a grid in LDS, lane l owns
 //                                lag l of its autocorrelation, Levinson-Durbin in the wave
 //   eaqhm_noise_envelope_kernel  one wave per frame, lanes over the frequency grid: the warped log power spectrum
+//   eaqhm_noise_warp_map_kernel, eaqhm_noise_envelope_map_kernel  the same two bodies with the piecewise-linear map of
+//                                DESIGN.md §10.3 (eaqhm_warp.h) as the read frequency in place of w / alpha
 //   eaqhm_noise_modulation_kernel   one wave per frame, lanes over the frame's samples: the Fourier coefficients of the
 //                                   residual's power over the fundamental's phase
 //   eaqhm_noise_combine_mod_kernel  the combine kernel with each frame's pitch-synchronous gain g_q(n')
 #include "eaqhm_common.h"
+#include "eaqhm_warp.h"
 
 // The synthesis follows the NumPy model of the definition operation by operation (no fused multiply-add), so the two
 // differ only where a library function does (cos); the autocorrelation sums ask for their FMAs by name.
@@ -204,36 +207,54 @@ __device__ __forceinline__ double poly_power(const double* a, int p, double w) {
   return re * re + im * im;
 }
 
-// LDS (static): the cosine table cos(pi j / M), j = 0..M (shared by the block), and per wave P'[0..M] and a[0..63]
-extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
-    eaqhm_noise_warp_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
-                            const double* __restrict__ alpha, double* __restrict__ sigma_out,
-                            double* __restrict__ refl_out) {
-  __shared__ double tab[NW_M + 1];
-  __shared__ double Pw[NW_WAVES][NW_M + 2];
-  __shared__ double aw[NW_WAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int m = blockIdx.x * NW_WAVES + wave;
-  const bool live = m < Nf;
+// Where a frame's spectrum is read: `grid(t)` is the angle for grid point t of the warp, `angle(f)` the one for the
+// normalised frequency f of the envelope readout, `unit()` says that the frame passes through bit for bit; `load`
+// fetches what the frame needs from memory where the body asks for it.
+struct ScaleRead {   // §10.1: the frequency axis divided by alpha
+  const double* __restrict__ alpha;
+  double al;
+  __device__ __forceinline__ void load(bool live, int m) { al = live ? alpha[m] : 1.0; }
+  __device__ __forceinline__ bool unit() const { return al == 1.0; }
+  __device__ __forceinline__ double grid(int t) const { return fmin(M_PI * (double)t / (double)NW_M / al, M_PI); }
+  __device__ __forceinline__ double angle(double f) const { return (2.0 * M_PI) * fmin(f / al, 0.5); }
+};
+
+struct MapRead {     // §10.3: the inverse of the piecewise-linear map, breakpoints in cycles per sample
+  WarpRow W;
+  __device__ __forceinline__ void load(bool, int) {}   // the kernel staged the row in LDS
+  __device__ __forceinline__ bool unit() const { return W.ident; }
+  __device__ __forceinline__ double grid(int t) const {
+    return fmin((2.0 * M_PI) * warp_inverse(W, (double)t / (double)(2 * NW_M)), M_PI);
+  }
+  __device__ __forceinline__ double angle(double f) const { return fmin((2.0 * M_PI) * warp_inverse(W, f), M_PI); }
+};
+
+// The warp of one frame by one wave (the body of both warp kernels).  tab: the cosine table cos(pi j / M), j = 0..M,
+// shared by the block; P: the wave's P'[0..M]; a: the wave's a[0..63].  Every wave of the block reaches both barriers.
+template <class Read>
+__device__ __forceinline__ void noise_warp_frame(const double* __restrict__ sigma, const double* __restrict__ refl,
+                                                 int p, int lane, int m, bool live, Read rd, double* tab, double* P,
+                                                 double* a, double* __restrict__ sigma_out,
+                                                 double* __restrict__ refl_out) {
   for (int j = threadIdx.x; j <= NW_M; j += 64 * NW_WAVES) tab[j] = cospi((double)j / (double)NW_M);
   const double sg = live ? sigma[m] : 0.0;
-  const double al = live ? alpha[m] : 1.0;
+  rd.load(live, m);
   const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
-  const bool work = live && al != 1.0 && sg > 0.0;     // uniform over the wave
-  if (work) aw[wave][lane] = stepup_lanes(kin, p, lane);
+  const bool unit = rd.unit();
+  const bool work = live && !unit && sg > 0.0;     // uniform over the wave
+  if (work) a[lane] = stepup_lanes(kin, p, lane);
   __syncthreads();
-  double* P = Pw[wave];
   if (work) {
     for (int t = lane; t <= NW_M; t += 64) {
-      const double w = fmin(M_PI * (double)t / (double)NW_M / al, M_PI);
-      P[t] = sg * sg / poly_power(aw[wave], p, w);
+      const double w = rd.grid(t);
+      P[t] = sg * sg / poly_power(a, p, w);
     }
   }
   __syncthreads();
   if (!live) return;
-  if (!work) {   // alpha == 1: the frame bit for bit; otherwise a silent frame
-    if (lane == 0) sigma_out[m] = al == 1.0 ? sg : 0.0;
-    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = al == 1.0 ? kin : 0.0;
+  if (!work) {   // a unit read: the frame bit for bit; otherwise a silent frame
+    if (lane == 0) sigma_out[m] = unit ? sg : 0.0;
+    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = unit ? kin : 0.0;
     return;
   }
 
@@ -260,7 +281,61 @@ extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
   if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = kk;
 }
 
-// out[m][t] = 2 ln sigma_m - ln |A_m(e^{jw})|^2 at w = 2 pi min(fnorm[t] / alpha_m, 1/2); -inf rows for silent frames
+// LDS (static): the cosine table (shared by the block), and per wave P'[0..M] and a[0..63]
+extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+    eaqhm_noise_warp_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
+                            const double* __restrict__ alpha, double* __restrict__ sigma_out,
+                            double* __restrict__ refl_out) {
+  __shared__ double tab[NW_M + 1];
+  __shared__ double Pw[NW_WAVES][NW_M + 2];
+  __shared__ double aw[NW_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NW_WAVES + wave;
+  const bool live = m < Nf;
+  const ScaleRead rd{alpha, 1.0};
+  noise_warp_frame(sigma, refl, p, lane, m, live, rd, tab, Pw[wave], aw[wave], sigma_out, refl_out);
+}
+
+// the same with frame m's row of the map; LDS: 2 x WARP_BMAX doubles more per wave and WARP_BMAX for the block
+extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+    eaqhm_noise_warp_map_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
+                                const double* __restrict__ f_in, const double* __restrict__ f_out, int B,
+                                double* __restrict__ sigma_out, double* __restrict__ refl_out) {
+  __shared__ double tab[NW_M + 1];
+  __shared__ double Pw[NW_WAVES][NW_M + 2];
+  __shared__ double aw[NW_WAVES][64];
+  __shared__ double wy[NW_WAVES][WARP_BMAX], ws[NW_WAVES][WARP_BMAX], wx[WARP_BMAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NW_WAVES + wave;
+  const bool live = m < Nf;
+  warp_stage_x(f_in, B, threadIdx.x, wx);
+  const bool ident = live ? warp_stage(f_in, f_out + (size_t)m * B, B, lane, wy[wave], ws[wave]) : true;
+  const MapRead rd{WarpRow{wx, wy[wave], ws[wave], B, ident}};   // read after the body's first barrier
+  noise_warp_frame(sigma, refl, p, lane, m, live, rd, tab, Pw[wave], aw[wave], sigma_out, refl_out);
+}
+
+// The envelope readout of one frame by one wave (the body of both envelope kernels): out[m][t] = 2 ln sigma_m -
+// ln |A_m(e^{jw})|^2 at w = rd.angle(fnorm[t]); -inf rows for silent frames.  a: the wave's a[0..63].
+template <class Read>
+__device__ __forceinline__ void noise_envelope_frame(const double* __restrict__ sigma, const double* __restrict__ refl,
+                                                     int p, int lane, int m, bool live, Read rd, double* a,
+                                                     const double* __restrict__ fnorm, int F,
+                                                     double* __restrict__ out) {
+  const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
+  a[lane] = stepup_lanes(kin, p, lane);
+  __syncthreads();
+  if (!live) return;
+  const double sg = sigma[m];
+  rd.load(true, m);
+  const double ls = 2.0 * log(sg);
+  double* row = out + (size_t)m * F;
+  for (int t = lane; t < F; t += 64) {
+    const double w = rd.angle(fnorm[t]);
+    row[t] = sg > 0.0 ? ls - log(poly_power(a, p, w)) : -INFINITY;
+  }
+}
+
+// w = 2 pi min(fnorm[t] / alpha_m, 1/2)
 extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
     eaqhm_noise_envelope_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
                                 const double* __restrict__ alpha, const double* __restrict__ fnorm, int F,
@@ -269,17 +344,24 @@ extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = blockIdx.x * NE_WAVES + wave;
   const bool live = m < Nf;
-  const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
-  aw[wave][lane] = stepup_lanes(kin, p, lane);
-  __syncthreads();
-  if (!live) return;
-  const double sg = sigma[m], al = alpha[m];
-  const double ls = 2.0 * log(sg);
-  double* row = out + (size_t)m * F;
-  for (int t = lane; t < F; t += 64) {
-    const double w = (2.0 * M_PI) * fmin(fnorm[t] / al, 0.5);
-    row[t] = sg > 0.0 ? ls - log(poly_power(aw[wave], p, w)) : -INFINITY;
-  }
+  const ScaleRead rd{alpha, 1.0};
+  noise_envelope_frame(sigma, refl, p, lane, m, live, rd, aw[wave], fnorm, F, out);
+}
+
+// w = min(2 pi V_m(fnorm[t]), pi)
+extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
+    eaqhm_noise_envelope_map_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p,
+                                    const double* __restrict__ f_in, const double* __restrict__ f_out, int B,
+                                    const double* __restrict__ fnorm, int F, double* __restrict__ out) {
+  __shared__ double aw[NE_WAVES][64];
+  __shared__ double wy[NE_WAVES][WARP_BMAX], ws[NE_WAVES][WARP_BMAX], wx[WARP_BMAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NE_WAVES + wave;
+  const bool live = m < Nf;
+  warp_stage_x(f_in, B, threadIdx.x, wx);
+  const bool ident = live ? warp_stage(f_in, f_out + (size_t)m * B, B, lane, wy[wave], ws[wave]) : true;
+  const MapRead rd{WarpRow{wx, wy[wave], ws[wave], B, ident}};   // read after the body's barrier
+  noise_envelope_frame(sigma, refl, p, lane, m, live, rd, aw[wave], fnorm, F, out);
 }
 
 // ---- pitch-synchronous modulation of the noise (tests/noise_modulation_ref.py)
@@ -493,6 +575,37 @@ extern "C" int eaqhm_noise_envelope(eaqhm_ctx* ctx, const double* sigma, const d
   if (order < 1 || order > 63) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope: need 1 <= order <= 63");
   hipLaunchKernelGGL(eaqhm_noise_envelope_kernel, dim3((unsigned)(((int64_t)Nf + NE_WAVES - 1) / NE_WAVES)),
                      dim3(64 * NE_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, alpha, fnorm, (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+// ---- the piecewise-linear formant warp of the noise model; breakpoints in cycles per sample
+extern "C" int eaqhm_noise_warp_map(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                                    const double* f_in, const double* f_out, int32_t B, double* sigma_out,
+                                    double* refl_out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !f_in || !f_out || !sigma_out || !refl_out || Nf < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_warp_map: bad argument");
+  if (order < 1 || order > 63) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_warp_map: need 1 <= order <= 63");
+  if (B < 1 || B > WARP_BMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_warp_map: need 1 <= B <= 16 breakpoints");
+  hipLaunchKernelGGL(eaqhm_noise_warp_map_kernel, dim3((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)),
+                     dim3(64 * NW_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, f_in, f_out, (int)B, sigma_out,
+                     refl_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_envelope_map(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf,
+                                        int32_t order, const double* f_in, const double* f_out, int32_t B,
+                                        const double* fnorm, int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !f_in || !f_out || !fnorm || !out || Nf < 1 || F < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope_map: bad argument");
+  if (order < 1 || order > 63) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope_map: need 1 <= order <= 63");
+  if (B < 1 || B > WARP_BMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_envelope_map: need 1 <= B <= 16 breakpoints");
+  hipLaunchKernelGGL(eaqhm_noise_envelope_map_kernel, dim3((unsigned)(((int64_t)Nf + NE_WAVES - 1) / NE_WAVES)),
+                     dim3(64 * NE_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, f_in, f_out, (int)B, fnorm,
+                     (int)F, out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -46,6 +46,10 @@ SYMBOLS = (
     ("eaqhm_noise_warp", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     ("eaqhm_noise_envelope", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P]),
     ("eaqhm_noise_modulation", C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _F64, _F64, _F64, _I32, _P]),
+    ("eaqhm_modify_amp_warp", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P]),
+    ("eaqhm_model_envelope_warp", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P]),
+    ("eaqhm_noise_warp_map", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P]),
+    ("eaqhm_noise_envelope_map", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P]),
 )
 
 
@@ -231,6 +235,23 @@ class Context:
     def noise_modulation(self, e, L, hop, theta, f0, voiced, No_ti, ti0, step, fs, harmonics, mod):
         self._ck(self.lib.eaqhm_noise_modulation(self.h, _ptr(e), L, hop, _ptr(theta), _ptr(f0), _ptr(voiced), No_ti,
                                                  float(ti0), float(step), float(fs), harmonics, _ptr(mod)))
+
+    # the piecewise-linear formant warp: f_in [B], f_out [rows][B] (Hz for the model, cycles per sample for the noise)
+    def modify_amp_warp(self, records, No_ti, Kmax, fs, beta, f_in, f_out, B, amp):
+        self._ck(self.lib.eaqhm_modify_amp_warp(self.h, _ptr(records), No_ti, Kmax, float(fs), _ptr(beta), _ptr(f_in),
+                                                _ptr(f_out), B, _ptr(amp)))
+
+    def model_envelope_warp(self, records, No_ti, Kmax, f_in, f_out, B, freqs, F, out):
+        self._ck(self.lib.eaqhm_model_envelope_warp(self.h, _ptr(records), No_ti, Kmax, _ptr(f_in), _ptr(f_out), B,
+                                                    _ptr(freqs), F, _ptr(out)))
+
+    def noise_warp_map(self, sigma, refl, Nf, order, f_in, f_out, B, sigma_out, refl_out):
+        self._ck(self.lib.eaqhm_noise_warp_map(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(f_in), _ptr(f_out), B,
+                                               _ptr(sigma_out), _ptr(refl_out)))
+
+    def noise_envelope_map(self, sigma, refl, Nf, order, f_in, f_out, B, fnorm, F, out):
+        self._ck(self.lib.eaqhm_noise_envelope_map(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(f_in), _ptr(f_out),
+                                                   B, _ptr(fnorm), F, _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

@@ -2,15 +2,19 @@
 
     unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
     eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, phase="independent", f0=None, device_index=0) -> float64[L_out]
+                   formant_scale=1.0, *, phase="independent", f0=None, formant_warp=None, device_index=0) -> float64[L_out]
     model_f0(DetComponents, fs) -> float64[No_ti]
-    model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[No_ti, len(freqs)]
+    model_envelope(DetComponents, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0)
+        -> float64[No_ti, len(freqs)]
+    formant_warp_vtln(fs, alpha, knee=0.875) -> (f_in, f_out): the two-breakpoint VTLN map
+    check_formant_warp(model, fs, formant_warp, formant_scale=1.0, preserve_envelope=True) -> (f_in[B], f_out[No_ti, B])
+    noise_formant_warp(noise, DetComponents, formant_warp) -> (f_in[B], f_out[Nf, B])
     scale_contour(DetComponents, fs, times_s, values) -> float64[No_ti]
     contour_time_map(rho, beta, step, length) -> dict(rate, gain, C, L_out, rate_min)
     eaQHMNoiseAnalysis(s, s_recon, fs, order=None, hop=None, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
     eaQHMNoiseSynthesis(noise, tau, L_out, seed=0, *, device_index=0) -> float64[L_out]
     noise_time_map(hop, L_out, rho) / noise_time_map_contour(hop, tm, step) -> float64[Nq]
-    eaQHMNoiseWarp(noise, formant_scale, *, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
+    eaQHMNoiseWarp(noise, formant_scale=1.0, *, formant_warp=None, device_index=0) -> dict(sigma, refl, hop, order, fs, length)
     noise_formant_contour(noise, DetComponents, formant_scale) -> float64[Nf]
     noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0) -> float64[Nf, len(freqs)]
     model_phase(DetComponents, fs, f0=None) -> float64[No_ti]
@@ -21,7 +25,8 @@
 the dict of arrays (det_format="arrays"), edited or not.  At time_scale = pitch_scale = 1 the result is the analysis's
 own s_recon; the definition for other settings is in DESIGN.md ("Resynthesis from the model", §9).  Either scale may
 also be a contour, one value per analysis instant (§9.1).  A formant scale moves the spectral envelope on its own
-(§9.2).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
+(§9.2); a formant warp, a piecewise-linear frequency map (f_in, f_out) such as formant_warp_vtln's, moves it along a
+curve instead of by one factor (§9.4, §10.3).  The residual s - s_recon is modelled apart, as an LPC envelope and a gain per 5 ms frame, and resynthesised as
 filtered white noise under the same time map (§10); its envelope follows a formant scale on request (§10.1).  phase="shape" keeps the phases of the harmonics relative to the
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
 eaqhm_modify_prep, eaqhm_modify_synth, eaqhm_model_envelope, eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp,
@@ -267,6 +272,83 @@ def check_formant_scale(model, formant_scale, preserve_envelope):
     return alpha
 
 
+FORMANT_WARP_MAX = 16    # breakpoints of a formant warp at most: the kernels keep a row in 16 doubles of LDS per wave
+
+
+def _warp_rows(formant_warp, rows, per):
+    """A formant warp (f_in, f_out) as (float64[B], float64[rows, B]), validated: f_in is [B], f_out [B] or [rows, B]
+    (one row per `per`), 1 <= B <= 16; all values finite and > 0; f_in and every row of f_out strictly increasing; every
+    segment slope, the one from the origin included, in SCALE_RANGE."""
+    try:
+        f_in, f_out = formant_warp
+    except (TypeError, ValueError):
+        raise ValueError("formant_warp must be the pair (f_in, f_out) of breakpoint frequencies in Hz") from None
+    x, y = np.asarray(f_in), np.asarray(f_out)
+    if x.dtype.kind not in "iuf" or y.dtype.kind not in "iuf":
+        raise ValueError("formant_warp must hold numbers")
+    if x.ndim != 1:
+        raise ValueError("formant_warp f_in must be 1-D, got shape %s" % (x.shape,))
+    B = len(x)
+    if not 1 <= B <= FORMANT_WARP_MAX:
+        raise ValueError("formant_warp must have 1 to %d breakpoints, got %d" % (FORMANT_WARP_MAX, B))
+    if y.shape != (B,) and y.shape != (rows, B):
+        raise ValueError("formant_warp f_out must have shape (%d,) or one row per %s (%d, %d), got %s"
+                         % (B, per, rows, B, y.shape))
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(np.broadcast_to(y, (rows, B)), dtype=np.float64)
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))) or np.any(x <= 0) or np.any(y <= 0):
+        raise ValueError("formant_warp frequencies must be finite and > 0 (the map starts at (0, 0) by itself)")
+    if np.any(np.diff(x) <= 0) or np.any(np.diff(y, axis=1) <= 0):
+        raise ValueError("formant_warp f_in and every row of f_out must be strictly increasing")
+    slope = np.diff(y, axis=1, prepend=0.0) / np.diff(x, prepend=0.0)
+    if np.any(slope < SCALE_RANGE[0]) or np.any(slope > SCALE_RANGE[1]):
+        raise ValueError("formant_warp: every segment slope (the one from the origin included) must be in [%g, %g]"
+                         % SCALE_RANGE)
+    return x, y
+
+
+def _warp_excludes_scale(formant_scale):
+    if _is_contour(formant_scale) or _scale(formant_scale, "formant_scale") != 1.0:
+        raise ValueError("formant_warp and formant_scale exclude each other: B = 1 with (x, alpha x) is the scale alpha")
+
+
+def check_formant_warp(model, fs, formant_warp, formant_scale=1.0, preserve_envelope=True):
+    """Validates a formant warp (no device work): `formant_warp` = (f_in, f_out) in Hz, f_in [B] model
+    frequencies, f_out [B] or [No_ti, B] (one row per analysis instant) output frequencies, 1 <= B <= 16, all finite and
+    > 0, each strictly increasing, every segment slope (from the origin included) in [0.25, 4].  It excludes a
+    formant_scale that is a contour or != 1 and needs preserve_envelope=True.  Returns (f_in float64[B],
+    f_out float64[No_ti, B])."""
+    _sample_rate(fs)
+    _warp_excludes_scale(formant_scale)
+    if not preserve_envelope:
+        raise ValueError("formant_warp needs preserve_envelope=True: there is no envelope to warp")
+    return _warp_rows(formant_warp, len(model["ti"]), "analysis instant")
+
+
+def formant_warp_vtln(fs, alpha, knee=0.875):
+    """The piecewise-linear map of vocal-tract length normalisation as a formant warp (host only): slope `alpha` from
+    the origin up to the knee, then straight to (fs/2, fs/2), so the whole band of the model fills the whole band of the
+    output.  The breakpoints are (f_k, alpha f_k) with f_k = knee (fs/2) min(1, 1/alpha), and (fs/2, fs/2).  Raises
+    ValueError when `knee` is not in (0, 1) or either slope leaves [0.25, 4].  Returns (f_in, f_out), float64[2] each:
+    eaQHMSynthesis's, model_envelope's, eaQHMNoiseWarp's and noise_envelope's `formant_warp`."""
+    fs = _sample_rate(fs)
+    alpha = _scale(alpha, "alpha")
+    try:
+        knee = float(knee)
+    except (TypeError, ValueError):
+        raise ValueError("knee must be a number") from None
+    if not 0.0 < knee < 1.0:
+        raise ValueError("knee must lie in (0, 1), got %r" % (knee,))
+    nyq = fs / 2
+    fk = knee * nyq * min(1.0, 1.0 / alpha)
+    f_in, f_out = np.array([fk, nyq]), np.array([alpha * fk, nyq])
+    upper = (f_out[1] - f_out[0]) / (f_in[1] - f_in[0])
+    if not SCALE_RANGE[0] <= upper <= SCALE_RANGE[1]:
+        raise ValueError("alpha %g with knee %g gives the slope %g above the knee, outside [%g, %g]"
+                         % ((alpha, knee, upper) + SCALE_RANGE))
+    return f_in, f_out
+
+
 PHASE_MODES = ("independent", "shape")
 
 
@@ -356,7 +438,7 @@ def _device_records(model, dev):
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
                    formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, noise_formant=False,
-                   noise_modulation=False, device_index=0, _ranges=None):
+                   noise_modulation=False, formant_warp=None, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -396,6 +478,16 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     scale and in both phase modes.  The result is bit for bit the synthesis without noise plus eaQHMNoiseSynthesis(noise,
     tau, L_out, noise_seed, fundamental=noise_fundamental(DetComponents, fs, tau, ...)).  The default ignores `mod`.
 
+    `formant_warp` = (f_in, f_out) generalises the formant scale from a number to a map (§9.4): a strictly increasing
+    piecewise-linear map W through (0, 0) and the breakpoints (f_in[j], f_out[j]) in Hz, continued past the last one
+    with its slope; a feature at F in the model sits at W(F) in the output, and each partial's amplitude is read off its
+    instant's envelope at W^-1(pitch_scale * f).  f_in is [B], f_out [B] or [No_ti, B] (a map per analysis instant),
+    1 <= B <= 16, every slope in [0.25, 4]; formant_warp_vtln builds the VTLN map.  It excludes a formant_scale != 1 and
+    needs preserve_envelope=True; the length and the path (scalar or contour) are those of the time and pitch scales.
+    With noise_formant=True the noise is synthesised from eaQHMNoiseWarp(noise, formant_warp=noise_formant_warp(noise,
+    DetComponents, formant_warp)) (§10.3), bit for bit as if that model were passed as `noise`.  None leaves every
+    result as it is.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     model = unpack_model(DetComponents)
@@ -405,6 +497,8 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     else:
         rho, beta, fs, length = check_arguments(model, fs, length, time_scale, pitch_scale)
     alpha = check_formant_scale(model, formant_scale, preserve_envelope)
+    wmap = None if formant_warp is None else check_formant_warp(model, fs, formant_warp, formant_scale,
+                                                                preserve_envelope)
     shape, f0 = check_phase_arguments(model, phase, f0)
     # alpha reaches the prep for a formant contour or a number != 1; without the envelope alpha is 1 throughout
     formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
@@ -438,8 +532,13 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
 
     gain_d = dv(tm["gain"]) if contour else None      # without it Delta stays unweighted: the scalar synthesis
     # phase="shape" leaves Delta unweighted on either path: the weight moves to the fundamental's advance S
-    c.modify_prep(rec, code, mom, n, K, D, fs, dv(beta), None if shape else gain_d, dv(alpha) if formant else None,
-                  preserve_envelope, amp, R, ph0)
+    beta_d = dv(beta)
+    if wmap is None:
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None if shape else gain_d, dv(alpha) if formant else None,
+                      preserve_envelope, amp, R, ph0)
+    else:   # R and ph0 do not depend on the envelope: the prep runs without it and the warp kernel writes amp
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None if shape else gain_d, None, False, amp, R, ph0)
+        c.modify_amp_warp(rec, n, K, fs, beta_d, dv(wmap[0]), dv(wmap[1]), len(wmap[0]), amp)
     # the two optional groups of eaqhm_modify_synth; the contour map holds rho and beta, which are then not read
     curve_d = (dv(tm["C"]), dv(tm["rate"]), gain_d, tm["rate_min"]) if contour else None
     shape_d = None
@@ -452,7 +551,10 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
         H = nz["hop"]
         tau = noise_time_map_contour(H, tm, D) if contour else noise_time_map(H, L_out, rho)
         sigma_d, refl_d, tau_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], tau))
-        if warp:
+        if warp and wmap is not None:
+            sigma_d, refl_d = _device_noise_warp_map(c, sigma_d, refl_d, nz["order"], *_warp_normalised(
+                wmap[0], _frame_rows(nz, model["ti"], wmap[1]), fs))
+        elif warp:
             sigma_d, refl_d = _device_noise_warp(c, sigma_d, refl_d, nz["order"],
                                                  _frame_alpha(nz, model["ti"], np.broadcast_to(alpha, (n,))))
         mod_d = None
@@ -485,23 +587,31 @@ def check_envelope_arguments(model, fs, freqs, formant_scale):
     return np.array(np.broadcast_to(alpha, (len(model["ti"]),)), dtype=np.float64), f
 
 
-def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, *, device_index=0):
+def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0):
     """The log-amplitude envelope of every analysis instant on a frequency grid: out[i, t] = E_i(freqs[t] / alpha_i)
     (DESIGN.md §9.2), the natural log of the amplitude |a|, not muted at Nyquist.  E_i interpolates ln |a| linearly
     between the instant's active partials ordered by frequency and is flat outside them; rows of instants without
     active partials are -inf.  With formant_scale = alpha (a number or one value per instant, in [0.25, 4]) it is the
     envelope eaQHMSynthesis reads the amplitudes from at that formant scale.  `freqs` (Hz) is 1-D, finite and >= 0.
 
+    With `formant_warp` = (f_in, f_out) (eaQHMSynthesis's; §9.4) it is out[i, t] = E_i(W_i^-1(freqs[t])) instead, the
+    envelope the synthesis reads under that map; it excludes a formant_scale != 1.
+
     The result takes No_ti * len(freqs) * 8 bytes, once on the device and once on the host (61 MB for a 60 s model at
     16 kHz, step 15, 64 000 instants, on a 120-point grid).  Returns float64[No_ti, len(freqs)]."""
     model = unpack_model(DetComponents)
     alpha, f = check_envelope_arguments(model, fs, freqs, formant_scale)
+    wmap = None if formant_warp is None else check_formant_warp(model, fs, formant_warp, formant_scale, True)
     torch, c, dev = _device(device_index)
     rec, n, K = _device_records(model, dev)
-    alpha_d = torch.as_tensor(np.ascontiguousarray(alpha), device=dev)
     f_d = torch.as_tensor(np.ascontiguousarray(f), device=dev)
     out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)
-    c.model_envelope(rec, n, K, alpha_d, f_d, len(f), out)
+    if wmap is None:
+        alpha_d = torch.as_tensor(np.ascontiguousarray(alpha), device=dev)
+        c.model_envelope(rec, n, K, alpha_d, f_d, len(f), out)
+    else:
+        x_d, y_d = (torch.as_tensor(v, device=dev) for v in wmap)
+        c.model_envelope_warp(rec, n, K, x_d, y_d, len(wmap[0]), f_d, len(f), out)
     return out.cpu().numpy()
 
 
@@ -696,6 +806,48 @@ def _frame_alpha(nz, ti, alpha):
     return np.interp(np.arange(Nf, dtype=np.float64) * float(nz["hop"]), np.asarray(ti, dtype=np.float64), alpha)
 
 
+def _frame_rows(nz, ti, f_out):
+    """f_out per noise frame from f_out per analysis instant ([No_ti, B] -> [Nf, B]): every column as _frame_alpha
+    takes alpha.  A convex combination of valid rows is a valid row; a constant column comes back exactly."""
+    return np.ascontiguousarray(np.stack([_frame_alpha(nz, ti, col) for col in f_out.T], axis=1))
+
+
+def _warp_normalised(f_in, f_out, fs):
+    """The breakpoints in cycles per sample, as eaqhm_noise_warp_map and eaqhm_noise_envelope_map take them.  A row
+    that equals f_in bit for bit still does."""
+    return np.ascontiguousarray(f_in / fs), np.ascontiguousarray(f_out / fs)
+
+
+def noise_formant_warp(noise, DetComponents, formant_warp):
+    """The formant warp of every frame of a noise model, for eaQHMNoiseWarp's `formant_warp` (host only; DESIGN.md
+    §10.3): `formant_warp` = (f_in, f_out) is what eaQHMSynthesis takes, f_out [B] or one row per analysis instant;
+    frame m takes, column by column, the linear interpolation at sample m hop over the instants' sample positions, flat
+    before the first and after the last.  Returns (f_in float64[B], f_out float64[Nf, B]) in Hz."""
+    nz = check_noise_model(noise)
+    ti = unpack_model(DetComponents)["ti"]
+    f_in, f_out = _warp_rows(formant_warp, len(ti), "analysis instant")
+    return f_in, _frame_rows(nz, ti, f_out)
+
+
+def check_noise_warp_map_arguments(noise, formant_warp, formant_scale=1.0):
+    """Validates eaQHMNoiseWarp's and noise_envelope's `formant_warp` (no device work): (f_in, f_out) in Hz with f_out
+    [B] or [Nf, B], under the rules of check_formant_warp; it excludes a formant_scale != 1.  Returns (model, f_in / fs
+    float64[B], f_out / fs float64[Nf, B])."""
+    nz = check_noise_model(noise)
+    _warp_excludes_scale(formant_scale)
+    f_in, f_out = _warp_rows(formant_warp, len(nz["sigma"]), "noise frame")
+    return (nz,) + _warp_normalised(f_in, f_out, nz["fs"])
+
+
+def _device_noise_warp_map(c, sigma_d, refl_d, order, x, y):
+    """eaqhm_noise_warp_map on device tensors: (sigma', refl') as new tensors; x [B], y [Nf, B] in cycles per sample."""
+    import torch
+    x_d, y_d = (torch.as_tensor(v, device=c.device) for v in (x, y))
+    sigma_o, refl_o = torch.empty_like(sigma_d), torch.empty_like(refl_d)
+    c.noise_warp_map(sigma_d, refl_d, sigma_d.shape[0], order, x_d, y_d, len(x), sigma_o, refl_o)
+    return sigma_o, refl_o
+
+
 def noise_formant_contour(noise, DetComponents, formant_scale):
     """The formant scale of every frame of a noise model, for eaQHMNoiseWarp (host only): `formant_scale` is a number
     or one value per analysis instant of the model (what eaQHMSynthesis takes); frame m takes the linear interpolation
@@ -739,7 +891,7 @@ def _device_noise_warp(c, sigma_d, refl_d, order, alpha):
     return sigma_o, refl_o
 
 
-def eaQHMNoiseWarp(noise, formant_scale, *, device_index=0):
+def eaQHMNoiseWarp(noise, formant_scale=1.0, *, formant_warp=None, device_index=0):
     """The noise model whose spectral envelope is `noise`'s moved up in frequency by `formant_scale` (alpha; DESIGN.md
     §10.1): a feature at F sits at alpha F.  Each frame's all-pole power spectrum sigma^2 / |A|^2 is read at w / alpha on
     a 1025-point grid (held at its Nyquist value above alpha pi), turned into an autocorrelation and re-fitted with the
@@ -747,28 +899,47 @@ def eaQHMNoiseWarp(noise, formant_scale, *, device_index=0):
     (noise_formant_contour gives them from a per-instant contour), finite and in [0.25, 4].  A frame with alpha == 1
     comes back bit for bit, a silent frame silent.  The total power is not renormalised.
 
+    `formant_warp` = (f_in, f_out) in Hz, f_out [B] or one row per noise frame (noise_formant_warp gives them from a map
+    per instant), moves the envelope along the piecewise-linear map W of eaQHMSynthesis's `formant_warp` instead (§10.3):
+    the spectrum is read at W^-1, held at its Nyquist value where W^-1 passes fs/2.  A frame whose row equals f_in comes
+    back bit for bit.  It excludes a formant_scale != 1.
+
     Returns a new dict(sigma, refl, hop, order, fs, length) of the same layout."""
-    nz, alpha = check_noise_warp_arguments(noise, formant_scale)
+    if formant_warp is not None:
+        nz, x, y = check_noise_warp_map_arguments(noise, formant_warp, formant_scale)
+    else:
+        nz, alpha = check_noise_warp_arguments(noise, formant_scale)
     torch, c, dev = _device(device_index)
-    sigma_d, refl_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"]))
-    sigma_o, refl_o = _device_noise_warp(c, sigma_d, refl_d, nz["order"], alpha)
+    sigma_d, refl_d = (torch.as_tensor(x_, device=dev) for x_ in (nz["sigma"], nz["refl"]))
+    if formant_warp is not None:
+        sigma_o, refl_o = _device_noise_warp_map(c, sigma_d, refl_d, nz["order"], x, y)
+    else:
+        sigma_o, refl_o = _device_noise_warp(c, sigma_d, refl_d, nz["order"], alpha)
     return dict(nz, sigma=sigma_o.cpu().numpy(), refl=refl_o.cpu().numpy())
 
 
-def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, device_index=0):
+def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, formant_warp=None, device_index=0):
     """The log power spectrum of every frame of a noise model on a frequency grid, read at the formant scale alpha
     (DESIGN.md §10.1): out[m, t] = 2 ln sigma_m - 2 ln |A_m(e^{jw})| at w = 2 pi min(freqs[t] / alpha_m, fs / 2) / fs,
     the natural log of the power; rows of silent frames are -inf.  It is the exact warped spectrum, the one
     eaQHMNoiseWarp's refit approximates; the counterpart of model_envelope for the noise.  `freqs` (Hz) is 1-D, finite
     and >= 0; `formant_scale` a number or one value per noise frame in [0.25, 4]; `fs` must be the model's.
 
+    With `formant_warp` = (f_in, f_out) (eaQHMNoiseWarp's; §10.3) the read angle is w = min(2 pi W_m^-1(freqs[t]) / fs,
+    pi) instead; it excludes a formant_scale != 1.
+
     Returns float64[Nf, len(freqs)]."""
     nz, alpha, fnorm = check_noise_envelope_arguments(noise, fs, freqs, formant_scale)
+    wmap = None if formant_warp is None else check_noise_warp_map_arguments(nz, formant_warp, formant_scale)[1:]
     torch, c, dev = _device(device_index)
-    sigma_d, refl_d, alpha_d, f_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], alpha, fnorm))
+    sigma_d, refl_d, f_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"], fnorm))
     Nf = len(nz["sigma"])
     out = torch.empty((Nf, len(fnorm)), dtype=torch.float64, device=dev)
-    c.noise_envelope(sigma_d, refl_d, Nf, nz["order"], alpha_d, f_d, len(fnorm), out)
+    if wmap is None:
+        c.noise_envelope(sigma_d, refl_d, Nf, nz["order"], torch.as_tensor(alpha, device=dev), f_d, len(fnorm), out)
+    else:
+        x_d, y_d = (torch.as_tensor(v, device=dev) for v in wmap)
+        c.noise_envelope_map(sigma_d, refl_d, Nf, nz["order"], x_d, y_d, len(wmap[0]), f_d, len(fnorm), out)
     return out.cpu().numpy()
 
 

@@ -316,6 +316,39 @@ int eaqhm_noise_modulation(eaqhm_ctx* ctx, const double* e, int64_t L, int32_t h
                            const double* f0, const uint8_t* voiced, int32_t No_ti, double ti0, double step, double fs,
                            int32_t harmonics, double* mod);
 
+/* the piecewise-linear formant warp (additions under ABI 6) ----------------------------------
+ * A formant warp is a strictly increasing piecewise-linear map W from model frequency to output frequency through
+ * (0, 0) and B breakpoints (x_j, y_j), 1 <= B <= 16, continued past the last one with the last slope: a feature at F in
+ * the model sits at W(F) in the output.  B = 1 with (x, alpha x) is the formant scale alpha.
+ *   f_in       double[B]          x_0 < x_1 < .. , all > 0; shared by all instants / frames
+ *   f_out      double[n][B]       y_0 < y_1 < .. , all > 0; one row per instant (n = No_ti) or per noise frame (n = Nf)
+ * The kernels evaluate the inverse V = W^-1 at an output frequency q: b = min(#{j : y_j <= q}, B - 1),
+ * V(q) = x_{b-1} + (q - y_{b-1}) * ((x_b - x_{b-1}) / (y_b - y_{b-1})) with x_{-1} = y_{-1} = 0, in this order of
+ * operations; a row that equals f_in bit for bit is the identity, V(q) = q with no arithmetic.
+ * Monotonicity and the range of the slopes are the CALLER'S contract (the Python host checks them): the entry points do
+ * not read the device arrays.  A row that breaks the contract gives wrong numbers, never an access out of bounds (the
+ * segment scan is bounded by B).
+ * eaqhm_modify_amp_warp (kernel: one wave per instant, the envelope nodes of eaqhm_modify_prep in LDS, the wave's row of
+ *   the map in LDS) overwrites the amp of an eaqhm_modify_prep that ran with preserve_envelope = 0 and alpha NULL, on the
+ *   same stream, with the same beta; eaqhm_modify_synth then runs unchanged:
+ *   amp        double[No_ti][Kmax]  A' = exp(E_i(V_i(beta_i f))) for an active slot, 0 for an inactive one and where
+ *                                   beta_i f >= fs/2; an instant with an identity row and beta_i == 1 gives |a|, a copy
+ * eaqhm_model_envelope_warp: eaqhm_model_envelope with V_i in place of / alpha_i: out[i][t] = E_i(V_i(freqs[t])).
+ * eaqhm_noise_warp_map: eaqhm_noise_warp with frame m's spectrum read at w = min(2 pi V_m(t / 2048), pi), t = 0..1024;
+ *   f_in, f_out in cycles per sample (Hz / fs).  An identity row returns the frame bit for bit, a silent frame silent.
+ * eaqhm_noise_envelope_map: eaqhm_noise_envelope at w = min(2 pi V_m(fnorm[t]), pi).
+ * EAQHM_EINVAL for null pointers, B < 1, B > 16 and the limits of the alpha siblings (No_ti < 4, Kmax beyond the LDS
+ * budget, F < 1, Nf < 1, order outside [1, 63], fs not finite and > 0).                                              */
+int eaqhm_modify_amp_warp(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                          const double* beta, const double* f_in, const double* f_out, int32_t B, double* amp);
+int eaqhm_model_envelope_warp(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, const double* f_in,
+                              const double* f_out, int32_t B, const double* freqs, int32_t F, double* out);
+int eaqhm_noise_warp_map(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                         const double* f_in, const double* f_out, int32_t B, double* sigma_out, double* refl_out);
+int eaqhm_noise_envelope_map(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                             const double* f_in, const double* f_out, int32_t B, const double* fnorm, int32_t F,
+                             double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 eaqhm_eval_synth on the same records, output samples per second, and unpack_model against pack_results on the host.
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
-                                          [--noise] [--noise-formant] [--noise-modulation] [--shape] [--out FILE]
+                                          [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
+                                          [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -21,7 +22,10 @@ same session, with the same windows.  --noise-modulation adds the pitch-synchron
 the plain one at rho in {0.5, 1, 2}, with the same windows.  --shape adds the shape-invariant phase
 mode (DESIGN.md §11): eaqhm_modify_synth with the shape group next to without at rho in {0.5, 1, 2} x beta in {1, 1.25}
 and on the four contour settings, each the median of three
-windows of 20 launches with the max - min of the existing kernel's three (the margin).  EAQHM_LIB selects another build of
+windows of 20 launches with the max - min of the existing kernel's three (the margin).  --formant-warp adds the
+piecewise-linear formant warp: eaqhm_modify_prep without the envelope + eaqhm_modify_amp_warp
+next to eaqhm_modify_prep with alpha at the same beta, and eaqhm_noise_warp_map next to eaqhm_noise_warp on the
+workload's residual, with the same windows and margin.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -100,7 +104,7 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False):
+          noise_modulation=False, formant_warp=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -137,7 +141,62 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
         res["noise_formant"] = noise_formant_rows(torch, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     if noise_modulation:
         res["noise_modulation"] = noise_modulation_rows(torch, st, residual)
+    if formant_warp:
+        import eaqhm_amd
+        res["formant_warp"] = formant_warp_rows(torch, st, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     return res
+
+
+def formant_warp_rows(torch, st, nz, reps=20, runs=3):
+    """The piecewise-linear formant warp next to the formant scale, same session, same model.
+    Deterministic rows: eaqhm_modify_prep without the envelope followed by eaqhm_modify_amp_warp (new_ms) against
+    eaqhm_modify_prep with alpha (base_ms) at beta in {1, 1.25}: the VTLN maps 0.85 and 1.2 against alpha = 0.85 and
+    1.2, and a 16-breakpoint map against alpha = 1.2.  Noise rows: eaqhm_noise_warp_map against eaqhm_noise_warp on
+    the model `nz`.  Each time: median of `runs` windows of `reps` launches; margin_ms = max - min of the existing
+    path's windows."""
+    from eaqhm_amd.model import formant_warp_vtln
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, fs = st["n"], st["K"], st["D"], st["fs"]
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    def row(setting, base, new, **more):
+        return dict(setting=setting, base_ms=round(base[0], 4), margin_ms=round(base[1], 4), new_ms=round(new[0], 4),
+                    new_spread_ms=round(new[1], 4), new_minus_base_ms=round(new[0] - base[0], 4),
+                    ratio=round(new[0] / base[0], 4), **more)
+
+    nyq = fs / 2.0
+    x16 = nyq * np.arange(1, 17) / 16.0
+    cases = [("vtln0.85", 0.85) + formant_warp_vtln(fs, 0.85), ("vtln1.2", 1.2) + formant_warp_vtln(fs, 1.2),
+             ("b16", 1.2, x16, x16 * (1.0 + 0.15 * np.sin(np.pi * np.arange(1, 17) / 16.0)))]
+    rows = []
+    for beta in (1.0, 1.25):
+        beta_d = torch.full((n,), beta, dtype=torch.float64, device=dev)
+        for name, alpha, x, y in cases:
+            alpha_d = torch.full((n,), alpha, dtype=torch.float64, device=dev)
+            x_d = torch.as_tensor(x, device=dev)
+            y_d = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(y, (n, len(x)))), device=dev)
+
+            def warp_path():
+                c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, False, amp, R, ph0)
+                c.modify_amp_warp(rec, n, K, fs, beta_d, x_d, y_d, len(x), amp)
+
+            base = med(lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, alpha_d, True, amp, R, ph0))
+            rows.append(row("prep_%s_beta%g" % (name, beta), base, med(warp_path), breakpoints=len(x)))
+    H, p, Nf = nz["hop"], nz["order"], len(nz["sigma"])
+    sigma, refl = (torch.as_tensor(np.ascontiguousarray(v), device=dev) for v in (nz["sigma"], nz["refl"]))
+    sigma_w, refl_w = torch.empty_like(sigma), torch.empty_like(refl)
+    for name, alpha, x, y in cases:
+        alpha_d = torch.full((Nf,), alpha, dtype=torch.float64, device=dev)
+        x_d = torch.as_tensor(x / fs, device=dev)
+        y_d = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(y / fs, (Nf, len(x)))), device=dev)
+        base = med(lambda: c.noise_warp(sigma, refl, Nf, p, alpha_d, sigma_w, refl_w))
+        new = med(lambda: c.noise_warp_map(sigma, refl, Nf, p, x_d, y_d, len(x), sigma_w, refl_w))
+        rows.append(row("noise_%s" % name, base, new, breakpoints=len(x), hop=H, order=p, frames=Nf))
+    return rows
 
 
 def noise_modulation_rows(torch, st, residual, harmonics=2, reps=20, runs=3):
@@ -393,10 +452,12 @@ def main():
     ap.add_argument("--noise-modulation", action="store_true",
                     help="also time the modulation analysis and the modulated noise synthesis")
     ap.add_argument("--shape", action="store_true", help="also time the shape-invariant phase kernels")
+    ap.add_argument("--formant-warp", action="store_true",
+                    help="also time the piecewise-linear formant warp next to the formant scale")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation) for w in a.workloads.split(",")]
+                 a.noise_modulation, a.formant_warp) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
