@@ -14,7 +14,10 @@ starting with # are comments), turned into a per-instant contour with model.scal
 (model.eaQHMNoiseAnalysis) and adds its resynthesis to `<name>_modified.wav`; without any scale flag it
 writes `<name>_resynthesis.wav`: model + noise at unit scales.  --noise-formant (with --noise and a formant scale flag) lets the
 noise's envelope follow the formant scale or warp (eaQHMSynthesis(noise_formant=True)).  --noise-modulation [M]
-(with --noise; M harmonics, default 2) modulates the noise pitch-synchronously (model.eaQHMNoiseModulation)."""
+(with --noise; M harmonics, default 2) modulates the noise pitch-synchronously (model.eaQHMNoiseModulation).
+--cepstral-envelope [P] (with --cepstral-lambda L, default 5e-4) reads the amplitudes of `<name>_modified.wav` off the model's
+own discrete-cepstrum envelope of order P (model.model_cepstrum, DESIGN.md §9.5; P defaults to min(63, 2 + round(fs / 1000)));
+it goes with any scale flag and not with --no-envelope."""
 import argparse
 
 import numpy as np
@@ -73,6 +76,11 @@ def parser():
                          "--formant-vtln): the noise's spectral envelope follows it")
     ap.add_argument("--noise-modulation", type=int, nargs="?", const=2, default=None, metavar="M",
                     help="with --noise: modulate the noise pitch-synchronously, M harmonics of the envelope (2)")
+    ap.add_argument("--cepstral-envelope", type=int, nargs="?", const=0, default=None, metavar="P",
+                    help="also write <name>_modified.wav: amplitudes read off the model's discrete-cepstrum envelope of "
+                         "order P (1 to 63; default min(63, 2 + round(fs / 1000)))")
+    ap.add_argument("--cepstral-lambda", type=float, default=None, metavar="L",
+                    help="with --cepstral-envelope: the regularisation weight, in [1e-6, 1] (5e-4)")
     return ap
 
 
@@ -97,8 +105,18 @@ def main(argv=None):
             _mod_harmonics(a.noise_modulation, "--noise-modulation")
     if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None or warped):
         ap.error("the formant flags move the spectral envelope: not with --no-envelope")
+    cepstral = a.cepstral_envelope is not None
+    if a.cepstral_lambda is not None and not cepstral:
+        ap.error("--cepstral-lambda needs --cepstral-envelope")
+    if cepstral and a.no_envelope:
+        ap.error("--cepstral-envelope supplies the spectral envelope: not with --no-envelope")
+    if cepstral:   # 0: the flag without a value, the default order
+        from .model import _cepstrum_lambda, _cepstrum_order
+        if a.cepstral_envelope != 0:
+            _cepstrum_order(a.cepstral_envelope)
+        _cepstrum_lambda(5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
-                                         a.formant_scale, a.formant_scale_curve)) or warped
+                                         a.formant_scale, a.formant_scale_curve)) or warped or cepstral
     curves = {}
     wmap = None
     if modify:   # reject bad scales and curves before the analysis runs
@@ -150,10 +168,16 @@ def main(argv=None):
                 nz = eaQHMNoiseAnalysis(sig, s_recon, fs)
                 if a.noise_modulation is not None:
                     nz = eaQHMNoiseModulation(sig, s_recon, nz, det, a.noise_modulation)
+            ceps = None
+            if cepstral:
+                from .model import model_cepstrum
+                ceps = model_cepstrum(det, fs, a.cepstral_envelope or None,
+                                      5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
                                    noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
-                                   noise_modulation=a.noise_modulation is not None, formant_warp=wmap)
+                                   noise_modulation=a.noise_modulation is not None, formant_warp=wmap,
+                                   envelope=ceps)
             out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)

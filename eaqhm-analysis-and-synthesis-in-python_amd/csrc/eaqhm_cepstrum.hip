@@ -1,0 +1,280 @@
+// eaqhm_cepstrum.hip — the discrete-cepstrum spectral envelope of an eaQHM model.  gfx950 (MI355X)
+// only, FP64.  Per analysis instant order + 1 coefficients c_p of a smooth log-amplitude envelope
+//   C(w) = c_0 + 2 sum_{p=1..P} c_p cos(p w),   w = 2 pi f / fs,
+// fitted to the instant's partial peaks by regularised least squares (Galas & Rodet 1990; Cappe & Moulines 1996).
+//
+//   eaqhm_model_cepstrum_kernel       one wave per instant: the fit (nodes to LDS, the cosine sums T_d, in-wave Cholesky)
+//   eaqhm_modify_amp_cepstrum_kernel  one wave per instant: the knot amplitudes A' read off a supplied cepstrum
+//   eaqhm_cepstrum_envelope_kernel    one wave per row: the envelope on a frequency grid
+// The last two share cep_read: the read frequency (none, / alpha, or the inverse formant warp of eaqhm_warp.h), the hold
+// outside [0, fs/2] and Clenshaw's recurrence from one cos.
+#include "eaqhm_common.h"
+#include "eaqhm_warp.h"
+
+namespace eaqhm {
+
+#define CEP_WAVES 4
+constexpr int CEP_PMAX = 63;   // order at most: lane r of a wave owns row r of the (order + 1)-square system
+
+// ------------------------------------------------------------------------------------------------
+// The fit.  (M^T M + lambda R) c = M^T v with M[n][0] = 1, M[n][p] = 2 cos(p w_n), R = diag(8 pi^2 p^2).
+// Product-to-sum makes M^T M Toeplitz + Hankel in T_d = sum_n cos(d w_n), d = 0..2P:
+//   G_00 = T_0,  G_p0 = 2 T_p,  G_pq = 2 (T_|p-q| + T_{p+q}),
+// so the nodes are visited (2P + 1) + (P + 1) times, not (P + 1)^2 times.
+// LDS of a wave (doubles): w_n [K], v_n [K], T [2P + 2], then the lower triangle of the factor, P + 1 rows at the odd
+// stride LS = (P + 1) | 1 (lane r reads its own row at r LS + j: 32 consecutive lanes hit 32 different 8-byte banks).
+__host__ __device__ inline int cep_stride(int P) { return (P + 1) | 1; }
+__host__ __device__ inline size_t cep_wave_doubles(int K, int P) {
+  return (size_t)2 * K + (size_t)(2 * P + 2) + (size_t)(P + 1) * cep_stride(P);
+}
+
+// entry (r, q), r >= q, of M^T M + lambda R from the cosine sums
+__device__ inline double cep_gram(const double* T, int r, int q, double lam) {
+  if (q == 0) return r == 0 ? T[0] : 2.0 * T[r];
+  double g = 2.0 * (T[r - q] + T[r + q]);
+  if (r == q) g += lam * ((8.0 * M_PI * M_PI) * (double)(r * r));
+  return g;
+}
+
+// x of the lane `src` (wave-uniform) in every lane
+__device__ inline double cep_lane(double x, int src) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), src);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src);
+  return __hiloint2double(hi, lo);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_model_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs, int P, double lam,
+                                double* __restrict__ ceps) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
+  if (i >= No_ti) return;   // the waves of a block share no data: no block barrier below
+  const int n = P + 1, LS = cep_stride(P);
+  double* sw = lds + (size_t)w * cep_wave_doubles(K, P);
+  double* sv = sw + K;
+  double* T = sv + K;
+  double* A = T + (2 * P + 2);
+  const double* row = records + (size_t)i * (3 * K + 1);
+  double* out = ceps + (size_t)i * n;
+
+  // ---- 1. the nodes: the active slots (am != 0, f > 0) in slot order
+  int nn = 0;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane;
+    const bool act = k < K && row[k] != 0.0 && row[K + k] > 0.0;
+    const unsigned long long m = __ballot(act);
+    if (act) {
+      const int p = nn + __popcll(m & ((1ull << lane) - 1ull));
+      sw[p] = ((2.0 * M_PI) * row[K + k]) / fs;
+      sv[p] = log(row[k]);
+    }
+    nn += __popcll(m);
+  }
+  if (nn == 0) {   // an empty instant: -inf, 0, .., 0
+    if (lane < n) out[lane] = lane == 0 ? -INFINITY : 0.0;
+    return;
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // ---- 2. T_d = sum_n cos(d w_n), d = 0..2P, and b_p = sum_n v_n m_p(w_n), p = 0..P: lanes over d, every lane walks
+  // the nodes (one LDS address for the wave: a broadcast).  Each cosine is taken at d w_n itself, so there is no
+  // phasor to drift.  d <= P <= 63 falls in the first round: b_r ends up in lane r, the owner of row r.
+  double b = 0.0;
+  for (int d = lane; d <= 2 * P; d += 64) {
+    const double dd = (double)d;
+    double t = 0.0, bv = 0.0;
+    for (int q = 0; q < nn; ++q) {
+      const double c = cos(dd * sw[q]);
+      t += c;
+      bv += sv[q] * c;
+    }
+    T[d] = t;
+    if (d <= P) b = d == 0 ? bv : 2.0 * bv;
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // ---- 3. Cholesky G = L L^T, column by column (left-looking): lane r >= j forms G_rj - sum_{k<j} L_rk L_jk from its
+  // own row and row j (a broadcast); the pivot comes from lane j.  A pivot that is not finite or not > 0 ends the fit
+  // with a NaN row.
+  const int r = lane;
+  bool bad = false;
+  for (int j = 0; j < n; ++j) {
+    double s = 0.0;
+    if (r >= j && r < n) {
+      s = cep_gram(T, r, j, lam);
+      for (int k = 0; k < j; ++k) s -= A[r * LS + k] * A[j * LS + k];
+    }
+    const double piv = cep_lane(s, j);
+    if (!(piv > 0.0) || !(piv < INFINITY)) { bad = true; break; }   // wave-uniform
+    const double dj = sqrt(piv);
+    if (r >= j && r < n) A[r * LS + j] = r == j ? dj : s / dj;
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (bad) {
+    if (r < n) out[r] = NAN;
+    return;
+  }
+  // forward: L y = b, column by column; lane j keeps y_j
+  double y = b;
+  for (int j = 0; j < n; ++j) {
+    const double yj = cep_lane(y, j) / A[j * LS + j];
+    if (r == j) y = yj;
+    else if (r > j && r < n) y -= A[r * LS + j] * yj;
+  }
+  // backward: L^T c = y; lane r < j reads L_jr along row j (consecutive addresses)
+  for (int j = n - 1; j >= 0; --j) {
+    const double cj = cep_lane(y, j) / A[j * LS + j];
+    if (r == j) y = cj;
+    else if (r < j) y -= A[j * LS + r] * cj;
+  }
+  if (r < n) out[r] = y;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The readout: C(q) = c_0 + 2 sum_p c_p cos(p wq), wq = 2 pi q^ / fs, q^ = min(max(read(q), 0), fs/2) (held past
+// Nyquist).  read(q) is q, q / alpha or V(q) (mode 0, 1, 2).  Clenshaw from one cos; c_0 is added last, so that the
+// -inf of an empty row stays -inf.  c: the row's P + 1 coefficients (LDS).
+struct CepRead { const double* c; int P; double fs; int mode; double alpha; };
+
+__device__ inline double cep_read(const CepRead& R, const WarpRow& W, double q) {
+  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
+  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double cw2 = 2.0 * cos(((2.0 * M_PI) * x) / R.fs);
+  double b1 = 0.0, b2 = 0.0;
+  for (int p = R.P; p >= 1; --p) {   // one LDS address for the wave: a broadcast
+    const double b0 = R.c[p] + (cw2 * b1 - b2);
+    b2 = b1;
+    b1 = b0;
+  }
+  return 2.0 * (0.5 * cw2 * b1 - b2) + R.c[0];
+}
+
+// LDS of the two readout kernels (doubles): per wave the row's coefficients [CEP_PMAX + 1] and its row of the map
+// [2 x WARP_BMAX], then the block's x [WARP_BMAX].  A block barrier follows the staging; every wave reaches it.
+constexpr int CEP_READ_WAVE = CEP_PMAX + 1 + 2 * WARP_BMAX;
+constexpr size_t CEP_READ_LDS = ((size_t)CEP_WAVES * CEP_READ_WAVE + WARP_BMAX) * sizeof(double);
+
+__device__ inline WarpRow cep_stage(double* lds, int w, int lane, bool live, const double* __restrict__ crow, int P,
+                                    const double* __restrict__ f_in, const double* __restrict__ yrow, int B) {
+  double* c = lds + (size_t)w * CEP_READ_WAVE;
+  double* wy = c + (CEP_PMAX + 1);
+  double* ws = wy + WARP_BMAX;
+  double* wx = lds + (size_t)CEP_WAVES * CEP_READ_WAVE;
+  if (live && lane <= P) c[lane] = crow[lane];
+  bool ident = true;
+  if (B > 0) {
+    warp_stage_x(f_in, B, threadIdx.x, wx);
+    if (live) ident = warp_stage(f_in, yrow, B, lane, wy, ws);
+  }
+  __syncthreads();
+  return WarpRow{wx, wy, ws, B, ident};
+}
+
+// A'[i][k] = exp(C_i(read_i(beta_i f_k))) for an active slot, 0 for an inactive one and where beta_i f_k >= fs/2.
+// There is no unit rule: the envelope is the caller's.  Overwrites the amp of a prep that ran without the envelope.
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_modify_amp_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs,
+                                     const double* __restrict__ betav, const double* __restrict__ ceps, int P,
+                                     const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                     const double* __restrict__ f_out, int B, double* __restrict__ amp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
+  const bool live = i < No_ti;
+  const int il = live ? i : 0;
+  const WarpRow W = cep_stage(lds, w, lane, live, ceps + (size_t)il * (P + 1), P, f_in, f_out + (size_t)il * B, B);
+  if (!live) return;
+  const double beta = betav[i];
+  const CepRead R{lds + (size_t)w * CEP_READ_WAVE, P, fs, B > 0 ? 2 : alphav ? 1 : 0, alphav ? alphav[i] : 1.0};
+  const double* row = records + (size_t)i * (3 * K + 1);
+  for (int k = lane; k < K; k += 64) {
+    const double ak = row[k], fk = row[K + k];
+    double a = 0.0;
+    if (ak != 0.0 && fk > 0.0) {
+      const double bf = beta * fk;   // the output frequency: it alone decides the muting
+      a = exp(cep_read(R, W, bf));
+      if (bf >= 0.5 * fs) a = 0.0;
+    }
+    amp[(size_t)i * K + k] = a;
+  }
+}
+
+// out[i][t] = C_i(read_i(freqs[t])), natural-log amplitude, not muted; -inf on a (-inf, 0, ..) row
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_cepstrum_envelope_kernel(const double* __restrict__ ceps, int n, int P, double fs,
+                                   const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                   const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
+                                   double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per row: scalar
+  const bool live = i < n;
+  const int il = live ? i : 0;
+  const WarpRow W = cep_stage(lds, w, lane, live, ceps + (size_t)il * (P + 1), P, f_in, f_out + (size_t)il * B, B);
+  if (!live) return;
+  const CepRead R{lds + (size_t)w * CEP_READ_WAVE, P, fs, B > 0 ? 2 : alphav ? 1 : 0, alphav ? alphav[i] : 1.0};
+  for (int t = lane; t < F; t += 64) out[(size_t)i * F + t] = cep_read(R, W, freqs[t]);
+}
+}  // namespace eaqhm
+
+using namespace eaqhm;
+
+static bool finite_pos(double x) { return std::isfinite(x) && x > 0.0; }
+static const size_t CEPSTRUM_LDS_MAX = 160 * 1024;
+
+// the optional read-frequency groups: alpha, or the whole warp group (f_in, f_out, B in [1, 16]), or neither
+static bool read_group_ok(const double* alpha, const double* f_in, const double* f_out, int32_t B) {
+  const bool none = !f_in && !f_out && B == 0;
+  const bool whole = f_in && f_out && B >= 1 && B <= WARP_BMAX;
+  return (none || whole) && !(alpha && whole);
+}
+
+extern "C" int eaqhm_model_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                                    int32_t order, double lambda, double* ceps) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !ceps || No_ti < 1 || Kmax <= 0 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: bad argument");
+  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: need 1 <= order <= 63");
+  if (!finite_pos(lambda)) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: lambda must be finite and > 0");
+  const size_t lds = (size_t)CEP_WAVES * cep_wave_doubles(Kmax, order) * sizeof(double);
+  if (lds > CEPSTRUM_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: Kmax too large for the nodes");
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+  hipLaunchKernelGGL(eaqhm_model_cepstrum_kernel, dim3((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)),
+                     dim3(64 * CEP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs, (int)order, lambda, ceps);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_modify_amp_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                                         const double* beta, const double* ceps, int32_t order, const double* alpha,
+                                         const double* f_in, const double* f_out, int32_t B, double* amp) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !beta || !ceps || !amp || No_ti < 4 || Kmax <= 0 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: bad argument");
+  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: need 1 <= order <= 63");
+  if (!read_group_ok(alpha, f_in, f_out, B))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
+  hipLaunchKernelGGL(eaqhm_modify_amp_cepstrum_kernel, dim3((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)),
+                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, records, (int)No_ti, (int)Kmax, fs, beta, ceps,
+                     (int)order, alpha, f_in, f_out, (int)B, amp);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_cepstrum_envelope(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
+                                       const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                       const double* freqs, int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!ceps || !freqs || !out || n < 1 || F < 1 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: bad argument");
+  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: need 1 <= order <= 63");
+  if (!read_group_ok(alpha, f_in, f_out, B))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
+  hipLaunchKernelGGL(eaqhm_cepstrum_envelope_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)),
+                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs, alpha, f_in, f_out,
+                     (int)B, freqs, (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}

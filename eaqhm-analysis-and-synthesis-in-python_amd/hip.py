@@ -50,6 +50,9 @@ SYMBOLS = (
     ("eaqhm_model_envelope_warp", C.c_int, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P]),
     ("eaqhm_noise_warp_map", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P]),
     ("eaqhm_noise_envelope_map", C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P]),
+    ("eaqhm_model_cepstrum", C.c_int, [_P, _P, _I32, _I32, _F64, _I32, _F64, _P]),
+    ("eaqhm_modify_amp_cepstrum", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P, _I32, _P]),
+    ("eaqhm_cepstrum_envelope", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
 )
 
 
@@ -252,6 +255,22 @@ class Context:
     def noise_envelope_map(self, sigma, refl, Nf, order, f_in, f_out, B, fnorm, F, out):
         self._ck(self.lib.eaqhm_noise_envelope_map(self.h, _ptr(sigma), _ptr(refl), Nf, order, _ptr(f_in), _ptr(f_out),
                                                    B, _ptr(fnorm), F, _ptr(out)))
+
+    # the discrete-cepstrum envelope: ceps [rows][order + 1]; warp = (f_in [B], f_out [rows][B], B) excludes alpha [rows]
+    def model_cepstrum(self, records, No_ti, Kmax, fs, order, lam, ceps):
+        self._ck(self.lib.eaqhm_model_cepstrum(self.h, _ptr(records), No_ti, Kmax, float(fs), order, float(lam),
+                                               _ptr(ceps)))
+
+    def modify_amp_cepstrum(self, records, No_ti, Kmax, fs, beta, ceps, order, amp, alpha=None, warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_modify_amp_cepstrum(self.h, _ptr(records), No_ti, Kmax, float(fs), _ptr(beta),
+                                                    _ptr(ceps), order, _ptr(alpha), _ptr(f_in), _ptr(f_out), B,
+                                                    _ptr(amp)))
+
+    def cepstrum_envelope(self, ceps, n, order, fs, freqs, F, out, alpha=None, warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_cepstrum_envelope(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha), _ptr(f_in),
+                                                  _ptr(f_out), B, _ptr(freqs), F, _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

@@ -2,7 +2,11 @@
 
     unpack_model(DetComponents) -> dict(records, step, Kmax, ti, quirk_cells)
     eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
-                   formant_scale=1.0, *, phase="independent", f0=None, formant_warp=None, device_index=0) -> float64[L_out]
+                   formant_scale=1.0, *, phase="independent", f0=None, formant_warp=None, envelope=None,
+                   device_index=0) -> float64[L_out]
+    model_cepstrum(DetComponents, fs, order=None, lam=5e-4, *, device_index=0) -> float64[No_ti, order + 1]
+    cepstrum_envelope(ceps, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0) -> float64[n, len(freqs)]
+    check_envelope_cepstrum(model, envelope, preserve_envelope) -> float64[No_ti, P + 1]
     model_f0(DetComponents, fs) -> float64[No_ti]
     model_envelope(DetComponents, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0)
         -> float64[No_ti, len(freqs)]
@@ -30,7 +34,8 @@ curve instead of by one factor (§9.4, §10.3).  The residual s - s_recon is mod
 filtered white noise under the same time map (§10); its envelope follows a formant scale on request (§10.1).  phase="shape" keeps the phases of the harmonics relative to the
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
 eaqhm_modify_prep, eaqhm_modify_synth, eaqhm_model_envelope, eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp,
-eaqhm_noise_envelope, eaqhm_noise_modulation); there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
+eaqhm_noise_envelope, eaqhm_noise_modulation, eaqhm_model_cepstrum, eaqhm_modify_amp_cepstrum, eaqhm_cepstrum_envelope);
+there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
 (§10.2): eaQHMNoiseModulation adds the Fourier coefficients of the residual's power over the fundamental's phase to the
 noise model, and the synthesis plays that envelope at the output's fundamental.
 """
@@ -438,7 +443,7 @@ def _device_records(model, dev):
 
 def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, preserve_envelope=True,
                    formant_scale=1.0, *, phase="independent", f0=None, noise=None, noise_seed=0, noise_formant=False,
-                   noise_modulation=False, formant_warp=None, device_index=0, _ranges=None):
+                   noise_modulation=False, formant_warp=None, envelope=None, device_index=0, _ranges=None):
     """Synthesises the model at `time_scale` (durations multiplied by it) and `pitch_scale` (every instantaneous
     frequency multiplied by it), both in [0.25, 4].  With `preserve_envelope` the amplitude of a scaled partial is read
     off the instant's log-amplitude envelope at its new frequency (the formants stay put); without it each partial keeps
@@ -488,6 +493,14 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     DetComponents, formant_warp)) (§10.3), bit for bit as if that model were passed as `noise`.  None leaves every
     result as it is.
 
+    `envelope` = C, float64[No_ti, P + 1] with 1 <= P <= 63, supplies the spectral envelope as a discrete cepstrum per
+    analysis instant (§9.5; model_cepstrum fits one, of this model or of another): every partial's amplitude is
+    exp(C_i(q)) with q the frequency the model's own envelope would be read at (pitch_scale * f, divided by the formant
+    scale or taken through W^-1), also at unit scales, since the envelope is the caller's and not the model's.  Entries
+    are finite, except that a whole row may be (-inf, 0, .., 0): an instant without amplitude.  It needs
+    preserve_envelope=True and goes with every scale, contour, formant_warp, phase mode and noise option; the noise
+    options keep following the formant scale or warp and never read C.  None leaves every result as it is.
+
     `_ranges` (tests): a list of (t_lo, t_hi) output ranges computed one after the other into the same buffer.
     Returns float64[L_out]."""
     model = unpack_model(DetComponents)
@@ -500,6 +513,7 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     wmap = None if formant_warp is None else check_formant_warp(model, fs, formant_warp, formant_scale,
                                                                 preserve_envelope)
     shape, f0 = check_phase_arguments(model, phase, f0)
+    ceps = None if envelope is None else check_envelope_cepstrum(model, envelope, preserve_envelope)
     # alpha reaches the prep for a formant contour or a number != 1; without the envelope alpha is 1 throughout
     formant = bool(preserve_envelope) and (_is_contour(formant_scale) or alpha != 1.0)
     if noise is not None:
@@ -533,7 +547,12 @@ def eaQHMSynthesis(DetComponents, fs, length, time_scale=1.0, pitch_scale=1.0, p
     gain_d = dv(tm["gain"]) if contour else None      # without it Delta stays unweighted: the scalar synthesis
     # phase="shape" leaves Delta unweighted on either path: the weight moves to the fundamental's advance S
     beta_d = dv(beta)
-    if wmap is None:
+    if ceps is not None:   # as for the warp: the prep runs without the envelope and the cepstrum kernel writes amp
+        c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None if shape else gain_d, None, False, amp, R, ph0)
+        c.modify_amp_cepstrum(rec, n, K, fs, beta_d, dv(ceps), ceps.shape[1] - 1, amp,
+                              alpha=dv(alpha) if formant else None,
+                              warp=None if wmap is None else (dv(wmap[0]), dv(wmap[1]), len(wmap[0])))
+    elif wmap is None:
         c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None if shape else gain_d, dv(alpha) if formant else None,
                       preserve_envelope, amp, R, ph0)
     else:   # R and ph0 do not depend on the envelope: the prep runs without it and the warp kernel writes amp
@@ -612,6 +631,118 @@ def model_envelope(DetComponents, fs, freqs, formant_scale=1.0, formant_warp=Non
     else:
         x_d, y_d = (torch.as_tensor(v, device=dev) for v in wmap)
         c.model_envelope_warp(rec, n, K, x_d, y_d, len(wmap[0]), f_d, len(f), out)
+    return out.cpu().numpy()
+
+
+# ---- the discrete-cepstrum envelope
+CEPSTRUM_MAX_ORDER = 63          # lane r of a wave owns row r of the (order + 1)-square system
+CEPSTRUM_LAMBDA_RANGE = (1e-6, 1.0)
+
+
+def _cepstrum_order(order):
+    order = _integer(order, "order")
+    if not 1 <= order <= CEPSTRUM_MAX_ORDER:
+        raise ValueError("order must be in [1, %d], got %d" % (CEPSTRUM_MAX_ORDER, order))
+    return order
+
+
+def _cepstrum_lambda(lam):
+    try:
+        lam = float(lam)
+    except (TypeError, ValueError):
+        raise ValueError("lam must be a number") from None
+    if not CEPSTRUM_LAMBDA_RANGE[0] <= lam <= CEPSTRUM_LAMBDA_RANGE[1]:     # also rejects NaN
+        raise ValueError("lam must be in [%g, %g], got %r" % (CEPSTRUM_LAMBDA_RANGE + (lam,)))
+    return lam
+
+
+def check_model_cepstrum_arguments(model, fs, order=None, lam=5e-4):
+    """Validates everything model_cepstrum gets (no device work): returns (fs, order, lam).  order defaults to
+    min(63, 2 + round(fs / 1000)), the LPC order of eaQHMNoiseAnalysis; lam must be in [1e-6, 1]."""
+    fs = _sample_rate(fs)
+    order = min(CEPSTRUM_MAX_ORDER, 2 + int(round(fs / 1000.0))) if order is None else _cepstrum_order(order)
+    lam = _cepstrum_lambda(lam)
+    rec = model["records"]
+    if not np.all(np.isfinite(rec)):
+        raise ValueError("the model holds non-finite values")
+    if np.any(rec[:, :model["Kmax"]] < 0):
+        raise ValueError("amplitudes must be >= 0 (the model holds |a_k|)")
+    return fs, order, lam
+
+
+def model_cepstrum(DetComponents, fs, order=None, lam=5e-4, *, device_index=0):
+    """The discrete cepstrum of every analysis instant: order + 1 coefficients of the smooth
+    log-amplitude envelope C(w) = c_0 + 2 sum_p c_p cos(p w), w = 2 pi f / fs, fitted to the instant's active partials
+    (w_n, ln |a_n|) by least squares with the penalty lam * sum_p 8 pi^2 p^2 c_p^2 (c_0 is free).  An instant with fewer
+    partials than coefficients is fitted like any other; one without any gives the row (-inf, 0, .., 0).  `order`
+    defaults to min(63, 2 + round(fs / 1000)), `lam` lies in [1e-6, 1].  The rows are plain arrays: they can be smoothed
+    over time, blended with another model's, and passed to eaQHMSynthesis(envelope=) and cepstrum_envelope.  Raises
+    numpy.linalg.LinAlgError when the factorisation of an instant broke down.  Returns float64[No_ti, order + 1]."""
+    model = unpack_model(DetComponents)
+    fs, order, lam = check_model_cepstrum_arguments(model, fs, order, lam)
+    torch, c, dev = _device(device_index)
+    rec, n, K = _device_records(model, dev)
+    ceps = torch.empty((n, order + 1), dtype=torch.float64, device=dev)
+    c.model_cepstrum(rec, n, K, fs, order, lam, ceps)
+    out = ceps.cpu().numpy()
+    bad = np.flatnonzero(np.isnan(out).any(axis=1))
+    if len(bad):
+        raise np.linalg.LinAlgError("the cepstral fit of %d instant(s) broke down (the first: %d)" % (len(bad), bad[0]))
+    return out
+
+
+def _cepstrum_rows(ceps, name, rows=None):
+    """A cepstrum as contiguous float64[n, P + 1], validated: 1 <= P <= 63, every entry finite except that a row may be
+    (-inf, 0, .., 0), the empty envelope."""
+    C = np.asarray(ceps)
+    if C.dtype.kind not in "iuf" or C.ndim != 2:
+        raise ValueError("%s must be a 2-D array of numbers, one row of order + 1 coefficients per instant" % name)
+    if rows is not None and C.shape[0] != rows:
+        raise ValueError("%s must have one row per analysis instant (%d), got %d" % (name, rows, C.shape[0]))
+    if C.shape[0] < 1 or not 1 <= C.shape[1] - 1 <= CEPSTRUM_MAX_ORDER:
+        raise ValueError("%s must have at least one row and 2 to %d columns (order 1 to %d), got shape %s"
+                         % (name, CEPSTRUM_MAX_ORDER + 1, CEPSTRUM_MAX_ORDER, C.shape))
+    C = np.ascontiguousarray(C, dtype=np.float64)
+    empty = np.isneginf(C[:, 0]) & np.all(C[:, 1:] == 0, axis=1)
+    if not np.all(np.isfinite(C[~empty])):
+        raise ValueError("%s must be finite; only a whole row may be (-inf, 0, .., 0), the empty envelope" % name)
+    return C
+
+
+def check_envelope_cepstrum(model, envelope, preserve_envelope):
+    """Validates eaQHMSynthesis's `envelope` (no device work): float64[No_ti, P + 1], 1 <= P <= 63, finite except for
+    rows (-inf, 0, .., 0); it needs preserve_envelope=True.  Returns it contiguous."""
+    if not preserve_envelope:
+        raise ValueError("envelope= needs preserve_envelope=True: without it each partial keeps its own amplitude")
+    return _cepstrum_rows(envelope, "envelope", len(model["ti"]))
+
+
+def cepstrum_envelope(ceps, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0):
+    """The envelope a cepstrum describes, on a frequency grid: out[i, t] = C_i(freqs[t] / alpha_i), the
+    natural log of the amplitude, with C_i(q) = c_0 + 2 sum_p c_p cos(2 pi p q^ / fs), q^ = min(max(q, 0), fs/2) (held
+    past Nyquist).  `ceps` is float64[n, P + 1] (model_cepstrum's, or any blend of such); a row (-inf, 0, .., 0) reads
+    -inf.  `formant_scale` = alpha is a number or one value per row, in [0.25, 4]; `formant_warp` = (f_in, f_out) reads
+    C_i(W_i^-1(freqs[t])) instead (f_out [B] or one row per row of `ceps`) and excludes a formant_scale != 1.  It is the
+    envelope eaQHMSynthesis(envelope=ceps) reads at that scale or map.  Returns float64[n, len(freqs)]."""
+    fs = _sample_rate(fs)
+    C = _cepstrum_rows(ceps, "ceps")
+    f = _freq_grid(freqs)
+    n, P = C.shape[0], C.shape[1] - 1
+    alpha = _contour(formant_scale, "formant_scale", n)
+    wmap = None
+    if formant_warp is not None:
+        _warp_excludes_scale(formant_scale)
+        wmap = _warp_rows(formant_warp, n, "row of ceps")
+    torch, c, dev = _device(device_index)
+    C_d, f_d = torch.as_tensor(C, device=dev), torch.as_tensor(np.ascontiguousarray(f), device=dev)
+    out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)
+    if wmap is not None:
+        x_d, y_d = (torch.as_tensor(np.array(v), device=dev) for v in wmap)      # a broadcast row is read-only: a copy
+        c.cepstrum_envelope(C_d, n, P, fs, f_d, len(f), out, warp=(x_d, y_d, len(wmap[0])))
+    elif np.any(alpha != 1.0):
+        c.cepstrum_envelope(C_d, n, P, fs, f_d, len(f), out, alpha=torch.as_tensor(alpha, device=dev))
+    else:
+        c.cepstrum_envelope(C_d, n, P, fs, f_d, len(f), out)
     return out.cpu().numpy()
 
 

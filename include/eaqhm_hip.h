@@ -349,6 +349,38 @@ int eaqhm_noise_envelope_map(eaqhm_ctx* ctx, const double* sigma, const double* 
                              const double* f_in, const double* f_out, int32_t B, const double* fnorm, int32_t F,
                              double* out);
 
+/* the discrete-cepstrum spectral envelope (additions under ABI 6) ----------------------------------------
+ * A smooth log-amplitude envelope per analysis instant, held as order + 1 coefficients:
+ *   C(w) = c_0 + 2 sum_{p=1..order} c_p cos(p w),  w = 2 pi f / fs.
+ *   ceps       double[n][order+1]   c_0..c_order per instant / row; a row (-inf, 0, .., 0) is an empty envelope
+ * eaqhm_model_cepstrum (kernel: one wave per instant, the nodes, the cosine sums and the Cholesky factor in LDS) fits
+ *   instant i to its active slots (am != 0, f > 0; w_n = 2 pi f_n / fs, v_n = ln am_n):
+ *   c = argmin sum_n (v_n - C(w_n))^2 + lambda sum_p 8 pi^2 p^2 c_p^2  (c_0 is not penalised).  With lambda > 0 and
+ *   at least one node the system is positive definite, so an instant with fewer nodes than coefficients is solved like
+ *   any other.  An instant without nodes gives (-inf, 0, .., 0); a pivot that is not finite or not > 0 gives a NaN row.
+ * eaqhm_modify_amp_cepstrum (one wave per instant) overwrites the amp of an eaqhm_modify_prep that ran with
+ *   preserve_envelope = 0 and alpha NULL, on the same stream, with the same beta; eaqhm_modify_synth then runs unchanged:
+ *   amp        double[No_ti][Kmax]  A' = exp(C_i(read_i(beta_i f))) for an active slot, 0 for an inactive one and where
+ *                                   beta_i f >= fs/2.  There is no unit rule: at beta = 1 the amplitudes are C's too.
+ *   read_i(q) is q (alpha NULL, no warp group), q / alpha_i (alpha double[No_ti]) or V_i(q), the inverse of the formant
+ *   warp above (f_in double[B], f_out double[No_ti][B]); C is read at min(max(read_i(q), 0), fs/2): held past Nyquist.
+ * eaqhm_cepstrum_envelope (one wave per row): out[i][t] = C_i(read_i(freqs[t])), natural-log amplitude, not muted;
+ *   -inf on an empty row.  alpha is double[n], f_out double[n][B].
+ * The readout is Clenshaw's recurrence from one cos; c_0 is added last.  The entry points do not read the device arrays:
+ * finite coefficients and a monotone map are the CALLER'S contract (the Python host checks them).
+ * EAQHM_EINVAL for null pointers (alpha and the warp group are optional: NULL, and NULL, NULL, 0), order outside [1, 63],
+ * lambda not finite or not > 0, alpha and the warp group both given, the warp group given in part or B outside [1, 16],
+ * No_ti < 1 (< 4 for eaqhm_modify_amp_cepstrum, as for its siblings), n < 1, F < 1, fs not finite and > 0, Kmax beyond
+ * the LDS budget of the fit (4 waves x (2 Kmax + 2 order + 2 + (order + 1) ((order + 1) | 1)) doubles <= 160 KiB).   */
+int eaqhm_model_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs, int32_t order,
+                         double lambda, double* ceps);
+int eaqhm_modify_amp_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                              const double* beta, const double* ceps, int32_t order, const double* alpha,
+                              const double* f_in, const double* f_out, int32_t B, double* amp);
+int eaqhm_cepstrum_envelope(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
+                            const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                            const double* freqs, int32_t F, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--out FILE]
+                                          [--cepstrum] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -25,7 +25,9 @@ and on the four contour settings, each the median of three
 windows of 20 launches with the max - min of the existing kernel's three (the margin).  --formant-warp adds the
 piecewise-linear formant warp: eaqhm_modify_prep without the envelope + eaqhm_modify_amp_warp
 next to eaqhm_modify_prep with alpha at the same beta, and eaqhm_noise_warp_map next to eaqhm_noise_warp on the
-workload's residual, with the same windows and margin.  EAQHM_LIB selects another build of
+workload's residual, with the same windows and margin.  --cepstrum adds the discrete-cepstrum envelope (DESIGN.md
+§9.5): eaqhm_model_cepstrum at the default order, and eaqhm_modify_prep without the envelope + eaqhm_modify_amp_cepstrum
+next to eaqhm_modify_prep with the envelope at the same beta, with the same windows and margin.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -104,7 +106,7 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False, formant_warp=False):
+          noise_modulation=False, formant_warp=False, cepstrum=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -144,7 +146,51 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
     if formant_warp:
         import eaqhm_amd
         res["formant_warp"] = formant_warp_rows(torch, st, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
+    if cepstrum:
+        res["cepstrum"] = cepstrum_rows(torch, st)
     return res
+
+
+def cepstrum_rows(torch, st, reps=20, runs=3):
+    """The discrete-cepstrum envelope, same session, same model.  fit rows: eaqhm_model_cepstrum at
+    the default order min(63, 2 + round(fs / 1000)) and at 63, lam = 5e-4 (new_ms only: there is no existing
+    counterpart).  prep rows: eaqhm_modify_prep without the envelope followed by eaqhm_modify_amp_cepstrum (new_ms)
+    against eaqhm_modify_prep with the envelope (base_ms) at beta in {1.25, 1} (at beta = 1 the existing path copies the
+    amplitudes), and with alpha = 1.2 on both sides.  Each time: median of `runs` windows of `reps` launches;
+    margin_ms = max - min of the existing path's windows."""
+    c, rec, code, mom, amp, R, ph0 = (st[k] for k in ("c", "rec", "code", "mom", "amp", "R", "ph0"))
+    n, K, D, fs = st["n"], st["K"], st["D"], st["fs"]
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    rows = []
+    P0 = min(63, 2 + int(round(fs / 1000.0)))
+    for P in sorted({P0, 63}):
+        ceps = torch.empty((n, P + 1), dtype=torch.float64, device=dev)
+        t = med(lambda: c.model_cepstrum(rec, n, K, fs, P, 5e-4, ceps))
+        rows.append(dict(setting="fit_P%d" % P, new_ms=round(t[0], 4), new_spread_ms=round(t[1], 4), order=P,
+                         instants=n, us_per_instant=round(1e3 * t[0] / n, 5),
+                         nan_rows=int(torch.isnan(ceps).any(dim=1).sum().item())))
+    ceps = torch.empty((n, P0 + 1), dtype=torch.float64, device=dev)
+    c.model_cepstrum(rec, n, K, fs, P0, 5e-4, ceps)
+    for beta, alpha in ((1.25, None), (1.0, None), (1.25, 1.2)):
+        beta_d = torch.full((n,), beta, dtype=torch.float64, device=dev)
+        alpha_d = None if alpha is None else torch.full((n,), alpha, dtype=torch.float64, device=dev)
+
+        def cepstrum_path():
+            c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, None, False, amp, R, ph0)
+            c.modify_amp_cepstrum(rec, n, K, fs, beta_d, ceps, P0, amp, alpha=alpha_d)
+
+        base = med(lambda: c.modify_prep(rec, code, mom, n, K, D, fs, beta_d, None, alpha_d, True, amp, R, ph0))
+        new = med(cepstrum_path)
+        rows.append(dict(setting="prep_beta%g%s" % (beta, "" if alpha is None else "_alpha%g" % alpha),
+                         base_ms=round(base[0], 4), margin_ms=round(base[1], 4), new_ms=round(new[0], 4),
+                         new_spread_ms=round(new[1], 4), new_minus_base_ms=round(new[0] - base[0], 4),
+                         ratio=round(new[0] / base[0], 4), order=P0))
+    return rows
 
 
 def formant_warp_rows(torch, st, nz, reps=20, runs=3):
@@ -454,10 +500,12 @@ def main():
     ap.add_argument("--shape", action="store_true", help="also time the shape-invariant phase kernels")
     ap.add_argument("--formant-warp", action="store_true",
                     help="also time the piecewise-linear formant warp next to the formant scale")
+    ap.add_argument("--cepstrum", action="store_true",
+                    help="also time the cepstral fit and the amplitudes read off it against the prep with the envelope")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation, a.formant_warp) for w in a.workloads.split(",")]
+                 a.noise_modulation, a.formant_warp, a.cepstrum) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
