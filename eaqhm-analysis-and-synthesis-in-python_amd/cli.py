@@ -17,7 +17,12 @@ noise's envelope follow the formant scale or warp (eaQHMSynthesis(noise_formant=
 (with --noise; M harmonics, default 2) modulates the noise pitch-synchronously (model.eaQHMNoiseModulation).
 --cepstral-envelope [P] (with --cepstral-lambda L, default 5e-4) reads the amplitudes of `<name>_modified.wav` off the model's
 own discrete-cepstrum envelope of order P (model.model_cepstrum, DESIGN.md §9.5; P defaults to min(63, 2 + round(fs / 1000)));
-it goes with any scale flag and not with --no-envelope."""
+it goes with any scale flag and not with --no-envelope.  --envelope-from OTHER.wav analyses OTHER with the same options, fits
+both cepstra (order and lambda of --cepstral-envelope / --cepstral-lambda, or their defaults), aligns the two in time
+(model.model_align) and reads the amplitudes of `<name>_modified.wav` off OTHER's envelope at the aligned
+instants; --timing-from OTHER.wav gives the output OTHER's local tempo instead of a --time-scale
+(model.alignment_time_scale).  --align-band SECONDS (2.0) is the half-width of the alignment band, raised to the least
+that admits a path."""
 import argparse
 
 import numpy as np
@@ -45,6 +50,8 @@ def parser():
     ts.add_argument("--time-scale", type=float, default=None, help="also write <name>_modified.wav: durations x R")
     ts.add_argument("--time-scale-curve", default=None, metavar="FILE",
                     help="like --time-scale, with a curve: lines 'seconds value' (# comments)")
+    ts.add_argument("--timing-from", default=None, metavar="OTHER.wav",
+                    help="also write <name>_modified.wav: the local tempo of OTHER.wav, aligned in time to this file")
     ps = ap.add_mutually_exclusive_group()
     ps.add_argument("--pitch-scale", type=float, default=None, help="also write <name>_modified.wav: pitch x B")
     ps.add_argument("--pitch-scale-curve", default=None, metavar="FILE",
@@ -81,6 +88,11 @@ def parser():
                          "order P (1 to 63; default min(63, 2 + round(fs / 1000)))")
     ap.add_argument("--cepstral-lambda", type=float, default=None, metavar="L",
                     help="with --cepstral-envelope: the regularisation weight, in [1e-6, 1] (5e-4)")
+    ap.add_argument("--envelope-from", default=None, metavar="OTHER.wav",
+                    help="also write <name>_modified.wav: amplitudes read off the cepstral envelope of OTHER.wav, aligned "
+                         "in time to this file (order and lambda: --cepstral-envelope, --cepstral-lambda)")
+    ap.add_argument("--align-band", type=float, default=None, metavar="SECONDS",
+                    help="with --envelope-from / --timing-from: half-width of the alignment band (2.0)")
     return ap
 
 
@@ -106,17 +118,24 @@ def main(argv=None):
     if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None or warped):
         ap.error("the formant flags move the spectral envelope: not with --no-envelope")
     cepstral = a.cepstral_envelope is not None
+    aligned = a.envelope_from is not None or a.timing_from is not None
     if a.cepstral_lambda is not None and not cepstral:
         ap.error("--cepstral-lambda needs --cepstral-envelope")
     if cepstral and a.no_envelope:
         ap.error("--cepstral-envelope supplies the spectral envelope: not with --no-envelope")
+    if a.envelope_from is not None and a.no_envelope:
+        ap.error("--envelope-from supplies the spectral envelope: not with --no-envelope")
+    if a.align_band is not None and not aligned:
+        ap.error("--align-band needs --envelope-from or --timing-from")
+    if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
+        ap.error("--align-band must be finite and >= 0")
     if cepstral:   # 0: the flag without a value, the default order
         from .model import _cepstrum_lambda, _cepstrum_order
         if a.cepstral_envelope != 0:
             _cepstrum_order(a.cepstral_envelope)
         _cepstrum_lambda(5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
-                                         a.formant_scale, a.formant_scale_curve)) or warped or cepstral
+                                         a.formant_scale, a.formant_scale_curve)) or warped or cepstral or aligned
     curves = {}
     wmap = None
     if modify:   # reject bad scales and curves before the analysis runs
@@ -137,11 +156,11 @@ def main(argv=None):
     if "," in gender:
         lo, hi = gender.split(",")
         gender = (float(lo), float(hi))
-    s_recon, srer, det, t = eaQHMAnalysisAndSynthesis(
-        a.wav, gender, step=a.step, maxAdpt=a.max_adpt, pitchPeriods=a.pitch_periods,
-        analysisWindow=a.analysis_window, fullWaveform=not a.voiced_only, fc=a.fc, partials=a.partials,
-        printPrompts=True, loadingScreen=False,
-        track_budget_bytes=int(a.track_budget_mb * 2 ** 20) if a.track_budget_mb > 0 else "auto")
+    analysis_options = dict(step=a.step, maxAdpt=a.max_adpt, pitchPeriods=a.pitch_periods,
+                            analysisWindow=a.analysis_window, fullWaveform=not a.voiced_only, fc=a.fc,
+                            partials=a.partials, printPrompts=True, loadingScreen=False,
+                            track_budget_bytes=int(a.track_budget_mb * 2 ** 20) if a.track_budget_mb > 0 else "auto")
+    s_recon, srer, det, t = eaQHMAnalysisAndSynthesis(a.wav, gender, **analysis_options)
     if not a.no_write:
         fs, _ = wavfile.read(a.wav)
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
@@ -169,10 +188,24 @@ def main(argv=None):
                 if a.noise_modulation is not None:
                     nz = eaQHMNoiseModulation(sig, s_recon, nz, det, a.noise_modulation)
             ceps = None
-            if cepstral:
+            if cepstral or aligned:
                 from .model import model_cepstrum
-                ceps = model_cepstrum(det, fs, a.cepstral_envelope or None,
-                                      5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
+                order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
+                ceps = model_cepstrum(det, fs, order, lam)
+            if aligned:
+                from .model import alignment_index, alignment_time_scale, warp_rows
+                others = {}
+                for path in (a.envelope_from, a.timing_from):
+                    if path is not None and path not in others:
+                        others[path] = align_other(path, gender, analysis_options, fs, ceps, order, lam,
+                                                   2.0 if a.align_band is None else a.align_band)
+                if a.timing_from is not None:
+                    rho = alignment_time_scale(others[a.timing_from][1], len(ceps))
+                if a.envelope_from is not None:
+                    C_other, pairs = others[a.envelope_from]
+                    ceps = warp_rows(C_other, alignment_index(pairs, len(ceps)))
+                elif not cepstral:
+                    ceps = None
             s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
                                    preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
                                    noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
@@ -182,6 +215,20 @@ def main(argv=None):
             wavfile.write(out, fs, np.float32(s_mod))
             print("wrote", out)
     return 0
+
+
+def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s):
+    """Analyses `path` with the same options, fits its cepstrum and aligns it to `ceps`: (its cepstrum, the path)."""
+    from .model import band_min_radius, model_align, model_cepstrum, unpack_model
+    fs_o, _ = wavfile.read(path)
+    if fs_o != fs:
+        raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (path, fs_o, fs))
+    det_o = eaQHMAnalysisAndSynthesis(path, gender, **analysis_options)[2]
+    C_o = model_cepstrum(det_o, fs, order, lam)
+    r = max(int(round(band_s * fs / unpack_model(det_o)["step"])), band_min_radius(len(ceps), len(C_o)))
+    pairs, cost = model_align(ceps, C_o, band=r)
+    print("aligned %s: %d pairs, cost %g" % (path, len(pairs), cost))
+    return C_o, pairs
 
 
 def _two_columns(path, name, what):

@@ -76,6 +76,10 @@ extern "C" int eaqhm_set_option(eaqhm_ctx* ctx, int32_t key, int32_t value) {
       (void)hipMemsetAsync((char*)ctx->scratch + ctx->scratch_bytes - 256 + 64, 0, 128, ctx->stream);
     return EAQHM_OK;
   }
+  if (key == EAQHM_OPT_DTW_PHASES && value >= 0 && value <= 2) {
+    ctx->dtw_phases = value;
+    return EAQHM_OK;
+  }
   return ctx->fail(EAQHM_EINVAL, "eaqhm_set_option: unknown key or value");
 }
 

@@ -18,6 +18,7 @@ struct eaqhm_ctx {
   int clock_khz = 0;
   int ls_variant = 3;  // 2: MFMA Gramian + tile Cholesky through memory (any size), 3: all-on-chip tiles (+2 for big frames)
   int dbg_keep = 0;    // 1: in-kernel phase stamps on, accumulated across launches (diagnostics only)
+  int dtw_phases = 0;  // 1: eaqhm_dtw runs the forward pass only, 2: the backtrack only (measurements), 0: both
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
   int* faults = nullptr;   // device counters: [0] LS systems whose Cholesky broke down (singular normal matrix),

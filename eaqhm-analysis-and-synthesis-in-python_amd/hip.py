@@ -53,6 +53,8 @@ SYMBOLS = (
     ("eaqhm_model_cepstrum", C.c_int, [_P, _P, _I32, _I32, _F64, _I32, _F64, _P]),
     ("eaqhm_modify_amp_cepstrum", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P, _I32, _P]),
     ("eaqhm_cepstrum_envelope", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
+    ("eaqhm_cepstrum_cost", C.c_int, [_P, _P, _I32, _P, _I32, _I32, _F64, _F64, _I32, _P]),
+    ("eaqhm_dtw", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
 )
 
 
@@ -271,6 +273,16 @@ class Context:
         f_in, f_out, B = warp or (None, None, 0)
         self._ck(self.lib.eaqhm_cepstrum_envelope(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha), _ptr(f_in),
                                                   _ptr(f_out), B, _ptr(freqs), F, _ptr(out)))
+
+    # the time alignment: band [nA][2 r + 1], cell (i, j) at [i][j - c_i + r] (include/eaqhm_hip.h)
+    def cepstrum_cost(self, cepsA, nA, cepsB, nB, order, c0_weight, empty_cost, r, band_out):
+        self._ck(self.lib.eaqhm_cepstrum_cost(self.h, _ptr(cepsA), nA, _ptr(cepsB), nB, order, float(c0_weight),
+                                              float(empty_cost), r, _ptr(band_out)))
+
+    def dtw(self, band, nA, nB, r, ptr, path, path_len, total):
+        """band holds the costs on entry and D on return; path int32[nA + nB - 1, 2], path_len int32[1], total
+        float64[1] are device tensors."""
+        self._ck(self.lib.eaqhm_dtw(self.h, _ptr(band), nA, nB, r, _ptr(ptr), _ptr(path), _ptr(path_len), _ptr(total)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

@@ -59,6 +59,8 @@ const char* eaqhm_last_error(eaqhm_ctx* ctx);
  *                             large-frame kernel for the rest (default) */
 #define EAQHM_OPT_LS_VARIANT 1
 #define EAQHM_OPT_DEBUG_KEEP 2   /* 1: accumulate the in-kernel phase stamps across launches; 2: also time diag_D */
+#define EAQHM_OPT_DTW_PHASES 3   /* measurements: 1 = eaqhm_dtw launches its forward pass only, 2 = its backtrack only
+                                    (on a band that holds D and a ptr that is filled), 0 = both (default) */
 int eaqhm_set_option(eaqhm_ctx* ctx, int32_t key, int32_t value);
 /* diagnostics: shader-clock cycles per phase of the LS tile kernel summed over frames (thread 0 of each
  * workgroup): {setup, basis build, contraction, factorisation total..., see csrc/eaqhm_ls_tile.hip STAMP} */
@@ -380,6 +382,40 @@ int eaqhm_modify_amp_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_
 int eaqhm_cepstrum_envelope(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
                             const double* alpha, const double* f_in, const double* f_out, int32_t B,
                             const double* freqs, int32_t F, double* out);
+
+/* time alignment of two models: banded DTW over cepstral rows (additions under ABI 6) ------------------
+ * The table has nA x nB cells, cell (i, j) pairing row i of A with row j of B.  THE BAND: half-width r rows of B around
+ * the scaled diagonal, centre c_i = (2 i (nB-1) + (nA-1)) / (2 (nA-1)) in 64-bit integer division (c_0 = 0 when nA = 1);
+ * cell (i, j) is in the band iff |j - c_i| <= r and 0 <= j < nB.
+ *   band       double[nA][W], W = 2 r + 1   cell (i, j) at [i][j - c_i + r]; cells outside the table hold +inf
+ *   ptr        uint8[nA][W]                 back-pointer per cell, same layout: 0 from (i-1, j-1), 1 from (i-1, j),
+ *                                           2 from (i, j-1), 3 the start (0, 0); written only inside the table
+ *   path       int32[(nA + nB - 1)][2]      8-byte aligned; on return the first *path_len pairs (i, j), from (0, 0) to
+ *                                           (nA-1, nB-1)
+ *   path_len   int32[1], total double[1]    device memory: the path's length (-1: the walk failed), D(nA-1, nB-1)
+ * r must admit a path: r >= nB - 1 when nA = 1, else r >= ceil((nB - 1) / (nA - 1)); r = max(nA, nB) - 1 is the full
+ * table.
+ * eaqhm_cepstrum_cost fills the whole band with the local cost between cepsA double[nA][order+1] and cepsB
+ *   double[nB][order+1] (the layout of eaqhm_model_cepstrum), dC = cepsA[i] - cepsB[j]:
+ *   d(i, j) = c0_weight dC_0^2 + 2 sum_{p=1..order} dC_p^2  (at c0_weight = 1 the mean over frequency of the squared
+ *   difference of the two log envelopes, neper^2), the differences formed directly; a row whose c_0 is -inf is empty:
+ *   d = 0 between two empty rows, empty_cost between an empty row and another.  Cells outside the table get +inf.
+ *   (Kernel: a block keeps 16 rows of A in LDS and streams the B rows of its band through LDS, 64 at a time.)
+ * eaqhm_dtw runs on any band of finite costs >= 0 (+inf outside the table), in place: band holds d on entry and
+ *   D(0,0) = d(0,0), D(i,j) = d(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)) on return, predecessors outside the table or
+ *   the band counting +inf; on equal values the lower code wins (a candidate replaces the current one only when strictly
+ *   smaller), so D, ptr and the path are fully determined.  Forward pass: one wave per 64 x 64 tile of the table, one
+ *   launch per tile anti-diagonal on the context's stream (ceil(nA/64) + ceil(nB/64) - 1 at most; only the tiles that
+ *   meet the band are launched); the order between dependent tiles is stream order, no workgroup waits on another.
+ *   Then one launch walks the back-pointers (a single lane, at most nA + nB - 1 steps).
+ * The entry points do not read the device arrays: finite costs >= 0 and (-inf, 0, .., 0) as the only non-finite rows
+ * are the CALLER'S contract (the Python host checks them).
+ * EAQHM_EINVAL for null pointers, order outside [1, 63], c0_weight or empty_cost not finite or < 0, nA or nB outside
+ * [1, 2^30], r < 0, r >= 2^30, or r too small to admit a path.                                                       */
+int eaqhm_cepstrum_cost(eaqhm_ctx* ctx, const double* cepsA, int32_t nA, const double* cepsB, int32_t nB, int32_t order,
+                        double c0_weight, double empty_cost, int32_t r, double* band_out);
+int eaqhm_dtw(eaqhm_ctx* ctx, double* band, int32_t nA, int32_t nB, int32_t r, uint8_t* ptr, int32_t* path,
+              int32_t* path_len, double* total);
 
 #ifdef __cplusplus
 }

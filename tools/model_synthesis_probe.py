@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--out FILE]
+                                          [--cepstrum] [--align] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -27,7 +27,11 @@ piecewise-linear formant warp: eaqhm_modify_prep witho
 next to eaqhm_modify_prep with alpha at the same beta, and eaqhm_noise_warp_map next to eaqhm_noise_warp on the
 workload's residual, with the same windows and margin.  --cepstrum adds the discrete-cepstrum envelope (DESIGN.md
 §9.5): eaqhm_model_cepstrum at the default order, and eaqhm_modify_prep without the envelope + eaqhm_modify_amp_cepstrum
-next to eaqhm_modify_prep with the envelope at the same beta, with the same windows and margin.  EAQHM_LIB selects another build of
+next to eaqhm_modify_prep with the envelope at the same beta, with the same windows and margin.  --align adds the time
+alignment: the model's cepstrum against a copy of itself stretched by warp_rows with a sinusoidal tempo
+0.8-1.25, band 2 s: eaqhm_cepstrum_cost, and eaqhm_dtw's forward pass (with its launch count) and backtrack apart
+(EAQHM_OPT_DTW_PHASES), each the median of three windows with their max - min, and the NumPy model's time for the same
+band on a 5 s excerpt on the host.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -106,7 +110,7 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False, formant_warp=False, cepstrum=False):
+          noise_modulation=False, formant_warp=False, cepstrum=False, align=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -148,7 +152,78 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
         res["formant_warp"] = formant_warp_rows(torch, st, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     if cepstrum:
         res["cepstrum"] = cepstrum_rows(torch, st)
+    if align:
+        res["align"] = align_rows(torch, st)
     return res
+
+
+def align_rows(torch, st, band_s=2.0, excerpt_s=5.0, runs=3):
+    """The time alignment of the model's cepstrum (default order) against a copy of itself stretched
+    by warp_rows with a 0.25 Hz sinusoidal tempo between 0.8 and 1.25, band `band_s` seconds.  One launch sequence per
+    window (the forward pass is thousands of launches), median of `runs` windows and their max - min: the cost kernel,
+    eaqhm_dtw's forward pass and its backtrack (EAQHM_OPT_DTW_PHASES).  numpy_model_s: tests/model_align_ref.py on the
+    first `excerpt_s` seconds with the same band, on the host."""
+    from eaqhm_amd.model import band_min_radius, warp_rows
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import model_align_ref as AR
+    c, rec, n, K, D, fs = (st[k] for k in ("c", "rec", "n", "K", "D", "fs"))
+    dev = c.device
+    P = min(63, 2 + int(round(fs / 1000.0)))
+    ceps = torch.empty((n, P + 1), dtype=torch.float64, device=dev)
+    c.model_cepstrum(rec, n, K, fs, P, 5e-4, ceps)
+    CA = ceps.cpu().numpy()
+    tempo = np.exp(np.log(1.25 / 0.8) / 2 * np.sin(2 * np.pi * 0.25 * np.arange(2 * n) * D / fs))   # 0.8 .. 1.25
+    idx = np.concatenate(([0.0], np.cumsum(1.0 / tempo)))
+    CB = warp_rows(CA, idx[idx <= n - 1])
+    nA, nB = len(CA), len(CB)
+    r = max(int(band_s * fs / D), band_min_radius(nA, nB))
+    W = 2 * r + 1
+    A_d, B_d = torch.as_tensor(CA, device=dev), torch.as_tensor(CB, device=dev)
+    band = torch.empty((nA, W), dtype=torch.float64, device=dev)
+    ptr = torch.empty((nA, W), dtype=torch.uint8, device=dev)
+    path = torch.empty((nA + nB - 1, 2), dtype=torch.int32, device=dev)
+    plen = torch.zeros(1, dtype=torch.int32, device=dev)
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def med(fn, before=None):
+        ts = []
+        for _ in range(runs + 1):              # the first window warms
+            if before:
+                before()
+            torch.cuda.synchronize()
+            ts.append(timed_once(torch, fn))
+        ts = sorted(ts[1:])
+        return round(ts[len(ts) // 2], 3), round(ts[-1] - ts[0], 3)
+
+    cost = lambda: c.cepstrum_cost(A_d, nA, B_d, nB, P, 0.0, 4.0, r, band)
+    t_cost = med(cost)
+    c.set_option(3, 1)
+    t_fwd = med(lambda: c.dtw(band, nA, nB, r, ptr, path, plen, total), before=cost)
+    c.set_option(3, 2)
+    t_back = med(lambda: c.dtw(band, nA, nB, r, ptr, path, plen, total))
+    c.set_option(3, 0)
+    L = int(plen.item())
+    m = min(nA, int(excerpt_s * fs / D))
+    mb = int(np.searchsorted(idx, m))
+    t = time.perf_counter()
+    dense = AR.cost(CA[:m], CB[:mb])
+    re = max(min(r, AR.full_radius(m, mb)), AR.min_radius(m, mb))
+    AR.align(dense, re)
+    t_np = time.perf_counter() - t
+    return dict(order=P, nA=nA, nB=nB, band_s=band_s, r=r, cells=nA * W, cost_ms=t_cost[0], cost_spread_ms=t_cost[1],
+                forward_ms=t_fwd[0], forward_spread_ms=t_fwd[1],
+                forward_launches_at_most=(nA + 63) // 64 + (nB + 63) // 64 - 1, backtrack_ms=t_back[0],
+                backtrack_spread_ms=t_back[1], path_len=L, total=float(total.item()),
+                numpy_model_s=round(t_np, 2), numpy_model_rows=(m, mb), numpy_model_r=re)
+
+
+def timed_once(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
 
 
 def cepstrum_rows(torch, st, reps=20, runs=3):
@@ -502,10 +577,12 @@ def main():
                     help="also time the piecewise-linear formant warp next to the formant scale")
     ap.add_argument("--cepstrum", action="store_true",
                     help="also time the cepstral fit and the amplitudes read off it against the prep with the envelope")
+    ap.add_argument("--align", action="store_true",
+                    help="also time the alignment kernels on the model against a time-stretched copy of itself")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation, a.formant_warp, a.cepstrum) for w in a.workloads.split(",")]
+                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
