@@ -22,7 +22,10 @@ both cepstra (order and lambda of --cepstral-envelope / --cepstral-lambda, or th
 (model.model_align) and reads the amplitudes of `<name>_modified.wav` off OTHER's envelope at the aligned
 instants; --timing-from OTHER.wav gives the output OTHER's local tempo instead of a --time-scale
 (model.alignment_time_scale).  --align-band SECONDS (2.0) is the half-width of the alignment band, raised to the least
-that admits a path."""
+that admits a path.  --from-parameters [P] reduces the analysed model to f0, voicing and a cepstrum of order P
+(model.model_parameters; lambda from --cepstral-lambda), rebuilds a harmonic model from those arrays alone with the
+envelope's minimum-phase response as its phases (model.model_from_parameters) and writes its synthesis, under
+whatever scale, formant, phase and noise flags are given, as `<name>_vocoded.wav`; not with --no-envelope."""
 import argparse
 
 import numpy as np
@@ -91,6 +94,9 @@ def parser():
     ap.add_argument("--envelope-from", default=None, metavar="OTHER.wav",
                     help="also write <name>_modified.wav: amplitudes read off the cepstral envelope of OTHER.wav, aligned "
                          "in time to this file (order and lambda: --cepstral-envelope, --cepstral-lambda)")
+    ap.add_argument("--from-parameters", type=int, nargs="?", const=0, default=None, metavar="P",
+                    help="also write <name>_vocoded.wav: the model rebuilt from its f0, voicing and cepstrum of order P "
+                         "(1 to 63; default min(63, 2 + round(fs / 1000))), with minimum-phase harmonics")
     ap.add_argument("--align-band", type=float, default=None, metavar="SECONDS",
                     help="with --envelope-from / --timing-from: half-width of the alignment band (2.0)")
     return ap
@@ -119,8 +125,11 @@ def main(argv=None):
         ap.error("the formant flags move the spectral envelope: not with --no-envelope")
     cepstral = a.cepstral_envelope is not None
     aligned = a.envelope_from is not None or a.timing_from is not None
-    if a.cepstral_lambda is not None and not cepstral:
-        ap.error("--cepstral-lambda needs --cepstral-envelope")
+    vocode = a.from_parameters is not None
+    if a.cepstral_lambda is not None and not (cepstral or vocode):
+        ap.error("--cepstral-lambda needs --cepstral-envelope or --from-parameters")
+    if vocode and a.no_envelope:
+        ap.error("--from-parameters builds the model from its spectral envelope: not with --no-envelope")
     if cepstral and a.no_envelope:
         ap.error("--cepstral-envelope supplies the spectral envelope: not with --no-envelope")
     if a.envelope_from is not None and a.no_envelope:
@@ -129,16 +138,17 @@ def main(argv=None):
         ap.error("--align-band needs --envelope-from or --timing-from")
     if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
         ap.error("--align-band must be finite and >= 0")
-    if cepstral:   # 0: the flag without a value, the default order
+    if cepstral or vocode:   # 0: the flag without a value, the default order
         from .model import _cepstrum_lambda, _cepstrum_order
-        if a.cepstral_envelope != 0:
-            _cepstrum_order(a.cepstral_envelope)
+        for order in (a.cepstral_envelope, a.from_parameters):
+            if order:
+                _cepstrum_order(order)
         _cepstrum_lambda(5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
                                          a.formant_scale, a.formant_scale_curve)) or warped or cepstral or aligned
     curves = {}
     wmap = None
-    if modify:   # reject bad scales and curves before the analysis runs
+    if modify or vocode:   # reject bad scales and curves before the analysis runs
         from .model import _scale
         _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
         _scale(1.0 if a.pitch_scale is None else a.pitch_scale, "--pitch-scale")
@@ -166,7 +176,7 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
-        if modify or a.noise:
+        if modify or a.noise or vocode:
             from .model import eaQHMNoiseAnalysis, eaQHMNoiseModulation, eaQHMSynthesis, scale_contour
             rho = 1.0 if a.time_scale is None else a.time_scale
             beta = 1.0 if a.pitch_scale is None else a.pitch_scale
@@ -206,14 +216,23 @@ def main(argv=None):
                     ceps = warp_rows(C_other, alignment_index(pairs, len(ceps)))
                 elif not cepstral:
                     ceps = None
-            s_mod = eaQHMSynthesis(det, fs, len(s_recon), time_scale=rho, pitch_scale=beta,
-                                   preserve_envelope=not a.no_envelope, formant_scale=alpha, phase=a.phase,
-                                   noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
-                                   noise_modulation=a.noise_modulation is not None, formant_warp=wmap,
-                                   envelope=ceps)
-            out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
-            wavfile.write(out, fs, np.float32(s_mod))
-            print("wrote", out)
+            common = dict(time_scale=rho, pitch_scale=beta, preserve_envelope=not a.no_envelope, formant_scale=alpha,
+                          phase=a.phase, noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
+                          noise_modulation=a.noise_modulation is not None, formant_warp=wmap)
+            if modify or a.noise:
+                s_mod = eaQHMSynthesis(det, fs, len(s_recon), envelope=ceps, **common)
+                out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
+                wavfile.write(out, fs, np.float32(s_mod))
+                print("wrote", out)
+            if vocode:   # the model reduced to arrays and rebuilt from them alone
+                from .model import model_from_parameters, model_parameters
+                p = model_parameters(det, fs, a.from_parameters or None,
+                                     5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
+                built = model_from_parameters(p["f0"], p["ceps"], p["fs"], p["step"], voiced=p["voiced"])
+                s_voc = eaQHMSynthesis(built, fs, len(s_recon), **common)
+                out = a.wav[:len(a.wav) - 4] + "_vocoded.wav"
+                wavfile.write(out, fs, np.float32(s_voc))
+                print("wrote", out)
     return 0
 
 

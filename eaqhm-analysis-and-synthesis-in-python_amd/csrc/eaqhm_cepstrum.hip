@@ -6,8 +6,10 @@
 //   eaqhm_model_cepstrum_kernel       one wave per instant: the fit (nodes to LDS, the cosine sums T_d, in-wave Cholesky)
 //   eaqhm_modify_amp_cepstrum_kernel  one wave per instant: the knot amplitudes A' read off a supplied cepstrum
 //   eaqhm_cepstrum_envelope_kernel    one wave per row: the envelope on a frequency grid
-// The last two share cep_read: the read frequency (none, / alpha, or the inverse formant warp of eaqhm_warp.h), the hold
-// outside [0, fs/2] and Clenshaw's recurrence from one cos.
+//   eaqhm_cepstrum_phase_kernel       its sibling: the minimum-phase response Phi of the envelope on the grid (§9.7)
+//   eaqhm_model_build_kernel          one wave per instant: the records of a harmonic model from f0 and a cepstrum (§9.7)
+// The readouts share cep_read: the read frequency (none, / alpha, or the inverse formant warp of eaqhm_warp.h), the hold
+// outside [0, fs/2] and Clenshaw's recurrence from one cos; cep_recur gives the kernels of §9.7 the sine sum as well.
 #include "eaqhm_common.h"
 #include "eaqhm_warp.h"
 
@@ -150,6 +152,30 @@ __device__ inline double cep_read(const CepRead& R, const WarpRow& W, double q) 
   return 2.0 * (0.5 * cw2 * b1 - b2) + R.c[0];
 }
 
+// The same recurrence for the kernels of §9.7, which need the sine sum too: from cw2 = 2 cos(t) it leaves b_1, b_2 with
+//   sum_p c_p cos(p t) = b_1 cos(t) - b_2   and   sum_p c_p sin(p t) = b_1 sin(t).
+// (A helper of its own: cep_read above stays as it is, and with it the code of the kernels that use it.)
+__device__ inline void cep_recur(const double* c, int P, double cw2, double& b1, double& b2) {
+  b1 = 0.0;
+  b2 = 0.0;
+  for (int p = P; p >= 1; --p) {   // one LDS address for the wave: a broadcast
+    const double b0 = c[p] + (cw2 * b1 - b2);
+    b2 = b1;
+    b1 = b0;
+  }
+}
+
+// Phi(q) = -2 sum_p c_p sin(p wq) at the read frequency of cep_read: the minimum-phase response of the envelope; an
+// empty row (every c_p = 0) reads 0.
+__device__ inline double cep_read_phase(const CepRead& R, const WarpRow& W, double q) {
+  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
+  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  double sn, cs, b1, b2;
+  sincos(((2.0 * M_PI) * x) / R.fs, &sn, &cs);
+  cep_recur(R.c, R.P, 2.0 * cs, b1, b2);
+  return -2.0 * (b1 * sn);
+}
+
 // LDS of the two readout kernels (doubles): per wave the row's coefficients [CEP_PMAX + 1] and its row of the map
 // [2 x WARP_BMAX], then the block's x [WARP_BMAX].  A block barrier follows the staging; every wave reaches it.
 constexpr int CEP_READ_WAVE = CEP_PMAX + 1 + 2 * WARP_BMAX;
@@ -200,13 +226,12 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
   }
 }
 
-// out[i][t] = C_i(read_i(freqs[t])), natural-log amplitude, not muted; -inf on a (-inf, 0, ..) row
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
-    eaqhm_cepstrum_envelope_kernel(const double* __restrict__ ceps, int n, int P, double fs,
-                                   const double* __restrict__ alphav, const double* __restrict__ f_in,
-                                   const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
-                                   double* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
+// out[i][t] = C_i(read_i(freqs[t])), natural-log amplitude, not muted; -inf on a (-inf, 0, ..) row.  PHASE: Phi_i there.
+template <bool PHASE>
+__device__ inline void cep_grid(double* lds, const double* __restrict__ ceps, int n, int P, double fs,
+                                const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
+                                double* __restrict__ out) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per row: scalar
   const bool live = i < n;
@@ -214,7 +239,73 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
   const WarpRow W = cep_stage(lds, w, lane, live, ceps + (size_t)il * (P + 1), P, f_in, f_out + (size_t)il * B, B);
   if (!live) return;
   const CepRead R{lds + (size_t)w * CEP_READ_WAVE, P, fs, B > 0 ? 2 : alphav ? 1 : 0, alphav ? alphav[i] : 1.0};
-  for (int t = lane; t < F; t += 64) out[(size_t)i * F + t] = cep_read(R, W, freqs[t]);
+  for (int t = lane; t < F; t += 64) out[(size_t)i * F + t] = PHASE ? cep_read_phase(R, W, freqs[t]) : cep_read(R, W, freqs[t]);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_cepstrum_envelope_kernel(const double* __restrict__ ceps, int n, int P, double fs,
+                                   const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                   const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
+                                   double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_grid<false>(lds, ceps, n, P, fs, alphav, f_in, f_out, B, freqs, F, out);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_cepstrum_phase_kernel(const double* __restrict__ ceps, int n, int P, double fs,
+                                const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
+                                double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_grid<true>(lds, ceps, n, P, fs, alphav, f_in, f_out, B, freqs, F, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The model from parameters (§9.7): the records [n][3 Kmax + 1] of the harmonic model with f = h f0_i, |a| = exp(C_i(f))
+// and phase = wrap(2 pi frac(h theta_i) + Phi_i(f)), h = k + 1.  Slot k is active iff the instant is voiced, its row is
+// not the empty row, k < Kcap, h f0_i < fs/2 (this product, as the host forms it) and exp did not underflow; every other
+// cell is written as 0 by the same stores.  One sincos per cell serves C and Phi through cep_recur.  The row's
+// coefficients sit in the wave's own LDS: the waves of a block share no data, so there is no block barrier.
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_model_build_kernel(const double* __restrict__ f0, const double* __restrict__ theta,
+                             const unsigned char* __restrict__ voiced, const double* __restrict__ ceps, int P,
+                             const double* __restrict__ a0, int n, double fs, int Kmax, int Kcap, int zero_phase,
+                             double* __restrict__ records) {
+  __shared__ double sc[CEP_WAVES][CEP_PMAX + 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
+  if (i >= n) return;
+  double* c = sc[w];
+  if (lane <= P) c[lane] = ceps[(size_t)i * (P + 1) + lane];
+  __builtin_amdgcn_wave_barrier();
+  const bool rowlive = voiced[i] != 0 && c[0] != -INFINITY;
+  const double fi = f0[i], th = theta[i], half = 0.5 * fs;
+  double* row = records + (size_t)i * (3 * (size_t)Kmax + 1);
+  for (int k0 = 0; k0 < Kmax; k0 += 64) {
+    const int k = k0 + lane;
+    if (k >= Kmax) break;
+    const double h = (double)(k + 1);
+    const double fm = __dmul_rn(h, fi);
+    double a = 0.0, f = 0.0, ph = 0.0;
+    if (rowlive && k < Kcap && fm < half) {
+      double sn, cs, b1, b2;
+      sincos(((2.0 * M_PI) * fm) / fs, &sn, &cs);
+      const double cw2 = 2.0 * cs;
+      cep_recur(c, P, cw2, b1, b2);
+      a = exp(2.0 * (0.5 * cw2 * b1 - b2) + c[0]);
+      if (a != 0.0) {
+        const double hs = __dmul_rn(h, th);           // the product rounded as the definition rounds it, then frac
+        double x = __dmul_rn(2.0 * M_PI, hs - floor(hs));
+        if (!zero_phase) x += -2.0 * (b1 * sn);
+        ph = x - (2.0 * M_PI) * ceil((x - M_PI) / (2.0 * M_PI));   // into (-pi, pi]
+        f = fm;
+      }
+    }
+    row[k] = a;
+    row[Kmax + k] = f;
+    row[2 * Kmax + k] = ph;
+  }
+  if (lane == 0) row[3 * (size_t)Kmax] = a0[i];
 }
 }  // namespace eaqhm
 
@@ -222,6 +313,7 @@ using namespace eaqhm;
 
 static bool finite_pos(double x) { return std::isfinite(x) && x > 0.0; }
 static const size_t CEPSTRUM_LDS_MAX = 160 * 1024;
+static const int BUILD_KCAP_MAX = 1706;   // the prep kernel's LDS limit on Kmax
 
 // the optional read-frequency groups: alpha, or the whole warp group (f_in, f_out, B in [1, 16]), or neither
 static bool read_group_ok(const double* alpha, const double* f_in, const double* f_out, int32_t B) {
@@ -275,6 +367,39 @@ extern "C" int eaqhm_cepstrum_envelope(eaqhm_ctx* ctx, const double* ceps, int32
   hipLaunchKernelGGL(eaqhm_cepstrum_envelope_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)),
                      dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs, alpha, f_in, f_out,
                      (int)B, freqs, (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_cepstrum_phase(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
+                                    const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                    const double* freqs, int32_t F, double* out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!ceps || !freqs || !out || n < 1 || F < 1 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: bad argument");
+  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: need 1 <= order <= 63");
+  if (!read_group_ok(alpha, f_in, f_out, B))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
+  hipLaunchKernelGGL(eaqhm_cepstrum_phase_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)),
+                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs, alpha, f_in, f_out,
+                     (int)B, freqs, (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_model_build(eaqhm_ctx* ctx, const double* f0, const double* theta, const uint8_t* voiced,
+                                 const double* ceps, int32_t order, const double* a0, int32_t n, double fs,
+                                 int32_t Kmax, int32_t Kcap, int32_t zero_phase, double* records) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!f0 || !theta || !voiced || !ceps || !a0 || !records || n < 2 || !finite_pos(fs))
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: bad argument");
+  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: need 1 <= order <= 63");
+  if (Kcap < 1 || Kcap > BUILD_KCAP_MAX || Kmax < 1 || Kmax > Kcap)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: need 1 <= Kmax <= Kcap <= 1706");
+  if (zero_phase != 0 && zero_phase != 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: zero_phase is 0 or 1");
+  hipLaunchKernelGGL(eaqhm_model_build_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)), dim3(64 * CEP_WAVES),
+                     0, ctx->stream, f0, theta, (const unsigned char*)voiced, ceps, (int)order, a0, (int)n, fs, (int)Kmax,
+                     (int)Kcap, (int)zero_phase, records);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

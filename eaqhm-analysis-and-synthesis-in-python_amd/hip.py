@@ -55,6 +55,8 @@ SYMBOLS = (
     ("eaqhm_cepstrum_envelope", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
     ("eaqhm_cepstrum_cost", C.c_int, [_P, _P, _I32, _P, _I32, _I32, _F64, _F64, _I32, _P]),
     ("eaqhm_dtw", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    ("eaqhm_model_build", C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _I32, _F64, _I32, _I32, _I32, _P]),
+    ("eaqhm_cepstrum_phase", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
 )
 
 
@@ -283,6 +285,16 @@ class Context:
         """band holds the costs on entry and D on return; path int32[nA + nB - 1, 2], path_len int32[1], total
         float64[1] are device tensors."""
         self._ck(self.lib.eaqhm_dtw(self.h, _ptr(band), nA, nB, r, _ptr(ptr), _ptr(path), _ptr(path_len), _ptr(total)))
+
+    # a harmonic model from f0 and cepstral rows (DESIGN.md §9.7): voiced uint8[n], records [n][3 Kmax + 1]
+    def model_build(self, f0, theta, voiced, ceps, order, a0, n, fs, Kmax, Kcap, zero_phase, records):
+        self._ck(self.lib.eaqhm_model_build(self.h, _ptr(f0), _ptr(theta), _ptr(voiced), _ptr(ceps), order, _ptr(a0), n,
+                                            float(fs), Kmax, Kcap, int(bool(zero_phase)), _ptr(records)))
+
+    def cepstrum_phase(self, ceps, n, order, fs, freqs, F, out, alpha=None, warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_cepstrum_phase(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha), _ptr(f_in),
+                                               _ptr(f_out), B, _ptr(freqs), F, _ptr(out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

@@ -11,6 +11,11 @@
     dtw(cost, band=None, *, device_index=0) -> (path int64[L, 2], total)
     alignment_index(path, nA) -> float64[nA]; warp_rows(X, idx) -> rows of X at fractional indices
     alignment_time_scale(path, nA, step_ratio=1.0) -> float64[nA]
+    model_parameters(DetComponents, fs, order=None, lam=5e-4, *, device_index=0) -> dict(f0, ceps, voiced, step, fs)
+    model_from_parameters(f0, ceps, fs, step, *, voiced=None, phase="minimum", theta0=0.0, kmax=None, a0=None,
+                          device_index=0) -> det_format="arrays" dict (ti, isVoiced, a0, amplitudes, frange, pk)
+    check_model_build_arguments(f0, ceps, fs, step, voiced=None, phase="minimum", theta0=0.0, kmax=None, a0=None)
+    cepstrum_phase(ceps, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0) -> float64[n, len(freqs)]
     model_f0(DetComponents, fs) -> float64[No_ti]
     model_envelope(DetComponents, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0)
         -> float64[No_ti, len(freqs)]
@@ -39,8 +44,9 @@ filtered white noise under the same time map (§10); its envelope follows a form
 fundamental, the waveform shape of a pitch period, at every scale (§11).  The work runs in libeaqhm_hip.so (eaqhm_spline_solve,
 eaqhm_modify_prep, eaqhm_modify_synth, eaqhm_model_envelope, eaqhm_noise_analyse, eaqhm_noise_synth, eaqhm_noise_warp,
 eaqhm_noise_envelope, eaqhm_noise_modulation, eaqhm_model_cepstrum, eaqhm_modify_amp_cepstrum, eaqhm_cepstrum_envelope,
-eaqhm_cepstrum_cost, eaqhm_dtw);
-there is no CPU path.  The noise of voiced frames is modulated pitch-synchronously on request
+eaqhm_cepstrum_cost, eaqhm_dtw, eaqhm_model_build, eaqhm_cepstrum_phase);
+there is no CPU path.  A model can also be built from parameters alone, f0 and cepstral rows, with the minimum-phase response of
+the envelope as the phases (§9.7): model_parameters reduces a model to such arrays, model_from_parameters is the way back.  The noise of voiced frames is modulated pitch-synchronously on request
 (§10.2): eaQHMNoiseModulation adds the Fourier coefficients of the residual's power over the fundamental's phase to the
 noise model, and the synthesis plays that envelope at the output's fundamental.
 """
@@ -939,6 +945,175 @@ def alignment_time_scale(path, nA, step_ratio=1.0):
     if len(idx) < 2:
         raise ValueError("a time-scale contour needs at least two instants of A")
     return np.clip(step_ratio * np.gradient(idx), *SCALE_RANGE)
+
+
+# ---- a harmonic model from f0 and cepstral rows
+BUILD_MAX_HARMONICS = 1706       # Kmax of a model at most: the LDS limit of eaqhm_modify_prep
+BUILD_PHASES = ("minimum", "zero")
+
+
+def harmonic_counts(f0, fs, cap):
+    """Per instant the number of harmonics h = 1, 2, .. with h * f0 < fs / 2 in float64 (this product against this
+    half: the comparison eaqhm_model_build makes), at most `cap`; 0 where f0 is not > 0.  int64[n]."""
+    f0 = np.asarray(f0, dtype=np.float64)
+    half = 0.5 * float(fs)
+    ok = f0 > 0
+    g = np.where(ok, f0, 1.0)
+    m = np.minimum(np.floor(half / g), float(cap))
+    for _ in range(4):           # the quotient is off by one at the most; the product decides
+        m = np.where(((m + 1.0) * g < half) & (m + 1.0 <= cap), m + 1.0, m)
+        m = np.where((m >= 1.0) & (m * g >= half), m - 1.0, m)
+    return np.where(ok, m, 0.0).astype(np.int64)
+
+
+def fundamental_phase(g, theta0, step, fs):
+    """theta of DESIGN.md §9.7: the fundamental's phase in cycles at every instant, theta_0 = theta0,
+    theta_{i+1} = frac(theta_i + (step / fs) (g_i + g_{i+1}) / 2), in float64 in this order (fundamental_advance's, with
+    the whole frequency in place of the excess)."""
+    g = np.asarray(g, dtype=np.float64)
+    inc = (float(step) / float(fs)) * (g[:-1] + g[1:]) / 2
+    th = np.zeros(len(g))
+    acc = th[0] = float(theta0)
+    for j, d in enumerate(inc.tolist()):
+        acc += d
+        acc -= np.floor(acc)
+        th[j + 1] = acc
+    return th
+
+
+def _held(x, has):
+    """x where `has`, elsewhere the value of the nearest earlier instant that has one, else of the nearest later one
+    (the rule of _records_f0); zeros when none has."""
+    n = len(x)
+    if not has.any():
+        return np.zeros(n)
+    src = np.maximum.accumulate(np.where(has, np.arange(n), -1))
+    src[src < 0] = int(np.flatnonzero(has)[0])
+    return np.where(has, x, 0.0)[src]
+
+
+def check_model_build_arguments(f0, ceps, fs, step, voiced=None, phase="minimum", theta0=0.0, kmax=None, a0=None):
+    """Validates everything model_from_parameters gets and prepares what the host owes the kernel (no device work).
+    Returns dict(f0, ceps, fs, step, voiced, zero_phase, a0, theta, counts, Kmax, Kcap): f0 with zeros at unvoiced
+    instants, theta the fundamental's phase in cycles, counts the harmonics below fs/2 per instant (0 at an unvoiced
+    instant or an empty row), Kmax = max(1, counts.max())."""
+    fs = _sample_rate(fs)
+    step = _integer(step, "step")
+    if step <= 0:
+        raise ValueError("step must be a positive integer (samples), got %d" % step)
+    f = np.asarray(f0)
+    if f.dtype.kind not in "iuf" or f.ndim != 1:
+        raise ValueError("f0 must be a 1-D array of numbers (Hz), one per analysis instant")
+    f = f.astype(np.float64)
+    n = len(f)
+    if n < 2:
+        raise ValueError("the model needs at least two analysis instants")
+    if voiced is None:
+        with np.errstate(invalid="ignore"):
+            v = f > 0
+    else:
+        v = np.asarray(voiced)
+        if v.dtype.kind not in "biu" or v.shape != (n,):
+            raise ValueError("voiced must be a 1-D array of booleans, one per analysis instant (%d)" % n)
+        v = v.astype(bool)
+    if not v.any():
+        raise ValueError("no voiced instant: there is nothing to build")
+    fv = f[v]
+    if not np.all(np.isfinite(fv)) or np.any(fv <= 0) or np.any(fv >= 0.5 * fs):
+        raise ValueError("f0 of a voiced instant must be finite and in (0, fs/2) Hz")
+    C = _cepstrum_rows(ceps, "ceps", n)
+    if phase not in BUILD_PHASES:
+        raise ValueError("phase must be one of %s, got %r" % (", ".join(map(repr, BUILD_PHASES)), phase))
+    try:
+        theta0 = float(theta0)
+    except (TypeError, ValueError):
+        raise ValueError("theta0 must be a number (cycles)") from None
+    if not np.isfinite(theta0):
+        raise ValueError("theta0 must be finite (cycles)")
+    Kcap = BUILD_MAX_HARMONICS
+    if kmax is not None:
+        Kcap = _integer(kmax, "kmax")
+        if not 1 <= Kcap <= BUILD_MAX_HARMONICS:
+            raise ValueError("kmax must be in [1, %d], got %d" % (BUILD_MAX_HARMONICS, Kcap))
+    if a0 is None:
+        a = np.zeros(n)
+    else:
+        a = _numeric_1d(a0, "a0")
+        if len(a) != n or not np.all(np.isfinite(a)):
+            raise ValueError("a0 must hold one finite value per analysis instant (%d)" % n)
+    has = v & ~np.isneginf(C[:, 0])
+    f = np.where(v, f, 0.0)
+    counts = harmonic_counts(np.where(has, f, 0.0), fs, Kcap)
+    theta = fundamental_phase(_held(f, has), theta0, step, fs)
+    return dict(f0=f, ceps=C, fs=fs, step=step, voiced=v, zero_phase=phase == "zero", a0=a, theta=theta, counts=counts,
+                Kmax=max(1, int(counts.max())), Kcap=Kcap)
+
+
+def model_from_parameters(f0, ceps, fs, step, *, voiced=None, phase="minimum", theta0=0.0, kmax=None, a0=None,
+                          device_index=0):
+    """A harmonic model from a fundamental track and a cepstral envelope, the inverse of
+    model_parameters: per analysis instant i (at sample i * step) `f0[i]` in Hz, `voiced[i]` (default f0 > 0) and the
+    row `ceps[i]` of model_cepstrum's layout, from this or another model or from a pipeline of the caller's own.  Slot k
+    holds harmonic h = k + 1 at h f0 with the amplitude exp(C_i(h f0)) and the phase 2 pi frac(h theta_i) + Phi_i(h f0),
+    wrapped; theta is the running phase of the fundamental in cycles from `theta0`, with f0 held across unvoiced
+    instants, and Phi the minimum-phase response of the envelope, -2 sum_p c_p sin(2 pi p f / fs) (phase="zero": 0,
+    pulse-like harmonics).  A slot is active while the instant is voiced, its row is not (-inf, 0, .., 0), h f0 < fs/2
+    and k < kmax (default and limit 1706).  `a0` is the DC term per instant (default 0; unpack_model drops it at
+    unvoiced instants, as for an analysed model).
+
+    Returns the model as a det_format="arrays" dict (ti, isVoiced, a0, amplitudes, frange, pk), which unpack_model,
+    eaQHMSynthesis and every other function here take like an analysed one.  The records take n * (3 Kmax + 1) * 8
+    bytes on the device and on the host."""
+    a = check_model_build_arguments(f0, ceps, fs, step, voiced, phase, theta0, kmax, a0)
+    torch, c, dev = _device(device_index)
+    n, K, C = len(a["f0"]), a["Kmax"], a["ceps"]
+    f_d, th_d, a0_d, C_d = (torch.as_tensor(np.ascontiguousarray(x), device=dev)
+                            for x in (a["f0"], a["theta"], a["a0"], C))
+    v_d = torch.as_tensor(a["voiced"].astype(np.uint8), device=dev)
+    rec = torch.empty((n, 3 * K + 1), dtype=torch.float64, device=dev)
+    c.model_build(f_d, th_d, v_d, C_d, C.shape[1] - 1, a0_d, n, a["fs"], K, a["Kcap"], a["zero_phase"], rec)
+    r = rec.cpu().numpy()
+    return dict(ti=np.arange(n, dtype=np.int64) * a["step"], isVoiced=a["voiced"].copy(), a0=r[:, 3 * K].copy(),
+                amplitudes=r[:, :K].copy(), frange=r[:, K:2 * K].copy(), pk=r[:, 2 * K:3 * K].copy())
+
+
+def cepstrum_phase(ceps, fs, freqs, formant_scale=1.0, formant_warp=None, *, device_index=0):
+    """The minimum-phase response of the envelope a cepstrum describes, on a frequency grid:
+    out[i, t] = Phi_i(freqs[t] / alpha_i), Phi_i(q) = -2 sum_p c_p sin(2 pi p q^ / fs) at cepstrum_envelope's read
+    frequency q^, in radians as the series gives it (not wrapped).  exp(C + j Phi) is the frequency response of the
+    causal, minimum-phase filter whose log magnitude is C.  The arguments are cepstrum_envelope's; a row
+    (-inf, 0, .., 0) reads 0.  Returns float64[n, len(freqs)]."""
+    fs = _sample_rate(fs)
+    C = _cepstrum_rows(ceps, "ceps")
+    f = _freq_grid(freqs)
+    n, P = C.shape[0], C.shape[1] - 1
+    alpha = _contour(formant_scale, "formant_scale", n)
+    wmap = None
+    if formant_warp is not None:
+        _warp_excludes_scale(formant_scale)
+        wmap = _warp_rows(formant_warp, n, "row of ceps")
+    torch, c, dev = _device(device_index)
+    C_d, f_d = torch.as_tensor(C, device=dev), torch.as_tensor(np.ascontiguousarray(f), device=dev)
+    out = torch.empty((n, len(f)), dtype=torch.float64, device=dev)
+    if wmap is not None:
+        x_d, y_d = (torch.as_tensor(np.array(v), device=dev) for v in wmap)      # a broadcast row is read-only: a copy
+        c.cepstrum_phase(C_d, n, P, fs, f_d, len(f), out, warp=(x_d, y_d, len(wmap[0])))
+    elif np.any(alpha != 1.0):
+        c.cepstrum_phase(C_d, n, P, fs, f_d, len(f), out, alpha=torch.as_tensor(alpha, device=dev))
+    else:
+        c.cepstrum_phase(C_d, n, P, fs, f_d, len(f), out)
+    return out.cpu().numpy() + 0.0        # the -0.0 of an empty row reads 0.0
+
+
+def model_parameters(DetComponents, fs, order=None, lam=5e-4, *, device_index=0):
+    """The model reduced to plain arrays: dict(f0=model_f0(..), ceps=model_cepstrum(..), voiced, step,
+    fs), `voiced` being "the instant has an active slot".  Each entry can be edited, smoothed, predicted or taken from
+    another model; model_from_parameters(p["f0"], p["ceps"], p["fs"], p["step"], voiced=p["voiced"]) is the way back."""
+    model = unpack_model(DetComponents)
+    K = model["Kmax"]
+    voiced = (model["records"][:, :K] != 0).any(axis=1)
+    return dict(f0=model_f0(DetComponents, fs), ceps=model_cepstrum(DetComponents, fs, order, lam, device_index=device_index),
+                voiced=voiced, step=model["step"], fs=_sample_rate(fs))
 
 
 # ---- the stochastic component (DESIGN.md §10)

@@ -417,6 +417,34 @@ int eaqhm_cepstrum_cost(eaqhm_ctx* ctx, const double* cepsA, int32_t nA, const d
 int eaqhm_dtw(eaqhm_ctx* ctx, double* band, int32_t nA, int32_t nB, int32_t r, uint8_t* ptr, int32_t* path,
               int32_t* path_len, double* total);
 
+/* a harmonic model from f0 and cepstral rows (additions under ABI 6) -----------------------------------
+ * eaqhm_model_build (kernel: one wave per instant, four per block, the row's coefficients in the wave's LDS, lanes over
+ *   the harmonics in chunks of 64) writes the records double[n][3 Kmax + 1] (|a| | f | phase | a0, the layout above) of
+ *   the model whose slot k holds harmonic h = k + 1 of f0:
+ *   f0         double[n]            Hz; read at voiced instants only
+ *   theta      double[n]            the fundamental's phase in cycles at the instant (the host's recurrence, §9.7)
+ *   voiced     uint8[n]             0: every slot of the instant is inactive
+ *   ceps       double[n][order+1]   the envelope, the layout of eaqhm_model_cepstrum; a row (-inf, 0, .., 0) is empty
+ *   a0         double[n]            copied to the records' last column
+ *   Slot k of instant i is active iff voiced[i], the row is not empty, k < Kcap, and h f0_i < fs/2 (the float64 product
+ *   against 0.5 fs, as the host forms it); then f = h f0_i, |a| = exp(C_i(f)) (Clenshaw from one cosine, c_0 added last,
+ *   as eaqhm_cepstrum_envelope reads it) and phase = wrap(2 pi frac(h theta_i) + Phi_i(f)) in (-pi, pi], with
+ *   Phi_i(f) = -2 sum_p c_p sin(2 pi p f / fs), the minimum-phase response of the envelope, from the same recurrence
+ *   (cosine sum b_1 cos t - b_2, sine sum b_1 sin t); zero_phase = 1 sets Phi = 0.  A cell whose exp underflows to 0 is
+ *   inactive.  Inactive cells are written as exact zeros in all three fields: the records need no memset.
+ * eaqhm_cepstrum_phase is eaqhm_cepstrum_envelope with Phi in place of C: out[i][t] = Phi_i(read_i(freqs[t])) in
+ *   radians, as the series gives it (not wrapped); 0 on an empty row.  The same grid and optional alpha / warp group.
+ * The entry points do not read the device arrays: finite f0 in (0, fs/2) at voiced instants, finite theta and
+ * coefficients are the CALLER'S contract (the Python host checks them).
+ * EAQHM_EINVAL for null pointers, n < 2 (n < 1 for eaqhm_cepstrum_phase), order outside [1, 63], fs not finite and > 0,
+ * Kcap outside [1, 1706], Kmax outside [1, Kcap], zero_phase not 0 or 1, and eaqhm_cepstrum_envelope's rules.         */
+int eaqhm_model_build(eaqhm_ctx* ctx, const double* f0, const double* theta, const uint8_t* voiced, const double* ceps,
+                      int32_t order, const double* a0, int32_t n, double fs, int32_t Kmax, int32_t Kcap,
+                      int32_t zero_phase, double* records);
+int eaqhm_cepstrum_phase(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs, const double* alpha,
+                         const double* f_in, const double* f_out, int32_t B, const double* freqs, int32_t F,
+                         double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--align] [--out FILE]
+                                          [--cepstrum] [--align] [--build] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -110,7 +110,7 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False, formant_warp=False, cepstrum=False, align=False):
+          noise_modulation=False, formant_warp=False, cepstrum=False, align=False, build=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -154,7 +154,43 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
         res["cepstrum"] = cepstrum_rows(torch, st)
     if align:
         res["align"] = align_rows(torch, st)
+    if build:
+        res["build"] = build_rows(torch, st)
     return res
+
+
+def build_rows(torch, st, reps=20, runs=3):
+    """The model from parameters, same session: eaqhm_model_build on the model's own f0, voicing and
+    cepstrum (default order; new_ms), next to eaqhm_modify_amp_cepstrum at beta = 1 on the same model (base_ms), which
+    does the same work per cell (one Clenshaw sum and one exp) and is the comparison, not a bar.  Each time: median of
+    `runs` warmed windows of `reps` launches; margin_ms = max - min of the existing kernel's windows."""
+    from eaqhm_amd.model import _records_f0, check_model_build_arguments
+    c, rec, amp = (st[k] for k in ("c", "rec", "amp"))
+    n, K, D, fs = st["n"], st["K"], st["D"], st["fs"]
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    P = min(63, 2 + int(round(fs / 1000.0)))
+    ceps = torch.empty((n, P + 1), dtype=torch.float64, device=dev)
+    c.model_cepstrum(rec, n, K, fs, P, 5e-4, ceps)
+    rec_h = rec.cpu().numpy()
+    a = check_model_build_arguments(_records_f0(rec_h, K), ceps.cpu().numpy(), fs, D,
+                                    voiced=(rec_h[:, :K] != 0).any(axis=1))
+    Kb = a["Kmax"]
+    f_d, th_d, a0_d = (torch.as_tensor(np.ascontiguousarray(a[k]), device=dev) for k in ("f0", "theta", "a0"))
+    v_d = torch.as_tensor(a["voiced"].astype(np.uint8), device=dev)
+    out = torch.empty((n, 3 * Kb + 1), dtype=torch.float64, device=dev)
+    beta_d = torch.ones(n, dtype=torch.float64, device=dev)
+    base = med(lambda: c.modify_amp_cepstrum(rec, n, K, fs, beta_d, ceps, P, amp))
+    new = med(lambda: c.model_build(f_d, th_d, v_d, ceps, P, a0_d, n, fs, Kb, a["Kcap"], False, out))
+    cells = int(a["counts"].sum())
+    return [dict(setting="build_P%d" % P, order=P, instants=n, Kmax_model=K, Kmax_built=Kb, active_cells_built=cells,
+                 active_cells_model=int(np.count_nonzero(rec_h[:, :K])), bytes_written=n * (3 * Kb + 1) * 8,
+                 base_ms=round(base[0], 4), margin_ms=round(base[1], 4), new_ms=round(new[0], 4),
+                 new_spread_ms=round(new[1], 4), new_gb_per_s=round(n * (3 * Kb + 1) * 8 / (new[0] * 1e-3) / 1e9, 1))]
 
 
 def align_rows(torch, st, band_s=2.0, excerpt_s=5.0, runs=3):
@@ -579,10 +615,12 @@ def main():
                     help="also time the cepstral fit and the amplitudes read off it against the prep with the envelope")
     ap.add_argument("--align", action="store_true",
                     help="also time the alignment kernels on the model against a time-stretched copy of itself")
+    ap.add_argument("--build", action="store_true",
+                    help="also time eaqhm_model_build next to eaqhm_modify_amp_cepstrum (the model from parameters)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align) for w in a.workloads.split(",")]
+                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build) for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
