@@ -9,6 +9,6 @@ from .hip import HipUnavailable, load_library  # noqa: F401
 from .structs import Deterministic, Frame  # noqa: F401
 from .model import (SCALE_RANGE, cepstrum_phase, model_from_parameters, model_parameters, alignment_index, alignment_time_scale, cepstrum_envelope, dtw, model_align, warp_rows, contour_time_map, eaQHMNoiseAnalysis, eaQHMNoiseModulation,  # noqa: F401
                     eaQHMNoiseSynthesis, eaQHMNoiseWarp, eaQHMSynthesis, formant_warp_vtln, model_cepstrum, model_envelope, model_f0,
-                    model_phase, noise_envelope, noise_formant_contour, noise_formant_warp, noise_fundamental, noise_time_map, noise_time_map_contour,
+                    model_phase, noise_alignment_index, noise_cepstrum, noise_envelope, noise_formant_contour, noise_formant_warp, noise_from_cepstrum, noise_fundamental, noise_time_map, noise_time_map_contour,
                     scale_contour, unpack_model)
 from .prologue import read_signal  # noqa: F401

@@ -25,7 +25,12 @@ instants; --timing-from OTHER.wav gives the output OTHER's local tempo instead o
 that admits a path.  --from-parameters [P] reduces the analysed model to f0, voicing and a cepstrum of order P
 (model.model_parameters; lambda from --cepstral-lambda), rebuilds a harmonic model from those arrays alone with the
 envelope's minimum-phase response as its phases (model.model_from_parameters) and writes its synthesis, under
-whatever scale, formant, phase and noise flags are given, as `<name>_vocoded.wav`; not with --no-envelope."""
+whatever scale, formant, phase and noise flags are given, as `<name>_vocoded.wav`; not with --no-envelope.
+--noise-cepstrum [Q] (with --noise; Q in 1..63, default 63) passes the noise model through its cepstral rows and back
+(model.noise_cepstrum, model.noise_from_cepstrum).  --noise-from OTHER.wav (with --noise) analyses OTHER
+with the same options (once, if --envelope-from / --timing-from name the same file), models its residual, aligns the two
+files as --envelope-from does and puts OTHER's noise at this file's timing (model.noise_alignment_index) in place of its
+own; it implies --noise-cepstrum and does not go with --noise-modulation."""
 import argparse
 
 import numpy as np
@@ -86,6 +91,11 @@ def parser():
                          "--formant-vtln): the noise's spectral envelope follows it")
     ap.add_argument("--noise-modulation", type=int, nargs="?", const=2, default=None, metavar="M",
                     help="with --noise: modulate the noise pitch-synchronously, M harmonics of the envelope (2)")
+    ap.add_argument("--noise-cepstrum", type=int, nargs="?", const=63, default=None, metavar="Q",
+                    help="with --noise: the noise model goes through its cepstral rows of order Q (1 to 63; 63) and back")
+    ap.add_argument("--noise-from", default=None, metavar="OTHER.wav",
+                    help="with --noise: the noise of OTHER.wav's residual, aligned in time to this file, in place of this "
+                         "file's own (implies --noise-cepstrum; not with --noise-modulation)")
     ap.add_argument("--cepstral-envelope", type=int, nargs="?", const=0, default=None, metavar="P",
                     help="also write <name>_modified.wav: amplitudes read off the model's discrete-cepstrum envelope of "
                          "order P (1 to 63; default min(63, 2 + round(fs / 1000)))")
@@ -98,7 +108,7 @@ def parser():
                     help="also write <name>_vocoded.wav: the model rebuilt from its f0, voicing and cepstrum of order P "
                          "(1 to 63; default min(63, 2 + round(fs / 1000))), with minimum-phase harmonics")
     ap.add_argument("--align-band", type=float, default=None, metavar="SECONDS",
-                    help="with --envelope-from / --timing-from: half-width of the alignment band (2.0)")
+                    help="with --envelope-from / --timing-from / --noise-from: half-width of the alignment band (2.0)")
     return ap
 
 
@@ -116,6 +126,17 @@ def main(argv=None):
         ap.error("--formant-knee needs --formant-vtln")
     if a.noise_modulation is not None and not a.noise:
         ap.error("--noise-modulation needs --noise")
+    if a.noise_cepstrum is not None and not a.noise:
+        ap.error("--noise-cepstrum needs --noise")
+    if a.noise_from is not None and not a.noise:
+        ap.error("--noise-from needs --noise")
+    if a.noise_from is not None and a.noise_modulation is not None:
+        ap.error("--noise-from takes the other file's noise: not with --noise-modulation, which follows this file's pitch")
+    if a.noise_from is not None and a.noise_cepstrum is None:
+        a.noise_cepstrum = 63
+    if a.noise_cepstrum is not None:
+        from .model import _cepstrum_order
+        _cepstrum_order(a.noise_cepstrum)
     if a.noise:
         from .model import _mod_harmonics, _seed
         _seed(0 if a.noise_seed is None else a.noise_seed)
@@ -124,7 +145,7 @@ def main(argv=None):
     if a.no_envelope and (a.formant_scale is not None or a.formant_scale_curve is not None or warped):
         ap.error("the formant flags move the spectral envelope: not with --no-envelope")
     cepstral = a.cepstral_envelope is not None
-    aligned = a.envelope_from is not None or a.timing_from is not None
+    aligned = a.envelope_from is not None or a.timing_from is not None or a.noise_from is not None
     vocode = a.from_parameters is not None
     if a.cepstral_lambda is not None and not (cepstral or vocode):
         ap.error("--cepstral-lambda needs --cepstral-envelope or --from-parameters")
@@ -135,7 +156,7 @@ def main(argv=None):
     if a.envelope_from is not None and a.no_envelope:
         ap.error("--envelope-from supplies the spectral envelope: not with --no-envelope")
     if a.align_band is not None and not aligned:
-        ap.error("--align-band needs --envelope-from or --timing-from")
+        ap.error("--align-band needs --envelope-from, --timing-from or --noise-from")
     if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
         ap.error("--align-band must be finite and >= 0")
     if cepstral or vocode:   # 0: the flag without a value, the default order
@@ -204,18 +225,30 @@ def main(argv=None):
                 ceps = model_cepstrum(det, fs, order, lam)
             if aligned:
                 from .model import alignment_index, alignment_time_scale, warp_rows
-                others = {}
-                for path in (a.envelope_from, a.timing_from):
+                others, n_inst = {}, len(ceps)
+                for path in (a.envelope_from, a.timing_from, a.noise_from):
                     if path is not None and path not in others:
                         others[path] = align_other(path, gender, analysis_options, fs, ceps, order, lam,
-                                                   2.0 if a.align_band is None else a.align_band)
+                                                   2.0 if a.align_band is None else a.align_band,
+                                                   a.fc if path == a.noise_from else None)
                 if a.timing_from is not None:
                     rho = alignment_time_scale(others[a.timing_from][1], len(ceps))
                 if a.envelope_from is not None:
-                    C_other, pairs = others[a.envelope_from]
+                    C_other, pairs = others[a.envelope_from][:2]
                     ceps = warp_rows(C_other, alignment_index(pairs, len(ceps)))
                 elif not cepstral:
                     ceps = None
+                if a.noise_from is not None:   # OTHER's residual noise at this file's noise frames
+                    from .model import noise_alignment_index, noise_cepstrum
+                    pairs, det_o, nz_o = others[a.noise_from][1:]
+                    j = noise_alignment_index(alignment_index(pairs, n_inst), det, nz, det_o, nz_o)
+                    noise_rows = warp_rows(noise_cepstrum(nz_o, a.noise_cepstrum), j)
+            if a.noise_cepstrum is not None:
+                from .model import noise_cepstrum, noise_from_cepstrum
+                if a.noise_from is None:
+                    noise_rows = noise_cepstrum(nz, a.noise_cepstrum)
+                kept = {k: nz[k] for k in ("mod", "mod_harmonics") if k in nz}
+                nz = noise_from_cepstrum(noise_rows, nz["hop"], fs, order=nz["order"], length=nz["length"], **kept)
             common = dict(time_scale=rho, pitch_scale=beta, preserve_envelope=not a.no_envelope, formant_scale=alpha,
                           phase=a.phase, noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
                           noise_modulation=a.noise_modulation is not None, formant_warp=wmap)
@@ -236,18 +269,23 @@ def main(argv=None):
     return 0
 
 
-def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s):
-    """Analyses `path` with the same options, fits its cepstrum and aligns it to `ceps`: (its cepstrum, the path)."""
-    from .model import band_min_radius, model_align, model_cepstrum, unpack_model
+def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, noise_fc=None):
+    """Analyses `path` with the same options, fits its cepstrum and aligns it to `ceps`: (its cepstrum, the path, its
+    model, and with `noise_fc` (the --fc of the analysis) the noise model of its residual, else None)."""
+    from .model import band_min_radius, eaQHMNoiseAnalysis, model_align, model_cepstrum, unpack_model
     fs_o, _ = wavfile.read(path)
     if fs_o != fs:
         raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (path, fs_o, fs))
-    det_o = eaQHMAnalysisAndSynthesis(path, gender, **analysis_options)[2]
+    s_recon_o, _, det_o, _ = eaQHMAnalysisAndSynthesis(path, gender, **analysis_options)
     C_o = model_cepstrum(det_o, fs, order, lam)
     r = max(int(round(band_s * fs / unpack_model(det_o)["step"])), band_min_radius(len(ceps), len(C_o)))
     pairs, cost = model_align(ceps, C_o, band=r)
     print("aligned %s: %d pairs, cost %g" % (path, len(pairs), cost))
-    return C_o, pairs
+    nz_o = None
+    if noise_fc is not None:
+        from .prologue import read_signal
+        nz_o = eaQHMNoiseAnalysis(read_signal(path, noise_fc)[1], s_recon_o, fs)
+    return C_o, pairs, det_o, nz_o
 
 
 def _two_columns(path, name, what):

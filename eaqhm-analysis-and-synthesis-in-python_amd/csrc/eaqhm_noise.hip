@@ -8,6 +8,10 @@
 //   eaqhm_noise_envelope_kernel  one wave per frame, lanes over the frequency grid: the warped log power spectrum
 //   eaqhm_noise_warp_map_kernel, eaqhm_noise_envelope_map_kernel  the same two bodies with the piecewise-linear map of
 //                                DESIGN.md §10.3 (eaqhm_warp.h) as the read frequency in place of w / alpha
+//   eaqhm_noise_cepstrum_kernel  one wave per frame: the cepstrum of the frame's log spectrum by the LPC-to-cepstrum
+//                                recursion, lanes over the terms of each step
+//   eaqhm_noise_from_cepstrum_kernel  one wave per row: the spectrum of a cepstral row on the warp kernel's grid by
+//                                Clenshaw's recurrence, then that kernel's lag sums and Levinson-Durbin recursion
 //   eaqhm_noise_modulation_kernel   one wave per frame, lanes over the frame's samples: the Fourier coefficients of the
 //                                   residual's power over the fundamental's phase
 //   eaqhm_noise_combine_mod_kernel  the combine kernel with each frame's pitch-synchronous gain g_q(n')
@@ -159,9 +163,11 @@ constexpr int NE_WAVES = 4;   // frames (waves) per block of the envelope kernel
 
 // The Levinson-Durbin recursion of eaqhm_noise_analyse_kernel on r[l] of lane l (r[0] > 0), a second copy: calling one
 // function from both changed the analysis kernel's machine code (tools/isa_diff.py).  Leaves k_lane in kk (lanes 1..p;
-// 0 from the stage it stopped at) and returns E.
+// 0 from the stage it stopped at) and returns E.  Inflate = false leaves r[0] as it is: the -90 dB white floor that
+// steadies an analysed frame would be the whole error of the exact way back from a cepstrum.
+template <bool Inflate = true>
 __device__ __forceinline__ double levinson_lanes(double r, int p, int lane, double& kk) {
-  if (lane == 0) r *= (1.0 + 1e-9);
+  if (Inflate && lane == 0) r *= (1.0 + 1e-9);
   double E = __shfl(r, 0, 64);
   double a = lane == 0 ? 1.0 : 0.0;
   for (int i = 1; i <= p; ++i) {
@@ -364,8 +370,111 @@ extern "C" __global__ void __launch_bounds__(64 * NE_WAVES)
   noise_envelope_frame(sigma, refl, p, lane, m, live, rd, aw[wave], fnorm, F, out);
 }
 
+// ---- the noise model to and from cepstral rows (tests/noise_cepstrum_ref.py)
+constexpr int NC_WAVES = 4;   // frames (waves) per block of the cepstrum kernel
+
+// ceps[m][0..Q] of C_m(w) = ln(sigma_m / |A_m(e^{jw})|) = c_0 + 2 sum_q c_q cos(q w): c_0 = ln sigma_m, c_q = h_q / 2 with
+// h_n = -a_n - (sum_{k=1}^{n-1} (k h_k) a_{n-k}) / n, a_j = 0 past p (the LPC-to-cepstrum recursion).  Lanes over k:
+// lane k keeps k h_k in a register, step n reads a[n - lane] (consecutive LDS addresses) and the sum is wave_sum's
+// butterfly, so a step costs one product and six cross-lane adds whatever p is.  A silent frame gives (-inf, 0, .., 0).
+// LDS (static): a[0..63] per wave.  Every wave of the block reaches the barrier.
+extern "C" __global__ void __launch_bounds__(64 * NC_WAVES)
+    eaqhm_noise_cepstrum_kernel(const double* __restrict__ sigma, const double* __restrict__ refl, int Nf, int p, int Q,
+                                double* __restrict__ ceps) {
+  __shared__ double aw[NC_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NC_WAVES + wave;
+  const bool live = m < Nf;
+  const double kin = (live && lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
+  double* a = aw[wave];
+  a[lane] = stepup_lanes(kin, p, lane);            // zero on the lanes past p
+  __syncthreads();
+  if (!live) return;
+  const double sg = sigma[m];
+  double kh = 0.0, cq = 0.0;                       // lane k: k h_k and c_k
+  for (int n = 1; n <= Q; ++n) {
+    const bool in = lane >= 1 && lane < n;
+    const double ak = a[in ? n - lane : 0];
+    const double s = wave_sum(in ? kh * ak : 0.0);
+    const double h = -a[n] - s / (double)n;
+    if (lane == n) {
+      kh = (double)n * h;
+      cq = 0.5 * h;
+    }
+  }
+  if (lane == 0) cq = log(sg);
+  if (!(sg > 0.0)) cq = lane == 0 ? -INFINITY : 0.0;
+  if (lane <= Q) ceps[(size_t)m * (Q + 1) + lane] = cq;
+}
+
+// The way back, by the route of the warp kernel: P[t] = exp(2 (C(w_t) - c_0)) = exp(4 sum_q c_q cos(q w_t)) on the grid
+// w_t = pi t / M (Clenshaw's recurrence from cos w_t, which is the block's table entry t), the lag sums and the
+// Levinson-Durbin recursion of noise_warp_frame (without the inflation of r[0]), written a second time so that the warp
+// kernels' machine code stays as it is, and sigma = exp(c_0) sqrt(E).  c_0 never enters P: the reflection coefficients do not depend on it.  An empty
+// row (c_0 = -inf) gives a silent frame.  LDS (static): the cosine table (shared by the block), and per wave P[0..M]
+// and the row c[0..63]: 77 968 bytes, two blocks per CU.  Every wave of the block reaches both barriers.
+extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+    eaqhm_noise_from_cepstrum_kernel(const double* __restrict__ ceps, int Nf, int Q, int p,
+                                     double* __restrict__ sigma_out, double* __restrict__ refl_out) {
+  __shared__ double tab[NW_M + 1];
+  __shared__ double Pw[NW_WAVES][NW_M + 2];
+  __shared__ double cw[NW_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NW_WAVES + wave;
+  const bool live = m < Nf;
+  for (int j = threadIdx.x; j <= NW_M; j += 64 * NW_WAVES) tab[j] = cospi((double)j / (double)NW_M);
+  const double cl = (live && lane <= Q) ? ceps[(size_t)m * (Q + 1) + lane] : 0.0;
+  double* c = cw[wave];
+  double* P = Pw[wave];
+  c[lane] = cl;
+  const double c0 = __shfl(cl, 0, 64);
+  const bool work = live && c0 != -INFINITY;       // uniform over the wave
+  __syncthreads();
+  if (work) {
+    for (int t = lane; t <= NW_M; t += 64) {
+      const double cw2 = 2.0 * tab[t];
+      double b1 = 0.0, b2 = 0.0;
+      for (int q = Q; q >= 1; --q) {               // one LDS address for the wave: a broadcast
+        const double b0 = c[q] + (cw2 * b1 - b2);
+        b2 = b1;
+        b1 = b0;
+      }
+      P[t] = exp(4.0 * (0.5 * cw2 * b1 - b2));
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (!work) {
+    if (lane == 0) sigma_out[m] = 0.0;
+    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = 0.0;
+    return;
+  }
+
+  // r[l] on lane l, as in noise_warp_frame
+  auto ct = [&](int t) {
+    const int idx = (lane * t) & (2 * NW_M - 1);
+    return tab[idx > NW_M ? 2 * NW_M - idx : idx];
+  };
+  double r0 = 0.5 * P[0], r1 = 0.0, r2 = 0.0, r3 = ((lane & 1) ? -0.5 : 0.5) * P[NW_M];
+  for (int t = 1; t + 3 < NW_M; t += 4) {
+    r0 = fma(P[t], ct(t), r0);
+    r1 = fma(P[t + 1], ct(t + 1), r1);
+    r2 = fma(P[t + 2], ct(t + 2), r2);
+    r3 = fma(P[t + 3], ct(t + 3), r3);
+  }
+  r0 = fma(P[NW_M - 3], ct(NW_M - 3), r0);
+  r1 = fma(P[NW_M - 2], ct(NW_M - 2), r1);
+  r2 = fma(P[NW_M - 1], ct(NW_M - 1), r2);
+  const double r = ((r0 + r1) + (r2 + r3)) / (double)NW_M;
+
+  double kk = 0.0;
+  const double E = levinson_lanes<false>(r, p, lane, kk);
+  if (lane == 0) sigma_out[m] = exp(c0) * sqrt(E);
+  if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = kk;
+}
+
 // ---- pitch-synchronous modulation of the noise (tests/noise_modulation_ref.py)
-constexpr int NM_WAVES = 4;   // frames (waves) per block of the modulation kernel
+constexpr int NM_WAVES = 4;  // frames (waves) per block of the modulation kernel
 constexpr int NM_MAX = 8;     // harmonics of the envelope (M of the definition) at most
 
 // i of the definition: the instant nearest to input position x
@@ -606,6 +715,32 @@ extern "C" int eaqhm_noise_envelope_map(eaqhm_ctx* ctx, const double* sigma, con
   hipLaunchKernelGGL(eaqhm_noise_envelope_map_kernel, dim3((unsigned)(((int64_t)Nf + NE_WAVES - 1) / NE_WAVES)),
                      dim3(64 * NE_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, f_in, f_out, (int)B, fnorm,
                      (int)F, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+// ---- the noise model to and from cepstral rows
+extern "C" int eaqhm_noise_cepstrum(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                                    int32_t ceps_order, double* ceps) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!sigma || !refl || !ceps || Nf < 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_cepstrum: bad argument");
+  if (order < 1 || order > 63 || ceps_order < 1 || ceps_order > 63)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_cepstrum: need 1 <= order <= 63 and 1 <= ceps_order <= 63");
+  hipLaunchKernelGGL(eaqhm_noise_cepstrum_kernel, dim3((unsigned)(((int64_t)Nf + NC_WAVES - 1) / NC_WAVES)),
+                     dim3(64 * NC_WAVES), 0, ctx->stream, sigma, refl, (int)Nf, (int)order, (int)ceps_order, ceps);
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_from_cepstrum(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order,
+                                         int32_t order, double* sigma_out, double* refl_out) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!ceps || !sigma_out || !refl_out || Nf < 1)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_from_cepstrum: bad argument");
+  if (order < 1 || order > 63 || ceps_order < 1 || ceps_order > 63)
+    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_from_cepstrum: need 1 <= order <= 63 and 1 <= ceps_order <= 63");
+  hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_kernel, dim3((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)),
+                     dim3(64 * NW_WAVES), 0, ctx->stream, ceps, (int)Nf, (int)ceps_order, (int)order, sigma_out, refl_out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -57,6 +57,8 @@ SYMBOLS = (
     ("eaqhm_dtw", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     ("eaqhm_model_build", C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _I32, _F64, _I32, _I32, _I32, _P]),
     ("eaqhm_cepstrum_phase", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
+    ("eaqhm_noise_cepstrum", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P]),
+    ("eaqhm_noise_from_cepstrum", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
 )
 
 
@@ -295,6 +297,13 @@ class Context:
         f_in, f_out, B = warp or (None, None, 0)
         self._ck(self.lib.eaqhm_cepstrum_phase(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha), _ptr(f_in),
                                                _ptr(f_out), B, _ptr(freqs), F, _ptr(out)))
+
+    # the noise model to and from cepstral rows: ceps [Nf][Q + 1], refl [Nf][p]
+    def noise_cepstrum(self, sigma, refl, Nf, p, Q, ceps):
+        self._ck(self.lib.eaqhm_noise_cepstrum(self.h, _ptr(sigma), _ptr(refl), Nf, p, Q, _ptr(ceps)))
+
+    def noise_from_cepstrum(self, ceps, Nf, Q, p, sigma_out, refl_out):
+        self._ck(self.lib.eaqhm_noise_from_cepstrum(self.h, _ptr(ceps), Nf, Q, p, _ptr(sigma_out), _ptr(refl_out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

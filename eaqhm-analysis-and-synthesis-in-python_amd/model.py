@@ -1444,6 +1444,115 @@ def noise_envelope(noise, fs, freqs, formant_scale=1.0, *, formant_warp=None, de
     return out.cpu().numpy()
 
 
+# ---- the noise model to and from cepstral rows
+NOISE_CEPSTRUM_EXP_MAX = 600.0   # 4 sum_q |c_q| at most: exp(2 (C - c_0)) stays in the normal range of a double
+NOISE_CEPSTRUM_LEVEL_MAX = 700.0  # c_0 + 2 sum_q |c_q| at most: sigma = exp(c_0) sqrt(E) stays finite
+
+
+def check_noise_cepstrum_arguments(noise, order=63):
+    """Validates everything noise_cepstrum gets (no device work): returns (model, Q) with Q = order in [1, 63]."""
+    return check_noise_model(noise), _cepstrum_order(order)
+
+
+def noise_cepstrum(noise, order=63, *, device_index=0):
+    """The noise model in cepstral rows: row m holds c_0..c_Q, Q = `order` in [1, 63] (independent of
+    the model's LPC order), of C_m(w) = ln(sigma_m / |A_m(e^{jw})|) = c_0 + 2 sum_q c_q cos(q w): the natural log of an
+    amplitude in model_cepstrum's layout, so cepstrum_envelope, warp_rows and model_align take the rows unchanged.
+    c_0 = ln sigma and c_q = h_q / 2 from the LPC-to-cepstrum recursion: the exact cepstrum of the all-pole frame cut
+    at Q, which is the best cosine approximation of that order in the mean square; nothing is fitted, there is no
+    lambda.  2 * cepstrum_envelope(rows, fs, f) is noise_envelope(noise, fs, f) up to the cut's remainder.  A silent
+    frame (sigma == 0) gives (-inf, 0, .., 0).  The level is that of a spectral density per sample (sigma is the
+    standard deviation of the white excitation): it is not comparable to the level of model_cepstrum's harmonic
+    envelope.  Returns float64[Nf, Q + 1]."""
+    nz, Q = check_noise_cepstrum_arguments(noise, order)
+    torch, c, dev = _device(device_index)
+    sigma_d, refl_d = (torch.as_tensor(x, device=dev) for x in (nz["sigma"], nz["refl"]))
+    Nf = len(nz["sigma"])
+    ceps = torch.empty((Nf, Q + 1), dtype=torch.float64, device=dev)
+    c.noise_cepstrum(sigma_d, refl_d, Nf, nz["order"], Q, ceps)
+    return ceps.cpu().numpy()
+
+
+def check_noise_from_cepstrum_arguments(ceps, hop, fs, order=None, length=None, mod=None, mod_harmonics=None):
+    """Validates everything noise_from_cepstrum gets (no device work): returns (rows float64[Nf, Q + 1], the model's
+    other entries as a dict: hop, order, fs, length and, when given, mod and mod_harmonics).  `order` defaults to
+    min(63, 2 + round(fs / 1000)), `length` to (Nf - 1) * hop + 1 and must give Nf = (length - 1) // hop + 1 rows.  A row
+    that is not empty needs 4 sum_{q>=1} |c_q| <= 600 and c_0 + 2 sum_{q>=1} |c_q| <= 700."""
+    C = _cepstrum_rows(ceps, "ceps")
+    fs = _sample_rate(fs)
+    hop = _integer(hop, "hop")
+    order = min(NOISE_MAX_ORDER, 2 + int(round(fs / 1000.0))) if order is None else _integer(order, "order")
+    _noise_shape(hop, order)
+    Nf = len(C)
+    length = (Nf - 1) * hop + 1 if length is None else _integer(length, "length")
+    if length < 1 or (length - 1) // hop + 1 != Nf:
+        raise ValueError("%d rows at hop %d need (length - 1) // hop + 1 == %d, got length %d" % (Nf, hop, Nf, length))
+    live = ~np.isneginf(C[:, 0])
+    swing = 2.0 * np.abs(C[:, 1:]).sum(axis=1)
+    if np.any(2.0 * swing[live] > NOISE_CEPSTRUM_EXP_MAX):
+        raise ValueError("row %d: 4 sum |c_q| must be <= %g, the spectrum's exp would leave the range of a double"
+                         % (int(np.flatnonzero(live & (2.0 * swing > NOISE_CEPSTRUM_EXP_MAX))[0]),
+                            NOISE_CEPSTRUM_EXP_MAX))
+    if np.any(C[live, 0] + swing[live] > NOISE_CEPSTRUM_LEVEL_MAX):
+        raise ValueError("c_0 + 2 sum |c_q| must be <= %g: sigma would not be finite" % NOISE_CEPSTRUM_LEVEL_MAX)
+    extra = {}
+    if mod is not None or mod_harmonics is not None:
+        if mod is None or mod_harmonics is None:
+            raise ValueError("mod and mod_harmonics come together")
+        extra = dict(mod=mod, mod_harmonics=mod_harmonics)
+    shell = check_noise_model(dict(sigma=np.zeros(Nf), refl=np.zeros((Nf, order)), hop=hop, order=order, fs=fs,
+                                   length=length, **extra))
+    del shell["sigma"], shell["refl"]
+    return C, shell
+
+
+def noise_from_cepstrum(ceps, hop, fs, *, order=None, length=None, mod=None, mod_harmonics=None, device_index=0):
+    """A noise model from cepstral rows, the way back from noise_cepstrum: `ceps` float64[Nf, Q + 1]
+    holds one row per noise frame (noise_cepstrum's, or rows blended, aligned or built by the caller), frames `hop`
+    samples apart.  Per row the power spectrum P[t] = exp(2 (C(w_t) - c_0)) is taken on eaQHMNoiseWarp's 1025-point
+    grid, turned into an autocorrelation and fitted by the analysis's Levinson-Durbin recursion at `order` (default
+    min(63, 2 + round(fs / 1000)), eaQHMNoiseAnalysis's); sigma = exp(c_0) sqrt(E).  c_0 is kept out of the exponent:
+    the reflection coefficients do not depend on column 0 bit for bit, adding d to it multiplies sigma by e^d, and the
+    level cannot overflow the grid sums.  A row (-inf, 0, .., 0) gives a silent frame.  `length` (default
+    (Nf - 1) * hop + 1) must give Nf = (length - 1) // hop + 1; `mod` / `mod_harmonics` (eaQHMNoiseModulation's) are
+    copied into the model under check_noise_model's rules.  A row needs 4 sum_{q>=1} |c_q| <= 600.
+
+    Returns dict(sigma, refl, hop, order, fs, length[, mod, mod_harmonics]), a model eaQHMNoiseSynthesis,
+    eaQHMNoiseWarp and eaQHMSynthesis(noise=) take."""
+    C, shell = check_noise_from_cepstrum_arguments(ceps, hop, fs, order, length, mod, mod_harmonics)
+    torch, c, dev = _device(device_index)
+    Nf, Q, p = len(C), C.shape[1] - 1, shell["order"]
+    sigma = torch.empty(Nf, dtype=torch.float64, device=dev)
+    refl = torch.empty((Nf, p), dtype=torch.float64, device=dev)
+    c.noise_from_cepstrum(torch.as_tensor(C, device=dev), Nf, Q, p, sigma, refl)
+    return check_noise_model(dict(shell, sigma=sigma.cpu().numpy(), refl=refl.cpu().numpy()))
+
+
+def noise_alignment_index(idx, detA, noiseA, detB, noiseB):
+    """An alignment of two models' instants carried over to their noise frames (host only).  `idx` is
+    alignment_index's output, B's (fractional) instant per instant of A.  Noise frame m of A sits at sample m hopA: its
+    fractional position among A's instants (held past the last one) reads `idx` by linear interpolation, B's instants
+    turn that into a sample position of B, and the position over hopB, clipped to [0, NfB - 1], is the (fractional)
+    frame of B.  The instants of a model are equally spaced, so the two interpolations are one: np.interp over A's
+    instants of the B sample positions idx maps them to, which returns arange(Nf) exactly for idx = arange(n), the same
+    instants and equal hops.  Both models need the same fs.  Returns float64[NfA]:
+    noise_from_cepstrum(warp_rows(noise_cepstrum(noiseB), j), noiseA["hop"], fs, length=noiseA["length"]) is B's noise at
+    A's timing."""
+    nzA, nzB = check_noise_model(noiseA), check_noise_model(noiseB)
+    if nzA["fs"] != nzB["fs"]:
+        raise ValueError("the two noise models have different fs: %g and %g" % (nzA["fs"], nzB["fs"]))
+    tiA = unpack_model(detA)["ti"].astype(np.float64)
+    tiB = unpack_model(detB)["ti"].astype(np.float64)
+    t = _numeric_1d(idx, "idx")
+    if len(t) != len(tiA):
+        raise ValueError("idx must have one value per analysis instant of A (%d), got %d" % (len(tiA), len(t)))
+    if not np.all(np.isfinite(t)):
+        raise ValueError("idx must be finite")
+    at_instants = np.interp(t, np.arange(len(tiB), dtype=np.float64), tiB)     # B's sample position per instant of A
+    pos = np.arange(len(nzA["sigma"]), dtype=np.float64) * float(nzA["hop"])
+    return np.clip(np.interp(pos, tiA, at_instants) / float(nzB["hop"]), 0.0, len(nzB["sigma"]) - 1.0)
+
+
 # ---- pitch-synchronous modulation of the noise (DESIGN.md §10.2)
 def _mod_harmonics(M, name="harmonics"):
     M = _integer(M, name)

@@ -445,6 +445,29 @@ int eaqhm_cepstrum_phase(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t 
                          const double* f_in, const double* f_out, int32_t B, const double* freqs, int32_t F,
                          double* out);
 
+/* the noise model to and from cepstral rows (additions under ABI 6) ----------------------------------
+ * A frame (sigma, k_1..k_order) has the log-amplitude spectrum C(w) = ln(sigma / |A(e^{jw})|) = c_0 + 2 sum_q c_q
+ * cos(q w), the layout of eaqhm_model_cepstrum.  The level is that of a spectral density per sample (sigma is the
+ * standard deviation of the excitation), not the level of the harmonic envelope.
+ * eaqhm_noise_cepstrum (kernel: one wave per frame, four per block; A(z) by the step-up into the wave's LDS, then
+ *   ceps_order steps of the LPC-to-cepstrum recursion, lanes over the terms of a step, one cross-lane sum per step):
+ *   ceps       double[Nf][ceps_order+1]  c_0 = ln sigma, c_q = h_q / 2, h_n = -a_n - (sum_{k=1..n-1} (k h_k) a_{n-k}) / n
+ *                                        with a_j = 0 for j > order: the exact cepstrum of the frame, cut at ceps_order;
+ *                                        a silent frame (sigma == 0) gives (-inf, 0, .., 0)
+ * eaqhm_noise_from_cepstrum (kernel: one wave per row, eight per block, the block shape of eaqhm_noise_warp: the cosine
+ *   table shared by the block, P[0..1024] and the row in the wave's LDS, 77 968 bytes) fits a frame of `order` to each
+ *   row: P[t] = exp(2 (C(w_t) - c_0)) on the grid w_t = pi t / 1024 by Clenshaw's recurrence, the autocorrelation and
+ *   the Levinson-Durbin recursion of eaqhm_noise_warp, sigma_out = exp(c_0) sqrt(E).  c_0 does not enter P, so refl_out
+ *   does not depend on it.  A row (-inf, 0, .., 0) gives sigma_out = 0 and zeros.
+ *   sigma_out  double[Nf], refl_out double[Nf][order]
+ * The entry points do not read the device arrays: |k| < 1, finite coefficients and 4 sum_q |c_q| <= 600 (exp stays in
+ * the normal range) are the CALLER'S contract (the Python host checks them).
+ * EAQHM_EINVAL for null pointers, Nf < 1, order or ceps_order outside [1, 63].                                        */
+int eaqhm_noise_cepstrum(eaqhm_ctx* ctx, const double* sigma, const double* refl, int32_t Nf, int32_t order,
+                         int32_t ceps_order, double* ceps);
+int eaqhm_noise_from_cepstrum(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order, int32_t order,
+                              double* sigma_out, double* refl_out);
+
 #ifdef __cplusplus
 }
 #endif

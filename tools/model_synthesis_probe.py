@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--align] [--build] [--out FILE]
+                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -31,7 +31,9 @@ next to eaqhm_modify_prep with the envelope at the same beta, with the same wind
 alignment: the model's cepstrum against a copy of itself stretched by warp_rows with a sinusoidal tempo
 0.8-1.25, band 2 s: eaqhm_cepstrum_cost, and eaqhm_dtw's forward pass (with its launch count) and backtrack apart
 (EAQHM_OPT_DTW_PHASES), each the median of three windows with their max - min, and the NumPy model's time for the same
-band on a 5 s excerpt on the host.  EAQHM_LIB selects another build of
+band on a 5 s excerpt on the host.  --noise-cepstrum adds the noise model to and from cepstral rows on
+the workload's residual model: eaqhm_noise_cepstrum (Q = 63) and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp at
+alpha = 1.2, with the same windows and the warp's max - min as the margin.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -110,7 +112,7 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False, formant_warp=False, cepstrum=False, align=False, build=False):
+          noise_modulation=False, formant_warp=False, cepstrum=False, align=False, build=False, noise_cepstrum=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -156,7 +158,37 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
         res["align"] = align_rows(torch, st)
     if build:
         res["build"] = build_rows(torch, st)
+    if noise_cepstrum:
+        import eaqhm_amd
+        res["noise_cepstrum"] = noise_cepstrum_rows(torch, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     return res
+
+
+def noise_cepstrum_rows(torch, nz, Q=63, reps=20, runs=3):
+    """The noise model `nz` to cepstral rows and back, same session: eaqhm_noise_cepstrum at order Q
+    and eaqhm_noise_from_cepstrum on its rows at the model's own LPC order, next to eaqhm_noise_warp at alpha = 1.2 on
+    the same model (base_ms), which shares the way back's lag sums and recursion and is the comparison, not a bar.
+    Each time: median of `runs` warmed windows of `reps` launches; margin_ms = max - min of the warp's windows."""
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+    p, Nf = nz["order"], len(nz["sigma"])
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    sigma, refl = (torch.as_tensor(np.ascontiguousarray(x), device=dev) for x in (nz["sigma"], nz["refl"]))
+    sigma_o, refl_o = torch.empty_like(sigma), torch.empty_like(refl)
+    alpha_d = torch.full((Nf,), 1.2, dtype=torch.float64, device=dev)
+    ceps = torch.empty((Nf, Q + 1), dtype=torch.float64, device=dev)
+    base = med(lambda: c.noise_warp(sigma, refl, Nf, p, alpha_d, sigma_o, refl_o))
+    fwd = med(lambda: c.noise_cepstrum(sigma, refl, Nf, p, Q, ceps))
+    back = med(lambda: c.noise_from_cepstrum(ceps, Nf, Q, p, sigma_o, refl_o))
+    return [dict(setting="Q%d" % Q, hop=nz["hop"], order=p, frames=Nf, silent=int((nz["sigma"] == 0).sum()),
+                 base_ms=base[0], margin_ms=base[1], cepstrum_ms=fwd[0], cepstrum_spread_ms=fwd[1],
+                 from_cepstrum_ms=back[0], from_cepstrum_spread_ms=back[1],
+                 from_cepstrum_to_warp=round(back[0] / base[0], 3), cepstrum_to_warp=round(fwd[0] / base[0], 3))]
 
 
 def build_rows(torch, st, reps=20, runs=3):
@@ -617,10 +649,13 @@ def main():
                     help="also time the alignment kernels on the model against a time-stretched copy of itself")
     ap.add_argument("--build", action="store_true",
                     help="also time eaqhm_model_build next to eaqhm_modify_amp_cepstrum (the model from parameters)")
+    ap.add_argument("--noise-cepstrum", action="store_true",
+                    help="also time eaqhm_noise_cepstrum and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build) for w in a.workloads.split(",")]
+                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build, a.noise_cepstrum)
+           for w in a.workloads.split(",")]
     for r in res:
         print(json.dumps(r))
     if a.out:
