@@ -1,12 +1,14 @@
 // eaqhm_interp.hip — track interpolation, phase integration, additive synthesis and SRER.
 // gfx950 (MI355X) only, FP64.
 //
-//   eaqhm_spline_kernel   one thread per (instant, slot): runs of consecutive accepted instants
+//   eaqhm_spline_kernel   one block per tile of 32 instants x 16 slots, its rows of the records (41 instants of halo
+//                         either side) staged in LDS once: runs of consecutive accepted instants
 //                         (functions.py:350-362) and the not-a-knot cubic second derivatives on their knots
 //                         (functions.py:340, :367; interp1d(kind=3)) through the closed-form inverse of the
 //                         (1,4,1) system — a local 69-term sum instead of a sequential tridiagonal sweep.
 //   eaqhm_spline_edge_kernel  not-a-knot end conditions of every run from its neighbours' moments.
-//   eaqhm_eval_kernel     one block per 16-64 samples x all slots: each knot interval is integrated once (linear
+//   eaqhm_eval_kernel     one block per group of whole knot intervals (about 45 samples; 16-64 samples of an
+//                         interval where the step is larger) x all slots: each knot interval is integrated once (linear
 //                         am, functions.py:364; cubic fm, :367-371 incl. the padded <4-knot case; phase by
 //                         frequency integration with the sine-bump correction, :537-575) into LDS tables; then
 //                         per (sample, slot) the next-iteration frequency from the unwrapped phase (:375) and
@@ -37,12 +39,19 @@ namespace eaqhm {
 #define SPL_CAP 40
 #define SPL_BIG 1000000
 
+// A block of eaqhm_spline_kernel solves SPL_TI instants x SPL_TS columns (slots; the a0 spline is column Kmax) from a
+// tile of the records in LDS: rows [first instant - SPL_HALO, last instant + SPL_HALO] of the accepted flag (the am
+// column; a0 is accepted everywhere) and of the value (the fm column, or a0).  The run masks look SPL_CAP + 1 rows
+// either way and the 69-term sum SPL_W + 2, so 41 rows of halo hold every read.
+#define SPL_HALO 41
+#define SPL_TI 32
+#define SPL_TS 16
+
+static_assert(SPL_TI + 2 * SPL_HALO <= 128, "the accepted flags of a tile column are kept as 128 bits");
+
 struct SplineCol {
-  const double* rec; int RS, off_y, off_acc, No_ti; bool all_acc; double h2;
-  __device__ double y(int i) const { return rec[(size_t)i * RS + off_y]; }
-  __device__ bool acc(int i) const {
-    return i >= 0 && i < No_ti && (all_acc || rec[(size_t)i * RS + off_acc] != 0.0);
-  }
+  const double* ys; int base, kk; double h2;
+  __device__ double y(int i) const { return ys[(i - base) * SPL_TS + kk]; }
   __device__ double d2(int i) const { return 6.0 * ((y(i - 1) - 2.0 * y(i)) + y(i + 1)) / h2; }
 };
 
@@ -50,8 +59,25 @@ __device__ inline double lam_pow(const double* lp, int e) { return e > 79 ? 0.0 
 
 // moment of a knot that is neither the first nor the last of its run; A / B = distance (in knots) to the
 // first / last knot of the run (>= 1), SPL_BIG when farther than SPL_CAP
-__device__ double inner_moment(const SplineCol& C, const double* lp, int i, int A, int B) {
+__device__ double inner_moment(const SplineCol& C, const double* lp, const double* wt, int i, int A, int B) {
   if (A == 1 || B == 1) return C.d2(i) / 6.0;
+  if (A >= SPL_BIG && B >= SPL_BIG) {
+    // farther than SPL_CAP from both ends of the run (most knots of a long run): the general expression below
+    // multiplies every weight by 1.0 twice and subtracts nothing from any row, so the weights come from the table
+    // wt[ad] = lam^(ad+1) / (1 - lam^2) — the same sum, term by term
+    const double ih2 = 6.0 / C.h2;
+    double ym = C.y(i - SPL_W - 1), y0 = C.y(i - SPL_W), yp;
+    double acc = 0.0;
+    for (int d = -SPL_W; d <= SPL_W; ++d) {
+      yp = C.y(i + d + 1);
+      const double rhs = ((ym - 2.0 * y0) + yp) * ih2;
+      const int ad = d < 0 ? -d : d;
+      const double w = wt[ad];
+      acc += (ad & 1) ? -w * rhs : w * rhs;
+      ym = y0; y0 = yp;
+    }
+    return acc;
+  }
   const int dlo = (A >= SPL_BIG) ? -SPL_W : max(-SPL_W, 2 - A);
   const int dhi = (B >= SPL_BIG) ? SPL_W : min(SPL_W, B - 2);
   const double lam2 = lp[2];
@@ -80,43 +106,78 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_spline_kernel(const doub
                                                                       unsigned char* __restrict__ code,
                                                                       double* __restrict__ mom) {
   __shared__ double lp[80];
+  __shared__ double ys[(SPL_TI + 2 * SPL_HALO) * SPL_TS];
+  __shared__ unsigned char as[(SPL_TI + 2 * SPL_HALO) * SPL_TS];
+  __shared__ double wt[SPL_W + 1];
+  __shared__ unsigned long long cm[SPL_TS][2];   // a column's accepted flags: row r of the tile is bit r
   if (threadIdx.x < 80) lp[threadIdx.x] = pow(2.0 - sqrt(3.0), (double)threadIdx.x);
-  __syncthreads();
-  const int ld = Kmax + 1;
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long long)ni * ld) return;
-  const int i = i0 + (int)(idx / ld), k = (int)(idx % ld);
-  SplineCol C;
-  C.rec = records; C.RS = 3 * Kmax + 1; C.No_ti = No_ti; C.all_acc = (k == Kmax);
-  C.off_y = (k == Kmax) ? 3 * Kmax : Kmax + k;
-  C.off_acc = (k == Kmax) ? 0 : k;
-  C.h2 = (double)step * (double)step;
-  double M = 0.0;
-  unsigned char cd = 0;
-  if (C.acc(i)) {
-    // accepted neighbours on both sides as bit masks (independent loads, no dependent chain), then the run
-    // lengths are the trailing ones of the masks
-    unsigned long long ml = 0ull, mr = 0ull;
-#pragma unroll 8
-    for (int d = 0; d < SPL_CAP; ++d) {
-      if (C.acc(i - d - 1)) ml |= 1ull << d;
-      if (C.acc(i + d + 1)) mr |= 1ull << d;
-    }
-    const int dl = min(SPL_CAP, __ffsll((long long)~ml) - 1), dr = min(SPL_CAP, __ffsll((long long)~mr) - 1);
-    const bool kl = dl < SPL_CAP, kr = dr < SPL_CAP;
-    const int m = dl + dr + 1;
-    if (kl && kr && m < 4) {
-      cd = (m == 1) ? 1 : (unsigned char)(16 + 4 * m + dl);
-    } else {
-      cd = 2;
-      const int A = kl ? dl : SPL_BIG, B = kr ? dr : SPL_BIG;
-      // the first / last knot of a run takes 2 M_1 - M_2 from its neighbours' moments: eaqhm_spline_edge_kernel
-      // (computing them here would make every wave that holds one edge knot run the 69-term sum three times)
-      if (A != 0 && B != 0) M = inner_moment(C, lp, i, A, B);
+  const int ld = Kmax + 1, nS = (ld + SPL_TS - 1) / SPL_TS;
+  const int ia = i0 + (int)(blockIdx.x / nS) * SPL_TI, ib = min(ia + SPL_TI, i0 + ni);   // instants [ia, ib)
+  const int k0 = (int)(blockIdx.x % nS) * SPL_TS;
+  const int base = ia - SPL_HALO, nrow = ib - ia + 2 * SPL_HALO;
+  {
+    // one row of the tile is SPL_TS neighbouring columns of a record: coalesced along the slot axis
+    const size_t RS = 3 * (size_t)Kmax + 1;
+    for (int q = threadIdx.x; q < nrow * SPL_TS; q += blockDim.x) {
+      const int i = base + q / SPL_TS, k = k0 + q % SPL_TS;
+      double y = 0.0;
+      unsigned char a = 0;
+      if (i >= 0 && i < No_ti && k < ld) {
+        const double* row = records + (size_t)i * RS;
+        if (k == Kmax) { y = row[3 * Kmax]; a = 1; }
+        else { y = row[Kmax + k]; a = row[k] != 0.0; }
+      }
+      ys[q] = y; as[q] = a;
     }
   }
-  mom[(size_t)i * ld + k] = M;
-  if (k < Kmax) code[(size_t)i * Kmax + k] = cd;
+  __syncthreads();
+  {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;   // (256 threads: four waves)
+    for (int c = w; c < SPL_TS; c += 4) {
+      const unsigned long long lo = __ballot(l < nrow && as[l * SPL_TS + c] != 0);
+      const unsigned long long hi = __ballot(64 + l < nrow && as[(64 + l) * SPL_TS + c] != 0);
+      if (l == 0) { cm[c][0] = lo; cm[c][1] = hi; }
+    }
+    if (threadIdx.x <= SPL_W) {
+      const double lam2 = lp[2], np1 = 0.0;
+      const double iden = 1.0 / ((1.0 - lam2) * (1.0 - np1));
+      wt[threadIdx.x] = (lp[threadIdx.x + 1] * 1.0) * (1.0 * iden);
+    }
+  }
+  __syncthreads();
+  for (int q = threadIdx.x; q < (ib - ia) * SPL_TS; q += blockDim.x) {
+    const int i = ia + q / SPL_TS, kk = q % SPL_TS, k = k0 + kk;
+    if (k >= ld) continue;
+    SplineCol C;
+    C.ys = ys; C.base = base; C.kk = kk;
+    C.h2 = (double)step * (double)step;
+    double M = 0.0;
+    unsigned char cd = 0;
+    const int p = i - base;   // the instant's row in the tile: SPL_HALO <= p < SPL_HALO + SPL_TI
+    const unsigned long long m0 = cm[kk][0], m1 = cm[kk][1];
+    if (((p < 64 ? m0 >> p : m1 >> (p - 64)) & 1ull) != 0) {
+      // accepted neighbours on both sides as bit masks (bit d: the instant d + 1 away), then the run lengths are the
+      // trailing ones of the masks
+      const int sr = p + 1;   // 42 .. 73
+      const unsigned long long mr = (sr < 64 ? (m0 >> sr) | (m1 << (64 - sr)) : m1 >> (sr - 64)) & ((1ull << SPL_CAP) - 1);
+      // rows p-1, p-2, ... from bit 63 downwards
+      const unsigned long long lt = p < 64 ? m0 << (64 - p) : (p == 64 ? m0 : (m1 << (128 - p)) | (m0 >> (p - 64)));
+      const int dl = min(SPL_CAP, ~lt ? (int)__clzll((long long)~lt) : 64), dr = min(SPL_CAP, __ffsll((long long)~mr) - 1);
+      const bool kl = dl < SPL_CAP, kr = dr < SPL_CAP;
+      const int m = dl + dr + 1;
+      if (kl && kr && m < 4) {
+        cd = (m == 1) ? 1 : (unsigned char)(16 + 4 * m + dl);
+      } else {
+        cd = 2;
+        const int A = kl ? dl : SPL_BIG, B = kr ? dr : SPL_BIG;
+        // the first / last knot of a run takes 2 M_1 - M_2 from its neighbours' moments: eaqhm_spline_edge_kernel
+        // (computing them here would make every wave that holds one edge knot run the 69-term sum three times)
+        if (A != 0 && B != 0) M = inner_moment(C, lp, wt, i, A, B);
+      }
+    }
+    mom[(size_t)i * ld + k] = M;
+    if (k < Kmax) code[(size_t)i * Kmax + k] = cd;
+  }
 }
 
 // not-a-knot end conditions: M_0 = 2 M_1 - M_2 and M_{m-1} = 2 M_{m-2} - M_{m-3} for runs of m >= 4 knots (code 2)
@@ -213,35 +274,49 @@ __device__ inline double unwrap_diff(double dd) {
   return m;
 }
 
-// Block of TBS consecutive samples x all slots, two stages.
+// Block of up to TBS consecutive samples x all slots.  Blocks sit on a grid that is fixed to sample 0 whatever the
+// range: block B owns the samples (B*TBS - TBS, B*TBS], clipped to [t_lo, t_hi) (block 0 is sample 0 alone).  Where the
+// step allows, TBS is a multiple of it, so a block owns whole knot intervals and every interval is integrated by
+// exactly one block; a step larger than a block leaves blocks that cover part of an interval.
 //   stage 1  one thread per (knot interval, slot) touching the block: phase_integr_interpolation
 //            (functions.py:537-575) of the whole interval ONCE, in the reference's summation order — cumulative
 //            sum of the instantaneous frequency, shifted to start at the analysed phase, minus the cumulative
-//            sine bump that closes the phase error at the next knot.  The values at the block's samples go to
-//            LDS:  X1[k][s] phase at sample s, X2[k][s] phase one sample earlier (same interval),
-//            X3[k][knot] fm_recon at the first sample of the interval that starts at the knot.
+//            sine bump that closes the phase error at the next knot.  The running sum goes to LDS as it is formed and
+//            takes the shift and the bump in place once the closing error is known, so the piece is evaluated once per
+//            sample.  X1[k][c] phase at sample t0 + c (c = 0: the sample before the block's first), XS[k][interval]
+//            phase at the interval's first sample as the interval itself integrates it, XA[k][interval] the slope of
+//            the linear amplitude, X3[k][knot] fm_recon at the
+//            first sample of the interval that starts at the knot (for the block's last knot that interval belongs
+//            to the next block: only its P(0) is taken).
 //   stage 2  one thread per (sample, slot group): amplitudes, next-iteration frequency from the unwrapped phase
-//            (functions.py:375), knot bookkeeping, am*cos(ph) into LDS; then one thread per sample adds the
-//            slots in slot order, the a0 spline and the reconstruction error (functions.py:385-388).
-extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, int TBS, int NK, int NR) {
+//            (functions.py:375; "one sample earlier" is the neighbouring cell of X1, or XS at an interval's first
+//            sample), knot bookkeeping, am*cos(ph) into LDS; then one thread per sample adds the slots in slot order,
+//            the a0 spline and the reconstruction error (functions.py:385-388).
+extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, int TBS, int NK, int NI, int NR,
+                                                                    long long B0) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int D = A.step, K = A.Kmax;
   double* ft = lds;                           // D+1
   double* X1 = lds + ((D + 1 + 1) & ~1);      // [K][TP]
-  const int TP = TBS + 1;                     // row stride: stage 1 writes a column of slots at once (bank spread)
-  double* X2 = X1 + (size_t)K * TP;           // [K][TP]
-  double* X3 = X2 + (size_t)K * TP;           // [K][NK]
-  double* crec = X3 + (size_t)K * NK;         // [NR][3K+1]   staged rows of the records
+  const int TP = (TBS + 1) | 1;               // odd row stride: stage 1 writes a column of slots at once (bank spread)
+  double* X3 = X1 + (size_t)K * TP;           // [K][NK]
+  double* XS = X3 + (size_t)K * NK;           // [K][NI]
+  double* XA = XS + (size_t)K * NI;           // [K][NI]
+  double* crec = XA + (size_t)K * NI;         // [NR][3K+1]   staged rows of the records
   double* cmom = crec + (size_t)NR * (3 * K + 1);                    // [NR][K+1]
   unsigned char* ccode = (unsigned char*)(cmom + (size_t)NR * (K + 1));   // [NR][K]
   const int tid = threadIdx.x;
-  const long long t0 = A.t_lo + (long long)blockIdx.x * TBS;
-  const long long t1 = (t0 + TBS < A.t_hi) ? (t0 + TBS) : A.t_hi;      // block covers [t0, t1)
-  const long long tk0 = ((t0 + D - 1) / D) * D;                        // first knot at or after t0
+  const long long Bi = B0 + blockIdx.x;
+  const long long t1 = Bi * TBS, t0 = (Bi == 0) ? -1 : t1 - TBS;      // the block owns (t0, t1] ...
+  const long long cl = (t0 + 1 > A.t_lo) ? t0 + 1 : A.t_lo;           // ... of which [cl, ch] lie in the range (never empty)
+  const long long ch = (t1 < A.t_hi - 1) ? t1 : A.t_hi - 1;
+  const long long tk0 = ((t0 + D) / D) * D;                           // first knot after t0
+  // intervals (j, j+1) that hold one of the samples [cl, ch] past their first
+  const int jlo = (cl > 0) ? (int)((cl - 1) / D) : 0, jhi = (ch > 0) ? (int)((ch - 1) / D) : -1;
+  const int nint = jhi - jlo + 1;
   // the instants this block touches: one before its first interval to two after its last (coalesced rows)
   RowCache C;
   {
-    const int jlo = (int)((t0 > 0) ? ((t0 - 1) / D) : 0), jhi = (int)((t1 - 1) / D);
     C.r0 = (jlo > 0) ? jlo - 1 : 0;
     C.r1 = (jhi + 2 < A.No_ti) ? jhi + 2 : A.No_ti - 1;
     if (C.r1 > C.r0 + NR - 1) C.r1 = C.r0 + NR - 1;
@@ -254,48 +329,51 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
   }
   for (int u = tid; u <= D; u += blockDim.x) ft[u] = sin(M_PI * (double)u / (double)D);
   __syncthreads();
-  // ---- stage 1: intervals (j, j+1) whose samples j*D .. (j+1)*D meet the block
+  // ---- stage 1: the intervals jlo .. jhi, and P(0) of interval jhi + 1 where it starts on a sample of the block
   {
-    const int jlo = (int)((t0 > 0) ? ((t0 - 1) / D) : 0), jhi = (int)((t1 - 1) / D);
-    const int nint = jhi - jlo + 1;
     const double scale = 2.0 * M_PI / A.fs;
-    for (int p = tid; p < nint * K; p += blockDim.x) {
+    for (int p = tid; p < (nint + 1) * K; p += blockDim.x) {
       const int jj = p / K, k = p - jj * K, j = jlo + jj;
       if (j + 1 >= A.No_ti) continue;
+      const long long tb = (long long)j * D;
+      if (jj == nint && tb > ch) continue;
       Slot S{A, C, k};
       const int cj = S.code(j);
       if (cj == 0 || S.code(j + 1) == 0) continue;
       const FmPiece P = make_piece(S, j, cj);
       const double p0 = P(0), w0 = scale * p0;
+      if (tb >= cl && tb <= ch) X3[(size_t)k * NK + (int)((tb - tk0) / D)] = p0;
+      if (jj == nint) continue;
+      {   // slope of the linear amplitude (functions.py:364), the same for every sample of the interval
+        const double x0 = (double)j * (double)D, x1 = (double)(j + 1) * (double)D;
+        XA[(size_t)k * NI + jj] = (S.am(j + 1) - S.am(j)) / (x1 - x0);
+      }
+      // the interval's samples tb + u with ua <= u <= ub have a cell in X1
+      const int ua = (int)(t0 - tb), ub = (int)(t1 - tb);
+      double* x = X1 + (size_t)k * TP - ua;
       double acc = w0;
-      for (int u = 1; u <= D; ++u) acc += scale * P(u);
+      for (int u = 1; u <= D; ++u) {
+        acc += scale * P(u);
+        if (u >= ua && u <= ub) x[u] = acc;
+      }
       const double shift = S.ph(j) - w0;
       const double e = (acc + shift) - S.ph(j + 1);
       const double Mr = rint(e / (2.0 * M_PI));
       const double er = M_PI * (e - 2.0 * M_PI * Mr) / (2.0 * (double)D);
-      const long long tb = (long long)j * D;
-      if (tb >= t0 && tb < t1) X3[(size_t)k * NK + (int)((tb - tk0) / D)] = p0;
       acc = w0;
       double c = ft[0] * er;
-      double prev = (acc + shift) - c;
+      XS[(size_t)k * NI + jj] = (acc + shift) - c;
       for (int u = 1; u <= D; ++u) {
-        acc += scale * P(u);
         c += ft[u] * er;
-        const double ph = (acc + shift) - c;
-        const long long t = tb + u;
-        if (t >= t0 && t < t1) {
-          X1[(size_t)k * TP + (int)(t - t0)] = ph;
-          X2[(size_t)k * TP + (int)(t - t0)] = prev;
-        }
-        prev = ph;
+        if (u >= ua && u <= ub) x[u] = (x[u] + shift) - c;
       }
     }
   }
   __syncthreads();
   // ---- stage 2
   const int s = tid % TBS, g = tid / TBS, G = blockDim.x / TBS;
-  const long long t = t0 + s;
-  const bool live = t < A.t_hi;
+  const long long t = t0 + 1 + s;
+  const bool live = g < G && t >= cl && t <= ch;
   int i = 0, r = 0;
   bool past = false;
   if (live) {
@@ -303,17 +381,23 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
     r = (int)(t - (long long)i * D);
     if (i >= A.No_ti) { i = A.No_ti - 1; r = (int)(t - (long long)i * D); }  // beyond the last instant
     past = (i == A.No_ti - 1) && (r > 0);
-    for (int k = g; k < K; k += G) {
+  }
+  // a thread reads its own cell of X1 and its left neighbour's, and then puts am*cos(ph) into its own: all the reads
+  // of a row come before the barrier, and each round of the loop works on rows of its own
+  for (int k = g; k - g < K; k += G) {   // (the same number of rounds for every thread: the barrier)
+    const bool on = live && k < K;
+    double prod = 0.0;
+    if (on) {
       Slot S{A, C, k};
+      const double* x = X1 + (size_t)k * TP + s + 1;   // this sample's cell
       double amv = 0.0, phv = 0.0, fnext = 0.0;
       const int ci = S.code(i);
       if (!past && r > 0) {
         const int cn = S.code(i + 1);
         if (ci != 0 && cn != 0) {  // inside the active interval (i, i+1)
-          const double x0 = (double)i * (double)D, x1 = (double)(i + 1) * (double)D;
-          const double a0v = S.am(i), a1v = S.am(i + 1);
-          amv = ((a1v - a0v) / (x1 - x0)) * ((double)t - x0) + a0v;
-          const double pr = X1[(size_t)k * TP + s], pm = X2[(size_t)k * TP + s];
+          const double x0 = (double)i * (double)D;
+          amv = XA[(size_t)k * NI + (i - jlo)] * ((double)t - x0) + S.am(i);
+          const double pr = x[0], pm = (r == 1) ? XS[(size_t)k * NI + (i - jlo)] : x[-1];
           phv = pr;
           fnext = A.fs / (2.0 * M_PI) * unwrap_diff(pr - pm);
         }
@@ -325,7 +409,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
             phv = S.ph(i);  // isolated accepted instant: frame-centre values stay as written
           } else {
             double pD = 0.0, pDm1 = 0.0;
-            if (prev) { pD = X1[(size_t)k * TP + s]; pDm1 = X2[(size_t)k * TP + s]; }
+            if (prev) { pD = x[0]; pDm1 = (D == 1) ? XS[(size_t)k * NI + (i - 1 - jlo)] : x[-1]; }
             if (next) {
               const double p0 = X3[(size_t)k * NK + (int)((t - tk0) / D)];
               const double w0 = (2.0 * M_PI / A.fs) * p0;
@@ -345,16 +429,20 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
         A.am_out[(size_t)k * A.Lt + t] = amv;
         A.fm_out[(size_t)k * A.Lt + t] = fnext;
       }
-      if (A.s_hat) X1[(size_t)k * TP + s] = (amv != 0.0) ? amv * cos(phv) : 0.0;   // same thread read this cell above
+      prod = (amv != 0.0) ? amv * cos(phv) : 0.0;
+    }
+    if (A.s_hat) {   // (uniform over the grid)
+      __syncthreads();
+      if (on) X1[(size_t)k * TP + s + 1] = prod;
     }
   }
   if (!A.s_hat) return;   // (uniform over the grid: a track-only pass)
   __syncthreads();
   long long e[ES_LIMBS - 1] = {0, 0, 0, 0, 0, 0, 0};
-  if (tid < TBS && live) {
+  if (g == 0 && live) {
     double synth = 0.0;
 #pragma unroll 8
-    for (int k = 0; k < K; ++k) synth += X1[(size_t)k * TP + s];   // slot order; the loads of eight slots in flight
+    for (int k = 0; k < K; ++k) synth += X1[(size_t)k * TP + s + 1];   // slot order; the loads of eight slots in flight
     // a0: not-a-knot spline through every instant, extrapolated past the last one (functions.py:340)
     int ia = i;
     if (ia > A.No_ti - 2) ia = A.No_ti - 2;
@@ -374,7 +462,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_eval_kernel(EvalArgs A, 
       }
     }
   }
-  if (tid < 64) {   // TBS <= 64: the block's samples sit in the first wave
+  if (tid < 64) {   // TBS <= 64 (EVAL_SAMPLES_MAX): the block's samples sit in the first wave
 #pragma unroll
     for (int q = 0; q < ES_LIMBS - 1; ++q) {
       for (int o = 32; o > 0; o >>= 1) e[q] += __shfl_xor(e[q], o);
@@ -472,14 +560,16 @@ extern "C" int eaqhm_spline_solve_range(eaqhm_ctx* ctx, const double* records, i
   if (No_ti < 4) return ctx->fail(EAQHM_EINVAL, "eaqhm_spline_solve: need at least 4 analysis instants (interp1d kind=3)");
   const int ld = Kmax + 1;
   auto blocks = [&](int n) { return dim3((unsigned)(((long long)n * ld + 255) / 256)); };
+  // eaqhm_spline_kernel: tiles of SPL_TI instants x SPL_TS columns
+  auto tiles = [&](int n) { return dim3((unsigned)(((n + SPL_TI - 1) / SPL_TI) * ((ld + SPL_TS - 1) / SPL_TS))); };
   // moments two instants beyond the range feed the end conditions of runs that start / stop inside it
   const int a = (i_lo - 2 > 0) ? i_lo - 2 : 0, b = (i_hi + 2 < No_ti) ? i_hi + 2 : No_ti;
-  hipLaunchKernelGGL(eaqhm_spline_kernel, blocks(b - a), dim3(256), 0, ctx->stream, records, No_ti, a, b - a, Kmax, step,
+  hipLaunchKernelGGL(eaqhm_spline_kernel, tiles(b - a), dim3(256), 0, ctx->stream, records, No_ti, a, b - a, Kmax, step,
                      code, mom);
   HIP_TRY(ctx, hipGetLastError());
   if (a > 0) {   // the padded <4-knot case looks at the run codes of instants 0..3 wherever it is evaluated
     const int n0 = (a < 4) ? a : 4;
-    hipLaunchKernelGGL(eaqhm_spline_kernel, blocks(n0), dim3(256), 0, ctx->stream, records, No_ti, 0, n0, Kmax, step, code, mom);
+    hipLaunchKernelGGL(eaqhm_spline_kernel, tiles(n0), dim3(256), 0, ctx->stream, records, No_ti, 0, n0, Kmax, step, code, mom);
     HIP_TRY(ctx, hipGetLastError());
   }
   hipLaunchKernelGGL(eaqhm_spline_edge_kernel, blocks(i_hi - i_lo), dim3(256), 0, ctx->stream, code, No_ti, i_lo,
@@ -493,24 +583,44 @@ extern "C" int eaqhm_spline_solve(eaqhm_ctx* ctx, const double* records, int32_t
   return eaqhm_spline_solve_range(ctx, records, No_ti, Kmax, step, 0, No_ti, code, mom);
 }
 
-// samples per block of eaqhm_eval_kernel: the largest of 64/32/16 whose LDS tables fit
-static int eval_block_samples(int Kmax, int step, size_t* lds_bytes, int* nk, int* nr) {
-  for (int tbs = 64; tbs >= 16; tbs >>= 1) {
-    const int NK = tbs / step + 2, NR = tbs / step + 5;   // staged instants: intervals of the block, one before, two after
-    const size_t bytes = (((size_t)step + 2) & ~(size_t)1) * 8 + ((size_t)2 * Kmax * (tbs + 1) + (size_t)Kmax * NK) * 8 +
-                         (size_t)NR * ((3 * (size_t)Kmax + 1) + (Kmax + 1)) * 8 + (((size_t)NR * Kmax + 7) & ~(size_t)7);
-    if (bytes <= 78 * 1024 || tbs == 16) {
-      *lds_bytes = bytes; *nk = NK; *nr = NR;
-      return tbs;
-    }
+// Launch geometry of eaqhm_eval_kernel.  A step of at most EVAL_SAMPLES: blocks of m whole knot intervals, m the
+// largest with m * step <= EVAL_SAMPLES whose LDS tables fit (never fewer than 16 samples: eaqhm_eval_partials_len
+// counts on it).  A larger step: the largest of 64/32/16 samples whose tables fit, as parts of an interval.  Either
+// way a block holds at most EVAL_SAMPLES_MAX samples: the kernel's error sums are reduced within its first wave.
+// 45: measured on synth16k_60s against 30, 60 and 120.
+constexpr int EVAL_SAMPLES = 45, EVAL_SAMPLES_MAX = 64;
+static_assert(EVAL_SAMPLES >= 16 && EVAL_SAMPLES <= EVAL_SAMPLES_MAX, "blocks of 16 .. 64 samples");
+struct EvalGeometry { int TBS, NK, NI, NR; size_t lds_bytes; };
+static EvalGeometry eval_geometry(int Kmax, int step) {
+  auto make = [&](int tbs, int ni) {
+    EvalGeometry g;
+    g.TBS = tbs; g.NK = tbs / step + 1; g.NI = ni; g.NR = ni + 3;   // staged instants: one before the intervals, two after
+    g.lds_bytes = (((size_t)step + 2) & ~(size_t)1) * 8 +
+                  ((size_t)Kmax * ((tbs + 1) | 1) + (size_t)Kmax * g.NK + (size_t)2 * Kmax * g.NI) * 8 +
+                  (size_t)g.NR * ((3 * (size_t)Kmax + 1) + (Kmax + 1)) * 8 + (((size_t)g.NR * Kmax + 7) & ~(size_t)7);
+    return g;
+  };
+  const size_t budget = 78 * 1024;   // two blocks per CU at the least
+  if (step <= EVAL_SAMPLES) {
+    const int m_min = (16 + step - 1) / step;
+    int m = EVAL_SAMPLES / step;
+    if (m < m_min) m = m_min;
+    while (m > m_min && make(m * step, m).lds_bytes > budget) --m;
+    return make(m * step, m);
   }
-  return 16;
+  for (int tbs = 64; tbs > 16; tbs >>= 1) {
+    const EvalGeometry g = make(tbs, tbs / step + 2);
+    if (g.lds_bytes <= budget) return g;
+  }
+  return make(16, 16 / step + 2);
 }
 
 extern "C" int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step) {
   (void)step;
   if (t_hi <= t_lo) return ES_LIMBS;
-  return ES_LIMBS * ((t_hi - t_lo + 15) / 16);   // eight 8-byte words per block of >= 16 samples
+  // eight 8-byte words per block of >= 16 samples; the blocks sit on a grid fixed to sample 0, so a range touches
+  // one block more than its length alone would need
+  return ES_LIMBS * ((t_hi - t_lo + 15) / 16 + 1);
 }
 
 extern "C" int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
@@ -531,13 +641,14 @@ extern "C" int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uin
   EvalArgs A{records, code, mom, No_ti, Kmax, step, fs, (long long)L, (long long)t_lo, (long long)t_hi,
              (long long)s_lo, (long long)s_hi, error_sum_shift(std_det), target, tracks ? am_out - track_t0 : nullptr,
              tracks ? fm_out - track_t0 : nullptr, (long long)track_len, ph_knot, s_hat, (long long*)partials};
-  size_t lds_bytes = 0;
-  int NK = 0, NR = 0;
-  const int TBS = eval_block_samples(Kmax, step, &lds_bytes, &NK, &NR);
-  if (lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_eval_synth: Kmax too large for the LDS tables");
-  const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL(eaqhm_eval_kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, A, TBS, NK, NR);
+  const EvalGeometry g = eval_geometry(Kmax, step);
+  if (g.lds_bytes > 160 * 1024) return ctx->fail(EAQHM_EINVAL, "eaqhm_eval_synth: Kmax too large for the LDS tables");
+  // blocks B_lo .. B_hi of the grid fixed to sample 0: block B owns (B*TBS - TBS, B*TBS]
+  const long long B_lo = (t_lo + g.TBS - 1) / g.TBS, B_hi = (t_hi - 1 + g.TBS - 1) / g.TBS;
+  const long long nblocks = B_hi - B_lo + 1;
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
+  hipLaunchKernelGGL(eaqhm_eval_kernel, dim3((unsigned)nblocks), dim3(256), g.lds_bytes, ctx->stream, A, g.TBS, g.NK, g.NI,
+                     g.NR, B_lo);
   HIP_TRY(ctx, hipGetLastError());
   if (!synth) return EAQHM_OK;
   hipLaunchKernelGGL(eaqhm_srer_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const long long*)partials, nblocks,

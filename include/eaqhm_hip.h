@@ -190,7 +190,9 @@ int eaqhm_eval_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code,
                      int64_t s_lo, int64_t s_hi, const double* target, double std_det, double* am_out,
                      double* fm_out, int64_t track_t0, int64_t track_len, double* ph_knot, double* s_hat,
                      double* partials, double* sums_out);
-/* number of 8-byte words `partials` must hold for a given range */
+/* number of 8-byte words `partials` must hold for a given range: eight per evaluation block.  Blocks hold at least 16
+ * samples and sit on a grid fixed to sample 0 (to the analysis instants where the step allows), so a range of n samples
+ * touches at most ceil(n / 16) + 1 of them, and that is what is counted */
 int64_t eaqhm_eval_partials_len(int64_t t_lo, int64_t t_hi, int32_t step);
 
 /* resynthesis from the model with a time scale rho, a pitch scale beta and a formant scale alpha (ABI 4) ----------
