@@ -30,7 +30,15 @@ whatever scale, formant, phase and noise flags are given, as `<name>_vocoded.wav
 (model.noise_cepstrum, model.noise_from_cepstrum).  --noise-from OTHER.wav (with --noise) analyses OTHER
 with the same options (once, if --envelope-from / --timing-from name the same file), models its residual, aligns the two
 files as --envelope-from does and puts OTHER's noise at this file's timing (model.noise_alignment_index) in place of its
-own; it implies --noise-cepstrum and does not go with --noise-modulation."""
+own; it implies --noise-cepstrum and does not go with --noise-modulation.
+--conversion-train TARGET.wav --conversion-save MAP.npz (with --conversion-components M, default 8) analyses TARGET with the
+same options, fits both cepstra (order and lambda of --cepstral-envelope / --cepstral-lambda, or their defaults), aligns the
+two, pairs the aligned rows (convert.conversion_pairs) and learns the map from this file's rows to TARGET's as a joint
+Gaussian mixture (convert.conversion_train); MAP.npz holds the map, the order, lambda, fs and both speakers'
+ln f0 statistics.  --conversion MAP.npz fits this file's cepstrum at the map's order and lambda, converts it
+(convert.conversion_apply) and reads the amplitudes of `<name>_modified.wav` off the result; unless a pitch flag is given the
+pitch follows the target speaker's statistics (convert.pitch_conversion_contour).  A different explicit --cepstral-envelope P
+or a different fs is an error; not with --envelope-from, --no-envelope or --conversion-train."""
 import argparse
 
 import numpy as np
@@ -109,7 +117,37 @@ def parser():
                          "(1 to 63; default min(63, 2 + round(fs / 1000))), with minimum-phase harmonics")
     ap.add_argument("--align-band", type=float, default=None, metavar="SECONDS",
                     help="with --envelope-from / --timing-from / --noise-from: half-width of the alignment band (2.0)")
+    ap.add_argument("--conversion-train", default=None, metavar="TARGET.wav",
+                    help="learn the spectral conversion from this file (source) to TARGET.wav, the same sentence by "
+                         "another speaker; needs --conversion-save")
+    ap.add_argument("--conversion-save", default=None, metavar="MAP.npz",
+                    help="with --conversion-train: where the learned map is written")
+    ap.add_argument("--conversion-components", type=int, default=None, metavar="M",
+                    help="with --conversion-train: components of the Gaussian mixture, 1 to 64 (8)")
+    ap.add_argument("--conversion", default=None, metavar="MAP.npz",
+                    help="also write <name>_modified.wav: amplitudes read off this file's cepstral envelope converted by "
+                         "the map of a --conversion-train run; the pitch follows the target's statistics unless a "
+                         "pitch flag is given")
     return ap
+
+
+def load_conversion(path):
+    """A --conversion-save file: (the validated map, order, lambda, fs, source (mean, std) of ln f0, target's)."""
+    from .convert import check_conversion
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            d = {k: z[k] for k in z.files}
+    except (OSError, ValueError) as e:
+        raise ValueError("--conversion %s: cannot read the map (%s)" % (path, e)) from None
+    conv = check_conversion(d)
+    try:
+        order, lam, fs = int(d["order"]), float(d["lam"]), int(d["fs"])
+        src, tgt = (tuple(float(v) for v in d[k]) for k in ("src_f0", "tgt_f0"))
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("--conversion %s: the file lacks order, lam, fs, src_f0 or tgt_f0" % path) from None
+    if len(src) != 2 or len(tgt) != 2 or order + 1 != conv["dx"] + (0 if conv["level"] else 1):
+        raise ValueError("--conversion %s: the order and the f0 statistics do not fit the map" % path)
+    return conv, order, lam, fs, src, tgt
 
 
 def main(argv=None):
@@ -147,16 +185,39 @@ def main(argv=None):
     cepstral = a.cepstral_envelope is not None
     aligned = a.envelope_from is not None or a.timing_from is not None or a.noise_from is not None
     vocode = a.from_parameters is not None
-    if a.cepstral_lambda is not None and not (cepstral or vocode):
-        ap.error("--cepstral-lambda needs --cepstral-envelope or --from-parameters")
+    if a.cepstral_lambda is not None and not (cepstral or vocode or a.conversion_train is not None
+                                              or a.conversion is not None):
+        ap.error("--cepstral-lambda needs --cepstral-envelope, --from-parameters or a conversion flag")
     if vocode and a.no_envelope:
         ap.error("--from-parameters builds the model from its spectral envelope: not with --no-envelope")
     if cepstral and a.no_envelope:
         ap.error("--cepstral-envelope supplies the spectral envelope: not with --no-envelope")
     if a.envelope_from is not None and a.no_envelope:
         ap.error("--envelope-from supplies the spectral envelope: not with --no-envelope")
-    if a.align_band is not None and not aligned:
-        ap.error("--align-band needs --envelope-from, --timing-from or --noise-from")
+    train, convert = a.conversion_train is not None, a.conversion is not None
+    if train != (a.conversion_save is not None):
+        ap.error("--conversion-train and --conversion-save go together")
+    if a.conversion_components is not None and not train:
+        ap.error("--conversion-components needs --conversion-train")
+    if train and convert:
+        ap.error("--conversion applies a map, --conversion-train learns one: not together")
+    if convert and a.envelope_from is not None:
+        ap.error("--conversion supplies the spectral envelope: not with --envelope-from")
+    if convert and a.no_envelope:
+        ap.error("--conversion supplies the spectral envelope: not with --no-envelope")
+    if train:
+        from .convert import GMM_MAX_COMPONENTS
+        if not 1 <= (8 if a.conversion_components is None else a.conversion_components) <= GMM_MAX_COMPONENTS:
+            ap.error("--conversion-components must be in [1, %d]" % GMM_MAX_COMPONENTS)
+    cmap = None
+    if convert:   # the map is read and checked before the analysis runs
+        cmap = load_conversion(a.conversion)
+        if a.cepstral_envelope and a.cepstral_envelope != cmap[1]:
+            ap.error("--cepstral-envelope %d differs from the map's order %d" % (a.cepstral_envelope, cmap[1]))
+        if a.cepstral_lambda is not None and a.cepstral_lambda != cmap[2]:
+            ap.error("--cepstral-lambda %g differs from the map's %g" % (a.cepstral_lambda, cmap[2]))
+    if a.align_band is not None and not (aligned or train):
+        ap.error("--align-band needs --envelope-from, --timing-from, --noise-from or --conversion-train")
     if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
         ap.error("--align-band must be finite and >= 0")
     if cepstral or vocode:   # 0: the flag without a value, the default order
@@ -166,7 +227,7 @@ def main(argv=None):
                 _cepstrum_order(order)
         _cepstrum_lambda(5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
     modify = any(x is not None for x in (a.time_scale, a.pitch_scale, a.time_scale_curve, a.pitch_scale_curve,
-                                         a.formant_scale, a.formant_scale_curve)) or warped or cepstral or aligned
+                                         a.formant_scale, a.formant_scale_curve)) or warped or cepstral or aligned or convert
     curves = {}
     wmap = None
     if modify or vocode:   # reject bad scales and curves before the analysis runs
@@ -197,6 +258,8 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
+        if train:
+            train_conversion(a, gender, analysis_options, fs, det)
         if modify or a.noise or vocode:
             from .model import eaQHMNoiseAnalysis, eaQHMNoiseModulation, eaQHMSynthesis, scale_contour
             rho = 1.0 if a.time_scale is None else a.time_scale
@@ -223,6 +286,16 @@ def main(argv=None):
                 from .model import model_cepstrum
                 order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
                 ceps = model_cepstrum(det, fs, order, lam)
+            if convert:   # this file's rows at the map's order and lambda, converted
+                from .convert import conversion_apply, pitch_conversion_contour
+                from .model import model_parameters
+                conv, c_order, c_lam, fs_map, src_f0, tgt_f0 = cmap   # the alignment keeps its own order, lam
+                if fs_map != fs:
+                    raise ValueError("%s was learned at %d Hz, the input is sampled at %d Hz" % (a.conversion, fs_map, fs))
+                p = model_parameters(det, fs, c_order, c_lam)
+                converted = conversion_apply(conv, p["ceps"])
+                if a.pitch_scale is None and "pitch" not in curves:
+                    beta = pitch_conversion_contour(p["f0"], p["voiced"] & (p["f0"] > 0), src_f0, tgt_f0)
             if aligned:
                 from .model import alignment_index, alignment_time_scale, warp_rows
                 others, n_inst = {}, len(ceps)
@@ -243,6 +316,8 @@ def main(argv=None):
                     pairs, det_o, nz_o = others[a.noise_from][1:]
                     j = noise_alignment_index(alignment_index(pairs, n_inst), det, nz, det_o, nz_o)
                     noise_rows = warp_rows(noise_cepstrum(nz_o, a.noise_cepstrum), j)
+            if convert:
+                ceps = converted
             if a.noise_cepstrum is not None:
                 from .model import noise_cepstrum, noise_from_cepstrum
                 if a.noise_from is None:
@@ -267,6 +342,24 @@ def main(argv=None):
                 wavfile.write(out, fs, np.float32(s_voc))
                 print("wrote", out)
     return 0
+
+
+def train_conversion(a, gender, analysis_options, fs, det):
+    """--conversion-train: analyses the target, aligns it to this file's model `det`, learns the map and saves it."""
+    from .convert import conversion_pairs, conversion_train, f0_statistics
+    from .model import model_parameters
+    order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
+    p = model_parameters(det, fs, order, lam)
+    C_t, pairs, det_t, _ = align_other(a.conversion_train, gender, analysis_options, fs, p["ceps"], order, lam,
+                                       2.0 if a.align_band is None else a.align_band)
+    X, Y = conversion_pairs(p["ceps"], C_t, pairs)
+    conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components)
+    p_t = model_parameters(det_t, fs, order, lam)
+    stats = [f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
+    np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),
+             src_f0=np.array(stats[0]), tgt_f0=np.array(stats[1]), **conv)
+    print("wrote %s: %d pairs, %d components, mean log-likelihood %g"
+          % (a.conversion_save, len(X), len(conv["weights"]), conv["loglik"][-1]))
 
 
 def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, noise_fc=None):

@@ -1,0 +1,423 @@
+"""Spectral conversion learned from aligned cepstral rows: a joint-density Gaussian mixture (not in the reference).
+
+    gmm_fit(Z, components, *, iters=20, tol=1e-5, floor=1e-6, init=None, split=None, device_index=0)
+        -> dict(weights[M], means[M, D], covs[M, D, D], zbar[D], phi[D], loglik[n_E_steps], n)
+    gmm_posteriors(gmm, Z, *, device_index=0) -> (gamma[N, M], ll[N])
+    conversion_pairs(CA, CB, path) -> (X, Y): the rows a model_align path pairs, empty rows dropped
+    conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, device_index=0)
+        -> flat dict of arrays (np.savez): the gmm fields + dx, dy, level, A[M, dy, dx], b[M, dy], Wx[M, dx, dx], kx[M]
+    conversion_apply(conv, C, *, device_index=0) -> float64[n, dy_cols] in model_cepstrum's layout
+    f0_statistics(f0, voiced) -> (mean, std) of ln f0 over the voiced instants
+    pitch_conversion_contour(f0, voiced, src_stats, tgt_stats) -> pitch_scale contour float64[n]
+    check_gmm_arguments, check_conversion_arguments, check_conversion: validation, no device work
+
+The definition is DESIGN.md §12: EM with full covariances on centred rows (Dempster, Laird & Rubin 1977), the
+regression of Stylianou, Cappe & Moulines (1998) in Kain & Macon's joint-density form.  Everything that scales with the
+number of rows runs in libeaqhm_hip.so (eaqhm_gmm_estep, eaqhm_gmm_mstep, eaqhm_gmm_regress); the per-component algebra
+(M Cholesky factors of D x D, their inverses, A_m) is host NumPy.  There is no CPU path.
+"""
+import math
+
+import numpy as np
+
+from .model import CEPSTRUM_MAX_ORDER, SCALE_RANGE, _cepstrum_rows, _integer, _numeric_1d, _path
+
+GMM_MAX_COLUMNS = 128      # D = dx + dy at most: nine 16-wide tile rows of [c | 1] in the M-step's registers
+GMM_MAX_SIDE = 64          # dx, dy at most
+GMM_MAX_COMPONENTS = 64
+GMM_FLOOR_RANGE = (1e-12, 1e-1)
+GMM_MAX_ITERS = 1000
+GMM_CHUNK_MIN = 512        # rows of an M-step chunk at least
+GMM_CHUNKS_MAX = 128       # chunks at most
+
+
+def gmm_chunk_rows(N):
+    """Rows per chunk of the M-step (include/eaqhm_hip.h): max(512, 64 ceil(ceil(N / 128) / 64)), a function of N alone."""
+    per = -(-int(N) // GMM_CHUNKS_MAX)
+    return max(GMM_CHUNK_MIN, -(-per // 64) * 64)
+
+
+def gmm_work_len(N, D, M):
+    """Doubles of the M-step's `work`: ceil(N / R) M T 256, T the lower-triangle 16 x 16 tiles of D + 1 columns."""
+    nt = (D + 1 + 15) // 16
+    return -(-int(N) // gmm_chunk_rows(N)) * M * (nt * (nt + 1) // 2) * 256
+
+
+# ---- validation (no device work)
+def _rows(Z, name, max_cols):
+    A = np.asarray(Z)
+    if A.dtype.kind not in "iuf" or A.ndim != 2 or A.shape[0] < 1:
+        raise ValueError("%s must be a 2-D array of numbers, one row per observation" % name)
+    if not 1 <= A.shape[1] <= max_cols:
+        raise ValueError("%s must have 1 to %d columns, got %d" % (name, max_cols, A.shape[1]))
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if not np.all(np.isfinite(A)):
+        raise ValueError("%s must be finite" % name)
+    return A
+
+
+def _real(x, name, lo, hi):
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number" % name) from None
+    if not (lo <= v <= hi):                       # NaN fails both
+        raise ValueError("%s must be in [%g, %g], got %r" % (name, lo, hi, x))
+    return v
+
+
+def check_gmm_arguments(Z, components, iters=20, tol=1e-5, floor=1e-6, init=None, split=None):
+    """Validates everything gmm_fit gets (no device work): returns (Z float64[N, D], M, iters, tol, floor, init, split),
+    init an int64[N] of labels or None."""
+    Z = _rows(Z, "Z", GMM_MAX_COLUMNS)
+    N, D = Z.shape
+    M = _integer(components, "components")
+    if not 1 <= M <= GMM_MAX_COMPONENTS:
+        raise ValueError("components must be in [1, %d], got %d" % (GMM_MAX_COMPONENTS, M))
+    if N < 2 * M:
+        raise ValueError("%d components need at least %d rows, got %d" % (M, 2 * M, N))
+    iters = _integer(iters, "iters")
+    if not 1 <= iters <= GMM_MAX_ITERS:
+        raise ValueError("iters must be in [1, %d], got %d" % (GMM_MAX_ITERS, iters))
+    tol = _real(tol, "tol", 0.0, np.inf)
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+    floor = _real(floor, "floor", *GMM_FLOOR_RANGE)
+    if init is not None:
+        lab = np.asarray(init)
+        if lab.dtype.kind not in "iu" or lab.shape != (N,):
+            raise ValueError("init must be an integer array of %d labels, one per row" % N)
+        lab = lab.astype(np.int64)
+        if lab.min() < 0 or lab.max() >= M:
+            raise ValueError("init labels must be in [0, %d)" % M)
+        count = np.bincount(lab, minlength=M)
+        if np.any(count == 0):
+            raise ValueError("init leaves component %d without a row" % int(np.flatnonzero(count == 0)[0]))
+        init = lab
+    if split is not None:
+        split = _integer(split, "split")
+        if not 1 <= split <= D:
+            raise ValueError("split must be in [1, %d], got %d" % (D, split))
+    return Z, M, iters, tol, floor, init, split
+
+
+def check_conversion_arguments(X, Y, components=8, level=False, iters=20, tol=1e-5, floor=1e-6, init=None):
+    """Validates everything conversion_train gets (no device work): returns (X, Y, level) with X, Y float64 rows.  With
+    level=False column 0 stays out of the map.  Rows are cepstral rows, order 1 to 63, 2 to 64 columns: what
+    conversion_apply and envelope= accept; so level=False maps at most 63 columns a side and level=True 64."""
+    X, Y = _rows(X, "X", CEPSTRUM_MAX_ORDER + 1), _rows(Y, "Y", CEPSTRUM_MAX_ORDER + 1)
+    if X.shape[0] != Y.shape[0]:
+        raise ValueError("X and Y must pair row by row, got %d and %d rows" % (X.shape[0], Y.shape[0]))
+    if not isinstance(level, (bool, np.bool_)):
+        raise ValueError("level must be True or False")
+    for A, name in ((X, "X"), (Y, "Y")):
+        if A.shape[1] < 2:
+            raise ValueError("%s must have 2 to %d columns (order 1 to %d), got %d"
+                             % (name, CEPSTRUM_MAX_ORDER + 1, CEPSTRUM_MAX_ORDER, A.shape[1]))
+    check_gmm_arguments(np.zeros((X.shape[0], 1)), components, iters, tol, floor, init, None)
+    return X, Y, bool(level)
+
+
+_CONVERSION_FIELDS = ("weights", "means", "covs", "zbar", "phi", "loglik", "n", "dx", "dy", "level", "A", "b", "Wx", "kx")
+
+
+def _field(conv, name, shape=None):
+    try:
+        a = np.asarray(conv[name])
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("the conversion lacks the field %r" % name) from None
+    if a.dtype.kind not in "iufb":
+        raise ValueError("the conversion's %s must be numbers" % name)
+    if shape is not None and a.shape != shape:
+        raise ValueError("the conversion's %s must have shape %s, got %s" % (name, shape, a.shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("the conversion's %s must be finite" % name)
+    return a
+
+
+def check_gmm(gmm):
+    """Validates a mixture dict (gmm_fit's, or one loaded from a file): shapes, finiteness, positive weights that sum to 1
+    within 1e-9, symmetric covariances with a positive diagonal.  Returns (weights, means, covs, zbar) as float64."""
+    w = _field(gmm, "weights").astype(np.float64)
+    if w.ndim != 1 or not 1 <= len(w) <= GMM_MAX_COMPONENTS:
+        raise ValueError("the mixture's weights must be a 1-D array of 1 to %d entries" % GMM_MAX_COMPONENTS)
+    M = len(w)
+    mu = _field(gmm, "means").astype(np.float64)
+    if mu.ndim != 2 or mu.shape[0] != M or not 1 <= mu.shape[1] <= GMM_MAX_COLUMNS:
+        raise ValueError("the mixture's means must have shape (%d, D), 1 <= D <= %d" % (M, GMM_MAX_COLUMNS))
+    D = mu.shape[1]
+    S = _field(gmm, "covs", (M, D, D)).astype(np.float64)
+    zbar = _field(gmm, "zbar", (D,)).astype(np.float64)
+    if np.any(w <= 0) or abs(math.fsum(w) - 1.0) > 1e-9:
+        raise ValueError("the mixture's weights must be positive and sum to 1 within 1e-9")
+    if not np.array_equal(S, S.transpose(0, 2, 1)):
+        raise ValueError("the mixture's covariances must be symmetric")
+    if np.any(np.einsum("mii->mi", S) <= 0):
+        raise ValueError("the mixture's covariances must have a positive diagonal")
+    return w, mu, S, zbar
+
+
+def check_conversion(conv):
+    """Validates a conversion dict (conversion_train's, or one loaded with np.load(allow_pickle=False)): every field,
+    shapes, finiteness, the mixture's rules (check_gmm).  Returns a dict of float64 / int arrays ready for use."""
+    for name in _CONVERSION_FIELDS:
+        _field(conv, name)
+    dx, dy = (int(_field(conv, k, ())) for k in ("dx", "dy"))
+    level = bool(_field(conv, "level", ()))
+    if not (1 <= dx <= GMM_MAX_SIDE and 1 <= dy <= GMM_MAX_SIDE):
+        raise ValueError("the conversion's dx and dy must be in [1, %d]" % GMM_MAX_SIDE)
+    w, mu, S, zbar = check_gmm(conv)
+    M = len(w)
+    if mu.shape[1] != dx + dy:
+        raise ValueError("the conversion's means must have dx + dy = %d columns, got %d" % (dx + dy, mu.shape[1]))
+    out = dict(weights=w, means=mu, covs=S, zbar=zbar, dx=dx, dy=dy, level=level)
+    for name, shape in (("A", (M, dy, dx)), ("b", (M, dy)), ("Wx", (M, dx, dx)), ("kx", (M,)), ("phi", (dx + dy,))):
+        out[name] = np.ascontiguousarray(_field(conv, name, shape), dtype=np.float64)
+    if np.any(np.einsum("mii->mi", out["Wx"]) <= 0) or np.any(np.triu(out["Wx"], 1) != 0):
+        raise ValueError("the conversion's Wx must be lower triangular with a positive diagonal")
+    out["loglik"] = _field(conv, "loglik").astype(np.float64).reshape(-1)
+    out["n"] = int(_field(conv, "n", ()))
+    return out
+
+
+# ---- host algebra (float64)
+def gmm_centre(Z, floor):
+    """(zbar, phi): the mean of the rows and the covariance floor, floor x the population variance of each column."""
+    zbar = Z.mean(axis=0)
+    return zbar, floor * (Z - zbar).var(axis=0)
+
+
+def gmm_init_labels(X, M):
+    """The default initialisation: standardise the columns, project on the principal axis of their covariance (sign: the
+    component of largest modulus positive), stable-sort, cut into M runs of equal count: the row of rank r gets r M // N."""
+    N = X.shape[0]
+    sd = X.std(axis=0)
+    U = (X - X.mean(axis=0)) / np.where(sd > 0, sd, 1.0)
+    _, vec = np.linalg.eigh(U.T @ U / N)
+    axis = vec[:, -1]
+    if axis[np.argmax(np.abs(axis))] < 0:
+        axis = -axis
+    order = np.argsort(U @ axis, kind="stable")
+    labels = np.empty(N, dtype=np.int64)
+    labels[order] = np.arange(N, dtype=np.int64) * M // N
+    return labels
+
+
+def gmm_finish_mstep(S0, S1, S2, N, phi):
+    """(w, mu, Sigma) from the sums; LinAlgError naming the component whose S0 < 1: there is no re-seeding."""
+    if np.any(S0 < 1):
+        m = int(np.flatnonzero(S0 < 1)[0])
+        raise np.linalg.LinAlgError("component %d is starved: its responsibilities sum to %.3g < 1" % (m, S0[m]))
+    mu = S1 / S0[:, None]
+    Sigma = S2 / S0[:, None, None] - mu[:, :, None] * mu[:, None, :] + np.diag(phi)[None]
+    return S0 / N, mu, Sigma
+
+
+def gmm_estep_parameters(w, mu, Sigma):
+    """(W [M, D, D] = L^-1 lower triangular, k [M]); LinAlgError naming the component whose Cholesky breaks down."""
+    M, D = mu.shape
+    W, k = np.empty_like(Sigma), np.empty(M)
+    for m in range(M):
+        try:
+            L = np.linalg.cholesky(Sigma[m])
+        except np.linalg.LinAlgError:
+            raise np.linalg.LinAlgError("the covariance of component %d is not positive definite" % m) from None
+        W[m] = np.tril(np.linalg.solve(L, np.eye(D)))
+        k[m] = math.log(w[m]) - 0.5 * (D * math.log(2.0 * math.pi) + 2.0 * float(np.log(np.diag(L)).sum()))
+    if not (np.all(np.isfinite(W)) and np.all(np.isfinite(k))):
+        raise np.linalg.LinAlgError("the covariance of a component is numerically singular")
+    return W, k
+
+
+def gmm_conversion_parameters(w, mu_c, Sigma, dx):
+    """(A [M, dy, dx], b [M, dy], Wx [M, dx, dx], kx [M]) on centred coordinates: A_m = Sigma_m^yx (Sigma_m^xx)^-1,
+    b_m = mu_m^y - A_m mu_m^x, and the E-step parameters of the marginal mixture on x."""
+    Wx, kx = gmm_estep_parameters(w, np.ascontiguousarray(mu_c[:, :dx]), np.ascontiguousarray(Sigma[:, :dx, :dx]))
+    A = np.stack([Sigma[m, dx:, :dx] @ Wx[m].T @ Wx[m] for m in range(len(w))])
+    b = mu_c[:, dx:] - np.einsum("mij,mj->mi", A, mu_c[:, :dx])
+    return np.ascontiguousarray(A), np.ascontiguousarray(b), Wx, kx
+
+
+# ---- device work
+def _device(device_index):
+    from . import model
+    return model._device(device_index)
+
+
+class _Mixture:
+    """The rows of one fit on the device, centred, and the buffers of its E and M steps."""
+
+    def __init__(self, Z, zbar, M, device_index):
+        self.torch, self.c, self.dev = _device(device_index)
+        t = self.torch
+        self.N, self.D, self.M = Z.shape[0], Z.shape[1], M
+        self.Z = t.as_tensor(Z, device=self.dev) - t.as_tensor(zbar, device=self.dev)
+        self.gamma = t.empty((self.N, M), dtype=t.float64, device=self.dev)
+        self.ll = t.empty(self.N, dtype=t.float64, device=self.dev)
+
+    def estep(self, mu, W, k):
+        """(gamma on the device, ll float64[N] on the host)."""
+        t = self.torch
+        mu_d, W_d, k_d = (t.as_tensor(np.ascontiguousarray(a), device=self.dev) for a in (mu, W, k))
+        self.c.gmm_estep(self.Z, self.N, self.D, self.M, mu_d, W_d, k_d, self.gamma, self.ll)
+        return self.gamma, self.ll.cpu().numpy()
+
+    def mstep(self, gamma):
+        """(S0, S1, S2) on the host from responsibilities on the device."""
+        t = self.torch
+        words = self.c.gmm_work_len(self.N, self.D, self.M)
+        if words != gmm_work_len(self.N, self.D, self.M):
+            raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the M-step's work buffer")
+        if getattr(self, "work", None) is None:
+            self.work = t.empty(words, dtype=t.float64, device=self.dev)
+            self.S0 = t.empty(self.M, dtype=t.float64, device=self.dev)
+            self.S1 = t.empty((self.M, self.D), dtype=t.float64, device=self.dev)
+            self.S2 = t.empty((self.M, self.D, self.D), dtype=t.float64, device=self.dev)
+        self.c.gmm_mstep(self.Z, gamma, self.N, self.D, self.M, self.work, self.S0, self.S1, self.S2)
+        return self.S0.cpu().numpy(), self.S1.cpu().numpy(), self.S2.cpu().numpy()
+
+
+def gmm_fit(Z, components, *, iters=20, tol=1e-5, floor=1e-6, init=None, split=None, device_index=0):
+    """Fits a Gaussian mixture with full covariances to the rows of `Z` float64[N, D] (all finite, D <= 128) by EM
+    (DESIGN.md §12): `components` = M in [1, 64], N >= 2 M.  E and M steps alternate for at most `iters` rounds and stop
+    after an E-step whose mean log-likelihood per row rose by less than `tol`.  `floor` x the variance of each column
+    is added to the diagonal of every covariance.  `init` is an int array [N] of labels in [0, M), every label present;
+    None sorts the rows along the principal axis of the standardised columns (the first `split` of them, all by default)
+    and cuts them into M equal runs.  Returns dict(weights[M], means[M, D], covs[M, D, D], zbar[D], phi[D],
+    loglik[n_E_steps], n).  Raises numpy.linalg.LinAlgError naming the component when one is starved (its
+    responsibilities sum to less than 1) or its covariance is not positive definite."""
+    Z, M, iters, tol, floor, init, split = check_gmm_arguments(Z, components, iters, tol, floor, init, split)
+    N, D = Z.shape
+    zbar, phi = gmm_centre(Z, floor)
+    labels = gmm_init_labels(Z[:, :split] if split else Z, M) if init is None else init
+    mix = _Mixture(Z, zbar, M, device_index)
+    onehot = np.zeros((N, M))
+    onehot[np.arange(N), labels] = 1.0
+    w, mu, Sigma = gmm_finish_mstep(*mix.mstep(mix.torch.as_tensor(onehot, device=mix.dev)), N, phi)
+    loglik = []
+    for _ in range(iters):
+        gamma, ll = mix.estep(mu, *gmm_estep_parameters(w, mu, Sigma))
+        loglik.append(math.fsum(ll) / N)
+        if len(loglik) > 1 and loglik[-1] - loglik[-2] < tol:
+            break
+        w, mu, Sigma = gmm_finish_mstep(*mix.mstep(gamma), N, phi)
+    return dict(weights=w, means=mu + zbar, covs=Sigma, zbar=zbar, phi=phi, loglik=np.array(loglik), n=N)
+
+
+def gmm_posteriors(gmm, Z, *, device_index=0):
+    """The E-step of a fitted mixture on rows `Z` float64[N, D]: (gamma float64[N, M], ll float64[N]), the
+    responsibilities and the log-likelihood of each row."""
+    w, mu, Sigma, zbar = check_gmm(gmm)
+    Z = _rows(Z, "Z", GMM_MAX_COLUMNS)
+    if Z.shape[1] != mu.shape[1]:
+        raise ValueError("Z must have the mixture's %d columns, got %d" % (mu.shape[1], Z.shape[1]))
+    mu_c = mu - zbar
+    W, k = gmm_estep_parameters(w, mu_c, Sigma)
+    mix = _Mixture(Z, zbar, len(w), device_index)
+    gamma, ll = mix.estep(mu_c, W, k)
+    return gamma.cpu().numpy(), ll
+
+
+def conversion_pairs(CA, CB, path):
+    """The rows a model_align path pairs: (X, Y) = (CA[i], CB[j]) for the pairs (i, j) of `path` int[L, 2], without the
+    pairs in which either row is empty, (-inf, 0, .., 0).  Host only.  np.vstack the results of several utterance pairs
+    for conversion_train.  CA and CB may have different orders."""
+    CA, CB = _cepstrum_rows(CA, "CA"), _cepstrum_rows(CB, "CB")
+    p, _ = _path(path, len(CA))
+    if p[:, 1].max() >= len(CB):
+        raise ValueError("path must pair instants of A with instants 0..%d of B" % (len(CB) - 1))
+    X, Y = CA[p[:, 0]], CB[p[:, 1]]
+    keep = ~(np.isneginf(X[:, 0]) | np.isneginf(Y[:, 0]))
+    return X[keep], Y[keep]
+
+
+def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, device_index=0):
+    """Learns the map from rows `X` float64[N, P + 1] to rows `Y` float64[N, Q + 1] (conversion_pairs') as a joint
+    mixture of `components` Gaussians over [x | y].  level=False leaves column 0, the level c_0, out of
+    both sides: conversion_apply copies it from the source row (a recording level is not a property of the speaker);
+    level=True maps it like any other column.  The default initialisation looks at the x columns only.  Returns a flat
+    dict of arrays that np.savez stores and np.load(allow_pickle=False) returns: gmm_fit's fields, dx, dy, level,
+    A[M, dy, dx], b[M, dy] and the marginal mixture's Wx[M, dx, dx], kx[M]."""
+    X, Y, level = check_conversion_arguments(X, Y, components, level, iters, tol, floor, init)
+    skip = 0 if level else 1
+    Z = np.ascontiguousarray(np.hstack((X[:, skip:], Y[:, skip:])))
+    dx, dy = X.shape[1] - skip, Y.shape[1] - skip
+    g = gmm_fit(Z, components, iters=iters, tol=tol, floor=floor, init=init, split=dx, device_index=device_index)
+    A, b, Wx, kx = gmm_conversion_parameters(g["weights"], g["means"] - g["zbar"], g["covs"], dx)
+    g.update(n=np.int64(g["n"]), dx=np.int64(dx), dy=np.int64(dy), level=np.bool_(level), A=A, b=b, Wx=Wx, kx=kx)
+    return g
+
+
+def conversion_apply(conv, C, *, device_index=0):
+    """Converts cepstral rows `C` float64[n, dx_cols] (model_cepstrum's layout) with a conversion_train map: yhat_n =
+    sum_m p(m | x_n) (b_m + A_m x_n).  An empty row (-inf, 0, .., 0) comes back empty; with level=False column 0 is the
+    source row's.  Returns float64[n, dy_cols], accepted by eaQHMSynthesis(envelope=), model_from_parameters and
+    cepstrum_envelope as it stands."""
+    v = check_conversion(conv)
+    skip = 0 if v["level"] else 1
+    dx, dy, M = v["dx"], v["dy"], len(v["weights"])
+    C = _cepstrum_rows(C, "C")
+    if C.shape[1] != dx + skip:
+        raise ValueError("C must have %d columns for this conversion, got %d" % (dx + skip, C.shape[1]))
+    full = ~np.isneginf(C[:, 0])
+    out = np.zeros((len(C), dy + skip))
+    out[~full, 0] = -np.inf
+    n = int(np.count_nonzero(full))
+    if n == 0:
+        return out
+    mu_c = v["means"] - v["zbar"]
+    mix = _Mixture(np.ascontiguousarray(C[full, skip:]), v["zbar"][:dx], M, device_index)
+    gamma, _ = mix.estep(mu_c[:, :dx], v["Wx"], v["kx"])
+    t = mix.torch
+    Y = t.empty((n, dy), dtype=t.float64, device=mix.dev)
+    mix.c.gmm_regress(mix.Z, gamma, t.as_tensor(v["A"], device=mix.dev), t.as_tensor(v["b"], device=mix.dev), n, dx, dy,
+                      M, Y)
+    out[full, skip:] = Y.cpu().numpy() + v["zbar"][dx:]
+    if skip:
+        out[full, 0] = C[full, 0]
+    return out
+
+
+# ---- pitch (host only)
+def _f0_track(f0, voiced):
+    f = _numeric_1d(f0, "f0")
+    vo = np.asarray(voiced)
+    if vo.shape != f.shape or vo.dtype.kind not in "biu":
+        raise ValueError("voiced must be one flag per entry of f0")
+    vo = vo.astype(bool)
+    if not (np.all(np.isfinite(f[vo])) and np.all(f[vo] > 0)):
+        raise ValueError("f0 must be finite and > 0 at the voiced instants")
+    return f, vo
+
+
+def f0_statistics(f0, voiced):
+    """(mean, std) of ln f0 over the voiced instants (population std); ValueError without a voiced instant."""
+    f, vo = _f0_track(f0, voiced)
+    if not vo.any():
+        raise ValueError("f0_statistics needs at least one voiced instant")
+    lf = np.log(f[vo])
+    return float(lf.mean()), float(lf.std())
+
+
+def _stats(s, name):
+    try:
+        m, d = (float(x) for x in s)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be (mean, std) of ln f0" % name) from None
+    if not (np.isfinite(m) and np.isfinite(d) and d >= 0):
+        raise ValueError("%s must be finite with std >= 0" % name)
+    return m, d
+
+
+def pitch_conversion_contour(f0, voiced, src_stats, tgt_stats):
+    """The log-Gaussian normalisation of pitch: ln f0' = mean_t + (std_t / std_s) (ln f0 - mean_s) at the voiced
+    instants (std_s = 0: the ratio is 1).  Returns the pitch_scale contour f0' / f0, float64[n], clipped to SCALE_RANGE,
+    1 at the unvoiced instants.  Host only."""
+    f, vo = _f0_track(f0, voiced)
+    (ms, ds), (mt, dt) = _stats(src_stats, "src_stats"), _stats(tgt_stats, "tgt_stats")
+    ratio = dt / ds if ds > 0 else 1.0
+    out = np.ones(len(f))
+    lf = np.log(f[vo])
+    with np.errstate(over="ignore"):
+        out[vo] = np.clip(np.exp(mt + ratio * (lf - ms) - lf), *SCALE_RANGE)
+    return out

@@ -59,6 +59,10 @@ SYMBOLS = (
     ("eaqhm_cepstrum_phase", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P]),
     ("eaqhm_noise_cepstrum", C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P]),
     ("eaqhm_noise_from_cepstrum", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    ("eaqhm_gmm_work_len", _I64, [_I64, _I32, _I32]),
+    ("eaqhm_gmm_estep", C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    ("eaqhm_gmm_mstep", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
+    ("eaqhm_gmm_regress", C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P]),
 )
 
 
@@ -304,6 +308,21 @@ class Context:
 
     def noise_from_cepstrum(self, ceps, Nf, Q, p, sigma_out, refl_out):
         self._ck(self.lib.eaqhm_noise_from_cepstrum(self.h, _ptr(ceps), Nf, Q, p, _ptr(sigma_out), _ptr(refl_out)))
+
+    # the joint-density mixture of the spectral conversion: Z [N][D] centred rows, gamma [N][M]
+    def gmm_work_len(self, N, D, M):
+        return int(self.lib.eaqhm_gmm_work_len(N, D, M))
+
+    def gmm_estep(self, Z, N, D, M, mu, W, k, gamma_out, ll_out):
+        self._ck(self.lib.eaqhm_gmm_estep(self.h, _ptr(Z), N, D, M, _ptr(mu), _ptr(W), _ptr(k), _ptr(gamma_out),
+                                          _ptr(ll_out)))
+
+    def gmm_mstep(self, Z, gamma, N, D, M, work, S0, S1, S2):
+        self._ck(self.lib.eaqhm_gmm_mstep(self.h, _ptr(Z), _ptr(gamma), N, D, M, _ptr(work), _ptr(S0), _ptr(S1),
+                                          _ptr(S2)))
+
+    def gmm_regress(self, X, gamma, A, b, N, dx, dy, M, Y_out):
+        self._ck(self.lib.eaqhm_gmm_regress(self.h, _ptr(X), _ptr(gamma), _ptr(A), _ptr(b), N, dx, dy, M, _ptr(Y_out)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

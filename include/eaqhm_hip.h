@@ -470,6 +470,42 @@ int eaqhm_noise_cepstrum(eaqhm_ctx* ctx, const double* sigma, const double* refl
 int eaqhm_noise_from_cepstrum(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order, int32_t order,
                               double* sigma_out, double* refl_out);
 
+/* the joint-density Gaussian mixture of the spectral conversion (additions under ABI 6) ------------------
+ * Rows Z double[N][D] are the CENTRED joint vectors c_n = [x_n | y_n] - zbar; the mixture has M components.
+ * 1 <= N <= 2^36, 1 <= D <= 128 (1 <= dx, dy <= 64 for the regression), 1 <= M <= 64; any value in range, none needs to
+ * be a multiple of 4 or 16: the kernels pad in LDS.  All three contract on the matrix pipe (v_mfma_f64_16x16x4_f64).
+ * eaqhm_gmm_estep (kernel: 64 rows per block, four waves of one 16-row tile; W_m in 16-row panels through LDS, each
+ *   contracted over its lower-triangle columns only; squared norms, the log-sum-exp over m and gamma in the same launch):
+ *   mu         double[M][D]      centred means
+ *   W          double[M][D][D]   W_m = L_m^-1, lower triangular, L_m L_m^T = Sigma_m; entries above the diagonal are not read
+ *   k          double[M]         k_m = ln w_m - (D ln 2 pi + 2 sum_i ln L_m[i][i]) / 2
+ *   gamma_out  double[N][M]      with q_nm = ||W_m (c_n - mu_m)||^2, lp_nm = k_m - q_nm / 2, max_n = max_m lp_nm,
+ *                                e_nm = exp(lp_nm - max_n), s_n = sum_m e_nm (m ascending): gamma_nm = e_nm / s_n
+ *   ll_out     double[N]         ll_n = max_n + ln s_n.  A row so far from every mean that each q_nm overflows to +inf
+ *                                (max_n = -inf) gets ll_n = -inf and gamma_nm = 1 / M instead of NaN.
+ *   The marginal E-step of the conversion is this entry point with D = dx.
+ * eaqhm_gmm_mstep (kernels: one block per (row chunk, component): the weighted Gramian of [c | 1] over the lower-triangle
+ *   16 x 16 tiles, A operand gamma c, B operand c, S1 and S0 in the row of the ones; then one thread per entry adds the
+ *   chunks in index order): S0[m] = sum_n gamma_nm, S1[m][i] = sum_n gamma_nm c_ni, S2[m][i][j] = sum_n gamma_nm c_ni c_nj.
+ *   S0 double[M], S1 double[M][D], S2 double[M][D][D], the upper triangle of S2_m a copy of the lower.
+ *   Rows are cut into chunks of R = max(512, 64 ceil(ceil(N / 128) / 64)) rows, a function of N alone: no atomics, no
+ *   dependence on the device or on timing, the same bits on every run.
+ *   work       double[eaqhm_gmm_work_len]  ceil(N / R) M T 256 words, T = nt (nt + 1) / 2, nt = ceil((D + 1) / 16):
+ *                                the chunks' tiles; 755 MB at N = 10^6, M = 64, D = 128.  eaqhm_gmm_work_len returns -1
+ *                                for sizes out of range.
+ * eaqhm_gmm_regress (kernel: 64 rows per block; x_n A_m^T on the matrix pipe in panels of 16 columns of y, then
+ *   y_n += gamma_nm (A_m x_n + b_m), m ascending):
+ *   X double[N][dx], gamma double[N][M], A double[M][dy][dx], b double[M][dy], Y_out double[N][dy]
+ * The entry points do not read the device arrays: finite values are the CALLER'S contract (the Python host checks them).
+ * EAQHM_EINVAL for null pointers and sizes outside the ranges above.                                                  */
+int64_t eaqhm_gmm_work_len(int64_t N, int32_t D, int32_t M);
+int eaqhm_gmm_estep(eaqhm_ctx* ctx, const double* Z, int64_t N, int32_t D, int32_t M, const double* mu, const double* W,
+                    const double* k, double* gamma_out, double* ll_out);
+int eaqhm_gmm_mstep(eaqhm_ctx* ctx, const double* Z, const double* gamma, int64_t N, int32_t D, int32_t M, double* work,
+                    double* S0, double* S1, double* S2);
+int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, const double* A, const double* b, int64_t N,
+                      int32_t dx, int32_t dy, int32_t M, double* Y_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,72 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
     return res
 
 
+FP64_MATRIX_PEAK = 78.6e12   # MI355X, FLOP/s
+
+
+def gmm_rows(torch, reps=20, runs=3, sizes=(65536, 1000000), shapes=((18, 18, 8), (50, 50, 32))):
+    """One E-step, one M-step and one regression of the joint-density mixture on random rows, next to
+    the same step written with torch matmuls on the same device (a comparison, not a bar).  Each time: median of `runs`
+    warmed windows of `reps` launches, and max - min of the windows.  Fractions of the FP64 matrix peak: the E-step at
+    its useful half N M D^2 (the lower triangle of W), the M-step at 2 N M D^2, the regression at 2 N M dx dy."""
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for N in sizes:
+        for dx, dy, M in shapes:
+            D = dx + dy
+            g = torch.Generator(device=dev).manual_seed(N + D + M)
+            rnd = lambda *shape: torch.randn(*shape, dtype=torch.float64, device=dev, generator=g)   # noqa: E731
+            Z = rnd(N, D)
+            mu = rnd(M, D)
+            W = torch.tril(0.1 * rnd(M, D, D), -1) + torch.eye(D, dtype=torch.float64, device=dev)
+            k = torch.full((M,), -np.log(M) - 0.5 * D * np.log(2 * np.pi), dtype=torch.float64, device=dev)
+            gamma = torch.empty((N, M), dtype=torch.float64, device=dev)
+            ll = torch.empty(N, dtype=torch.float64, device=dev)
+            work = torch.empty(c.gmm_work_len(N, D, M), dtype=torch.float64, device=dev)
+            S0 = torch.empty(M, dtype=torch.float64, device=dev)
+            S1 = torch.empty((M, D), dtype=torch.float64, device=dev)
+            S2 = torch.empty((M, D, D), dtype=torch.float64, device=dev)
+            A, b = rnd(M, dy, dx) / np.sqrt(dx), rnd(M, dy)
+            X = Z[:, :dx].contiguous()
+            Y = torch.empty((N, dy), dtype=torch.float64, device=dev)
+
+            def t_estep():
+                lp = torch.stack([k[m] - 0.5 * (((Z - mu[m]) @ W[m].T) ** 2).sum(dim=1) for m in range(M)], dim=1)
+                l = torch.logsumexp(lp, dim=1)
+                return torch.exp(lp - l[:, None]), l
+
+            def t_mstep():
+                return gamma.sum(dim=0), gamma.T @ Z, torch.stack([(Z * gamma[:, m:m + 1]).T @ Z for m in range(M)])
+
+            def t_regress():
+                T = (X @ A.reshape(M * dy, dx).T).reshape(N, M, dy) + b[None]
+                return (gamma[:, :, None] * T).sum(dim=1)
+
+            e = med(lambda: c.gmm_estep(Z, N, D, M, mu, W, k, gamma, ll))
+            m_ = med(lambda: c.gmm_mstep(Z, gamma, N, D, M, work, S0, S1, S2))
+            r = med(lambda: c.gmm_regress(X, gamma, A, b, N, dx, dy, M, Y))
+            te, tm, tr = med(t_estep), med(t_mstep), med(t_regress)
+            frac = lambda flops, ms: round(flops / (ms * 1e-3) / FP64_MATRIX_PEAK, 4)   # noqa: E731
+            rows.append(dict(N=N, dx=dx, dy=dy, M=M,
+                             estep_ms=e[0], estep_spread_ms=e[1], estep_torch_ms=te[0], estep_torch_spread_ms=te[1],
+                             estep_peak_fraction=frac(float(N) * M * D * D, e[0]),
+                             mstep_ms=m_[0], mstep_spread_ms=m_[1], mstep_torch_ms=tm[0], mstep_torch_spread_ms=tm[1],
+                             mstep_peak_fraction=frac(2.0 * N * M * D * D, m_[0]),
+                             regress_ms=r[0], regress_spread_ms=r[1], regress_torch_ms=tr[0],
+                             regress_torch_spread_ms=tr[1], regress_peak_fraction=frac(2.0 * N * M * dx * dy, r[0])))
+            print(json.dumps(rows[-1]), flush=True)
+            del Z, gamma, work, X, Y
+            torch.cuda.empty_cache()
+    return rows
+
+
 def noise_cepstrum_rows(torch, nz, Q=63, reps=20, runs=3):
     """The noise model `nz` to cepstral rows and back, same session: eaqhm_noise_cepstrum at order Q
     and eaqhm_noise_from_cepstrum on its rows at the model's own LPC order, next to eaqhm_noise_warp at alpha = 1.2 on
@@ -651,11 +717,24 @@ def main():
                     help="also time eaqhm_model_build next to eaqhm_modify_amp_cepstrum (the model from parameters)")
     ap.add_argument("--noise-cepstrum", action="store_true",
                     help="also time eaqhm_noise_cepstrum and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp")
+    ap.add_argument("--gmm", action="store_true",
+                    help="time eaqhm_gmm_estep, eaqhm_gmm_mstep and eaqhm_gmm_regress next to torch matmuls (random rows; "
+                         "needs no workload: pass --workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.gmm:
+        import torch
+        res_gmm = dict(gmm=gmm_rows(torch))
+        if not a.workloads:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump([res_gmm], f, indent=1)
+            return 0
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
                  a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build, a.noise_cepstrum)
            for w in a.workloads.split(",")]
+    if a.gmm:
+        res.append(res_gmm)
     for r in res:
         print(json.dumps(r))
     if a.out:
