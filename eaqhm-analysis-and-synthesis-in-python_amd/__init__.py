@@ -12,6 +12,6 @@ from .model import (SCALE_RANGE, cepstrum_phase, model_from_parameters, model_pa
                     model_phase, noise_alignment_index, noise_cepstrum, noise_envelope, noise_formant_contour, noise_formant_warp, noise_from_cepstrum, noise_fundamental, noise_time_map, noise_time_map_contour,
                     scale_contour, unpack_model)
 from .convert import (check_conversion, check_conversion_arguments, check_gmm_arguments, conversion_apply,  # noqa: F401
-                      conversion_pairs, conversion_train, f0_statistics, gmm_fit, gmm_posteriors,
-                      pitch_conversion_contour)
+                      conversion_pairs, conversion_train, conversion_trajectory, dynamic_rows, f0_statistics, gmm_fit,
+                      gmm_posteriors, pitch_conversion_contour)
 from .prologue import read_signal  # noqa: F401

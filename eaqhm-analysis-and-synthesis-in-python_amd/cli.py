@@ -38,7 +38,12 @@ Gaussian mixture (convert.conversion_train); MAP.npz holds the m
 ln f0 statistics.  --conversion MAP.npz fits this file's cepstrum at the map's order and lambda, converts it
 (convert.conversion_apply) and reads the amplitudes of `<name>_modified.wav` off the result; unless a pitch flag is given the
 pitch follows the target speaker's statistics (convert.pitch_conversion_contour).  A different explicit --cepstral-envelope P
-or a different fs is an error; not with --envelope-from, --no-envelope or --conversion-train."""
+or a different fs is an error; not with --envelope-from, --no-envelope or --conversion-train.
+--conversion-span L (with --conversion-train; L in 1..8, 2 is the usual choice) learns a dynamic map instead: both cepstra are
+extended with their delta features over a window of L instants a side before the pairing (convert.conversion_pairs(span=)),
+the mixture is over the extended rows, and MAP.npz carries the span.  --conversion MAP.npz with such a map converts this
+file to the most likely trajectory under the static and the delta statistics (convert.conversion_trajectory, DESIGN.md
+§12.1) in place of the row-by-row rule, so that the converted envelope does not jump where the posterior changes component."""
 import argparse
 
 import numpy as np
@@ -124,6 +129,9 @@ def parser():
                     help="with --conversion-train: where the learned map is written")
     ap.add_argument("--conversion-components", type=int, default=None, metavar="M",
                     help="with --conversion-train: components of the Gaussian mixture, 1 to 64 (8)")
+    ap.add_argument("--conversion-span", type=int, default=None, metavar="L",
+                    help="with --conversion-train: learn a dynamic map on rows extended with their delta features over L "
+                         "instants a side, 1 to 8; --conversion then converts to the most likely trajectory")
     ap.add_argument("--conversion", default=None, metavar="MAP.npz",
                     help="also write <name>_modified.wav: amplitudes read off this file's cepstral envelope converted by "
                          "the map of a --conversion-train run; the pitch follows the target's statistics unless a "
@@ -145,7 +153,8 @@ def load_conversion(path):
         src, tgt = (tuple(float(v) for v in d[k]) for k in ("src_f0", "tgt_f0"))
     except (KeyError, TypeError, ValueError):
         raise ValueError("--conversion %s: the file lacks order, lam, fs, src_f0 or tgt_f0" % path) from None
-    if len(src) != 2 or len(tgt) != 2 or order + 1 != conv["dx"] + (0 if conv["level"] else 1):
+    dxs = conv["dx"] // 2 if "span" in conv else conv["dx"]       # a dynamic map counts the delta columns
+    if len(src) != 2 or len(tgt) != 2 or order + 1 != dxs + (0 if conv["level"] else 1):
         raise ValueError("--conversion %s: the order and the f0 statistics do not fit the map" % path)
     return conv, order, lam, fs, src, tgt
 
@@ -199,6 +208,8 @@ def main(argv=None):
         ap.error("--conversion-train and --conversion-save go together")
     if a.conversion_components is not None and not train:
         ap.error("--conversion-components needs --conversion-train")
+    if a.conversion_span is not None and not train:
+        ap.error("--conversion-span needs --conversion-train")
     if train and convert:
         ap.error("--conversion applies a map, --conversion-train learns one: not together")
     if convert and a.envelope_from is not None:
@@ -206,9 +217,11 @@ def main(argv=None):
     if convert and a.no_envelope:
         ap.error("--conversion supplies the spectral envelope: not with --no-envelope")
     if train:
-        from .convert import GMM_MAX_COMPONENTS
+        from .convert import DELTA_SPAN_RANGE, GMM_MAX_COMPONENTS
         if not 1 <= (8 if a.conversion_components is None else a.conversion_components) <= GMM_MAX_COMPONENTS:
             ap.error("--conversion-components must be in [1, %d]" % GMM_MAX_COMPONENTS)
+        if a.conversion_span is not None and not DELTA_SPAN_RANGE[0] <= a.conversion_span <= DELTA_SPAN_RANGE[1]:
+            ap.error("--conversion-span must be in [%d, %d]" % DELTA_SPAN_RANGE)
     cmap = None
     if convert:   # the map is read and checked before the analysis runs
         cmap = load_conversion(a.conversion)
@@ -287,13 +300,15 @@ def main(argv=None):
                 order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
                 ceps = model_cepstrum(det, fs, order, lam)
             if convert:   # this file's rows at the map's order and lambda, converted
-                from .convert import conversion_apply, pitch_conversion_contour
+                from . import convert as _convert
+                from .convert import pitch_conversion_contour
                 from .model import model_parameters
                 conv, c_order, c_lam, fs_map, src_f0, tgt_f0 = cmap   # the alignment keeps its own order, lam
                 if fs_map != fs:
                     raise ValueError("%s was learned at %d Hz, the input is sampled at %d Hz" % (a.conversion, fs_map, fs))
                 p = model_parameters(det, fs, c_order, c_lam)
-                converted = conversion_apply(conv, p["ceps"])
+                apply = _convert.conversion_trajectory if "span" in conv else _convert.conversion_apply
+                converted = apply(conv, p["ceps"])
                 if a.pitch_scale is None and "pitch" not in curves:
                     beta = pitch_conversion_contour(p["f0"], p["voiced"] & (p["f0"] > 0), src_f0, tgt_f0)
             if aligned:
@@ -352,8 +367,9 @@ def train_conversion(a, gender, analysis_options, fs, det):
     p = model_parameters(det, fs, order, lam)
     C_t, pairs, det_t, _ = align_other(a.conversion_train, gender, analysis_options, fs, p["ceps"], order, lam,
                                        2.0 if a.align_band is None else a.align_band)
-    X, Y = conversion_pairs(p["ceps"], C_t, pairs)
-    conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components)
+    X, Y = conversion_pairs(p["ceps"], C_t, pairs, a.conversion_span)
+    conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components,
+                            span=a.conversion_span)
     p_t = model_parameters(det_t, fs, order, lam)
     stats = [f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
     np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),

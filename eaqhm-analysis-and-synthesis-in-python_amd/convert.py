@@ -3,10 +3,15 @@
     gmm_fit(Z, components, *, iters=20, tol=1e-5, floor=1e-6, init=None, split=None, device_index=0)
         -> dict(weights[M], means[M, D], covs[M, D, D], zbar[D], phi[D], loglik[n_E_steps], n)
     gmm_posteriors(gmm, Z, *, device_index=0) -> (gamma[N, M], ll[N])
-    conversion_pairs(CA, CB, path) -> (X, Y): the rows a model_align path pairs, empty rows dropped
-    conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, device_index=0)
-        -> flat dict of arrays (np.savez): the gmm fields + dx, dy, level, A[M, dy, dx], b[M, dy], Wx[M, dx, dx], kx[M]
-    conversion_apply(conv, C, *, device_index=0) -> float64[n, dy_cols] in model_cepstrum's layout
+    conversion_pairs(CA, CB, path, span=None) -> (X, Y): the rows a model_align path pairs, empty rows dropped; with a
+        span the dynamic rows [c | delta c] of both sides
+    conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None,
+                     device_index=0)
+        -> flat dict of arrays (np.savez): the gmm fields + dx, dy, level, A[M, dy, dx], b[M, dy], Wx[M, dx, dx], kx[M];
+        with a span also span and py[M, dy], and dx, dy count the delta columns
+    conversion_apply(conv, C, *, device_index=0) -> float64[n, dy_cols] in model_cepstrum's layout (a static map)
+    dynamic_rows(C, span=2, *, device_index=0) -> float64[n, 2 (P + 1)]: [c | delta c] over the runs of non-empty rows
+    conversion_trajectory(conv, C, *, device_index=0) -> float64[n, Q + 1]: the most likely trajectory under a dynamic map
     f0_statistics(f0, voiced) -> (mean, std) of ln f0 over the voiced instants
     pitch_conversion_contour(f0, voiced, src_stats, tgt_stats) -> pitch_scale contour float64[n]
     check_gmm_arguments, check_conversion_arguments, check_conversion: validation, no device work
@@ -15,6 +20,11 @@ The definition is DESIGN.md §12: EM with full covariances on centred rows (Demp
 regression of Stylianou, Cappe & Moulines (1998) in Kain & Macon's joint-density form.  Everything that scales with the
 number of rows runs in libeaqhm_hip.so (eaqhm_gmm_estep, eaqhm_gmm_mstep, eaqhm_gmm_regress); the per-component algebra
 (M Cholesky factors of D x D, their inverses, A_m) is host NumPy.  There is no CPU path.
+
+DESIGN.md §12.1 adds the trajectory conversion of Toda, Black & Tokuda (2007): the mixture is trained on rows extended
+with their delta features (eaqhm_ceps_delta) and an utterance is converted to the trajectory that is most likely under
+the static and the delta statistics together (Tokuda et al. 2000): one banded positive-definite system per voiced run and
+cepstral dimension (eaqhm_mlpg_solve).
 """
 import math
 
@@ -29,6 +39,7 @@ GMM_FLOOR_RANGE = (1e-12, 1e-1)
 GMM_MAX_ITERS = 1000
 GMM_CHUNK_MIN = 512        # rows of an M-step chunk at least
 GMM_CHUNKS_MAX = 128       # chunks at most
+DELTA_SPAN_RANGE = (1, 8)  # span L of the delta window: tau = 1 .. L on each side
 
 
 def gmm_chunk_rows(N):
@@ -101,15 +112,37 @@ def check_gmm_arguments(Z, components, iters=20, tol=1e-5, floor=1e-6, init=None
     return Z, M, iters, tol, floor, init, split
 
 
-def check_conversion_arguments(X, Y, components=8, level=False, iters=20, tol=1e-5, floor=1e-6, init=None):
+def check_span(span):
+    """The span of the delta window as an int in [1, 8]."""
+    span = _integer(span, "span")
+    if not DELTA_SPAN_RANGE[0] <= span <= DELTA_SPAN_RANGE[1]:
+        raise ValueError("span must be in [%d, %d], got %d" % (DELTA_SPAN_RANGE + (span,)))
+    return span
+
+
+def check_conversion_arguments(X, Y, components=8, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None):
     """Validates everything conversion_train gets (no device work): returns (X, Y, level) with X, Y float64 rows.  With
     level=False column 0 stays out of the map.  Rows are cepstral rows, order 1 to 63, 2 to 64 columns: what
-    conversion_apply and envelope= accept; so level=False maps at most 63 columns a side and level=True 64."""
-    X, Y = _rows(X, "X", CEPSTRUM_MAX_ORDER + 1), _rows(Y, "Y", CEPSTRUM_MAX_ORDER + 1)
+    conversion_apply and envelope= accept; so level=False maps at most 63 columns a side and level=True 64.  With a span
+    the rows are dynamic rows [c | delta c], an even number of columns, and the mapped columns with their deltas are at
+    most 64 a side (the regression's limit) and 128 together (the mixture's)."""
+    if span is not None:
+        span = check_span(span)
+    width = (CEPSTRUM_MAX_ORDER + 1) * (1 if span is None else 2)
+    X, Y = _rows(X, "X", width), _rows(Y, "Y", width)
     if X.shape[0] != Y.shape[0]:
         raise ValueError("X and Y must pair row by row, got %d and %d rows" % (X.shape[0], Y.shape[0]))
     if not isinstance(level, (bool, np.bool_)):
         raise ValueError("level must be True or False")
+    if span is not None:
+        for A, name in ((X, "X"), (Y, "Y")):
+            if A.shape[1] % 2 or A.shape[1] < 4:
+                raise ValueError("%s must be dynamic rows [c | delta c]: an even number of columns, 4 to %d, got %d"
+                                 % (name, width, A.shape[1]))
+        dx, dy = (A.shape[1] - (0 if level else 2) for A in (X, Y))
+        if dx > GMM_MAX_SIDE or dy > GMM_MAX_SIDE or dx + dy > GMM_MAX_COLUMNS:
+            raise ValueError("a dynamic map takes at most %d mapped columns a side with their deltas and %d together, got "
+                             "%d and %d" % (GMM_MAX_SIDE, GMM_MAX_COLUMNS, dx, dy))
     for A, name in ((X, "X"), (Y, "Y")):
         if A.shape[1] < 2:
             raise ValueError("%s must have 2 to %d columns (order 1 to %d), got %d"
@@ -177,7 +210,25 @@ def check_conversion(conv):
         raise ValueError("the conversion's Wx must be lower triangular with a positive diagonal")
     out["loglik"] = _field(conv, "loglik").astype(np.float64).reshape(-1)
     out["n"] = int(_field(conv, "n", ()))
+    if _has(conv, "span"):                        # a dynamic map
+        span = _field(conv, "span", ())
+        if span.dtype.kind not in "iu":
+            raise ValueError("the conversion's span must be an integer")
+        out["span"] = check_span(int(span))
+        if dx % 2 or dy % 2:
+            raise ValueError("a dynamic conversion's dx and dy count the delta columns: they must be even")
+        out["py"] = np.ascontiguousarray(_field(conv, "py", (M, dy)), dtype=np.float64)
+        if np.any(out["py"] <= 0):
+            raise ValueError("the conversion's py must be positive")
     return out
+
+
+def _has(conv, name):
+    try:
+        conv[name]
+    except (KeyError, TypeError, IndexError):
+        return False
+    return True
 
 
 # ---- host algebra (float64)
@@ -236,6 +287,31 @@ def gmm_conversion_parameters(w, mu_c, Sigma, dx):
     A = np.stack([Sigma[m, dx:, :dx] @ Wx[m].T @ Wx[m] for m in range(len(w))])
     b = mu_c[:, dx:] - np.einsum("mij,mj->mi", A, mu_c[:, :dx])
     return np.ascontiguousarray(A), np.ascontiguousarray(b), Wx, kx
+
+
+def gmm_conditional_precisions(Sigma, A, dx):
+    """py [M, dy] = 1 / diag(Sigma_m^yy - A_m Sigma_m^xy): the reciprocal diagonals of the conditional covariances of y
+    given x; LinAlgError naming the component when one is not positive."""
+    py = np.empty((len(A), A.shape[1]))
+    for m in range(len(A)):
+        v = np.diag(Sigma[m, dx:, dx:]) - np.einsum("ij,ji->i", A[m], Sigma[m, :dx, dx:])
+        if not np.all(v > 0) or not np.all(np.isfinite(1.0 / v)):
+            raise np.linalg.LinAlgError("the conditional covariance of component %d has a diagonal entry that is not "
+                                        "positive" % m)
+        py[m] = 1.0 / v
+    return py
+
+
+def delta_runs(full):
+    """(start, length) int64 arrays of the runs: the maximal stretches of True in the bool array `full`."""
+    f = np.concatenate(([False], np.asarray(full, dtype=bool), [False]))
+    edges = np.flatnonzero(f[1:] != f[:-1])
+    return edges[0::2].astype(np.int64), (edges[1::2] - edges[0::2]).astype(np.int64)
+
+
+def _dynamic_columns(D, cols, skip):
+    """The mapped columns of dynamic rows of `cols` static columns: both halves without their first `skip` columns."""
+    return np.ascontiguousarray(np.hstack((D[:, skip:cols], D[:, cols + skip:])))
 
 
 # ---- device work
@@ -318,33 +394,64 @@ def gmm_posteriors(gmm, Z, *, device_index=0):
     return gamma.cpu().numpy(), ll
 
 
-def conversion_pairs(CA, CB, path):
+def conversion_pairs(CA, CB, path, span=None, *, device_index=0):
     """The rows a model_align path pairs: (X, Y) = (CA[i], CB[j]) for the pairs (i, j) of `path` int[L, 2], without the
-    pairs in which either row is empty, (-inf, 0, .., 0).  Host only.  np.vstack the results of several utterance pairs
-    for conversion_train.  CA and CB may have different orders."""
+    pairs in which either row is empty, (-inf, 0, .., 0).  np.vstack the results of several utterance pairs for
+    conversion_train.  CA and CB may have different orders.  span=None is host only; with a `span` in [1, 8] the rows
+    paired are the dynamic rows [c | delta c] of both sides (dynamic_rows: the deltas are taken on each utterance,
+    before the pairing), for conversion_train(span=)."""
     CA, CB = _cepstrum_rows(CA, "CA"), _cepstrum_rows(CB, "CB")
     p, _ = _path(path, len(CA))
     if p[:, 1].max() >= len(CB):
         raise ValueError("path must pair instants of A with instants 0..%d of B" % (len(CB) - 1))
+    if span is not None:
+        span = check_span(span)
+        CA, CB = (dynamic_rows(C, span, device_index=device_index) for C in (CA, CB))
     X, Y = CA[p[:, 0]], CB[p[:, 1]]
     keep = ~(np.isneginf(X[:, 0]) | np.isneginf(Y[:, 0]))
     return X[keep], Y[keep]
 
 
-def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, device_index=0):
+def dynamic_rows(C, span=2, *, device_index=0):
+    """Cepstral rows `C` float64[n, P + 1] extended with their delta features: float64[n, 2 (P + 1)],
+    row t = [c_t | delta c_t], delta c_t = sum_tau w_tau (c_clip(t + tau) - c_clip(t - tau)), tau = 1 .. span, w_tau =
+    tau / (2 sum_k k^2).  `clip` holds the index inside the row's own run of consecutive non-empty rows (the edge row is
+    repeated, the HTK convention), so nothing crosses an unvoiced gap and a run of one row has delta 0.  An empty row
+    (-inf, 0, .., 0) gives (-inf, 0, .. | 0, ..).  `span` is in [1, 8]."""
+    C = _cepstrum_rows(C, "C")
+    span = check_span(span)
+    torch, c, dev = _device(device_index)
+    n, cols = C.shape
+    out = torch.empty((n, cols), dtype=torch.float64, device=dev)
+    c.ceps_delta(torch.as_tensor(C, device=dev), n, cols, span, out)
+    return np.hstack((C, out.cpu().numpy()))
+
+
+def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None,
+                     device_index=0):
     """Learns the map from rows `X` float64[N, P + 1] to rows `Y` float64[N, Q + 1] (conversion_pairs') as a joint
     mixture of `components` Gaussians over [x | y].  level=False leaves column 0, the level c_0, out of
     both sides: conversion_apply copies it from the source row (a recording level is not a property of the speaker);
     level=True maps it like any other column.  The default initialisation looks at the x columns only.  Returns a flat
     dict of arrays that np.savez stores and np.load(allow_pickle=False) returns: gmm_fit's fields, dx, dy, level,
-    A[M, dy, dx], b[M, dy] and the marginal mixture's Wx[M, dx, dx], kx[M]."""
-    X, Y, level = check_conversion_arguments(X, Y, components, level, iters, tol, floor, init)
+    A[M, dy, dx], b[M, dy] and the marginal mixture's Wx[M, dx, dx], kx[M].
+    With `span` in [1, 8] the rows are dynamic rows [c | delta c] (conversion_pairs(span=)) and the map is a dynamic one
+    for conversion_trajectory: the mixture is over [x | delta x | y | delta y], level=False leaves
+    column 0 and its delta out, dx and dy count the delta columns (at most 64 a side), and the dict gains span and
+    py[M, dy], the reciprocal diagonals of the conditional covariances."""
+    X, Y, level = check_conversion_arguments(X, Y, components, level, iters, tol, floor, init, span)
     skip = 0 if level else 1
-    Z = np.ascontiguousarray(np.hstack((X[:, skip:], Y[:, skip:])))
-    dx, dy = X.shape[1] - skip, Y.shape[1] - skip
+    if span is None:
+        x, y = X[:, skip:], Y[:, skip:]
+    else:
+        x, y = _dynamic_columns(X, X.shape[1] // 2, skip), _dynamic_columns(Y, Y.shape[1] // 2, skip)
+    Z = np.ascontiguousarray(np.hstack((x, y)))
+    dx, dy = x.shape[1], y.shape[1]
     g = gmm_fit(Z, components, iters=iters, tol=tol, floor=floor, init=init, split=dx, device_index=device_index)
     A, b, Wx, kx = gmm_conversion_parameters(g["weights"], g["means"] - g["zbar"], g["covs"], dx)
     g.update(n=np.int64(g["n"]), dx=np.int64(dx), dy=np.int64(dy), level=np.bool_(level), A=A, b=b, Wx=Wx, kx=kx)
+    if span is not None:
+        g.update(span=np.int64(check_span(span)), py=gmm_conditional_precisions(g["covs"], A, dx))
     return g
 
 
@@ -354,6 +461,8 @@ def conversion_apply(conv, C, *, device_index=0):
     source row's.  Returns float64[n, dy_cols], accepted by eaQHMSynthesis(envelope=), model_from_parameters and
     cepstrum_envelope as it stands."""
     v = check_conversion(conv)
+    if "span" in v:
+        raise ValueError("this conversion is a dynamic map (span %d): use conversion_trajectory" % v["span"])
     skip = 0 if v["level"] else 1
     dx, dy, M = v["dx"], v["dy"], len(v["weights"])
     C = _cepstrum_rows(C, "C")
@@ -373,6 +482,53 @@ def conversion_apply(conv, C, *, device_index=0):
     mix.c.gmm_regress(mix.Z, gamma, t.as_tensor(v["A"], device=mix.dev), t.as_tensor(v["b"], device=mix.dev), n, dx, dy,
                       M, Y)
     out[full, skip:] = Y.cpu().numpy() + v["zbar"][dx:]
+    if skip:
+        out[full, 0] = C[full, 0]
+    return out
+
+
+def conversion_trajectory(conv, C, *, device_index=0):
+    """Converts cepstral rows `C` float64[n, dx_cols] (model_cepstrum's layout) with a dynamic map, conversion_train(span=)'s,
+    to the trajectory that is most likely under the static and the delta statistics together (Toda,
+    Black & Tokuda 2007, the posterior-weighted initial estimate).  With X_t = [x_t | delta x_t], gamma the posteriors of
+    the marginal mixture on X, P_t = sum_m gamma_tm py_m and r_t = sum_m gamma_tm py_m (b_m + A_m X_t) (un-centred), every
+    run of non-empty rows and every static column d solves (diag(P^s) + W^T diag(P^D) W) y = r^s + W^T r^D, W the run's
+    delta matrix.  Nothing couples across an empty row; an empty row comes back empty; with level=False column 0 is the
+    source row's.  Returns float64[n, dy_cols], accepted wherever conversion_apply's result is."""
+    v = check_conversion(conv)
+    if "span" not in v:
+        raise ValueError("this conversion is a static map (no span): use conversion_apply")
+    skip = 0 if v["level"] else 1
+    span, dx, dy, M = v["span"], v["dx"], v["dy"], len(v["weights"])
+    dxs, dys = dx // 2, dy // 2
+    C = _cepstrum_rows(C, "C")
+    if C.shape[1] != dxs + skip:
+        raise ValueError("C must have %d columns for this conversion, got %d" % (dxs + skip, C.shape[1]))
+    full = ~np.isneginf(C[:, 0])
+    out = np.zeros((len(C), dys + skip))
+    out[~full, 0] = -np.inf
+    n = int(np.count_nonzero(full))
+    if n == 0:
+        return out
+    D = dynamic_rows(C, span, device_index=device_index)
+    mu_c = v["means"] - v["zbar"]
+    mix = _Mixture(_dynamic_columns(D[full], C.shape[1], skip), v["zbar"][:dx], M, device_index)
+    gamma, _ = mix.estep(mu_c[:, :dx], v["Wx"], v["kx"])
+    t, dev = mix.torch, mix.dev
+    py = v["py"]
+    r = t.empty((n, dy), dtype=t.float64, device=dev)
+    mix.c.gmm_regress(mix.Z, gamma, t.as_tensor(np.ascontiguousarray(py[:, :, None] * v["A"]), device=dev),
+                      t.as_tensor(np.ascontiguousarray(py * (v["b"] + v["zbar"][dx:])), device=dev), n, dx, dy, M, r)
+    P = gamma @ t.as_tensor(py, device=dev)
+    _, length = delta_runs(full)                       # the runs on the compacted rows: back to back
+    start = np.concatenate(([0], np.cumsum(length)[:-1])).astype(np.int64)
+    words = mix.c.mlpg_work_len(n, dys, span)
+    if words != n * (2 * span + 2) * dys:
+        raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the trajectory solve's work buffer")
+    Y = t.empty((n, dys), dtype=t.float64, device=dev)
+    mix.c.mlpg_solve(P.contiguous(), r, n, dys, span, t.as_tensor(start, device=dev), t.as_tensor(length, device=dev),
+                     len(start), t.empty(words, dtype=t.float64, device=dev), Y)
+    out[full, skip:] = Y.cpu().numpy()
     if skip:
         out[full, 0] = C[full, 0]
     return out

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # EAQHM_LIB: A/B measurements with an alternative build of the same library (tools/); the product default is in-tree
 LIB_PATH = os.environ.get("EAQHM_LIB") or os.path.join(_HERE, "csrc", "libeaqhm_hip.so")
 
-# every symbol include/eaqhm_hip.h declares: (name, restype, argtypes)
+# every symbol include/eaqhm_hip.h itself declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
 # EAQHM_ABI_VERSION (csrc/eaqhm_common.h) this binding was written for: argument lists change under unchanged names
@@ -64,6 +64,12 @@ SYMBOLS = (
     ("eaqhm_gmm_mstep", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
     ("eaqhm_gmm_regress", C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P]),
 )
+# every symbol include/eaqhm_mlpg.h declares: a table of its own, bound with SYMBOLS
+SYMBOLS_MLPG = (
+    ("eaqhm_ceps_delta", C.c_int, [_P, _P, _I64, _I32, _I32, _P]),
+    ("eaqhm_mlpg_work_len", _I64, [_I64, _I32, _I32]),
+    ("eaqhm_mlpg_solve", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -86,7 +92,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + SYMBOLS_MLPG:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -323,6 +329,17 @@ class Context:
 
     def gmm_regress(self, X, gamma, A, b, N, dx, dy, M, Y_out):
         self._ck(self.lib.eaqhm_gmm_regress(self.h, _ptr(X), _ptr(gamma), _ptr(A), _ptr(b), N, dx, dy, M, _ptr(Y_out)))
+
+    # delta rows and the trajectory solve: P, r [n][2 dy] static half first, runs int64 device tensors
+    def ceps_delta(self, C_, n, cols, span, out):
+        self._ck(self.lib.eaqhm_ceps_delta(self.h, _ptr(C_), n, cols, span, _ptr(out)))
+
+    def mlpg_work_len(self, n, dy, span):
+        return int(self.lib.eaqhm_mlpg_work_len(n, dy, span))
+
+    def mlpg_solve(self, P, r, n, dy, span, run_start, run_len, n_runs, work, Y):
+        self._ck(self.lib.eaqhm_mlpg_solve(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
+                                           _ptr(work), _ptr(Y)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

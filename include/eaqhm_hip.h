@@ -506,6 +506,10 @@ int eaqhm_gmm_mstep(eaqhm_ctx* ctx, const double* Z, const double* gamma, int64_
 int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, const double* A, const double* b, int64_t N,
                       int32_t dx, int32_t dy, int32_t M, double* Y_out);
 
+/* delta rows and the maximum-likelihood trajectory of the conversion (additions under ABI 6): the
+ * declarations are in eaqhm_mlpg.h, which this header includes.                                                      */
+#include "eaqhm_mlpg.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,9 @@ alignment: the model's cepstrum against a copy of itself stret
 (EAQHM_OPT_DTW_PHASES), each the median of three windows with their max - min, and the NumPy model's time for the same
 band on a 5 s excerpt on the host.  --noise-cepstrum adds the noise model to and from cepstral rows on
 the workload's residual model: eaqhm_noise_cepstrum (Q = 63) and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp at
-alpha = 1.2, with the same windows and the warp's max - min as the margin.  EAQHM_LIB selects another build of
+alpha = 1.2, with the same windows and the warp's max - min as the margin.  --mlpg times the delta rows and the
+trajectory solve on random rows, once as one run and once as 200 runs, next to
+scipy.linalg.solveh_banded on the host.  EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -227,6 +229,78 @@ def gmm_rows(torch, reps=20, runs=3, sizes=(65536, 1000000), shapes=((18, 18, 8)
             print(json.dumps(rows[-1]), flush=True)
             del Z, gamma, work, X, Y
             torch.cuda.empty_cache()
+    return rows
+
+
+def host_band(P, r, span):
+    """(ab [2 span + 1, T, dy], q [T, dy]): the lower band of R = diag(P^s) + W^T diag(P^D) W in solveh_banded's layout
+    (ab[k, i] = R[i + k, i]) and q = r^s + W^T r^D for one run of T rows, every column at once.  NumPy on the host."""
+    T, dy = P.shape[0], P.shape[1] // 2
+    L, u = span, np.arange(T)
+    w = np.arange(1, L + 1) / (2.0 * sum(k * k for k in range(1, L + 1)))
+    A = np.zeros((T, 2 * L + 1))                         # A[u, c - u + L] = W[u, c]
+    for tau in range(1, L + 1):
+        np.add.at(A, (u, np.minimum(u + tau, T - 1) - u + L), w[tau - 1])
+        np.add.at(A, (u, np.maximum(u - tau, 0) - u + L), -w[tau - 1])
+    ab = np.zeros((2 * L + 1, T, dy))
+    ab[0] = P[:, :dy]
+    q = r[:, :dy].copy()
+    for e in range(2 * L + 1):                           # row u of W touches column i = u + e - L
+        i = u + e - L
+        ok = (i >= 0) & (i < T)
+        q[i[ok]] += A[ok, e, None] * r[ok, dy:]
+        for f in range(e, 2 * L + 1):                    # ... and column i + k, k = f - e
+            ok2 = ok & (i + f - e < T)
+            np.add.at(ab[f - e], i[ok2], (A[ok2, e] * A[ok2, f])[:, None] * P[ok2, dy:])
+    return ab, q
+
+
+def mlpg_rows(torch, n=60000, dys=24, span=2, reps=5, runs=3):
+    """eaqhm_ceps_delta on n rows of dys + 1 columns and eaqhm_mlpg_solve on n rows of dys static columns (DESIGN.md
+    §12.1), once with all rows in one run and once cut into 200 equal runs.  Each time: median of `runs` warmed windows of
+    `reps` launches, and max - min of the windows.  Beside them scipy.linalg.solveh_banded on the host for the same dys
+    systems per run, from the band the host forms with NumPy (forming not timed): a comparison, not a bar."""
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    g = torch.Generator(device=dev).manual_seed(n + dys + span)
+    C = torch.randn(n, dys + 1, dtype=torch.float64, device=dev, generator=g)
+    D = torch.empty_like(C)
+    P = torch.exp(torch.randn(n, 2 * dys, dtype=torch.float64, device=dev, generator=g))
+    P[:, dys:] *= 100.0
+    r = torch.randn(n, 2 * dys, dtype=torch.float64, device=dev, generator=g) * P
+    work = torch.empty(c.mlpg_work_len(n, dys, span), dtype=torch.float64, device=dev)
+    Y = torch.empty((n, dys), dtype=torch.float64, device=dev)
+    d = med(lambda: c.ceps_delta(C, n, dys + 1, span, D))
+    rows = []
+    for n_runs in (1, 200):
+        T = n // n_runs
+        start = torch.arange(n_runs, dtype=torch.int64, device=dev) * T
+        length = torch.full((n_runs,), T, dtype=torch.int64, device=dev)
+        t = med(lambda: c.mlpg_solve(P, r, n, dys, span, start, length, n_runs, work, Y))
+        row = dict(n=n, dys=dys, span=span, n_runs=n_runs, delta_ms=d[0], delta_spread_ms=d[1], solve_ms=t[0],
+                   solve_spread_ms=t[1])
+        try:
+            from scipy.linalg import solveh_banded
+            Ph, rh = P.cpu().numpy(), r.cpu().numpy()
+            bands = []
+            for k in range(n_runs):                      # one contiguous band and right-hand side per system
+                ab, q = host_band(Ph[k * T:(k + 1) * T], rh[k * T:(k + 1) * T], span)
+                bands.append((np.ascontiguousarray(ab.transpose(2, 0, 1)), np.ascontiguousarray(q.T)))
+            t0 = time.perf_counter()
+            for ab, q in bands:
+                for j in range(dys):
+                    solveh_banded(ab[j], q[j], lower=True)
+            row["host_solveh_banded_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        except ImportError:
+            row["host_solveh_banded_ms"] = None
+        rows.append(row)
+        print(json.dumps(row), flush=True)
     return rows
 
 
@@ -720,8 +794,19 @@ def main():
     ap.add_argument("--gmm", action="store_true",
                     help="time eaqhm_gmm_estep, eaqhm_gmm_mstep and eaqhm_gmm_regress next to torch matmuls (random rows; "
                          "needs no workload: pass --workloads '')")
+    ap.add_argument("--mlpg", action="store_true",
+                    help="time eaqhm_ceps_delta and eaqhm_mlpg_solve next to scipy.linalg.solveh_banded on the host (random "
+                         "rows; needs no workload: pass --workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.mlpg:
+        import torch
+        res_mlpg = dict(mlpg=mlpg_rows(torch))
+        if not a.workloads and not a.gmm:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump([res_mlpg], f, indent=1)
+            return 0
     if a.gmm:
         import torch
         res_gmm = dict(gmm=gmm_rows(torch))
@@ -735,6 +820,8 @@ def main():
            for w in a.workloads.split(",")]
     if a.gmm:
         res.append(res_gmm)
+    if a.mlpg:
+        res.append(res_mlpg)
     for r in res:
         print(json.dumps(r))
     if a.out:
