@@ -17,7 +17,8 @@
 //          loaded directly, phase = running sum (16-lane DPP scan + per-slot carry); the pair shares its sincos
 //          because the negative-frequency column at u is the time-reversed positive one (functions.py:284-285);
 //          contracted with v_mfma_f64_16x16x4_f64, LDS operand reads software-pipelined one k-step ahead; frames of
-//          <= 10 tile rows: only X = w [E2 | s] in the chunk, three-weight Gramian G_p = X^H diag(n^p) X (TW in tile_frame)
+//          <= 12 tile rows: only X = w [E2 | s] in the chunk, three-weight Gramian G_p = X^H diag(n^p) X (TW in tile_frame;
+//          11-12 tile rows: dealt out by the unit table eaqhm_ls_twunits.h, UA / UB in tile_frame)
 //   B0     adaptation 0: no basis at all — the Gramian in closed form from Toeplitz tables, then two real systems of
 //          half the order factorised side by side (a0_frame, eaqhm_ls_a0.h)
 //   C      right-looking tile Cholesky with look-ahead, 2 workgroup barriers per tile row: trailing update with the
@@ -30,10 +31,12 @@
 //
 // Frames with more than 13 tile rows (Kc > 103) do not fit the register budget and are left to
 // eaqhm_ls_mfma_kernel (same Gramian, factorisation through scratch memory).
+#include <type_traits>
 #include "eaqhm_ls_common.h"
 #include "eaqhm_ls_chol.h"
 #include "eaqhm_ls_a0.h"
 #include "eaqhm_ls_tilemap.h"
+#include "eaqhm_ls_twunits.h"
 
 namespace eaqhm {
 
@@ -77,7 +80,50 @@ __device__ inline void tw_step(d4 (&g)[9], double aR, double aI, double bR, doub
   g[8] = __builtin_amdgcn_mfma_f64_16x16x4f64(nsA, ndB, g[8], 0, 0, 0);
 }
 
-template <int NS, int TW>
+// A whole pair in K3 slots: tw_step on three accumulator triples.
+__device__ inline void twu_pair_k3(d4 (&g0)[3], d4 (&g1)[3], d4 (&g2)[3], double aR, double aI, double bR, double bI, double nk) {
+  const double sA = aR + aI, dB = bI - bR;
+  const double naR = nk * aR, naI = nk * aI, nsA = nk * sA;
+  const double nbR = nk * bR, nbI = nk * bI, ndB = nk * dB;
+  g0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g0[0], 0, 0, 0);
+  g0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g0[1], 0, 0, 0);
+  g0[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(sA, dB, g0[2], 0, 0, 0);
+  g1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, bR, g1[0], 0, 0, 0);
+  g1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, bI, g1[1], 0, 0, 0);
+  g1[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(nsA, dB, g1[2], 0, 0, 0);
+  g2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, nbR, g2[0], 0, 0, 0);
+  g2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, nbI, g2[1], 0, 0, 0);
+  g2[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(nsA, ndB, g2[2], 0, 0, 0);
+}
+// A whole pair in two-accumulator slots: g[0] = re re' + im im', g[1] = re im' (- im re' with k4: form K4; without: form H,
+// the diagonal pair's RI).  Four scaled operands, no sums.
+__device__ inline void twu_pair_2acc(d4 (&g0)[2], d4 (&g1)[2], d4 (&g2)[2], double aR, double aI, double bR, double bI, double nk,
+                                     bool k4) {
+  const double naR = nk * aR, naI = nk * aI, nbR = nk * bR, nbI = nk * bI;
+  g0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g0[0], 0, 0, 0);
+  g1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, bR, g1[0], 0, 0, 0);
+  g2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, nbR, g2[0], 0, 0, 0);
+  g0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bI, g0[1], 0, 0, 0);
+  g1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, bI, g1[1], 0, 0, 0);
+  g2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(naR, nbI, g2[1], 0, 0, 0);
+  g0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g0[0], 0, 0, 0);
+  g1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, bI, g1[0], 0, 0, 0);
+  g2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(naI, nbI, g2[0], 0, 0, 0);
+  if (k4) {
+    const double maI = -aI, mnaI = -naI;
+    g0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(maI, bR, g0[1], 0, 0, 0);
+    g1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(mnaI, bR, g1[1], 0, 0, 0);
+    g2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(mnaI, nbR, g2[1], 0, 0, 0);
+  }
+}
+
+// UA + UB > 0 (TW = 0): the three-weight Gramian of a frame with TWU_T basis tile columns, dealt out by the unit table
+// (eaqhm_ls_twunits.h: a unit is one tile G_p[I][J]).  A wave has UA slots of three accumulators (form K3: the three real
+// products of tw_step) and UB slots of two (K4: four real products, re re' + im im' and re im' - im re'; H, diagonal pairs
+// only: the K4 form without its fourth product, the second accumulator holds RI = sum re im' and the gather takes
+// Im = RI - RI^T).  3 UA + 2 UB accumulators per wave whatever the number of basis pairs; the first 3 (UA / 3) and
+// 3 (UB / 3) slots hold whole pairs, contracted like a pair of the TW form, the others single units.
+template <int NS, int TW, int UA = 0, int UB = 0>
 __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, int ldx_max_, double* lds, int f_) {
   const int TS = uni(TS_), ldx_max = uni(ldx_max_), f = uni(f_);
   const int tid = threadIdx.x, nt_thr = TL_THREADS;
@@ -127,7 +173,12 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     const int c = uni(A.frame_c[f]), wl = uni(A.frame_wl[f]), inst = uni(A.frame_inst[f]);
     const int N = 2 * wl + 1, mid = wl;
     const int T = (Kc + 16) >> 4;                      // three-weight basis: tile columns of X = w [E2 | s]
-    const int nb = TW ? T : nt;                        // tile columns of the basis chunk
+    constexpr int UN = UA + UB;                        // unit slots of a wave
+    constexpr int GA = UA / 3, GB = UB / 3;            // ... of which 3 GA + 3 GB hold whole pairs (weights 0, 1, 2 in a row)
+    constexpr bool G3 = TW > 0 || UN > 0;              // three-weight Gramian (whole pairs or units)
+    static_assert(TW == 0 || UN == 0, "whole pairs or units");
+    static_assert(UN == 0 || (UA == TWU_UA && UB == TWU_UB), "slot layout of eaqhm_ls_twunits.h");
+    const int nb = G3 ? T : nt;                        // tile columns of the basis chunk
     const int ldx = (nb << 4) + ((nb & 1) ? 0 : 16);  // ≡ 16 (mod 32): MFMA operand reads hit disjoint bank halves
     const int npair = T * (T + 1) / 2;
     const int is = 2 * Kc - 16 * (nt - 1);  // position of the signal column inside the last tile row (2,6,10,14)
@@ -191,6 +242,21 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       for (int p = 0; p < 9; ++p) g[sl][p] = (d4){0, 0, 0, 0};
     }
 
+    // unit slots: the first UA with three accumulators, the others with two; code as in TWU_MAP, wave-uniform
+    constexpr int UAA = UA > 3 ? UA : 3, UBA = UB > 3 ? UB : 3;   // (at least one whole pair: the unused ones cost nothing)
+    d4 ga[UAA][3], gb[UBA][2];
+    int ucode[UN ? UN : 1];
+    if constexpr (UN > 0) {
+#pragma unroll
+      for (int sl = 0; sl < UN; ++sl) ucode[sl] = __builtin_amdgcn_readfirstlane((int)TWU_MAP[wave][sl]);
+#pragma unroll
+      for (int sl = 0; sl < UA; ++sl)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) ga[sl][p] = (d4){0, 0, 0, 0};
+#pragma unroll
+      for (int sl = 0; sl < UB; ++sl) gb[sl][0] = gb[sl][1] = (d4){0, 0, 0, 0};
+    }
+
     // ================= Gramian =================
     // sample pairs (u, v) = (mid-d-1, mid+d), d = 0..mid, taken from the centre outwards so that the phase
     // integral of functions.py:508-515 relative to the centre is a running sum
@@ -241,12 +307,12 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           const double wu = win[u], nu = (double)(u - mid);
           pur *= wu; pui *= wu; nur *= wu; nui *= wu;
           xr[cpos] = pur;      xi[cpos] = pui;      xr[cneg] = nur;      xi[cneg] = nui;
-          if (!TW) { xr[spos] = nu * pur; xi[spos] = nu * pui; xr[sneg] = nu * nur; xi[sneg] = nu * nui; }
+          if (!G3) { xr[spos] = nu * pur; xi[spos] = nu * pui; xr[sneg] = nu * nur; xi[sneg] = nu * nui; }
         }
         pvr *= wv; pvi *= wv; nvr *= wv; nvi *= wv;
         xr += ldx; xi += ldx;
         xr[cpos] = pvr;      xi[cpos] = pvi;      xr[cneg] = nvr;      xi[cneg] = nvi;
-        if (!TW) { xr[spos] = nv * pvr; xi[spos] = nv * pvi; xr[sneg] = nv * nvr; xi[sneg] = nv * nvi; }
+        if (!G3) { xr[spos] = nv * pvr; xi[spos] = nv * pvi; xr[sneg] = nv * nvr; xi[sneg] = nv * nvi; }
       }
       // DC / signal columns: one thread per chunk row, spread over the waves (lanes 0, 16, 32, 48)
       if ((tid & 15) == 0 && (tid >> 4) < TS) {
@@ -261,10 +327,10 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         double* xr = Xre + row * ldx;
         double* xi = Xim + row * ldx;
         xr[XCOL(n, el)] = w;               xi[XCOL(n, el)] = 0.0;            // DC column
-        if (!TW) {
+        if (!G3) {
           xr[XCOL(Kc + n, el)] = w * nn;   xi[XCOL(Kc + n, el)] = 0.0;       // its slope copy
         }
-        const int scol = TW ? Kc : 2 * Kc;
+        const int scol = G3 ? Kc : 2 * Kc;
         xr[XCOL(scol, el)] = w * sval;     xi[XCOL(scol, el)] = 0.0;         // signal column
       }
       // rows beyond the window (the virtual sample u = -1 and the tail of the last chunk): zero
@@ -281,7 +347,84 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       LS_STAMP(1);
       const int pcs = (npairs - d0 < PE) ? (npairs - d0) : PE;   // sample pairs in this chunk
       const int ksl = (pcs + 1) >> 1;                             // k-steps (4 rows each) that hold samples
-      if constexpr (TW > 0) {
+      if constexpr (UN > 0) {
+        // Whole pairs first — a pair's three weights share the four LDS reads and the n-scaled operands of a k-step (the
+        // f64 vector instructions that prepare operands do not run beside the f64 MFMAs here: dealt out as 63 single units
+        // with their own scaling, the contraction was slower than the stacked one in spite of 30 % fewer MFMAs) — then the
+        // single units.  Not software-pipelined, like the whole-pair loop below.
+        const int plane = TS * ldx_max;
+        const int kn = (ksl < 8) ? ksl : 8;
+#pragma unroll
+        for (int gi = 0; gi < GA + GB; ++gi) {
+          const int s0 = (gi < GA) ? 3 * gi : UA + 3 * (gi - GA);   // first slot of the group
+          const int code = ucode[s0];
+          if (code == 0xFFFF) continue;
+          const int ca = 16 * (code >> 8), cb = 16 * ((code >> 4) & 15);
+          const bool k4 = (code & 3) == 1;
+          int rb = lq * ldx;
+          const int sw0 = lcol + (lq >> 1);
+          // n_k of this lane's row 4 ks + lq: sample pair d = d0 + 2 ks + lq/2, odd rows t = mid + d, even rows t = mid - d - 1
+          int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
+          asm volatile("" : "+v"(rb), "+v"(nk));   // (hoisted out of the chunk loop, these spill)
+#pragma clang loop unroll(disable)
+          for (int ks = 0; ks < kn; ++ks) {
+            const int sw = (sw0 + 2 * ks) & 15;
+            const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
+            const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
+            rb += 4 * ldx;
+            if (gi < GA) {
+              const int q = (gi < GA) ? 3 * gi : 0;
+              twu_pair_k3(ga[q], ga[q + 1], ga[q + 2], aR, aI, bR, bI, (double)nk);
+            } else {
+              const int q = (gi >= GA) ? 3 * (gi - GA) : 0;
+              twu_pair_2acc(gb[q], gb[q + 1], gb[q + 2], aR, aI, bR, bI, (double)nk, k4);
+            }
+            nk += (lq & 1) ? 2 : -2;
+          }
+        }
+#pragma unroll
+        for (int sl = 0; sl < UN; ++sl) {
+          if ((sl < UA) ? (sl < 3 * GA) : (sl - UA < 3 * GB)) continue;   // a slot of a whole pair
+          const int code = ucode[sl];
+          if (code == 0xFFFF) continue;
+          const int ca = 16 * (code >> 8), cb = 16 * ((code >> 4) & 15), up = (code >> 2) & 3;
+          const bool k4 = (code & 3) == 1;
+          int rb = lq * ldx;
+          const int sw0 = lcol + (lq >> 1);
+          int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
+          asm volatile("" : "+v"(rb), "+v"(nk));
+          // the weight scales the operands (p >= 1: a by n_k, p = 2: b as well): one loop per weight, so that a unit pays
+          // for the scalings it needs and for no selects
+          auto run = [&](auto pc) {
+            constexpr int P = decltype(pc)::value;
+#pragma clang loop unroll(disable)
+            for (int ks = 0; ks < kn; ++ks) {
+              const int sw = (sw0 + 2 * ks) & 15;
+              double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
+              double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
+              rb += 4 * ldx;
+              if constexpr (P >= 1) { aR *= (double)nk; aI *= (double)nk; }
+              if constexpr (P == 2) { bR *= (double)nk; bI *= (double)nk; }
+              nk += (lq & 1) ? 2 : -2;
+              if (sl < UA) {
+                d4 (&g)[3] = ga[sl < UA ? sl : 0];
+                g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g[0], 0, 0, 0);
+                g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g[1], 0, 0, 0);
+                g[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR + aI, bI - bR, g[2], 0, 0, 0);
+              } else {
+                d4 (&g)[2] = gb[sl >= UA ? sl - UA : 0];
+                g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g[0], 0, 0, 0);
+                g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bI, g[1], 0, 0, 0);
+                g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g[0], 0, 0, 0);
+                if (k4) g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aI, bR, g[1], 0, 0, 0);
+              }
+            }
+          };
+          if (up == 0) run(std::integral_constant<int, 0>{});
+          else if (up == 1) run(std::integral_constant<int, 1>{});
+          else run(std::integral_constant<int, 2>{});
+        }
+      } else if constexpr (TW > 0) {
 #pragma unroll
         for (int sl = 0; sl < TW; ++sl) {
           if (!glive[sl]) continue;
@@ -304,25 +447,52 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             nk += (lq & 1) ? 2 : -2;
           }
         }
-      } else
+      } else {
 #pragma unroll
-      for (int sl = 0; sl < NS; ++sl) {
-        if (!live[sl]) continue;
-        const int ca = 16 * tP[sl], cb = 16 * tQ[sl];
-        // operands of k-step ks+1 are requested before the MFMAs of k-step ks are issued (LDS latency hidden
-        // behind the matrix pipe); row = 4 ks + lq, column swizzle (lcol + row/2) & 15
-        int rb = lq * ldx;
-        const int sw0 = lcol + (lq >> 1);
-        asm volatile("" : "+v"(rb));   // keep the address arithmetic inside the loop (hoisted, it spills)
-        const int plane = TS * ldx_max;
-        if (ksl < 8) {   // last chunk of the window: only the k-steps that hold samples (the other rows are zero)
+        for (int sl = 0; sl < NS; ++sl) {
+          if (!live[sl]) continue;
+          const int ca = 16 * tP[sl], cb = 16 * tQ[sl];
+          // operands of k-step ks+1 are requested before the MFMAs of k-step ks are issued (LDS latency hidden
+          // behind the matrix pipe); row = 4 ks + lq, column swizzle (lcol + row/2) & 15
+          int rb = lq * ldx;
+          const int sw0 = lcol + (lq >> 1);
+          asm volatile("" : "+v"(rb));   // keep the address arithmetic inside the loop (hoisted, it spills)
+          const int plane = TS * ldx_max;
+          if (ksl < 8) {   // last chunk of the window: only the k-steps that hold samples (the other rows are zero)
 #pragma clang loop unroll(disable)
-          for (int ks = 0; ks < ksl; ++ks) {
-            const int sw = (sw0 + 2 * ks) & 15;
-            const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
-            const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
-            rb += 4 * ldx;
-            if (sl < NM3) {
+            for (int ks = 0; ks < ksl; ++ks) {
+              const int sw = (sw0 + 2 * ks) & 15;
+              const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
+              const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
+              rb += 4 * ldx;
+              if (sl < NM3) {
+                accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, accR[sl], 0, 0, 0);
+                acc3[sl < NM3 ? sl : 0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, acc3[sl < NM3 ? sl : 0], 0, 0, 0);
+                accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR + aI, bI - bR, accI[sl], 0, 0, 0);
+              } else {
+                accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, accR[sl], 0, 0, 0);
+                accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bI, accI[sl], 0, 0, 0);
+                accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, accR[sl], 0, 0, 0);
+                accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aI, bR, accI[sl], 0, 0, 0);
+              }
+            }
+            continue;
+          }
+          double aR, aI, bR, bI;
+          {
+            const int sw = sw0 & 15;
+            aR = Xre[rb + ca + sw]; aI = Xre[rb + ca + sw + plane]; bR = Xre[rb + cb + sw]; bI = Xre[rb + cb + sw + plane];
+          }
+#pragma unroll
+          for (int ks = 0; ks < 8; ++ks) {   // TS = 32 rows
+            double naR = 0, naI = 0, nbR = 0, nbI = 0;
+            if (ks < 7) {
+              rb += 4 * ldx;
+              const int sw = (sw0 + 2 * (ks + 1)) & 15;
+              naR = Xre[rb + ca + sw]; naI = Xre[rb + ca + sw + plane]; nbR = Xre[rb + cb + sw]; nbI = Xre[rb + cb + sw + plane];
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the requests above stay ahead of the MFMAs below
+            if (sl < NM3) {   // three real products per complex one: P1 = aR bR, P2 = aI bI, P3 = (aR+aI)(bI-bR)
               accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, accR[sl], 0, 0, 0);
               acc3[sl < NM3 ? sl : 0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, acc3[sl < NM3 ? sl : 0], 0, 0, 0);
               accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR + aI, bI - bR, accI[sl], 0, 0, 0);
@@ -332,34 +502,8 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
               accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, accR[sl], 0, 0, 0);
               accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aI, bR, accI[sl], 0, 0, 0);
             }
+            aR = naR; aI = naI; bR = nbR; bI = nbI;
           }
-          continue;
-        }
-        double aR, aI, bR, bI;
-        {
-          const int sw = sw0 & 15;
-          aR = Xre[rb + ca + sw]; aI = Xre[rb + ca + sw + plane]; bR = Xre[rb + cb + sw]; bI = Xre[rb + cb + sw + plane];
-        }
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {   // TS = 32 rows
-          double naR = 0, naI = 0, nbR = 0, nbI = 0;
-          if (ks < 7) {
-            rb += 4 * ldx;
-            const int sw = (sw0 + 2 * (ks + 1)) & 15;
-            naR = Xre[rb + ca + sw]; naI = Xre[rb + ca + sw + plane]; nbR = Xre[rb + cb + sw]; nbI = Xre[rb + cb + sw + plane];
-          }
-          __builtin_amdgcn_sched_barrier(0);   // the requests above stay ahead of the MFMAs below
-          if (sl < NM3) {   // three real products per complex one: P1 = aR bR, P2 = aI bI, P3 = (aR+aI)(bI-bR)
-            accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, accR[sl], 0, 0, 0);
-            acc3[sl < NM3 ? sl : 0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, acc3[sl < NM3 ? sl : 0], 0, 0, 0);
-            accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR + aI, bI - bR, accI[sl], 0, 0, 0);
-          } else {
-            accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, accR[sl], 0, 0, 0);
-            accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bI, accI[sl], 0, 0, 0);
-            accR[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, accR[sl], 0, 0, 0);
-            accI[sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aI, bR, accI[sl], 0, 0, 0);
-          }
-          aR = naR; aI = naI; bR = nbR; bI = nbI;
         }
       }
       __syncthreads();
@@ -373,13 +517,35 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         accI[sl] = accI[sl] + (p1 - p2);
       }
     }
-    if constexpr (TW > 0) {
+    if constexpr (G3) {
       // The G_p tiles go through the workgroup's scratch area (the bridged track rows are dead now; <= 3 * 21 tiles of
       // 16 x 16 complex values, see ls_tile_scratch_stride), then every wave gathers its system tiles.  Y = [X_E | n X_E | s]
       // with X = [X_E | s], so entry (R, C) of Y^H Y is G_p[a][b]: a = R (amplitude row), R - Kc (slope row) or Kc
       // (signal row), likewise b for C, p = the number of slope indices among R and C.  Every G_p is Hermitian (n is
       // real): entries above the tile diagonal of G_p are conjugates of computed ones.
       double* Gs = Qs;
+      if constexpr (UN > 0) {
+        // a unit's tile: (Re, Im) for K3 and K4, (Re, RI) for H — the gather below takes Im = RI - RI^T there
+#pragma unroll
+        for (int sl = 0; sl < UN; ++sl) {
+          const int code = ucode[sl];
+          if (code == 0xFFFF) continue;
+          const int I = code >> 8, J = (code >> 4) & 15, up = (code >> 2) & 3;
+          d4 re, im;
+          if (sl < UA) {
+            const d4 p1 = ga[sl < UA ? sl : 0][0], p2 = ga[sl < UA ? sl : 0][1];
+            re = p1 + p2; im = ga[sl < UA ? sl : 0][2] + (p1 - p2);
+          } else {
+            re = gb[sl >= UA ? sl - UA : 0][0]; im = gb[sl >= UA ? sl - UA : 0][1];
+          }
+          double* gt = Gs + (size_t)(up * npair + I * (I + 1) / 2 + J) * 512;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = 2 * (16 * (lq + 4 * r) + lcol);
+            gt[o] = re[r]; gt[o + 1] = im[r];
+          }
+        }
+      } else
 #pragma unroll
       for (int sl = 0; sl < TWA; ++sl) {
         if (!glive[sl]) continue;
@@ -411,8 +577,10 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
           double vr = 0.0, vi = 0.0;
           if (!pad) {
-            const double2 v = *(const double2*)(Gs + (size_t)(p * npair + I * (I + 1) / 2 + J) * 512 + 2 * (16 * i + j));
+            const double* gt = Gs + (size_t)(p * npair + I * (I + 1) / 2 + J) * 512;
+            const double2 v = *(const double2*)(gt + 2 * (16 * i + j));
             vr = v.x; vi = lo ? v.y : -v.y;
+            if (UN > 0 && I == J) vi = v.y - gt[2 * (16 * j + i) + 1];   // H unit (lo holds): Im = RI - RI^T
           }
           accR[sl][r] = vr; accI[sl][r] = vi;
         }
@@ -682,6 +850,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_ls_zero_prefix_kernel(co
 extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(LsArgs A, int TS, int ldx_max) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int nxt;
+#define TW_UNITS 0, TWU_UA, TWU_UB   /* template arguments TW, UA, UB of a class that contracts units */
 #define RUN_CLASS(NSV, TWV, C)                                                             \
   for (;;) {                                                                             \
     if (threadIdx.x == 0) nxt = atomicAdd(A.cls + 8 + C, 1);                             \
@@ -692,13 +861,14 @@ extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(Ls
     if (A.mode == 0) a0_frame<A0_NS, A0_M, 2>(A, lds, A.cls[16 + (size_t)C * A.n_frames + item], TZ_TB, TZ_NCH, 520, 64 * CI_NCH);                          \
     else tile_frame<NSV, TWV>(A, TS, ldx_max, lds, A.cls[16 + (size_t)C * A.n_frames + item]);          \
   }
-  RUN_CLASS(12, 0, 5)   // 91 tiles
-  RUN_CLASS(10, 0, 4)   // 78 tiles
-  RUN_CLASS(9, 0, 3)    // 66 tiles
+  RUN_CLASS(12, 0, 5)   // 91 tiles, T = 7: stacked
+  RUN_CLASS(10, TW_UNITS, 4)   // 78 tiles, T = 6: 63 units of the three-weight Gramian (eaqhm_ls_twunits.h)
+  RUN_CLASS(9, TW_UNITS, 3)    // 66 tiles, T = 6
   RUN_CLASS(7, 2, 2)    // 55 tiles, T = 5: 15 basis pairs
   RUN_CLASS(6, 2, 1)    // 45 tiles, T = 5
   RUN_CLASS(5, 2, 0)    // <= 36 tiles, T <= 4: <= 10 basis pairs
 #undef RUN_CLASS
+#undef TW_UNITS
 }
 
 // dynamic LDS the kernel may ask for: it also has a static __shared__ word (the frame cursor), and dynamic + static must
