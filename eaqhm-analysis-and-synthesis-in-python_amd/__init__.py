@@ -11,7 +11,7 @@ from .model import (SCALE_RANGE, cepstrum_phase, model_from_parameters, model_pa
                     eaQHMNoiseSynthesis, eaQHMNoiseWarp, eaQHMSynthesis, formant_warp_vtln, model_cepstrum, model_envelope, model_f0,
                     model_phase, noise_alignment_index, noise_cepstrum, noise_envelope, noise_formant_contour, noise_formant_warp, noise_from_cepstrum, noise_fundamental, noise_time_map, noise_time_map_contour,
                     scale_contour, unpack_model)
-from .convert import (check_conversion, check_conversion_arguments, check_gmm_arguments, conversion_apply,  # noqa: F401
-                      conversion_pairs, conversion_train, conversion_trajectory, dynamic_rows, f0_statistics, gmm_fit,
-                      gmm_posteriors, pitch_conversion_contour)
+from .convert import (check_conversion, check_conversion_arguments, check_gmm_arguments, check_gv_arguments,  # noqa: F401
+                      conversion_apply, conversion_pairs, conversion_train, conversion_trajectory, dynamic_rows,
+                      f0_statistics, global_variance, gmm_fit, gmm_posteriors, gv_statistics, pitch_conversion_contour)
 from .prologue import read_signal  # noqa: F401

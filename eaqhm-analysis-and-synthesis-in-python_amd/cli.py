@@ -43,7 +43,13 @@ or a different fs is an error; not with --envelope-from, --no-envelope or --conv
 extended with their delta features over a window of L instants a side before the pairing (convert.conversion_pairs(span=)),
 the mixture is over the extended rows, and MAP.npz carries the span.  --conversion MAP.npz with such a map converts this
 file to the most likely trajectory under the static and the delta statistics (convert.conversion_trajectory, DESIGN.md
-§12.1) in place of the row-by-row rule, so that the converted envelope does not jump where the posterior changes component."""
+§12.1) in place of the row-by-row rule, so that the converted envelope does not jump where the posterior changes component.
+--conversion-gv [S] (with --conversion-train and --conversion-span) also stores the target's global-variance statistics in
+MAP.npz (convert.gv_statistics of TARGET's cepstrum): the variance of each coefficient over the utterance, with a stated
+relative spread S (0.25 when left out: one utterance has no spread of its own).  --conversion MAP.npz with such a map adds
+the global-variance term to the trajectory, which gives the converted coefficients the target's variance
+back; --conversion-no-gv switches it off, --conversion-gv-iters K (30) and --conversion-gv-weight G (1) set the number of
+sweeps and the weight of the term."""
 import argparse
 
 import numpy as np
@@ -132,6 +138,16 @@ def parser():
     ap.add_argument("--conversion-span", type=int, default=None, metavar="L",
                     help="with --conversion-train: learn a dynamic map on rows extended with their delta features over L "
                          "instants a side, 1 to 8; --conversion then converts to the most likely trajectory")
+    ap.add_argument("--conversion-gv", type=float, nargs="?", const=0.25, default=None, metavar="S",
+                    help="with --conversion-train and --conversion-span: store the target's global variance in the map, "
+                         "with the relative spread S, 0 < S <= 10 (0.25); S is optional, so the flag must not stand directly "
+                         "before the input file, which it would take for S")
+    ap.add_argument("--conversion-no-gv", action="store_true",
+                    help="with --conversion: leave the global-variance term out although the map carries it")
+    ap.add_argument("--conversion-gv-iters", type=int, default=None, metavar="K",
+                    help="with --conversion and a map that carries the global variance: sweeps, 0 to 10000 (30)")
+    ap.add_argument("--conversion-gv-weight", type=float, default=None, metavar="G",
+                    help="with --conversion and a map that carries the global variance: weight of the term, 1e-6 to 1e6 (1)")
     ap.add_argument("--conversion", default=None, metavar="MAP.npz",
                     help="also write <name>_modified.wav: amplitudes read off this file's cepstral envelope converted by "
                          "the map of a --conversion-train run; the pitch follows the target's statistics unless a "
@@ -212,6 +228,21 @@ def main(argv=None):
         ap.error("--conversion-span needs --conversion-train")
     if train and convert:
         ap.error("--conversion applies a map, --conversion-train learns one: not together")
+    if a.conversion_gv is not None and not (train and a.conversion_span is not None):
+        ap.error("--conversion-gv needs --conversion-train and --conversion-span")
+    tuned = a.conversion_gv_iters is not None or a.conversion_gv_weight is not None
+    if (a.conversion_no_gv or tuned) and not convert:
+        ap.error("--conversion-no-gv, --conversion-gv-iters and --conversion-gv-weight need --conversion")
+    if a.conversion_no_gv and tuned:
+        ap.error("--conversion-no-gv leaves the term out: not with --conversion-gv-iters or --conversion-gv-weight")
+    if convert or a.conversion_gv is not None:
+        from .convert import GV_MAX_ITERS, GV_REL_STD_MAX, GV_WEIGHT_RANGE
+        if a.conversion_gv is not None and not 0 < a.conversion_gv <= GV_REL_STD_MAX:
+            ap.error("--conversion-gv must be in (0, %g]" % GV_REL_STD_MAX)
+        if a.conversion_gv_iters is not None and not 0 <= a.conversion_gv_iters <= GV_MAX_ITERS:
+            ap.error("--conversion-gv-iters must be in [0, %d]" % GV_MAX_ITERS)
+        if a.conversion_gv_weight is not None and not GV_WEIGHT_RANGE[0] <= a.conversion_gv_weight <= GV_WEIGHT_RANGE[1]:
+            ap.error("--conversion-gv-weight must be in [%g, %g]" % GV_WEIGHT_RANGE)
     if convert and a.envelope_from is not None:
         ap.error("--conversion supplies the spectral envelope: not with --envelope-from")
     if convert and a.no_envelope:
@@ -229,6 +260,9 @@ def main(argv=None):
             ap.error("--cepstral-envelope %d differs from the map's order %d" % (a.cepstral_envelope, cmap[1]))
         if a.cepstral_lambda is not None and a.cepstral_lambda != cmap[2]:
             ap.error("--cepstral-lambda %g differs from the map's %g" % (a.cepstral_lambda, cmap[2]))
+        if (a.conversion_no_gv or tuned) and "gv_mean" not in cmap[0]:
+            ap.error("%s carries no global variance (--conversion-gv when it was learned): not with "
+                     "--conversion-no-gv, --conversion-gv-iters or --conversion-gv-weight" % a.conversion)
     if a.align_band is not None and not (aligned or train):
         ap.error("--align-band needs --envelope-from, --timing-from, --noise-from or --conversion-train")
     if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
@@ -307,8 +341,10 @@ def main(argv=None):
                 if fs_map != fs:
                     raise ValueError("%s was learned at %d Hz, the input is sampled at %d Hz" % (a.conversion, fs_map, fs))
                 p = model_parameters(det, fs, c_order, c_lam)
-                apply = _convert.conversion_trajectory if "span" in conv else _convert.conversion_apply
-                converted = apply(conv, p["ceps"])
+                if "span" in conv:
+                    converted = _convert.conversion_trajectory(conv, p["ceps"], **gv_options(a))
+                else:
+                    converted = _convert.conversion_apply(conv, p["ceps"])
                 if a.pitch_scale is None and "pitch" not in curves:
                     beta = pitch_conversion_contour(p["f0"], p["voiced"] & (p["f0"] > 0), src_f0, tgt_f0)
             if aligned:
@@ -359,17 +395,30 @@ def main(argv=None):
     return 0
 
 
+def gv_options(a):
+    """The global-variance arguments of conversion_trajectory that the flags set."""
+    kw = {}
+    if a.conversion_no_gv:
+        kw["gv"] = False
+    if a.conversion_gv_iters is not None:
+        kw["gv_iters"] = a.conversion_gv_iters
+    if a.conversion_gv_weight is not None:
+        kw["gv_weight"] = a.conversion_gv_weight
+    return kw
+
+
 def train_conversion(a, gender, analysis_options, fs, det):
     """--conversion-train: analyses the target, aligns it to this file's model `det`, learns the map and saves it."""
-    from .convert import conversion_pairs, conversion_train, f0_statistics
+    from .convert import conversion_pairs, conversion_train, f0_statistics, gv_statistics
     from .model import model_parameters
     order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
     p = model_parameters(det, fs, order, lam)
     C_t, pairs, det_t, _ = align_other(a.conversion_train, gender, analysis_options, fs, p["ceps"], order, lam,
                                        2.0 if a.align_band is None else a.align_band)
     X, Y = conversion_pairs(p["ceps"], C_t, pairs, a.conversion_span)
+    gv = None if a.conversion_gv is None else gv_statistics([C_t], rel_std=a.conversion_gv)
     conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components,
-                            span=a.conversion_span)
+                            span=a.conversion_span, gv=gv)
     p_t = model_parameters(det_t, fs, order, lam)
     stats = [f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
     np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),

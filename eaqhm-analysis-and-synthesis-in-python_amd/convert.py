@@ -5,16 +5,20 @@
     gmm_posteriors(gmm, Z, *, device_index=0) -> (gamma[N, M], ll[N])
     conversion_pairs(CA, CB, path, span=None) -> (X, Y): the rows a model_align path pairs, empty rows dropped; with a
         span the dynamic rows [c | delta c] of both sides
-    conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None,
+    conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None, gv=None,
                      device_index=0)
         -> flat dict of arrays (np.savez): the gmm fields + dx, dy, level, A[M, dy, dx], b[M, dy], Wx[M, dx, dx], kx[M];
-        with a span also span and py[M, dy], and dx, dy count the delta columns
+        with a span also span and py[M, dy], and dx, dy count the delta columns; with gv also gv_mean, gv_prec[dy / 2]
     conversion_apply(conv, C, *, device_index=0) -> float64[n, dy_cols] in model_cepstrum's layout (a static map)
     dynamic_rows(C, span=2, *, device_index=0) -> float64[n, 2 (P + 1)]: [c | delta c] over the runs of non-empty rows
-    conversion_trajectory(conv, C, *, device_index=0) -> float64[n, Q + 1]: the most likely trajectory under a dynamic map
+    conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace=False, device_index=0)
+        -> float64[n, Q + 1]: the most likely trajectory under a dynamic map, with the global-variance term when the map
+        or `gv` carries its statistics; with trace=True also the objective float64[gv_iters + 1, dys]
+    global_variance(C, level=False) -> float64[cols]: the variance of each mapped static column over the non-empty rows
+    gv_statistics(utterances, *, level=False, rel_std=None) -> dict(gv_mean[dys], gv_prec[dys]) for conversion_train(gv=)
     f0_statistics(f0, voiced) -> (mean, std) of ln f0 over the voiced instants
     pitch_conversion_contour(f0, voiced, src_stats, tgt_stats) -> pitch_scale contour float64[n]
-    check_gmm_arguments, check_conversion_arguments, check_conversion: validation, no device work
+    check_gmm_arguments, check_conversion_arguments, check_conversion, check_gv_arguments: validation, no device work
 
 The definition is DESIGN.md §12: EM with full covariances on centred rows (Dempster, Laird & Rubin 1977), the
 regression of Stylianou, Cappe & Moulines (1998) in Kain & Macon's joint-density form.  Everything that scales with the
@@ -24,7 +28,8 @@ number of rows runs in libeaqhm_hip.so (eaqhm_gmm_estep, eaqhm_gmm_mstep, eaqhm_
 DESIGN.md §12.1 adds the trajectory conversion of Toda, Black & Tokuda (2007): the mixture is trained on rows extended
 with their delta features (eaqhm_ceps_delta) and an utterance is converted to the trajectory that is most likely under
 the static and the delta statistics together (Tokuda et al. 2000): one banded positive-definite system per voiced run and
-cepstral dimension (eaqhm_mlpg_solve).
+cepstral dimension (eaqhm_mlpg_solve).  DESIGN.md §12.2 adds the same paper's global-variance term: from that trajectory,
+sweeps up the likelihood joined with a Gaussian prior on each column's variance over the utterance (eaqhm_gv_ascend).
 """
 import math
 
@@ -40,6 +45,11 @@ GMM_MAX_ITERS = 1000
 GMM_CHUNK_MIN = 512        # rows of an M-step chunk at least
 GMM_CHUNKS_MAX = 128       # chunks at most
 DELTA_SPAN_RANGE = (1, 8)  # span L of the delta window: tau = 1 .. L on each side
+GV_CHUNK_MIN = 64          # rows of a reduction chunk of the global-variance ascent at least
+GV_CHUNKS_MAX = 512        # chunks at most
+GV_WEIGHT_RANGE = (1e-6, 1e6)
+GV_MAX_ITERS = 10000
+GV_REL_STD_MAX = 10.0
 
 
 def gmm_chunk_rows(N):
@@ -52,6 +62,20 @@ def gmm_work_len(N, D, M):
     """Doubles of the M-step's `work`: ceil(N / R) M T 256, T the lower-triangle 16 x 16 tiles of D + 1 columns."""
     nt = (D + 1 + 15) // 16
     return -(-int(N) // gmm_chunk_rows(N)) * M * (nt * (nt + 1) // 2) * 256
+
+
+def gv_chunk_rows(n):
+    """Rows per reduction chunk of the global-variance ascent (include/eaqhm_gv.h): max(64, 64 ceil(ceil(n / 512) / 64)),
+    a function of n alone."""
+    per = -(-int(n) // GV_CHUNKS_MAX)
+    return max(GV_CHUNK_MIN, -(-per // GV_CHUNK_MIN) * GV_CHUNK_MIN)
+
+
+def gv_work_len(n, dy, span):
+    """Doubles of the ascent's `work`: the band and q, n (2 span + 2) dy; a word per row; a second trajectory, n dy; five
+    sums per (chunk, column) and one per chunk; two words per column."""
+    chunks = -(-int(n) // gv_chunk_rows(n))
+    return n * (2 * span + 2) * dy + n + n * dy + chunks * (5 * dy + 1) + 2 * dy
 
 
 # ---- validation (no device work)
@@ -220,7 +244,54 @@ def check_conversion(conv):
         out["py"] = np.ascontiguousarray(_field(conv, "py", (M, dy)), dtype=np.float64)
         if np.any(out["py"] <= 0):
             raise ValueError("the conversion's py must be positive")
+    if _has(conv, "gv_mean") or _has(conv, "gv_prec"):    # the global-variance statistics
+        if "span" not in out:
+            raise ValueError("the conversion's gv_mean and gv_prec need a dynamic map (span)")
+        out.update(_gv_fields(conv, dy // 2, "the conversion"))
     return out
+
+
+def _gv_fields(gv, dys, what):
+    """dict(gv_mean, gv_prec) float64[dys] of a mapping that must hold both: finite and > 0."""
+    out = {}
+    for name in ("gv_mean", "gv_prec"):
+        try:
+            a = np.asarray(gv[name])
+        except (KeyError, TypeError, IndexError):
+            raise ValueError("%s lacks the field %r" % (what, name)) from None
+        if a.dtype.kind not in "iuf" or a.shape != (dys,):
+            raise ValueError("%s's %s must be %d numbers, one per mapped static column, got shape %s"
+                             % (what, name, dys, a.shape))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not (np.all(np.isfinite(a)) and np.all(a > 0)):
+            raise ValueError("%s's %s must be finite and > 0" % (what, name))
+        out[name] = a
+    return out
+
+
+def check_gv_arguments(conv, gv=None, gv_weight=1.0, gv_iters=30, trace=False):
+    """Validates the global-variance arguments of conversion_trajectory against a validated dynamic map (check_conversion's
+    result; no device work): returns (stats, gv_weight, gv_iters, trace), stats dict(gv_mean, gv_prec) float64[dys] or
+    None when the ascent does not run (gv=False, or gv=None with a map that has no statistics)."""
+    if "span" not in conv:
+        raise ValueError("the global-variance term needs a dynamic map (span)")
+    if gv is None:
+        stats = {k: conv[k] for k in ("gv_mean", "gv_prec")} if "gv_mean" in conv else None
+    elif isinstance(gv, (bool, np.bool_)):
+        if gv:
+            raise ValueError("gv must be None (the map's statistics), False or a gv_statistics dict")
+        stats = None
+    else:
+        stats = _gv_fields(gv, conv["dy"] // 2, "gv")
+    gv_weight = _real(gv_weight, "gv_weight", *GV_WEIGHT_RANGE)
+    gv_iters = _integer(gv_iters, "gv_iters")
+    if not 0 <= gv_iters <= GV_MAX_ITERS:
+        raise ValueError("gv_iters must be in [0, %d], got %d" % (GV_MAX_ITERS, gv_iters))
+    if not isinstance(trace, (bool, np.bool_)):
+        raise ValueError("trace must be True or False")
+    if trace and stats is None:
+        raise ValueError("trace=True needs the global-variance term: a map with gv_mean and gv_prec, or gv=")
+    return stats, gv_weight, gv_iters, bool(trace)
 
 
 def _has(conv, name):
@@ -312,6 +383,55 @@ def delta_runs(full):
 def _dynamic_columns(D, cols, skip):
     """The mapped columns of dynamic rows of `cols` static columns: both halves without their first `skip` columns."""
     return np.ascontiguousarray(np.hstack((D[:, skip:cols], D[:, cols + skip:])))
+
+
+def global_variance(C, level=False):
+    """The population variance of each mapped static column of cepstral rows `C` float64[n, P + 1] over their non-empty
+    rows: float64[P], or float64[P + 1] with level=True.  Host NumPy.  ValueError without a non-empty
+    row."""
+    C = _cepstrum_rows(C, "C")
+    if not isinstance(level, (bool, np.bool_)):
+        raise ValueError("level must be True or False")
+    full = ~np.isneginf(C[:, 0])
+    if not full.any():
+        raise ValueError("global_variance needs at least one non-empty row")
+    return C[full, 0 if level else 1:].var(axis=0)
+
+
+def gv_statistics(utterances, *, level=False, rel_std=None):
+    """The target speaker's global-variance statistics for conversion_train(gv=) and conversion_trajectory(gv=)
+    (DESIGN.md §12.2): dict(gv_mean[dys], gv_prec[dys]) from a sequence of cepstral-row arrays, all of one width.  With
+    rel_std=None gv_mean is the mean and gv_prec the reciprocal of the population variance of global_variance over at least
+    2 utterances (ValueError when a variance is 0).  With `rel_std` in (0, 10] the spread is stated instead of measured:
+    gv_prec = 1 / (rel_std gv_mean)^2, and one utterance suffices.  gv_mean must come out > 0 and finite."""
+    try:
+        rows = list(utterances)
+    except TypeError:
+        raise ValueError("utterances must be a sequence of cepstral-row arrays") from None
+    if rel_std is not None:
+        rel_std = _real(rel_std, "rel_std", 0.0, GV_REL_STD_MAX)
+        if rel_std == 0.0:
+            raise ValueError("rel_std must be in (0, %g]" % GV_REL_STD_MAX)
+    if len(rows) < (2 if rel_std is None else 1):
+        raise ValueError("gv_statistics needs at least %s" % ("2 utterances, or rel_std" if rel_std is None
+                                                              else "1 utterance"))
+    V = [global_variance(C, level) for C in rows]
+    if any(v.shape != V[0].shape for v in V):
+        raise ValueError("the utterances must all have the same number of columns")
+    V = np.stack(V)
+    mean = V.mean(axis=0)
+    if not (np.all(np.isfinite(mean)) and np.all(mean > 0)):
+        raise ValueError("a column's global variance is 0 or not finite: gv_mean must be > 0")
+    if rel_std is None:
+        var = V.var(axis=0)
+        if np.any(var == 0):
+            raise ValueError("a column's global variance is the same in every utterance: pass rel_std")
+        prec = 1.0 / var
+    else:
+        prec = 1.0 / (rel_std * mean) ** 2
+    if not np.all(np.isfinite(prec)):
+        raise ValueError("gv_prec is not finite")
+    return dict(gv_mean=mean, gv_prec=prec)
 
 
 # ---- device work
@@ -428,7 +548,7 @@ def dynamic_rows(C, span=2, *, device_index=0):
 
 
 def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, floor=1e-6, init=None, span=None,
-                     device_index=0):
+                     gv=None, device_index=0):
     """Learns the map from rows `X` float64[N, P + 1] to rows `Y` float64[N, Q + 1] (conversion_pairs') as a joint
     mixture of `components` Gaussians over [x | y].  level=False leaves column 0, the level c_0, out of
     both sides: conversion_apply copies it from the source row (a recording level is not a property of the speaker);
@@ -438,9 +558,15 @@ def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, flo
     With `span` in [1, 8] the rows are dynamic rows [c | delta c] (conversion_pairs(span=)) and the map is a dynamic one
     for conversion_trajectory: the mixture is over [x | delta x | y | delta y], level=False leaves
     column 0 and its delta out, dx and dy count the delta columns (at most 64 a side), and the dict gains span and
-    py[M, dy], the reciprocal diagonals of the conditional covariances."""
+    py[M, dy], the reciprocal diagonals of the conditional covariances.  `gv`, a gv_statistics dict of the target speaker
+    (span= only), is stored in the map as gv_mean[dy / 2] and gv_prec[dy / 2]: conversion_trajectory then adds the
+    global-variance term."""
     X, Y, level = check_conversion_arguments(X, Y, components, level, iters, tol, floor, init, span)
     skip = 0 if level else 1
+    if gv is not None:
+        if span is None:
+            raise ValueError("gv needs span=: a static map has no trajectory to trade against")
+        gv = _gv_fields(gv, Y.shape[1] // 2 - skip, "gv")
     if span is None:
         x, y = X[:, skip:], Y[:, skip:]
     else:
@@ -452,6 +578,8 @@ def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, flo
     g.update(n=np.int64(g["n"]), dx=np.int64(dx), dy=np.int64(dy), level=np.bool_(level), A=A, b=b, Wx=Wx, kx=kx)
     if span is not None:
         g.update(span=np.int64(check_span(span)), py=gmm_conditional_precisions(g["covs"], A, dx))
+    if gv is not None:
+        g.update(gv)
     return g
 
 
@@ -487,17 +615,25 @@ def conversion_apply(conv, C, *, device_index=0):
     return out
 
 
-def conversion_trajectory(conv, C, *, device_index=0):
+def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace=False, device_index=0):
     """Converts cepstral rows `C` float64[n, dx_cols] (model_cepstrum's layout) with a dynamic map, conversion_train(span=)'s,
     to the trajectory that is most likely under the static and the delta statistics together (Toda,
     Black & Tokuda 2007, the posterior-weighted initial estimate).  With X_t = [x_t | delta x_t], gamma the posteriors of
     the marginal mixture on X, P_t = sum_m gamma_tm py_m and r_t = sum_m gamma_tm py_m (b_m + A_m X_t) (un-centred), every
     run of non-empty rows and every static column d solves (diag(P^s) + W^T diag(P^D) W) y = r^s + W^T r^D, W the run's
     delta matrix.  Nothing couples across an empty row; an empty row comes back empty; with level=False column 0 is the
-    source row's.  Returns float64[n, dy_cols], accepted wherever conversion_apply's result is."""
+    source row's.  Returns float64[n, dy_cols], accepted wherever conversion_apply's result is.
+    The global-variance term follows when there are statistics for it: gv=None takes the map's gv_mean
+    and gv_prec if it has them, gv=False never does, a gv_statistics dict overrides the map.  From the trajectory above,
+    scaled per column to the variance gv_mean, `gv_iters` sweeps (0 to 10000; 0 returns the scaled start) climb the
+    likelihood joined with the prior of precision `gv_weight` gv_prec (gv_weight in [1e-6, 1e6]) on each column's
+    variance over all non-empty rows.  A column that is constant, or an utterance of one non-empty row, stays as it is.
+    trace=True returns (rows, float64[gv_iters + 1, dys]), the objective of every column before each sweep and after the
+    last."""
     v = check_conversion(conv)
     if "span" not in v:
         raise ValueError("this conversion is a static map (no span): use conversion_apply")
+    stats, gv_weight, gv_iters, trace = check_gv_arguments(v, gv, gv_weight, gv_iters, trace)
     skip = 0 if v["level"] else 1
     span, dx, dy, M = v["span"], v["dx"], v["dy"], len(v["weights"])
     dxs, dys = dx // 2, dy // 2
@@ -509,7 +645,7 @@ def conversion_trajectory(conv, C, *, device_index=0):
     out[~full, 0] = -np.inf
     n = int(np.count_nonzero(full))
     if n == 0:
-        return out
+        return (out, np.zeros((gv_iters + 1, dys))) if trace else out
     D = dynamic_rows(C, span, device_index=device_index)
     mu_c = v["means"] - v["zbar"]
     mix = _Mixture(_dynamic_columns(D[full], C.shape[1], skip), v["zbar"][:dx], M, device_index)
@@ -526,12 +662,22 @@ def conversion_trajectory(conv, C, *, device_index=0):
     if words != n * (2 * span + 2) * dys:
         raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the trajectory solve's work buffer")
     Y = t.empty((n, dys), dtype=t.float64, device=dev)
-    mix.c.mlpg_solve(P.contiguous(), r, n, dys, span, t.as_tensor(start, device=dev), t.as_tensor(length, device=dev),
-                     len(start), t.empty(words, dtype=t.float64, device=dev), Y)
+    P, start_d, length_d = P.contiguous(), t.as_tensor(start, device=dev), t.as_tensor(length, device=dev)
+    mix.c.mlpg_solve(P, r, n, dys, span, start_d, length_d, len(start), t.empty(words, dtype=t.float64, device=dev), Y)
+    objective = None
+    if stats is not None:                              # P, r, the runs and y_ML stay where they are
+        words = mix.c.gv_work_len(n, dys, span)
+        if words != gv_work_len(n, dys, span) or mix.c.gv_chunk_rows(n) != gv_chunk_rows(n):
+            raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the global-variance ascent's work buffer")
+        if trace:
+            objective = t.empty((gv_iters + 1, dys), dtype=t.float64, device=dev)
+        mix.c.gv_ascend(P, r, n, dys, span, start_d, length_d, len(start), t.as_tensor(stats["gv_mean"], device=dev),
+                        t.as_tensor(gv_weight * stats["gv_prec"], device=dev), gv_iters,
+                        t.empty(words, dtype=t.float64, device=dev), Y, objective)
     out[full, skip:] = Y.cpu().numpy()
     if skip:
         out[full, 0] = C[full, 0]
-    return out
+    return (out, objective.cpu().numpy()) if trace else out
 
 
 # ---- pitch (host only)

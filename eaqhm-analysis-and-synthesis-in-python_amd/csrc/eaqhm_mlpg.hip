@@ -13,19 +13,12 @@
 // Both sweeps take `work` in chunks of 8 rows through the same strip: the chunk's loads are issued together.
 // Every index into a per-lane array is an LDS address: no scratch.  No atomics, every word has one writer, the order of
 // every sum is fixed: the same input gives the same bits.
-#include "eaqhm_common.h"
+#include "eaqhm_mlpg_band.h"
 
 namespace eaqhm {
 
-typedef long long i64;
-
-constexpr int MLPG_SPAN_MAX = 8;
-constexpr int MLPG_DY_MAX = 64;          // static target columns at most
-constexpr int MLPG_COLS_MAX = 128;       // columns of the delta builder at most
-constexpr i64 MLPG_NMAX = (i64)1 << 31;  // rows at most: n * 128 / 256 blocks stay below 2^31
 constexpr int MLPG_CHUNK = 8;            // rows of `work` a lane stages into its LDS strip at a time
 
-__host__ __device__ inline int mlpg_slots(int span) { return 2 * span + 2; }   // band entries 0 .. 2 span, then q / z
 __host__ __device__ inline int mlpg_window(int b) { return (b > 0 ? b : 1) * (b + 1) + 2 * (b + 1) + (b > 0 ? b : 1); }
 // lanes of a solve block and doubles of its LDS: 64 lanes while span <= 2 (41 984 bytes at span 2), 32 while span <= 4
 // (45 568 at 4), 16 beyond (59 648 at 8): under the 64 KB a block gets without asking
@@ -33,12 +26,6 @@ __host__ __device__ inline int mlpg_lanes(int span) { return span <= 2 ? 64 : sp
 __host__ __device__ inline size_t mlpg_lds_doubles(int span) {
   return (size_t)(mlpg_window(2 * span) + MLPG_CHUNK * mlpg_slots(span)) * mlpg_lanes(span);
 }
-__host__ __device__ inline double mlpg_denominator(int span) {
-  int s = 0;
-  for (int k = 1; k <= span; ++k) s += k * k;
-  return 2.0 * s;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Delta rows.  A row's run is found from column 0 of at most `span` neighbours on each side; beyond the run's edge the
 // edge row is repeated (the HTK convention).  tau ascending.  An empty row, (-inf, ..), gets zeros.
@@ -71,19 +58,6 @@ extern "C" __global__ void __launch_bounds__(256)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Entry (u, c) of W, the T x T matrix of the delta rule on a run of T rows: sum over tau (ascending) of
-// w_tau ([clip(u + tau) = c] - [clip(u - tau) = c]).  It is zero unless |u - c| <= span.
-__device__ inline double mlpg_coef(i64 u, i64 c, i64 T, int span, double den) {
-  double a = 0.0;
-  for (int tau = 1; tau <= span; ++tau) {
-    const i64 hi = u + tau < T - 1 ? u + tau : T - 1, lo = u - tau > 0 ? u - tau : 0;
-    const double w = (double)tau / den;
-    if (hi == c) a += w;
-    if (lo == c) a -= w;
-  }
-  return a;
-}
-
 // `count` doubles of a lane's column of `work` (stride dy) into its LDS strip (stride lanes): the loads of a batch are
 // independent, so a chunk waits for the memory about once, not once per entry
 __device__ inline void mlpg_stage(double* st, int lanes, const double* g, int dy, int count) {
@@ -93,21 +67,6 @@ __device__ inline void mlpg_stage(double* st, int lanes, const double* g, int dy
 
 // x mod bw for x in [-bw, 2 bw)
 __device__ inline int mlpg_ring(int x, int bw) { return x < 0 ? x + bw : x >= bw ? x - bw : x; }
-
-// The run that holds row t (runs disjoint and ascending): -1 when none does or its bounds leave [0, n).
-__device__ inline i64 mlpg_find_run(const i64* __restrict__ run_start, const i64* __restrict__ run_len, i64 n_runs, i64 n,
-                                    i64 t) {
-  i64 lo = 0, hi = n_runs;   // the last run with run_start <= t
-  while (lo < hi) {
-    const i64 mid = (lo + hi) >> 1;
-    if (run_start[mid] <= t) lo = mid + 1; else hi = mid;
-  }
-  const i64 r = lo - 1;
-  if (r < 0) return -1;
-  const i64 s = run_start[r], T = run_len[r];
-  if (s < 0 || T < 1 || T > n || s > n - T || t >= s + T) return -1;
-  return r;
-}
 
 // work[(t S + k) dy + d], S = 2 span + 2: k = 0 .. 2 span holds R[i][i - k] (i the row's index in its run, entries with
 // i - k < 0 are not written or read), k = 2 span + 1 holds q_i.  u ascending in every sum.
@@ -223,10 +182,6 @@ extern "C" __global__ void
 }  // namespace eaqhm
 
 using namespace eaqhm;
-
-static bool mlpg_sizes_ok(int64_t n, int32_t dy, int32_t span) {
-  return n >= 1 && n <= MLPG_NMAX && dy >= 1 && dy <= MLPG_DY_MAX && span >= 1 && span <= MLPG_SPAN_MAX;
-}
 
 extern "C" int eaqhm_ceps_delta(eaqhm_ctx* ctx, const double* C, int64_t n, int32_t cols, int32_t span, double* out) {
   if (!ctx) return EAQHM_EINVAL;

@@ -70,6 +70,12 @@ SYMBOLS_MLPG = (
     ("eaqhm_mlpg_work_len", _I64, [_I64, _I32, _I32]),
     ("eaqhm_mlpg_solve", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P]),
 )
+# every symbol include/eaqhm_gv.h declares: likewise
+SYMBOLS_GV = (
+    ("eaqhm_gv_chunk_rows", _I64, [_I64]),
+    ("eaqhm_gv_work_len", _I64, [_I64, _I32, _I32]),
+    ("eaqhm_gv_ascend", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P, _I32, _P, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -92,7 +98,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS + SYMBOLS_MLPG:
+    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -340,6 +346,17 @@ class Context:
     def mlpg_solve(self, P, r, n, dy, span, run_start, run_len, n_runs, work, Y):
         self._ck(self.lib.eaqhm_mlpg_solve(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
                                            _ptr(work), _ptr(Y)))
+
+    # the global-variance ascent: Y holds y_ML on entry; trace a float64[iters + 1, dy] tensor or None
+    def gv_chunk_rows(self, n):
+        return int(self.lib.eaqhm_gv_chunk_rows(n))
+
+    def gv_work_len(self, n, dy, span):
+        return int(self.lib.eaqhm_gv_work_len(n, dy, span))
+
+    def gv_ascend(self, P, r, n, dy, span, run_start, run_len, n_runs, gv_mean, gv_prec, iters, work, Y, trace=None):
+        self._ck(self.lib.eaqhm_gv_ascend(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
+                                          _ptr(gv_mean), _ptr(gv_prec), iters, _ptr(work), _ptr(Y), _ptr(trace)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

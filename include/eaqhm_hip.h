@@ -509,6 +509,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 /* delta rows and the maximum-likelihood trajectory of the conversion (additions under ABI 6): the
  * declarations are in eaqhm_mlpg.h, which this header includes.                                                      */
 #include "eaqhm_mlpg.h"
+/* the global-variance ascent from that trajectory (additions under ABI 6): declared in eaqhm_gv.h.     */
+#include "eaqhm_gv.h"
 
 #ifdef __cplusplus
 }

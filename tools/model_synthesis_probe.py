@@ -35,7 +35,10 @@ band on a 5 s excerpt on the host.  --noise-cepstrum adds the noise model to and
 the workload's residual model: eaqhm_noise_cepstrum (Q = 63) and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp at
 alpha = 1.2, with the same windows and the warp's max - min as the margin.  --mlpg times the delta rows and the
 trajectory solve on random rows, once as one run and once as 200 runs, next to
-scipy.linalg.solveh_banded on the host.  EAQHM_LIB selects another build of
+scipy.linalg.solveh_banded on the host.  --gv times the global-variance ascent (eaqhm_gv_ascend, 30
+sweeps) from the solve's trajectory on the same kind of rows, as one run and as 200, next to eaqhm_mlpg_solve in the same
+session and to the same iteration in NumPy on the host's band, with the largest difference between the two results.
+EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
 import argparse
@@ -299,6 +302,88 @@ def mlpg_rows(torch, n=60000, dys=24, span=2, reps=5, runs=3):
             row["host_solveh_banded_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
         except ImportError:
             row["host_solveh_banded_ms"] = None
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def host_gv(bands, n, span, mean, prec, iters, y):
+    """The ascent of DESIGN.md §12.2 in NumPy on the host's bands [(start, ab [2 span + 1, T, dy], q [T, dy])], every
+    column at once; y float64[n, dy] is y_ML, every row in a run."""
+    q = np.vstack([b[2] for b in bands])
+    diag = np.vstack([b[1][0] for b in bands])
+    omega = 1.0 / (2 * n)
+
+    def Ry(y):
+        out = np.empty_like(y)
+        for s, ab, _ in bands:
+            T = ab.shape[1]
+            v, o = y[s:s + T], out[s:s + T]
+            o[:] = ab[0] * v
+            for k in range(1, min(2 * span, T - 1) + 1):
+                o[k:] += ab[k, :T - k] * v[:-k]
+                o[:-k] += ab[k, :T - k] * v[k:]
+        return out
+    m = y.mean(axis=0)
+    v = ((y - m) ** 2).mean(axis=0)
+    y = m + np.sqrt(mean / v) * (y - m)
+    for _ in range(iters):
+        m = y.mean(axis=0)
+        v = ((y - m) ** 2).mean(axis=0)
+        g = omega * (q - Ry(y)) - prec * (v - mean) * (2.0 / n) * (y - m)
+        h = (4 * span + 1) * omega * diag + prec * (2.0 / n) * (np.abs(v - mean) + 2 * v)
+        y = y + g / h
+    return y
+
+
+def gv_rows(torch, n=60000, dys=24, span=2, iters=30, reps=20, runs=3):
+    """eaqhm_gv_ascend (`iters` sweeps, no trace) on n rows of dys static columns from eaqhm_mlpg_solve's trajectory
+    (DESIGN.md §12.2), once with all rows in one run and once cut into 200 equal runs: median of `runs` warmed windows of
+    `reps` calls and max - min of the windows (each call starts from a fresh copy of y_ML; the copy is timed apart and
+    taken off).  Beside it eaqhm_mlpg_solve on the same rows in the same session, and the same iteration in NumPy on the
+    band the host forms (forming not timed), with the largest difference between the two results: comparisons, not bars."""
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    g = torch.Generator(device=dev).manual_seed(n + dys + span)
+    P = torch.exp(torch.randn(n, 2 * dys, dtype=torch.float64, device=dev, generator=g))
+    P[:, dys:] *= 100.0
+    r = torch.randn(n, 2 * dys, dtype=torch.float64, device=dev, generator=g) * P
+    work = torch.empty(c.mlpg_work_len(n, dys, span), dtype=torch.float64, device=dev)
+    gwork = torch.empty(c.gv_work_len(n, dys, span), dtype=torch.float64, device=dev)
+    Yml = torch.empty((n, dys), dtype=torch.float64, device=dev)
+    Y = torch.empty_like(Yml)
+    rows = []
+    for n_runs in (1, 200):
+        T = n // n_runs
+        start = torch.arange(n_runs, dtype=torch.int64, device=dev) * T
+        length = torch.full((n_runs,), T, dtype=torch.int64, device=dev)
+        solve = med(lambda: c.mlpg_solve(P, r, n, dys, span, start, length, n_runs, work, Yml))
+        mean = 2.0 * Yml.var(dim=0, unbiased=False)              # twice the trajectory's own variance, spread 0.15
+        prec = 1.0 / (0.15 * mean) ** 2
+
+        def ascend():
+            Y.copy_(Yml)
+            c.gv_ascend(P, r, n, dys, span, start, length, n_runs, mean, prec, iters, gwork, Y, None)
+        copy = med(lambda: Y.copy_(Yml))
+        t = med(ascend)
+        row = dict(n=n, dys=dys, span=span, iters=iters, n_runs=n_runs, launches=2 * iters + 4 + (iters + 1) % 2,   # without a trace: the copy home only after an even number of sweeps
+                   
+                   ascend_ms=round(t[0] - copy[0], 4), ascend_spread_ms=round(t[1], 4), copy_ms=round(copy[0], 4),
+                   solve_ms=round(solve[0], 4), solve_spread_ms=round(solve[1], 4))
+        Ph, rh = P.cpu().numpy(), r.cpu().numpy()
+        bands = [(k * T,) + host_band(Ph[k * T:(k + 1) * T], rh[k * T:(k + 1) * T], span) for k in range(n_runs)]
+        # host_band's ab[k, i] = R[i + k, i]: what host_gv reads as ab[k, :T - k]
+        t0 = time.perf_counter()
+        ref = host_gv(bands, n, span, mean.cpu().numpy(), prec.cpu().numpy(), iters, Yml.cpu().numpy())
+        row["host_numpy_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        row["max_abs_difference_from_host"] = float(np.abs(Y.cpu().numpy() - ref).max())
+        row["max_abs_result"] = float(np.abs(ref).max())
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
@@ -797,8 +882,19 @@ def main():
     ap.add_argument("--mlpg", action="store_true",
                     help="time eaqhm_ceps_delta and eaqhm_mlpg_solve next to scipy.linalg.solveh_banded on the host (random "
                          "rows; needs no workload: pass --workloads '')")
+    ap.add_argument("--gv", action="store_true",
+                    help="time eaqhm_gv_ascend next to eaqhm_mlpg_solve and the same iteration in NumPy on the host (random "
+                         "rows; needs no workload: pass --workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.gv:
+        import torch
+        res_gv = dict(gv=gv_rows(torch))
+        if not a.workloads and not a.gmm and not a.mlpg:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump([res_gv], f, indent=1)
+            return 0
     if a.mlpg:
         import torch
         res_mlpg = dict(mlpg=mlpg_rows(torch))
@@ -822,6 +918,8 @@ def main():
         res.append(res_gmm)
     if a.mlpg:
         res.append(res_mlpg)
+    if a.gv:
+        res.append(res_gv)
     for r in res:
         print(json.dumps(r))
     if a.out:
