@@ -18,7 +18,8 @@
 //          because the negative-frequency column at u is the time-reversed positive one (functions.py:284-285);
 //          contracted with v_mfma_f64_16x16x4_f64, LDS operand reads software-pipelined one k-step ahead; frames of
 //          <= 12 tile rows: only X = w [E2 | s] in the chunk, three-weight Gramian G_p = X^H diag(n^p) X (TW in tile_frame;
-//          11-12 tile rows: dealt out by the unit table eaqhm_ls_twunits.h, UA / UB in tile_frame)
+//          11-12 tile rows: dealt out by the unit tables of eaqhm_ls_twunits.h, UA / UB / TB in tile_frame; 11 tile rows with
+//          the part-filled last basis tile column packed as [x_e | n x_e])
 //   B0     adaptation 0: no basis at all — the Gramian in closed form from Toeplitz tables, then two real systems of
 //          half the order factorised side by side (a0_frame, eaqhm_ls_a0.h)
 //   C      right-looking tile Cholesky with look-ahead, 2 workgroup barriers per tile row: trailing update with the
@@ -117,13 +118,30 @@ __device__ inline void twu_pair_2acc(d4 (&g0)[2], d4 (&g1)[2], d4 (&g2)[2], doub
   }
 }
 
-// UA + UB > 0 (TW = 0): the three-weight Gramian of a frame with TWU_T basis tile columns, dealt out by the unit table
+// An edge pair of a packed table, in two-accumulator slots (form K4): a = E = [x_e | n x_e] is never scaled, b = X_J for
+// q = 0 (g0) and n X_J for q = 1 (g1).
+__device__ inline void twu_edge_k4(d4 (&g0)[2], d4 (&g1)[2], double aR, double aI, double bR, double bI, double nk) {
+  const double nbR = nk * bR, nbI = nk * bI, maI = -aI;
+  g0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bR, g0[0], 0, 0, 0);
+  g1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, nbR, g1[0], 0, 0, 0);
+  g0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, bI, g0[1], 0, 0, 0);
+  g1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aR, nbI, g1[1], 0, 0, 0);
+  g0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, bI, g0[0], 0, 0, 0);
+  g1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aI, nbI, g1[0], 0, 0, 0);
+  g0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(maI, bR, g0[1], 0, 0, 0);
+  g1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(maI, nbR, g1[1], 0, 0, 0);
+}
+
+// UA + UB > 0 (TW = 0): the three-weight Gramian of a frame with TWU_TT[TB] basis tile columns, dealt out by unit table TB
 // (eaqhm_ls_twunits.h: a unit is one tile G_p[I][J]).  A wave has UA slots of three accumulators (form K3: the three real
 // products of tw_step) and UB slots of two (K4: four real products, re re' + im im' and re im' - im re'; H, diagonal pairs
 // only: the K4 form without its fourth product, the second accumulator holds RI = sum re im' and the gather takes
 // Im = RI - RI^T).  3 UA + 2 UB accumulators per wave whatever the number of basis pairs; the first 3 (UA / 3) and
 // 3 (UB / 3) slots hold whole pairs, contracted like a pair of the TW form, the others single units.
-template <int NS, int TW, int UA = 0, int UB = 0>
+// Packed tables (TWU_PACKED[TB]; classes whose last basis tile column E = T - 1 has at most 8 live columns): the chunk holds
+// that tile column as [x_e | n x_e], so E^H X_J carries weights 0 and 1 of the pair (E, J) in its upper and lower eight rows
+// and E^H (n X_J) weights 1 and 2 — two edge units in place of three — and the corner E^H E, one H unit, all three.
+template <int NS, int TW, int UA = 0, int UB = 0, int TB = 0>
 __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, int ldx_max_, double* lds, int f_) {
   const int TS = uni(TS_), ldx_max = uni(ldx_max_), f = uni(f_);
   const int tid = threadIdx.x, nt_thr = TL_THREADS;
@@ -178,6 +196,9 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     constexpr bool G3 = TW > 0 || UN > 0;              // three-weight Gramian (whole pairs or units)
     static_assert(TW == 0 || UN == 0, "whole pairs or units");
     static_assert(UN == 0 || (UA == TWU_UA && UB == TWU_UB), "slot layout of eaqhm_ls_twunits.h");
+    static_assert(TB >= 0 && TB < TWU_NTB, "unit table");
+    constexpr bool PK = UN > 0 && TWU_PACKED[TB];      // last basis tile column packed: [x_e | n x_e]
+    constexpr int EC = 16 * (TWU_TT[TB] - 1);          // ... its first basis column (the caller picks the table by T)
     const int nb = G3 ? T : nt;                        // tile columns of the basis chunk
     const int ldx = (nb << 4) + ((nb & 1) ? 0 : 16);  // ≡ 16 (mod 32): MFMA operand reads hit disjoint bank halves
     const int npair = T * (T + 1) / 2;
@@ -242,13 +263,13 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       for (int p = 0; p < 9; ++p) g[sl][p] = (d4){0, 0, 0, 0};
     }
 
-    // unit slots: the first UA with three accumulators, the others with two; code as in TWU_MAP, wave-uniform
+    // unit slots: the first UA with three accumulators, the others with two; code as in TWU_MAPS, wave-uniform
     constexpr int UAA = UA > 3 ? UA : 3, UBA = UB > 3 ? UB : 3;   // (at least one whole pair: the unused ones cost nothing)
     d4 ga[UAA][3], gb[UBA][2];
     int ucode[UN ? UN : 1];
     if constexpr (UN > 0) {
 #pragma unroll
-      for (int sl = 0; sl < UN; ++sl) ucode[sl] = __builtin_amdgcn_readfirstlane((int)TWU_MAP[wave][sl]);
+      for (int sl = 0; sl < UN; ++sl) ucode[sl] = __builtin_amdgcn_readfirstlane((int)TWU_MAPS[TB][wave][sl]);
 #pragma unroll
       for (int sl = 0; sl < UA; ++sl)
 #pragma unroll
@@ -308,11 +329,13 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           pur *= wu; pui *= wu; nur *= wu; nui *= wu;
           xr[cpos] = pur;      xi[cpos] = pui;      xr[cneg] = nur;      xi[cneg] = nui;
           if (!G3) { xr[spos] = nu * pur; xi[spos] = nu * pui; xr[sneg] = nu * nur; xi[sneg] = nu * nui; }
+          if (PK && n + 1 + j >= EC) { xr[XCOL(n + 9 + j, el)] = nu * pur; xi[XCOL(n + 9 + j, el)] = nu * pui; }   // packed half
         }
         pvr *= wv; pvi *= wv; nvr *= wv; nvi *= wv;
         xr += ldx; xi += ldx;
         xr[cpos] = pvr;      xi[cpos] = pvi;      xr[cneg] = nvr;      xi[cneg] = nvi;
         if (!G3) { xr[spos] = nv * pvr; xi[spos] = nv * pvi; xr[sneg] = nv * nvr; xi[sneg] = nv * nvi; }
+        if (PK && n + 1 + j >= EC) { xr[XCOL(n + 9 + j, el)] = nv * pvr; xi[XCOL(n + 9 + j, el)] = nv * pvi; }
       }
       // DC / signal columns: one thread per chunk row, spread over the waves (lanes 0, 16, 32, 48)
       if ((tid & 15) == 0 && (tid >> 4) < TS) {
@@ -332,6 +355,8 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         }
         const int scol = G3 ? Kc : 2 * Kc;
         xr[XCOL(scol, el)] = w * sval;     xi[XCOL(scol, el)] = 0.0;         // signal column
+        // packed half: weight 1 of the right-hand side's slope entries is read from the n-scaled signal's rows
+        if (PK) { xr[XCOL(Kc + 8, el)] = w * sval * nn;  xi[XCOL(Kc + 8, el)] = 0.0; }
       }
       // rows beyond the window (the virtual sample u = -1 and the tail of the last chunk): zero
       if (d0 + PE > mid) {
@@ -359,13 +384,28 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           const int s0 = (gi < GA) ? 3 * gi : UA + 3 * (gi - GA);   // first slot of the group
           const int code = ucode[s0];
           if (code == 0xFFFF) continue;
-          const int ca = 16 * (code >> 8), cb = 16 * ((code >> 4) & 15);
+          const int ca = 16 * ((code >> 8) & 15), cb = 16 * ((code >> 4) & 15);
           const bool k4 = (code & 3) == 1;
           int rb = lq * ldx;
           const int sw0 = lcol + (lq >> 1);
           // n_k of this lane's row 4 ks + lq: sample pair d = d0 + 2 ks + lq/2, odd rows t = mid + d, even rows t = mid - d - 1
           int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
           asm volatile("" : "+v"(rb), "+v"(nk));   // (hoisted out of the chunk loop, these spill)
+          if (PK && gi >= GA) {   // (constant once the group loop is unrolled: edge pairs sit in two-accumulator groups only)
+            if (code & 0x1000) {   // an edge pair: its two units in the group's first two slots
+              const int q = (gi >= GA) ? 3 * (gi - GA) : 0;
+#pragma clang loop unroll(disable)
+              for (int ks = 0; ks < kn; ++ks) {
+                const int sw = (sw0 + 2 * ks) & 15;
+                const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
+                const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
+                rb += 4 * ldx;
+                twu_edge_k4(gb[q], gb[q + 1], aR, aI, bR, bI, (double)nk);
+                nk += (lq & 1) ? 2 : -2;
+              }
+              continue;
+            }
+          }
 #pragma clang loop unroll(disable)
           for (int ks = 0; ks < kn; ++ks) {
             const int sw = (sw0 + 2 * ks) & 15;
@@ -387,14 +427,15 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           if ((sl < UA) ? (sl < 3 * GA) : (sl - UA < 3 * GB)) continue;   // a slot of a whole pair
           const int code = ucode[sl];
           if (code == 0xFFFF) continue;
-          const int ca = 16 * (code >> 8), cb = 16 * ((code >> 4) & 15), up = (code >> 2) & 3;
+          const int ca = 16 * ((code >> 8) & 15), cb = 16 * ((code >> 4) & 15), up = (code >> 2) & 3;
           const bool k4 = (code & 3) == 1;
           int rb = lq * ldx;
           const int sw0 = lcol + (lq >> 1);
           int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
           asm volatile("" : "+v"(rb), "+v"(nk));
           // the weight scales the operands (p >= 1: a by n_k, p = 2: b as well): one loop per weight, so that a unit pays
-          // for the scalings it needs and for no selects
+          // for the scalings it needs and for no selects.  P = 3: an edge unit with q = 1, b alone is scaled (q = 0 and the
+          // corner run unscaled, as P = 0)
           auto run = [&](auto pc) {
             constexpr int P = decltype(pc)::value;
 #pragma clang loop unroll(disable)
@@ -403,8 +444,8 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
               double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
               double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
               rb += 4 * ldx;
-              if constexpr (P >= 1) { aR *= (double)nk; aI *= (double)nk; }
-              if constexpr (P == 2) { bR *= (double)nk; bI *= (double)nk; }
+              if constexpr (P == 1 || P == 2) { aR *= (double)nk; aI *= (double)nk; }
+              if constexpr (P >= 2) { bR *= (double)nk; bI *= (double)nk; }
               nk += (lq & 1) ? 2 : -2;
               if (sl < UA) {
                 d4 (&g)[3] = ga[sl < UA ? sl : 0];
@@ -421,6 +462,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             }
           };
           if (up == 0) run(std::integral_constant<int, 0>{});
+          else if (PK && (code & 0x1000)) run(std::integral_constant<int, PK ? 3 : 1>{});
           else if (up == 1) run(std::integral_constant<int, 1>{});
           else run(std::integral_constant<int, 2>{});
         }
@@ -530,7 +572,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         for (int sl = 0; sl < UN; ++sl) {
           const int code = ucode[sl];
           if (code == 0xFFFF) continue;
-          const int I = code >> 8, J = (code >> 4) & 15, up = (code >> 2) & 3;
+          const int I = (code >> 8) & 15, J = (code >> 4) & 15, up = (code >> 2) & 3;   // (edge units: plane q, the corner: plane 0)
           d4 re, im;
           if (sl < UA) {
             const d4 p1 = ga[sl < UA ? sl : 0][0], p2 = ga[sl < UA ? sl : 0][1];
@@ -577,10 +619,16 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
           double vr = 0.0, vi = 0.0;
           if (!pad) {
-            const double* gt = Gs + (size_t)(p * npair + I * (I + 1) / 2 + J) * 512;
-            const double2 v = *(const double2*)(gt + 2 * (16 * i + j));
+            // packed last tile column (i < 8 there): weights 0 and 1 of (E, J) in rows i and i + 8 of edge unit q = 0, weight
+            // 2 in row i + 8 of q = 1; entry (i + 8 pa, j + 8 pb), pa + pb = p, of the corner
+            const bool edge = PK && I == T - 1;
+            const int q = (edge && I != J) ? (int)(p == 2) : edge ? 0 : p;
+            const int ii = edge ? i + ((I != J) ? 8 * (p - q) : (p >= 1 ? 8 : 0)) : i;
+            const int jj = (edge && I == J && p == 2) ? j + 8 : j;
+            const double* gt = Gs + (size_t)(q * npair + I * (I + 1) / 2 + J) * 512;
+            const double2 v = *(const double2*)(gt + 2 * (16 * ii + jj));
             vr = v.x; vi = lo ? v.y : -v.y;
-            if (UN > 0 && I == J) vi = v.y - gt[2 * (16 * j + i) + 1];   // H unit (lo holds): Im = RI - RI^T
+            if (UN > 0 && I == J) vi = v.y - gt[2 * (16 * jj + ii) + 1];   // H unit (lo holds): Im = RI - RI^T
           }
           accR[sl][r] = vr; accI[sl][r] = vi;
         }
@@ -850,7 +898,7 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_ls_zero_prefix_kernel(co
 extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(LsArgs A, int TS, int ldx_max) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int nxt;
-#define TW_UNITS 0, TWU_UA, TWU_UB   /* template arguments TW, UA, UB of a class that contracts units */
+#define TW_UNITS(TB) 0, TWU_UA, TWU_UB, TB   /* template arguments TW, UA, UB, TB of a class that contracts units by table TB */
 #define RUN_CLASS(NSV, TWV, C)                                                             \
   for (;;) {                                                                             \
     if (threadIdx.x == 0) nxt = atomicAdd(A.cls + 8 + C, 1);                             \
@@ -862,8 +910,8 @@ extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(Ls
     else tile_frame<NSV, TWV>(A, TS, ldx_max, lds, A.cls[16 + (size_t)C * A.n_frames + item]);          \
   }
   RUN_CLASS(12, 0, 5)   // 91 tiles, T = 7: stacked
-  RUN_CLASS(10, TW_UNITS, 4)   // 78 tiles, T = 6: 63 units of the three-weight Gramian (eaqhm_ls_twunits.h)
-  RUN_CLASS(9, TW_UNITS, 3)    // 66 tiles, T = 6
+  RUN_CLASS(10, TW_UNITS(TWU_TB_12), 4)   // 78 tiles, T = 6: 63 units of the three-weight Gramian (eaqhm_ls_twunits.h)
+  RUN_CLASS(9, TW_UNITS(TWU_TB_11), 3)    // 66 tiles, T = 6, last tile column packed: 45 units + 10 edge units + the corner
   RUN_CLASS(7, 2, 2)    // 55 tiles, T = 5: 15 basis pairs
   RUN_CLASS(6, 2, 1)    // 45 tiles, T = 5
   RUN_CLASS(5, 2, 0)    // <= 36 tiles, T <= 4: <= 10 basis pairs
