@@ -10,7 +10,8 @@ from .structs import Deterministic, Frame  # noqa: F401
 from .model import (SCALE_RANGE, cepstrum_phase, model_from_parameters, model_parameters, alignment_index, alignment_time_scale, cepstrum_envelope, dtw, model_align, warp_rows, contour_time_map, eaQHMNoiseAnalysis, eaQHMNoiseModulation,  # noqa: F401
                     eaQHMNoiseSynthesis, eaQHMNoiseWarp, eaQHMSynthesis, formant_warp_vtln, model_cepstrum, model_envelope, model_f0,
                     model_phase, noise_alignment_index, noise_cepstrum, noise_envelope, noise_formant_contour, noise_formant_warp, noise_from_cepstrum, noise_fundamental, noise_time_map, noise_time_map_contour,
-                    scale_contour, unpack_model)
+                    scale_contour, unpack_model, allpass_warp, cepstrum_rewarp, cepstrum_warp, check_cepstrum_warp,
+                    rewarp_matrix)
 from .convert import (check_conversion, check_conversion_arguments, check_gmm_arguments, check_gv_arguments,  # noqa: F401
                       conversion_apply, conversion_pairs, conversion_train, conversion_trajectory, dynamic_rows,
                       f0_statistics, global_variance, gmm_fit, gmm_posteriors, gv_statistics, pitch_conversion_contour)

@@ -49,13 +49,33 @@ MAP.npz (convert.gv_statistics of TARGET's cepstrum): the variance of each coeff
 relative spread S (0.25 when left out: one utterance has no spread of its own).  --conversion MAP.npz with such a map adds
 the global-variance term to the trajectory, which gives the converted coefficients the target's variance
 back; --conversion-no-gv switches it off, --conversion-gv-iters K (30) and --conversion-gv-weight G (1) set the number of
-sweeps and the weight of the term."""
+sweeps and the weight of the term.
+--cepstral-warp A|mel|bark (with --cepstral-envelope, --from-parameters, --envelope-from, --timing-from, --conversion-train
+or --conversion) puts every cepstrum of the model on the all-pass warped frequency axis of DESIGN.md §9.8: a number in
+[-0.9, 0.9], or the coefficient model.cepstrum_warp gives for the file's sampling rate.  --conversion-train stores it in
+MAP.npz, and --conversion MAP.npz fits at the map's axis (a map without the entry lies on the linear axis); a different
+explicit --cepstral-warp is an error.  The noise flags keep their linear rows."""
 import argparse
 
 import numpy as np
 from scipy.io import wavfile
 
 from .functions import eaQHMAnalysisAndSynthesis
+
+
+def cepstral_warp_argument(text):
+    """--cepstral-warp: 'mel', 'bark' or a number in [-0.9, 0.9]."""
+    from .model import CEPSTRUM_WARP_MAX, CEPSTRUM_WARP_SCALES
+    if text in CEPSTRUM_WARP_SCALES:
+        return text
+    try:
+        a = float(text)
+    except ValueError:
+        a = float("nan")
+    if not abs(a) <= CEPSTRUM_WARP_MAX:
+        raise argparse.ArgumentTypeError("%r is not mel, bark or a number in [-%g, %g]"
+                                         % (text, CEPSTRUM_WARP_MAX, CEPSTRUM_WARP_MAX))
+    return a
 
 
 def parser():
@@ -120,6 +140,10 @@ def parser():
                          "order P (1 to 63; default min(63, 2 + round(fs / 1000)))")
     ap.add_argument("--cepstral-lambda", type=float, default=None, metavar="L",
                     help="with --cepstral-envelope: the regularisation weight, in [1e-6, 1] (5e-4)")
+    ap.add_argument("--cepstral-warp", type=cepstral_warp_argument, default=None, metavar="A|mel|bark",
+                    help="with --cepstral-envelope, --from-parameters, --envelope-from, --timing-from or a conversion "
+                         "flag: the cepstra lie on the all-pass warped frequency axis with the coefficient A in [-0.9, 0.9], "
+                         "or with the one that follows the mel or the Bark scale at the file's sampling rate")
     ap.add_argument("--envelope-from", default=None, metavar="OTHER.wav",
                     help="also write <name>_modified.wav: amplitudes read off the cepstral envelope of OTHER.wav, aligned "
                          "in time to this file (order and lambda: --cepstral-envelope, --cepstral-lambda)")
@@ -156,7 +180,8 @@ def parser():
 
 
 def load_conversion(path):
-    """A --conversion-save file: (the validated map, order, lambda, fs, source (mean, std) of ln f0, target's)."""
+    """A --conversion-save file: (the validated map, order, lambda, fs, source (mean, std) of ln f0, target's).  The map
+    holds cep_warp when the file does."""
     from .convert import check_conversion
     try:
         with np.load(path, allow_pickle=False) as z:
@@ -213,13 +238,22 @@ def main(argv=None):
     if a.cepstral_lambda is not None and not (cepstral or vocode or a.conversion_train is not None
                                               or a.conversion is not None):
         ap.error("--cepstral-lambda needs --cepstral-envelope, --from-parameters or a conversion flag")
+    train, convert = a.conversion_train is not None, a.conversion is not None
+    axis = 0.0
+    if a.cepstral_warp is not None:
+        if not (cepstral or vocode or a.envelope_from is not None or a.timing_from is not None or train or convert):
+            ap.error("--cepstral-warp needs --cepstral-envelope, --from-parameters, --envelope-from, --timing-from, "
+                     "--conversion-train or --conversion")
+        axis = a.cepstral_warp
+        if isinstance(axis, str):    # mel, bark: the coefficient depends on the file's sampling rate
+            from .model import cepstrum_warp
+            axis = cepstrum_warp(wavfile.read(a.wav)[0], axis)
     if vocode and a.no_envelope:
         ap.error("--from-parameters builds the model from its spectral envelope: not with --no-envelope")
     if cepstral and a.no_envelope:
         ap.error("--cepstral-envelope supplies the spectral envelope: not with --no-envelope")
     if a.envelope_from is not None and a.no_envelope:
         ap.error("--envelope-from supplies the spectral envelope: not with --no-envelope")
-    train, convert = a.conversion_train is not None, a.conversion is not None
     if train != (a.conversion_save is not None):
         ap.error("--conversion-train and --conversion-save go together")
     if a.conversion_components is not None and not train:
@@ -260,6 +294,8 @@ def main(argv=None):
             ap.error("--cepstral-envelope %d differs from the map's order %d" % (a.cepstral_envelope, cmap[1]))
         if a.cepstral_lambda is not None and a.cepstral_lambda != cmap[2]:
             ap.error("--cepstral-lambda %g differs from the map's %g" % (a.cepstral_lambda, cmap[2]))
+        if a.cepstral_warp is not None and axis != cmap[0].get("cep_warp", 0.0):
+            ap.error("--cepstral-warp %g differs from the map's %g" % (axis, cmap[0].get("cep_warp", 0.0)))
         if (a.conversion_no_gv or tuned) and "gv_mean" not in cmap[0]:
             ap.error("%s carries no global variance (--conversion-gv when it was learned): not with "
                      "--conversion-no-gv, --conversion-gv-iters or --conversion-gv-weight" % a.conversion)
@@ -299,6 +335,7 @@ def main(argv=None):
                             analysisWindow=a.analysis_window, fullWaveform=not a.voiced_only, fc=a.fc,
                             partials=a.partials, printPrompts=True, loadingScreen=False,
                             track_budget_bytes=int(a.track_budget_mb * 2 ** 20) if a.track_budget_mb > 0 else "auto")
+    on_axis = dict(cep_warp=axis) if axis != 0.0 else {}     # without the flag every call below is made without it
     s_recon, srer, det, t = eaQHMAnalysisAndSynthesis(a.wav, gender, **analysis_options)
     if not a.no_write:
         fs, _ = wavfile.read(a.wav)
@@ -306,7 +343,7 @@ def main(argv=None):
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
         if train:
-            train_conversion(a, gender, analysis_options, fs, det)
+            train_conversion(a, gender, analysis_options, fs, det, **on_axis)
         if modify or a.noise or vocode:
             from .model import eaQHMNoiseAnalysis, eaQHMNoiseModulation, eaQHMSynthesis, scale_contour
             rho = 1.0 if a.time_scale is None else a.time_scale
@@ -332,7 +369,7 @@ def main(argv=None):
             if cepstral or aligned:
                 from .model import model_cepstrum
                 order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
-                ceps = model_cepstrum(det, fs, order, lam)
+                ceps = model_cepstrum(det, fs, order, lam, **on_axis)
             if convert:   # this file's rows at the map's order and lambda, converted
                 from . import convert as _convert
                 from .convert import pitch_conversion_contour
@@ -340,7 +377,8 @@ def main(argv=None):
                 conv, c_order, c_lam, fs_map, src_f0, tgt_f0 = cmap   # the alignment keeps its own order, lam
                 if fs_map != fs:
                     raise ValueError("%s was learned at %d Hz, the input is sampled at %d Hz" % (a.conversion, fs_map, fs))
-                p = model_parameters(det, fs, c_order, c_lam)
+                synth_axis = dict(cep_warp=conv["cep_warp"]) if conv.get("cep_warp", 0.0) != 0.0 else {}
+                p = model_parameters(det, fs, c_order, c_lam, **synth_axis)
                 if "span" in conv:
                     converted = _convert.conversion_trajectory(conv, p["ceps"], **gv_options(a))
                 else:
@@ -354,7 +392,7 @@ def main(argv=None):
                     if path is not None and path not in others:
                         others[path] = align_other(path, gender, analysis_options, fs, ceps, order, lam,
                                                    2.0 if a.align_band is None else a.align_band,
-                                                   a.fc if path == a.noise_from else None)
+                                                   a.fc if path == a.noise_from else None, **on_axis)
                 if a.timing_from is not None:
                     rho = alignment_time_scale(others[a.timing_from][1], len(ceps))
                 if a.envelope_from is not None:
@@ -379,15 +417,17 @@ def main(argv=None):
                           phase=a.phase, noise=nz, noise_seed=a.noise_seed or 0, noise_formant=a.noise_formant,
                           noise_modulation=a.noise_modulation is not None, formant_warp=wmap)
             if modify or a.noise:
-                s_mod = eaQHMSynthesis(det, fs, len(s_recon), envelope=ceps, **common)
+                if not convert:          # the rows' axis: the flag's, or the map's
+                    synth_axis = on_axis if ceps is not None else {}
+                s_mod = eaQHMSynthesis(det, fs, len(s_recon), envelope=ceps, **synth_axis, **common)
                 out = a.wav[:len(a.wav) - 4] + ("_modified.wav" if modify else "_resynthesis.wav")
                 wavfile.write(out, fs, np.float32(s_mod))
                 print("wrote", out)
             if vocode:   # the model reduced to arrays and rebuilt from them alone
                 from .model import model_from_parameters, model_parameters
                 p = model_parameters(det, fs, a.from_parameters or None,
-                                     5e-4 if a.cepstral_lambda is None else a.cepstral_lambda)
-                built = model_from_parameters(p["f0"], p["ceps"], p["fs"], p["step"], voiced=p["voiced"])
+                                     5e-4 if a.cepstral_lambda is None else a.cepstral_lambda, **on_axis)
+                built = model_from_parameters(p["f0"], p["ceps"], p["fs"], p["step"], voiced=p["voiced"], **on_axis)
                 s_voc = eaQHMSynthesis(built, fs, len(s_recon), **common)
                 out = a.wav[:len(a.wav) - 4] + "_vocoded.wav"
                 wavfile.write(out, fs, np.float32(s_voc))
@@ -407,35 +447,38 @@ def gv_options(a):
     return kw
 
 
-def train_conversion(a, gender, analysis_options, fs, det):
-    """--conversion-train: analyses the target, aligns it to this file's model `det`, learns the map and saves it."""
+def train_conversion(a, gender, analysis_options, fs, det, **on_axis):
+    """--conversion-train: analyses the target, aligns it to this file's model `det`, learns the map and saves it.
+    on_axis is empty or cep_warp=a (--cepstral-warp): it reaches every fit and is stored in the map."""
     from .convert import conversion_pairs, conversion_train, f0_statistics, gv_statistics
     from .model import model_parameters
     order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
-    p = model_parameters(det, fs, order, lam)
+    p = model_parameters(det, fs, order, lam, **on_axis)
     C_t, pairs, det_t, _ = align_other(a.conversion_train, gender, analysis_options, fs, p["ceps"], order, lam,
-                                       2.0 if a.align_band is None else a.align_band)
+                                       2.0 if a.align_band is None else a.align_band, **on_axis)
     X, Y = conversion_pairs(p["ceps"], C_t, pairs, a.conversion_span)
     gv = None if a.conversion_gv is None else gv_statistics([C_t], rel_std=a.conversion_gv)
     conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components,
                             span=a.conversion_span, gv=gv)
-    p_t = model_parameters(det_t, fs, order, lam)
+    p_t = model_parameters(det_t, fs, order, lam, **on_axis)
     stats = [f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
     np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),
-             src_f0=np.array(stats[0]), tgt_f0=np.array(stats[1]), **conv)
+             src_f0=np.array(stats[0]), tgt_f0=np.array(stats[1]), **{k: np.float64(v) for k, v in on_axis.items()},
+             **conv)
     print("wrote %s: %d pairs, %d components, mean log-likelihood %g"
           % (a.conversion_save, len(X), len(conv["weights"]), conv["loglik"][-1]))
 
 
-def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, noise_fc=None):
-    """Analyses `path` with the same options, fits its cepstrum and aligns it to `ceps`: (its cepstrum, the path, its
-    model, and with `noise_fc` (the --fc of the analysis) the noise model of its residual, else None)."""
+def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, noise_fc=None, **on_axis):
+    """Analyses `path` with the same options, fits its cepstrum (on the axis of `ceps`: on_axis is empty or cep_warp=a)
+    and aligns it to `ceps`: (its cepstrum, the path, its model, and with `noise_fc` (the --fc of the analysis) the noise
+    model of its residual, else None)."""
     from .model import band_min_radius, eaQHMNoiseAnalysis, model_align, model_cepstrum, unpack_model
     fs_o, _ = wavfile.read(path)
     if fs_o != fs:
         raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (path, fs_o, fs))
     s_recon_o, _, det_o, _ = eaQHMAnalysisAndSynthesis(path, gender, **analysis_options)
-    C_o = model_cepstrum(det_o, fs, order, lam)
+    C_o = model_cepstrum(det_o, fs, order, lam, **on_axis)
     r = max(int(round(band_s * fs / unpack_model(det_o)["step"])), band_min_radius(len(ceps), len(C_o)))
     pairs, cost = model_align(ceps, C_o, band=r)
     print("aligned %s: %d pairs, cost %g" % (path, len(pairs), cost))

@@ -35,7 +35,8 @@ import math
 
 import numpy as np
 
-from .model import CEPSTRUM_MAX_ORDER, SCALE_RANGE, _cepstrum_rows, _integer, _numeric_1d, _path
+from .model import (CEPSTRUM_MAX_ORDER, SCALE_RANGE, _cepstrum_rows, _integer, _numeric_1d, _path,
+                    check_cepstrum_warp)
 
 GMM_MAX_COLUMNS = 128      # D = dx + dy at most: nine 16-wide tile rows of [c | 1] in the M-step's registers
 GMM_MAX_SIDE = 64          # dx, dy at most
@@ -248,6 +249,11 @@ def check_conversion(conv):
         if "span" not in out:
             raise ValueError("the conversion's gv_mean and gv_prec need a dynamic map (span)")
         out.update(_gv_fields(conv, dy // 2, "the conversion"))
+    if _has(conv, "cep_warp"):    # the axis of the rows the map was learned on; without it the linear one
+        a = _field(conv, "cep_warp", ())
+        if a.dtype.kind not in "iuf":
+            raise ValueError("the conversion's cep_warp must be a number")
+        out["cep_warp"] = check_cepstrum_warp(float(a), "the conversion's cep_warp")
     return out
 
 

@@ -10,6 +10,9 @@
 //   eaqhm_model_build_kernel          one wave per instant: the records of a harmonic model from f0 and a cepstrum (§9.7)
 // The readouts share cep_read: the read frequency (none, / alpha, or the inverse formant warp of eaqhm_warp.h), the hold
 // outside [0, fs/2] and Clenshaw's recurrence from one cos; cep_recur gives the kernels of §9.7 the sine sum as well.
+// Every kernel has a *_warped sibling (§9.8; include/eaqhm_cepwarp.h) on the all-pass warped axis Omega_a(w): the same
+// body, shared as a template where that leaves the unwarped kernel's machine code as it was (tools/isa_diff.py) and as
+// an included text (eaqhm_cepstrum_fit.inc, eaqhm_cepstrum_build.inc) where it does not.
 #include "eaqhm_common.h"
 #include "eaqhm_warp.h"
 
@@ -45,92 +48,50 @@ __device__ inline double cep_lane(double x, int src) {
   return __hiloint2double(hi, lo);
 }
 
+// The warped axis (§9.8): Omega_a(w) = w + 2 atan2(a sin w, 1 - a cos w), |a| <= 0.9.  The fit takes it as it is, once
+// per node.  The readouts need only its cosine and sine, which are a rational map of those of w / 2: with
+// u = (1 + a) sin(w/2), v = (1 - a) cos(w/2), tan(Omega/2) = u / v, so
+//   cos Omega = (v - u)(v + u) / (u^2 + v^2),   sin Omega = 2 u v / (u^2 + v^2):
+// one division, no atan2, and a denominator of two squares (>= (1 - |a|)^2) that cannot cancel.
+struct CepAxis { double p, m; };   // 1 + a, 1 - a
+__device__ inline CepAxis cep_axis(double a) { return CepAxis{1.0 + a, 1.0 - a}; }
+
+__device__ inline double cep_omega(double a, double w) {
+  double sn, cs;
+  sincos(w, &sn, &cs);
+  return w + 2.0 * atan2(a * sn, 1.0 - a * cs);
+}
+
+// cs = cos Omega_a(w) (and sn = sin Omega_a(w)) from wh = w / 2
+__device__ inline double cep_axis_cos(const CepAxis& X, double wh) {
+  double sh, ch;
+  sincos(wh, &sh, &ch);
+  const double u = X.p * sh, v = X.m * ch;
+  return ((v - u) * (v + u)) / (u * u + v * v);
+}
+__device__ inline void cep_axis_sincos(const CepAxis& X, double wh, double& sn, double& cs) {
+  double sh, ch;
+  sincos(wh, &sh, &ch);
+  const double u = X.p * sh, v = X.m * ch;
+  const double r = 1.0 / (u * u + v * v);
+  cs = ((v - u) * (v + u)) * r;
+  sn = (2.0 * (u * v)) * r;
+}
+
 extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
     eaqhm_model_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs, int P, double lam,
                                 double* __restrict__ ceps) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
-  if (i >= No_ti) return;   // the waves of a block share no data: no block barrier below
-  const int n = P + 1, LS = cep_stride(P);
-  double* sw = lds + (size_t)w * cep_wave_doubles(K, P);
-  double* sv = sw + K;
-  double* T = sv + K;
-  double* A = T + (2 * P + 2);
-  const double* row = records + (size_t)i * (3 * K + 1);
-  double* out = ceps + (size_t)i * n;
+#define CEP_WARPED 0
+#include "eaqhm_cepstrum_fit.inc"
+#undef CEP_WARPED
+}
 
-  // ---- 1. the nodes: the active slots (am != 0, f > 0) in slot order
-  int nn = 0;
-  for (int k0 = 0; k0 < K; k0 += 64) {
-    const int k = k0 + lane;
-    const bool act = k < K && row[k] != 0.0 && row[K + k] > 0.0;
-    const unsigned long long m = __ballot(act);
-    if (act) {
-      const int p = nn + __popcll(m & ((1ull << lane) - 1ull));
-      sw[p] = ((2.0 * M_PI) * row[K + k]) / fs;
-      sv[p] = log(row[k]);
-    }
-    nn += __popcll(m);
-  }
-  if (nn == 0) {   // an empty instant: -inf, 0, .., 0
-    if (lane < n) out[lane] = lane == 0 ? -INFINITY : 0.0;
-    return;
-  }
-  __builtin_amdgcn_wave_barrier();
-
-  // ---- 2. T_d = sum_n cos(d w_n), d = 0..2P, and b_p = sum_n v_n m_p(w_n), p = 0..P: lanes over d, every lane walks
-  // the nodes (one LDS address for the wave: a broadcast).  Each cosine is taken at d w_n itself, so there is no
-  // phasor to drift.  d <= P <= 63 falls in the first round: b_r ends up in lane r, the owner of row r.
-  double b = 0.0;
-  for (int d = lane; d <= 2 * P; d += 64) {
-    const double dd = (double)d;
-    double t = 0.0, bv = 0.0;
-    for (int q = 0; q < nn; ++q) {
-      const double c = cos(dd * sw[q]);
-      t += c;
-      bv += sv[q] * c;
-    }
-    T[d] = t;
-    if (d <= P) b = d == 0 ? bv : 2.0 * bv;
-  }
-  __builtin_amdgcn_wave_barrier();
-
-  // ---- 3. Cholesky G = L L^T, column by column (left-looking): lane r >= j forms G_rj - sum_{k<j} L_rk L_jk from its
-  // own row and row j (a broadcast); the pivot comes from lane j.  A pivot that is not finite or not > 0 ends the fit
-  // with a NaN row.
-  const int r = lane;
-  bool bad = false;
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    if (r >= j && r < n) {
-      s = cep_gram(T, r, j, lam);
-      for (int k = 0; k < j; ++k) s -= A[r * LS + k] * A[j * LS + k];
-    }
-    const double piv = cep_lane(s, j);
-    if (!(piv > 0.0) || !(piv < INFINITY)) { bad = true; break; }   // wave-uniform
-    const double dj = sqrt(piv);
-    if (r >= j && r < n) A[r * LS + j] = r == j ? dj : s / dj;
-    __builtin_amdgcn_wave_barrier();
-  }
-  if (bad) {
-    if (r < n) out[r] = NAN;
-    return;
-  }
-  // forward: L y = b, column by column; lane j keeps y_j
-  double y = b;
-  for (int j = 0; j < n; ++j) {
-    const double yj = cep_lane(y, j) / A[j * LS + j];
-    if (r == j) y = yj;
-    else if (r > j && r < n) y -= A[r * LS + j] * yj;
-  }
-  // backward: L^T c = y; lane r < j reads L_jr along row j (consecutive addresses)
-  for (int j = n - 1; j >= 0; --j) {
-    const double cj = cep_lane(y, j) / A[j * LS + j];
-    if (r == j) y = cj;
-    else if (r < j) y -= A[j * LS + r] * cj;
-  }
-  if (r < n) out[r] = y;
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_model_cepstrum_warped_kernel(const double* __restrict__ records, int No_ti, int K, double fs, int P,
+                                       double lam, double* __restrict__ ceps, double cep_a) {
+#define CEP_WARPED 1
+#include "eaqhm_cepstrum_fit.inc"
+#undef CEP_WARPED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -176,6 +137,26 @@ __device__ inline double cep_read_phase(const CepRead& R, const WarpRow& W, doub
   return -2.0 * (b1 * sn);
 }
 
+// The two readouts on the warped axis (§9.8): the read frequency and the hold as above, in Hz, then cos and sin of
+// Omega_a through cep_axis_*.  (Helpers of their own, like cep_recur: cep_read and cep_read_phase keep their text.)
+__device__ inline double cep_read_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
+  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
+  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double cw2 = 2.0 * cep_axis_cos(X, (M_PI * x) / R.fs);
+  double b1, b2;
+  cep_recur(R.c, R.P, cw2, b1, b2);
+  return 2.0 * (0.5 * cw2 * b1 - b2) + R.c[0];
+}
+
+__device__ inline double cep_read_phase_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
+  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
+  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  double sn, cs, b1, b2;
+  cep_axis_sincos(X, (M_PI * x) / R.fs, sn, cs);
+  cep_recur(R.c, R.P, 2.0 * cs, b1, b2);
+  return -2.0 * (b1 * sn);
+}
+
 // LDS of the two readout kernels (doubles): per wave the row's coefficients [CEP_PMAX + 1] and its row of the map
 // [2 x WARP_BMAX], then the block's x [WARP_BMAX].  A block barrier follows the staging; every wave reaches it.
 constexpr int CEP_READ_WAVE = CEP_PMAX + 1 + 2 * WARP_BMAX;
@@ -199,12 +180,11 @@ __device__ inline WarpRow cep_stage(double* lds, int w, int lane, bool live, con
 
 // A'[i][k] = exp(C_i(read_i(beta_i f_k))) for an active slot, 0 for an inactive one and where beta_i f_k >= fs/2.
 // There is no unit rule: the envelope is the caller's.  Overwrites the amp of a prep that ran without the envelope.
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
-    eaqhm_modify_amp_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs,
-                                     const double* __restrict__ betav, const double* __restrict__ ceps, int P,
-                                     const double* __restrict__ alphav, const double* __restrict__ f_in,
-                                     const double* __restrict__ f_out, int B, double* __restrict__ amp) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
+template <bool WARP>
+__device__ __forceinline__ void cep_amp(double* lds, const double* __restrict__ records, int No_ti, int K, double fs,
+                                        const double* __restrict__ betav, const double* __restrict__ ceps, int P,
+                                        const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                        const double* __restrict__ f_out, int B, double* __restrict__ amp, double aw) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
   const bool live = i < No_ti;
@@ -213,25 +193,45 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
   if (!live) return;
   const double beta = betav[i];
   const CepRead R{lds + (size_t)w * CEP_READ_WAVE, P, fs, B > 0 ? 2 : alphav ? 1 : 0, alphav ? alphav[i] : 1.0};
+  const CepAxis X = cep_axis(aw);
   const double* row = records + (size_t)i * (3 * K + 1);
   for (int k = lane; k < K; k += 64) {
     const double ak = row[k], fk = row[K + k];
     double a = 0.0;
     if (ak != 0.0 && fk > 0.0) {
       const double bf = beta * fk;   // the output frequency: it alone decides the muting
-      a = exp(cep_read(R, W, bf));
+      a = exp(WARP ? cep_read_warped(R, X, W, bf) : cep_read(R, W, bf));
       if (bf >= 0.5 * fs) a = 0.0;
     }
     amp[(size_t)i * K + k] = a;
   }
 }
 
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_modify_amp_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs,
+                                     const double* __restrict__ betav, const double* __restrict__ ceps, int P,
+                                     const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                     const double* __restrict__ f_out, int B, double* __restrict__ amp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_amp<false>(lds, records, No_ti, K, fs, betav, ceps, P, alphav, f_in, f_out, B, amp, 0.0);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_modify_amp_cepstrum_warped_kernel(const double* __restrict__ records, int No_ti, int K, double fs,
+                                            const double* __restrict__ betav, const double* __restrict__ ceps, int P,
+                                            const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                            const double* __restrict__ f_out, int B, double* __restrict__ amp,
+                                            double aw) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_amp<true>(lds, records, No_ti, K, fs, betav, ceps, P, alphav, f_in, f_out, B, amp, aw);
+}
+
 // out[i][t] = C_i(read_i(freqs[t])), natural-log amplitude, not muted; -inf on a (-inf, 0, ..) row.  PHASE: Phi_i there.
-template <bool PHASE>
+template <bool PHASE, bool WARP = false>
 __device__ inline void cep_grid(double* lds, const double* __restrict__ ceps, int n, int P, double fs,
                                 const double* __restrict__ alphav, const double* __restrict__ f_in,
                                 const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
-                                double* __restrict__ out) {
+                                double* __restrict__ out, double aw = 0.0) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per row: scalar
   const bool live = i < n;
@@ -239,6 +239,12 @@ __device__ inline void cep_grid(double* lds, const double* __restrict__ ceps, in
   const WarpRow W = cep_stage(lds, w, lane, live, ceps + (size_t)il * (P + 1), P, f_in, f_out + (size_t)il * B, B);
   if (!live) return;
   const CepRead R{lds + (size_t)w * CEP_READ_WAVE, P, fs, B > 0 ? 2 : alphav ? 1 : 0, alphav ? alphav[i] : 1.0};
+  if (WARP) {
+    const CepAxis X = cep_axis(aw);
+    for (int t = lane; t < F; t += 64)
+      out[(size_t)i * F + t] = PHASE ? cep_read_phase_warped(R, X, W, freqs[t]) : cep_read_warped(R, X, W, freqs[t]);
+    return;
+  }
   for (int t = lane; t < F; t += 64) out[(size_t)i * F + t] = PHASE ? cep_read_phase(R, W, freqs[t]) : cep_read(R, W, freqs[t]);
 }
 
@@ -260,6 +266,24 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
   cep_grid<true>(lds, ceps, n, P, fs, alphav, f_in, f_out, B, freqs, F, out);
 }
 
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_cepstrum_envelope_warped_kernel(const double* __restrict__ ceps, int n, int P, double fs,
+                                          const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                          const double* __restrict__ f_out, int B, const double* __restrict__ freqs,
+                                          int F, double* __restrict__ out, double aw) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_grid<false, true>(lds, ceps, n, P, fs, alphav, f_in, f_out, B, freqs, F, out, aw);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_cepstrum_phase_warped_kernel(const double* __restrict__ ceps, int n, int P, double fs,
+                                       const double* __restrict__ alphav, const double* __restrict__ f_in,
+                                       const double* __restrict__ f_out, int B, const double* __restrict__ freqs, int F,
+                                       double* __restrict__ out, double aw) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  cep_grid<true, true>(lds, ceps, n, P, fs, alphav, f_in, f_out, B, freqs, F, out, aw);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The model from parameters (§9.7): the records [n][3 Kmax + 1] of the harmonic model with f = h f0_i, |a| = exp(C_i(f))
 // and phase = wrap(2 pi frac(h theta_i) + Phi_i(f)), h = k + 1.  Slot k is active iff the instant is voiced, its row is
@@ -271,41 +295,19 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
                              const unsigned char* __restrict__ voiced, const double* __restrict__ ceps, int P,
                              const double* __restrict__ a0, int n, double fs, int Kmax, int Kcap, int zero_phase,
                              double* __restrict__ records) {
-  __shared__ double sc[CEP_WAVES][CEP_PMAX + 1];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
-  if (i >= n) return;
-  double* c = sc[w];
-  if (lane <= P) c[lane] = ceps[(size_t)i * (P + 1) + lane];
-  __builtin_amdgcn_wave_barrier();
-  const bool rowlive = voiced[i] != 0 && c[0] != -INFINITY;
-  const double fi = f0[i], th = theta[i], half = 0.5 * fs;
-  double* row = records + (size_t)i * (3 * (size_t)Kmax + 1);
-  for (int k0 = 0; k0 < Kmax; k0 += 64) {
-    const int k = k0 + lane;
-    if (k >= Kmax) break;
-    const double h = (double)(k + 1);
-    const double fm = __dmul_rn(h, fi);
-    double a = 0.0, f = 0.0, ph = 0.0;
-    if (rowlive && k < Kcap && fm < half) {
-      double sn, cs, b1, b2;
-      sincos(((2.0 * M_PI) * fm) / fs, &sn, &cs);
-      const double cw2 = 2.0 * cs;
-      cep_recur(c, P, cw2, b1, b2);
-      a = exp(2.0 * (0.5 * cw2 * b1 - b2) + c[0]);
-      if (a != 0.0) {
-        const double hs = __dmul_rn(h, th);           // the product rounded as the definition rounds it, then frac
-        double x = __dmul_rn(2.0 * M_PI, hs - floor(hs));
-        if (!zero_phase) x += -2.0 * (b1 * sn);
-        ph = x - (2.0 * M_PI) * ceil((x - M_PI) / (2.0 * M_PI));   // into (-pi, pi]
-        f = fm;
-      }
-    }
-    row[k] = a;
-    row[Kmax + k] = f;
-    row[2 * Kmax + k] = ph;
-  }
-  if (lane == 0) row[3 * (size_t)Kmax] = a0[i];
+#define CEP_WARPED 0
+#include "eaqhm_cepstrum_build.inc"
+#undef CEP_WARPED
+}
+
+extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+    eaqhm_model_build_warped_kernel(const double* __restrict__ f0, const double* __restrict__ theta,
+                                    const unsigned char* __restrict__ voiced, const double* __restrict__ ceps, int P,
+                                    const double* __restrict__ a0, int n, double fs, int Kmax, int Kcap, int zero_phase,
+                                    double* __restrict__ records, double cep_a) {
+#define CEP_WARPED 1
+#include "eaqhm_cepstrum_build.inc"
+#undef CEP_WARPED
 }
 }  // namespace eaqhm
 
@@ -322,19 +324,69 @@ static bool read_group_ok(const double* alpha, const double* f_in, const double*
   return (none || whole) && !(alpha && whole);
 }
 
+// Each entry point and its *_warped sibling (include/eaqhm_cepwarp.h) share one checked launch: `warp` is null for the
+// linear axis, else it points at cep_warp.  fn names the entry point in the messages.
+static int cep_fail(eaqhm_ctx* ctx, const char* fn, const char* what) {
+  snprintf(ctx->err, sizeof(ctx->err), "%s: %s", fn, what);
+  return EAQHM_EINVAL;
+}
+static bool warp_ok(const double* warp) { return !warp || (std::isfinite(*warp) && fabs(*warp) <= 0.9); }
+static const char* const WARP_MSG = "cep_warp must be finite with |cep_warp| <= 0.9";
+static const char* const ORDER_MSG = "need 1 <= order <= 63";
+static const char* const GROUP_MSG = "alpha, or f_in and f_out with 1 <= B <= 16, or neither";
+
+static int model_cepstrum_launch(eaqhm_ctx* ctx, const char* fn, const double* records, int32_t No_ti, int32_t Kmax,
+                                 double fs, int32_t order, double lambda, double* ceps, const double* warp) {
+  if (!ctx) return EAQHM_EINVAL;
+  if (!records || !ceps || No_ti < 1 || Kmax <= 0 || !finite_pos(fs)) return cep_fail(ctx, fn, "bad argument");
+  if (order < 1 || order > CEP_PMAX) return cep_fail(ctx, fn, ORDER_MSG);
+  if (!finite_pos(lambda)) return cep_fail(ctx, fn, "lambda must be finite and > 0");
+  if (!warp_ok(warp)) return cep_fail(ctx, fn, WARP_MSG);
+  const size_t lds = (size_t)CEP_WAVES * cep_wave_doubles(Kmax, order) * sizeof(double);
+  if (lds > CEPSTRUM_LDS_MAX) return cep_fail(ctx, fn, "Kmax too large for the nodes");
+  const dim3 grid((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
+  if (warp) {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_warped_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(eaqhm_model_cepstrum_warped_kernel, grid, block, lds, ctx->stream, records, (int)No_ti, (int)Kmax,
+                       fs, (int)order, lambda, ceps, *warp);
+  } else {
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(eaqhm_model_cepstrum_kernel, grid, block, lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs,
+                       (int)order, lambda, ceps);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return EAQHM_OK;
+}
+
 extern "C" int eaqhm_model_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
                                     int32_t order, double lambda, double* ceps) {
+  return model_cepstrum_launch(ctx, "eaqhm_model_cepstrum", records, No_ti, Kmax, fs, order, lambda, ceps, nullptr);
+}
+extern "C" int eaqhm_model_cepstrum_warped(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
+                                           int32_t order, double lambda, double* ceps, double cep_warp) {
+  return model_cepstrum_launch(ctx, "eaqhm_model_cepstrum_warped", records, No_ti, Kmax, fs, order, lambda, ceps,
+                               &cep_warp);
+}
+
+static int modify_amp_cepstrum_launch(eaqhm_ctx* ctx, const char* fn, const double* records, int32_t No_ti, int32_t Kmax,
+                                      double fs, const double* beta, const double* ceps, int32_t order,
+                                      const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                      double* amp, const double* warp) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!records || !ceps || No_ti < 1 || Kmax <= 0 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: bad argument");
-  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: need 1 <= order <= 63");
-  if (!finite_pos(lambda)) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: lambda must be finite and > 0");
-  const size_t lds = (size_t)CEP_WAVES * cep_wave_doubles(Kmax, order) * sizeof(double);
-  if (lds > CEPSTRUM_LDS_MAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_cepstrum: Kmax too large for the nodes");
-  HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-  hipLaunchKernelGGL(eaqhm_model_cepstrum_kernel, dim3((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)),
-                     dim3(64 * CEP_WAVES), lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs, (int)order, lambda, ceps);
+  if (!records || !beta || !ceps || !amp || No_ti < 4 || Kmax <= 0 || !finite_pos(fs))
+    return cep_fail(ctx, fn, "bad argument");
+  if (order < 1 || order > CEP_PMAX) return cep_fail(ctx, fn, ORDER_MSG);
+  if (!read_group_ok(alpha, f_in, f_out, B)) return cep_fail(ctx, fn, GROUP_MSG);
+  if (!warp_ok(warp)) return cep_fail(ctx, fn, WARP_MSG);
+  const dim3 grid((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
+  if (warp)
+    hipLaunchKernelGGL(eaqhm_modify_amp_cepstrum_warped_kernel, grid, block, CEP_READ_LDS, ctx->stream, records,
+                       (int)No_ti, (int)Kmax, fs, beta, ceps, (int)order, alpha, f_in, f_out, (int)B, amp, *warp);
+  else
+    hipLaunchKernelGGL(eaqhm_modify_amp_cepstrum_kernel, grid, block, CEP_READ_LDS, ctx->stream, records, (int)No_ti,
+                       (int)Kmax, fs, beta, ceps, (int)order, alpha, f_in, f_out, (int)B, amp);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
@@ -342,15 +394,41 @@ extern "C" int eaqhm_model_cepstrum(eaqhm_ctx* ctx, const double* records, int32
 extern "C" int eaqhm_modify_amp_cepstrum(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax, double fs,
                                          const double* beta, const double* ceps, int32_t order, const double* alpha,
                                          const double* f_in, const double* f_out, int32_t B, double* amp) {
+  return modify_amp_cepstrum_launch(ctx, "eaqhm_modify_amp_cepstrum", records, No_ti, Kmax, fs, beta, ceps, order, alpha,
+                                    f_in, f_out, B, amp, nullptr);
+}
+extern "C" int eaqhm_modify_amp_cepstrum_warped(eaqhm_ctx* ctx, const double* records, int32_t No_ti, int32_t Kmax,
+                                                double fs, const double* beta, const double* ceps, int32_t order,
+                                                const double* alpha, const double* f_in, const double* f_out,
+                                                int32_t B, double* amp, double cep_warp) {
+  return modify_amp_cepstrum_launch(ctx, "eaqhm_modify_amp_cepstrum_warped", records, No_ti, Kmax, fs, beta, ceps, order,
+                                    alpha, f_in, f_out, B, amp, &cep_warp);
+}
+
+// the two grid readouts: phase selects Phi
+static int cepstrum_grid_launch(eaqhm_ctx* ctx, const char* fn, bool phase, const double* ceps, int32_t n, int32_t order,
+                                double fs, const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                const double* freqs, int32_t F, double* out, const double* warp) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!records || !beta || !ceps || !amp || No_ti < 4 || Kmax <= 0 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: bad argument");
-  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: need 1 <= order <= 63");
-  if (!read_group_ok(alpha, f_in, f_out, B))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_modify_amp_cepstrum: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
-  hipLaunchKernelGGL(eaqhm_modify_amp_cepstrum_kernel, dim3((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)),
-                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, records, (int)No_ti, (int)Kmax, fs, beta, ceps,
-                     (int)order, alpha, f_in, f_out, (int)B, amp);
+  if (!ceps || !freqs || !out || n < 1 || F < 1 || !finite_pos(fs)) return cep_fail(ctx, fn, "bad argument");
+  if (order < 1 || order > CEP_PMAX) return cep_fail(ctx, fn, ORDER_MSG);
+  if (!read_group_ok(alpha, f_in, f_out, B)) return cep_fail(ctx, fn, GROUP_MSG);
+  if (!warp_ok(warp)) return cep_fail(ctx, fn, WARP_MSG);
+  const dim3 grid((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
+  if (warp) {
+    if (phase)
+      hipLaunchKernelGGL(eaqhm_cepstrum_phase_warped_kernel, grid, block, CEP_READ_LDS, ctx->stream, ceps, (int)n,
+                         (int)order, fs, alpha, f_in, f_out, (int)B, freqs, (int)F, out, *warp);
+    else
+      hipLaunchKernelGGL(eaqhm_cepstrum_envelope_warped_kernel, grid, block, CEP_READ_LDS, ctx->stream, ceps, (int)n,
+                         (int)order, fs, alpha, f_in, f_out, (int)B, freqs, (int)F, out, *warp);
+  } else if (phase) {
+    hipLaunchKernelGGL(eaqhm_cepstrum_phase_kernel, grid, block, CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs,
+                       alpha, f_in, f_out, (int)B, freqs, (int)F, out);
+  } else {
+    hipLaunchKernelGGL(eaqhm_cepstrum_envelope_kernel, grid, block, CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order,
+                       fs, alpha, f_in, f_out, (int)B, freqs, (int)F, out);
+  }
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
@@ -358,31 +436,48 @@ extern "C" int eaqhm_modify_amp_cepstrum(eaqhm_ctx* ctx, const double* records, 
 extern "C" int eaqhm_cepstrum_envelope(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
                                        const double* alpha, const double* f_in, const double* f_out, int32_t B,
                                        const double* freqs, int32_t F, double* out) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!ceps || !freqs || !out || n < 1 || F < 1 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: bad argument");
-  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: need 1 <= order <= 63");
-  if (!read_group_ok(alpha, f_in, f_out, B))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_envelope: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
-  hipLaunchKernelGGL(eaqhm_cepstrum_envelope_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)),
-                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs, alpha, f_in, f_out,
-                     (int)B, freqs, (int)F, out);
-  HIP_TRY(ctx, hipGetLastError());
-  return EAQHM_OK;
+  return cepstrum_grid_launch(ctx, "eaqhm_cepstrum_envelope", false, ceps, n, order, fs, alpha, f_in, f_out, B, freqs, F,
+                              out, nullptr);
 }
-
+extern "C" int eaqhm_cepstrum_envelope_warped(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
+                                              const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                              const double* freqs, int32_t F, double* out, double cep_warp) {
+  return cepstrum_grid_launch(ctx, "eaqhm_cepstrum_envelope_warped", false, ceps, n, order, fs, alpha, f_in, f_out, B,
+                              freqs, F, out, &cep_warp);
+}
 extern "C" int eaqhm_cepstrum_phase(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
                                     const double* alpha, const double* f_in, const double* f_out, int32_t B,
                                     const double* freqs, int32_t F, double* out) {
+  return cepstrum_grid_launch(ctx, "eaqhm_cepstrum_phase", true, ceps, n, order, fs, alpha, f_in, f_out, B, freqs, F, out,
+                              nullptr);
+}
+extern "C" int eaqhm_cepstrum_phase_warped(eaqhm_ctx* ctx, const double* ceps, int32_t n, int32_t order, double fs,
+                                           const double* alpha, const double* f_in, const double* f_out, int32_t B,
+                                           const double* freqs, int32_t F, double* out, double cep_warp) {
+  return cepstrum_grid_launch(ctx, "eaqhm_cepstrum_phase_warped", true, ceps, n, order, fs, alpha, f_in, f_out, B, freqs,
+                              F, out, &cep_warp);
+}
+
+static int model_build_launch(eaqhm_ctx* ctx, const char* fn, const double* f0, const double* theta,
+                              const uint8_t* voiced, const double* ceps, int32_t order, const double* a0, int32_t n,
+                              double fs, int32_t Kmax, int32_t Kcap, int32_t zero_phase, double* records,
+                              const double* warp) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!ceps || !freqs || !out || n < 1 || F < 1 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: bad argument");
-  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: need 1 <= order <= 63");
-  if (!read_group_ok(alpha, f_in, f_out, B))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_cepstrum_phase: alpha, or f_in and f_out with 1 <= B <= 16, or neither");
-  hipLaunchKernelGGL(eaqhm_cepstrum_phase_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)),
-                     dim3(64 * CEP_WAVES), CEP_READ_LDS, ctx->stream, ceps, (int)n, (int)order, fs, alpha, f_in, f_out,
-                     (int)B, freqs, (int)F, out);
+  if (!f0 || !theta || !voiced || !ceps || !a0 || !records || n < 2 || !finite_pos(fs))
+    return cep_fail(ctx, fn, "bad argument");
+  if (order < 1 || order > CEP_PMAX) return cep_fail(ctx, fn, ORDER_MSG);
+  if (Kcap < 1 || Kcap > BUILD_KCAP_MAX || Kmax < 1 || Kmax > Kcap)
+    return cep_fail(ctx, fn, "need 1 <= Kmax <= Kcap <= 1706");
+  if (zero_phase != 0 && zero_phase != 1) return cep_fail(ctx, fn, "zero_phase is 0 or 1");
+  if (!warp_ok(warp)) return cep_fail(ctx, fn, WARP_MSG);
+  const dim3 grid((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
+  if (warp)
+    hipLaunchKernelGGL(eaqhm_model_build_warped_kernel, grid, block, 0, ctx->stream, f0, theta,
+                       (const unsigned char*)voiced, ceps, (int)order, a0, (int)n, fs, (int)Kmax, (int)Kcap,
+                       (int)zero_phase, records, *warp);
+  else
+    hipLaunchKernelGGL(eaqhm_model_build_kernel, grid, block, 0, ctx->stream, f0, theta, (const unsigned char*)voiced,
+                       ceps, (int)order, a0, (int)n, fs, (int)Kmax, (int)Kcap, (int)zero_phase, records);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
@@ -390,16 +485,13 @@ extern "C" int eaqhm_cepstrum_phase(eaqhm_ctx* ctx, const double* ceps, int32_t 
 extern "C" int eaqhm_model_build(eaqhm_ctx* ctx, const double* f0, const double* theta, const uint8_t* voiced,
                                  const double* ceps, int32_t order, const double* a0, int32_t n, double fs,
                                  int32_t Kmax, int32_t Kcap, int32_t zero_phase, double* records) {
-  if (!ctx) return EAQHM_EINVAL;
-  if (!f0 || !theta || !voiced || !ceps || !a0 || !records || n < 2 || !finite_pos(fs))
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: bad argument");
-  if (order < 1 || order > CEP_PMAX) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: need 1 <= order <= 63");
-  if (Kcap < 1 || Kcap > BUILD_KCAP_MAX || Kmax < 1 || Kmax > Kcap)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: need 1 <= Kmax <= Kcap <= 1706");
-  if (zero_phase != 0 && zero_phase != 1) return ctx->fail(EAQHM_EINVAL, "eaqhm_model_build: zero_phase is 0 or 1");
-  hipLaunchKernelGGL(eaqhm_model_build_kernel, dim3((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)), dim3(64 * CEP_WAVES),
-                     0, ctx->stream, f0, theta, (const unsigned char*)voiced, ceps, (int)order, a0, (int)n, fs, (int)Kmax,
-                     (int)Kcap, (int)zero_phase, records);
-  HIP_TRY(ctx, hipGetLastError());
-  return EAQHM_OK;
+  return model_build_launch(ctx, "eaqhm_model_build", f0, theta, voiced, ceps, order, a0, n, fs, Kmax, Kcap, zero_phase,
+                            records, nullptr);
+}
+extern "C" int eaqhm_model_build_warped(eaqhm_ctx* ctx, const double* f0, const double* theta, const uint8_t* voiced,
+                                        const double* ceps, int32_t order, const double* a0, int32_t n, double fs,
+                                        int32_t Kmax, int32_t Kcap, int32_t zero_phase, double* records,
+                                        double cep_warp) {
+  return model_build_launch(ctx, "eaqhm_model_build_warped", f0, theta, voiced, ceps, order, a0, n, fs, Kmax, Kcap,
+                            zero_phase, records, &cep_warp);
 }

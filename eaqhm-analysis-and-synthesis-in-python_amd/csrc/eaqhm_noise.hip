@@ -416,61 +416,19 @@ extern "C" __global__ void __launch_bounds__(64 * NC_WAVES)
 extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
     eaqhm_noise_from_cepstrum_kernel(const double* __restrict__ ceps, int Nf, int Q, int p,
                                      double* __restrict__ sigma_out, double* __restrict__ refl_out) {
-  __shared__ double tab[NW_M + 1];
-  __shared__ double Pw[NW_WAVES][NW_M + 2];
-  __shared__ double cw[NW_WAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int m = blockIdx.x * NW_WAVES + wave;
-  const bool live = m < Nf;
-  for (int j = threadIdx.x; j <= NW_M; j += 64 * NW_WAVES) tab[j] = cospi((double)j / (double)NW_M);
-  const double cl = (live && lane <= Q) ? ceps[(size_t)m * (Q + 1) + lane] : 0.0;
-  double* c = cw[wave];
-  double* P = Pw[wave];
-  c[lane] = cl;
-  const double c0 = __shfl(cl, 0, 64);
-  const bool work = live && c0 != -INFINITY;       // uniform over the wave
-  __syncthreads();
-  if (work) {
-    for (int t = lane; t <= NW_M; t += 64) {
-      const double cw2 = 2.0 * tab[t];
-      double b1 = 0.0, b2 = 0.0;
-      for (int q = Q; q >= 1; --q) {               // one LDS address for the wave: a broadcast
-        const double b0 = c[q] + (cw2 * b1 - b2);
-        b2 = b1;
-        b1 = b0;
-      }
-      P[t] = exp(4.0 * (0.5 * cw2 * b1 - b2));
-    }
-  }
-  __syncthreads();
-  if (!live) return;
-  if (!work) {
-    if (lane == 0) sigma_out[m] = 0.0;
-    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = 0.0;
-    return;
-  }
+#define CEP_WARPED 0
+#include "eaqhm_noise_from_cepstrum.inc"
+#undef CEP_WARPED
+}
 
-  // r[l] on lane l, as in noise_warp_frame
-  auto ct = [&](int t) {
-    const int idx = (lane * t) & (2 * NW_M - 1);
-    return tab[idx > NW_M ? 2 * NW_M - idx : idx];
-  };
-  double r0 = 0.5 * P[0], r1 = 0.0, r2 = 0.0, r3 = ((lane & 1) ? -0.5 : 0.5) * P[NW_M];
-  for (int t = 1; t + 3 < NW_M; t += 4) {
-    r0 = fma(P[t], ct(t), r0);
-    r1 = fma(P[t + 1], ct(t + 1), r1);
-    r2 = fma(P[t + 2], ct(t + 2), r2);
-    r3 = fma(P[t + 3], ct(t + 3), r3);
-  }
-  r0 = fma(P[NW_M - 3], ct(NW_M - 3), r0);
-  r1 = fma(P[NW_M - 2], ct(NW_M - 2), r1);
-  r2 = fma(P[NW_M - 1], ct(NW_M - 1), r2);
-  const double r = ((r0 + r1) + (r2 + r3)) / (double)NW_M;
-
-  double kk = 0.0;
-  const double E = levinson_lanes<false>(r, p, lane, kk);
-  if (lane == 0) sigma_out[m] = exp(c0) * sqrt(E);
-  if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = kk;
+// the same on the all-pass warped axis (include/eaqhm_cepwarp.h)
+extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+    eaqhm_noise_from_cepstrum_warped_kernel(const double* __restrict__ ceps, int Nf, int Q, int p,
+                                            double* __restrict__ sigma_out, double* __restrict__ refl_out,
+                                            double cep_a) {
+#define CEP_WARPED 1
+#include "eaqhm_noise_from_cepstrum.inc"
+#undef CEP_WARPED
 }
 
 // ---- pitch-synchronous modulation of the noise (tests/noise_modulation_ref.py)
@@ -732,15 +690,38 @@ extern "C" int eaqhm_noise_cepstrum(eaqhm_ctx* ctx, const double* sigma, const d
   return EAQHM_OK;
 }
 
-extern "C" int eaqhm_noise_from_cepstrum(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order,
-                                         int32_t order, double* sigma_out, double* refl_out) {
+static int noise_from_cepstrum_launch(eaqhm_ctx* ctx, const char* fn, const double* ceps, int32_t Nf,
+                                      int32_t ceps_order, int32_t order, double* sigma_out, double* refl_out,
+                                      const double* warp) {
   if (!ctx) return EAQHM_EINVAL;
-  if (!ceps || !sigma_out || !refl_out || Nf < 1)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_from_cepstrum: bad argument");
-  if (order < 1 || order > 63 || ceps_order < 1 || ceps_order > 63)
-    return ctx->fail(EAQHM_EINVAL, "eaqhm_noise_from_cepstrum: need 1 <= order <= 63 and 1 <= ceps_order <= 63");
-  hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_kernel, dim3((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)),
-                     dim3(64 * NW_WAVES), 0, ctx->stream, ceps, (int)Nf, (int)ceps_order, (int)order, sigma_out, refl_out);
+  char msg[160];
+  const char* what = nullptr;
+  if (!ceps || !sigma_out || !refl_out || Nf < 1) what = "bad argument";
+  else if (order < 1 || order > 63 || ceps_order < 1 || ceps_order > 63)
+    what = "need 1 <= order <= 63 and 1 <= ceps_order <= 63";
+  else if (warp && !(std::isfinite(*warp) && fabs(*warp) <= 0.9)) what = "cep_warp must be finite with |cep_warp| <= 0.9";
+  if (what) {
+    snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+    return ctx->fail(EAQHM_EINVAL, msg);
+  }
+  const dim3 grid((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)), block(64 * NW_WAVES);
+  if (warp)
+    hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_warped_kernel, grid, block, 0, ctx->stream, ceps, (int)Nf,
+                       (int)ceps_order, (int)order, sigma_out, refl_out, *warp);
+  else
+    hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_kernel, grid, block, 0, ctx->stream, ceps, (int)Nf, (int)ceps_order,
+                       (int)order, sigma_out, refl_out);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
+}
+
+extern "C" int eaqhm_noise_from_cepstrum(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order,
+                                         int32_t order, double* sigma_out, double* refl_out) {
+  return noise_from_cepstrum_launch(ctx, "eaqhm_noise_from_cepstrum", ceps, Nf, ceps_order, order, sigma_out, refl_out,
+                                    nullptr);
+}
+extern "C" int eaqhm_noise_from_cepstrum_warped(eaqhm_ctx* ctx, const double* ceps, int32_t Nf, int32_t ceps_order,
+                                                int32_t order, double* sigma_out, double* refl_out, double cep_warp) {
+  return noise_from_cepstrum_launch(ctx, "eaqhm_noise_from_cepstrum_warped", ceps, Nf, ceps_order, order, sigma_out,
+                                    refl_out, &cep_warp);
 }

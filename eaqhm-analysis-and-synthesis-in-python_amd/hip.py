@@ -76,6 +76,15 @@ SYMBOLS_GV = (
     ("eaqhm_gv_work_len", _I64, [_I64, _I32, _I32]),
     ("eaqhm_gv_ascend", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _P, _I32, _P, _P, _P]),
 )
+# every symbol include/eaqhm_cepwarp.h declares: each is its sibling's list plus one double, cep_warp
+SYMBOLS_CEPWARP = (
+    ("eaqhm_model_cepstrum_warped", C.c_int, [_P, _P, _I32, _I32, _F64, _I32, _F64, _P, _F64]),
+    ("eaqhm_modify_amp_cepstrum_warped", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _I32, _P, _P, _P, _I32, _P, _F64]),
+    ("eaqhm_cepstrum_envelope_warped", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P, _F64]),
+    ("eaqhm_cepstrum_phase_warped", C.c_int, [_P, _P, _I32, _I32, _F64, _P, _P, _P, _I32, _P, _I32, _P, _F64]),
+    ("eaqhm_model_build_warped", C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _I32, _F64, _I32, _I32, _I32, _P, _F64]),
+    ("eaqhm_noise_from_cepstrum_warped", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _F64]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -98,7 +107,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV:
+    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -357,6 +366,38 @@ class Context:
     def gv_ascend(self, P, r, n, dy, span, run_start, run_len, n_runs, gv_mean, gv_prec, iters, work, Y, trace=None):
         self._ck(self.lib.eaqhm_gv_ascend(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
                                           _ptr(gv_mean), _ptr(gv_prec), iters, _ptr(work), _ptr(Y), _ptr(trace)))
+
+    # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
+    def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):
+        self._ck(self.lib.eaqhm_model_cepstrum_warped(self.h, _ptr(records), No_ti, Kmax, float(fs), order, float(lam),
+                                                      _ptr(ceps), float(cep_warp)))
+
+    def modify_amp_cepstrum_warped(self, records, No_ti, Kmax, fs, beta, ceps, order, amp, cep_warp, alpha=None,
+                                   warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_modify_amp_cepstrum_warped(self.h, _ptr(records), No_ti, Kmax, float(fs), _ptr(beta),
+                                                           _ptr(ceps), order, _ptr(alpha), _ptr(f_in), _ptr(f_out), B,
+                                                           _ptr(amp), float(cep_warp)))
+
+    def cepstrum_envelope_warped(self, ceps, n, order, fs, freqs, F, out, cep_warp, alpha=None, warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_cepstrum_envelope_warped(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha),
+                                                         _ptr(f_in), _ptr(f_out), B, _ptr(freqs), F, _ptr(out),
+                                                         float(cep_warp)))
+
+    def cepstrum_phase_warped(self, ceps, n, order, fs, freqs, F, out, cep_warp, alpha=None, warp=None):
+        f_in, f_out, B = warp or (None, None, 0)
+        self._ck(self.lib.eaqhm_cepstrum_phase_warped(self.h, _ptr(ceps), n, order, float(fs), _ptr(alpha), _ptr(f_in),
+                                                      _ptr(f_out), B, _ptr(freqs), F, _ptr(out), float(cep_warp)))
+
+    def model_build_warped(self, f0, theta, voiced, ceps, order, a0, n, fs, Kmax, Kcap, zero_phase, records, cep_warp):
+        self._ck(self.lib.eaqhm_model_build_warped(self.h, _ptr(f0), _ptr(theta), _ptr(voiced), _ptr(ceps), order,
+                                                   _ptr(a0), n, float(fs), Kmax, Kcap, int(bool(zero_phase)),
+                                                   _ptr(records), float(cep_warp)))
+
+    def noise_from_cepstrum_warped(self, ceps, Nf, Q, p, sigma_out, refl_out, cep_warp):
+        self._ck(self.lib.eaqhm_noise_from_cepstrum_warped(self.h, _ptr(ceps), Nf, Q, p, _ptr(sigma_out), _ptr(refl_out),
+                                                           float(cep_warp)))
 
     def eval_partials_len(self, t_lo, t_hi, step):
         return int(self.lib.eaqhm_eval_partials_len(t_lo, t_hi, step))

@@ -511,6 +511,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_mlpg.h"
 /* the global-variance ascent from that trajectory (additions under ABI 6): declared in eaqhm_gv.h.     */
 #include "eaqhm_gv.h"
+/* the discrete cepstrum on an all-pass warped axis (additions under ABI 6): declared in eaqhm_cepwarp.h. */
+#include "eaqhm_cepwarp.h"
 
 #ifdef __cplusplus
 }

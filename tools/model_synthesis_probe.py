@@ -38,6 +38,9 @@ trajectory solve on random rows, once as one run and once as 
 scipy.linalg.solveh_banded on the host.  --gv times the global-variance ascent (eaqhm_gv_ascend, 30
 sweeps) from the solve's trajectory on the same kind of rows, as one run and as 200, next to eaqhm_mlpg_solve in the same
 session and to the same iteration in NumPy on the host's band, with the largest difference between the two results.
+--cepstrum-warp times every entry point of the warped cepstrum (include/eaqhm_cepwarp.h) next to its
+sibling on the linear axis, same session, same model, same rows' shapes, at the default order and at order 24 with
+a = cepstrum_warp(fs): the ratio to the sibling with the sibling's max - min beside it.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -117,7 +120,8 @@ def prepare(torch, det, fs, L, reps):
 
 
 def probe(workload, reps, contours=False, formant=False, noise=False, shape=False, noise_formant=False,
-          noise_modulation=False, formant_warp=False, cepstrum=False, align=False, build=False, noise_cepstrum=False):
+          noise_modulation=False, formant_warp=False, cepstrum=False, align=False, build=False, noise_cepstrum=False,
+          cepstrum_warp=False):
     import torch
     fs, L, det, arrays, t_pack, residual = analyse(workload)
     st = prepare(torch, det, fs, L, reps)
@@ -166,6 +170,9 @@ def probe(workload, reps, contours=False, formant=False, noise=False, shape=Fals
     if noise_cepstrum:
         import eaqhm_amd
         res["noise_cepstrum"] = noise_cepstrum_rows(torch, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
+    if cepstrum_warp:
+        import eaqhm_amd
+        res["cepstrum_warp"] = cepwarp_rows(torch, st, eaqhm_amd.eaQHMNoiseAnalysis(residual, np.zeros(L), fs))
     return res
 
 
@@ -414,6 +421,66 @@ def noise_cepstrum_rows(torch, nz, Q=63, reps=20, runs=3):
                  base_ms=base[0], margin_ms=base[1], cepstrum_ms=fwd[0], cepstrum_spread_ms=fwd[1],
                  from_cepstrum_ms=back[0], from_cepstrum_spread_ms=back[1],
                  from_cepstrum_to_warp=round(back[0] / base[0], 3), cepstrum_to_warp=round(fwd[0] / base[0], 3))]
+
+
+def cepwarp_rows(torch, st, nz, reps=20, runs=3, grid=120):
+    """Every *_warped entry point next to its sibling, same session, same model: the fit, the knot
+    amplitudes at beta = 1.25, the envelope and the phase on a `grid`-point grid up to fs/2, the model build and the noise
+    frames from cepstral rows, at the default order min(63, 2 + round(fs / 1000)) and at order 24, a = cepstrum_warp(fs).
+    The warped kernels read rows fitted on the warped axis, the siblings rows fitted on the linear one (the noise rows are
+    noise_cepstrum's, cut to the order, and those moved by cepstrum_rewarp).  Each time: median of `runs` warmed windows
+    of `reps` launches; margin_ms = max - min of the sibling's windows; ratio = warped / sibling."""
+    from eaqhm_amd.model import _records_f0, cepstrum_rewarp, cepstrum_warp, check_model_build_arguments, noise_cepstrum
+    c, rec, amp = (st[k] for k in ("c", "rec", "amp"))
+    n, K, D, fs = st["n"], st["K"], st["D"], st["fs"]
+    dev = c.device
+    a = cepstrum_warp(fs)
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return ts[len(ts) // 2], ts[-1] - ts[0]
+
+    def row(setting, P, base, new, **more):
+        return dict(setting=setting, order=P, cep_warp=round(a, 6), base_ms=round(base[0], 4), margin_ms=round(base[1], 4),
+                    new_ms=round(new[0], 4), new_spread_ms=round(new[1], 4), ratio=round(new[0] / base[0], 4), **more)
+
+    rows = []
+    rec_h = rec.cpu().numpy()
+    f_grid = torch.as_tensor(np.linspace(0.0, fs / 2.0, grid), device=dev)
+    beta_d = torch.full((n,), 1.25, dtype=torch.float64, device=dev)
+    noise_rows = noise_cepstrum(nz, 63)
+    Nf, p = len(noise_rows), nz["order"]
+    sigma_o = torch.empty(Nf, dtype=torch.float64, device=dev)
+    refl_o = torch.empty((Nf, p), dtype=torch.float64, device=dev)
+    for P in sorted({min(63, 2 + int(round(fs / 1000.0))), 24}):
+        lin = torch.empty((n, P + 1), dtype=torch.float64, device=dev)
+        wrp = torch.empty((n, P + 1), dtype=torch.float64, device=dev)
+        rows.append(row("fit_P%d" % P, P, med(lambda: c.model_cepstrum(rec, n, K, fs, P, 5e-4, lin)),
+                        med(lambda: c.model_cepstrum_warped(rec, n, K, fs, P, 5e-4, wrp, a)), instants=n,
+                        nan_rows=int(torch.isnan(wrp).any(dim=1).sum().item())))
+        rows.append(row("amp_P%d" % P, P, med(lambda: c.modify_amp_cepstrum(rec, n, K, fs, beta_d, lin, P, amp)),
+                        med(lambda: c.modify_amp_cepstrum_warped(rec, n, K, fs, beta_d, wrp, P, amp, a)), cells=n * K))
+        out = torch.empty((n, grid), dtype=torch.float64, device=dev)
+        rows.append(row("envelope_P%d" % P, P, med(lambda: c.cepstrum_envelope(lin, n, P, fs, f_grid, grid, out)),
+                        med(lambda: c.cepstrum_envelope_warped(wrp, n, P, fs, f_grid, grid, out, a)), cells=n * grid))
+        rows.append(row("phase_P%d" % P, P, med(lambda: c.cepstrum_phase(lin, n, P, fs, f_grid, grid, out)),
+                        med(lambda: c.cepstrum_phase_warped(wrp, n, P, fs, f_grid, grid, out, a)), cells=n * grid))
+        b = check_model_build_arguments(_records_f0(rec_h, K), lin.cpu().numpy(), fs, D,
+                                        voiced=(rec_h[:, :K] != 0).any(axis=1))
+        Kb = b["Kmax"]
+        f_d, th_d, a0_d = (torch.as_tensor(np.ascontiguousarray(b[k]), device=dev) for k in ("f0", "theta", "a0"))
+        v_d = torch.as_tensor(b["voiced"].astype(np.uint8), device=dev)
+        built = torch.empty((n, 3 * Kb + 1), dtype=torch.float64, device=dev)
+        rows.append(row("build_P%d" % P, P,
+                        med(lambda: c.model_build(f_d, th_d, v_d, lin, P, a0_d, n, fs, Kb, b["Kcap"], False, built)),
+                        med(lambda: c.model_build_warped(f_d, th_d, v_d, wrp, P, a0_d, n, fs, Kb, b["Kcap"], False, built,
+                                                         a)), Kmax_built=Kb, cells=int(b["counts"].sum())))
+        nl = torch.as_tensor(np.ascontiguousarray(noise_rows[:, :P + 1]), device=dev)
+        nw = torch.as_tensor(cepstrum_rewarp(noise_rows, 0.0, a, P), device=dev)
+        rows.append(row("noise_from_cepstrum_Q%d" % P, P,
+                        med(lambda: c.noise_from_cepstrum(nl, Nf, P, p, sigma_o, refl_o)),
+                        med(lambda: c.noise_from_cepstrum_warped(nw, Nf, P, p, sigma_o, refl_o, a)), frames=Nf, lpc_order=p))
+    return rows
 
 
 def build_rows(torch, st, reps=20, runs=3):
@@ -876,6 +943,8 @@ def main():
                     help="also time eaqhm_model_build next to eaqhm_modify_amp_cepstrum (the model from parameters)")
     ap.add_argument("--noise-cepstrum", action="store_true",
                     help="also time eaqhm_noise_cepstrum and eaqhm_noise_from_cepstrum next to eaqhm_noise_warp")
+    ap.add_argument("--cepstrum-warp", action="store_true",
+                    help="also time every *_warped entry point of the warped cepstrum next to its sibling")
     ap.add_argument("--gmm", action="store_true",
                     help="time eaqhm_gmm_estep, eaqhm_gmm_mstep and eaqhm_gmm_regress next to torch matmuls (random rows; "
                          "needs no workload: pass --workloads '')")
@@ -912,7 +981,7 @@ def main():
                     json.dump([res_gmm], f, indent=1)
             return 0
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
-                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build, a.noise_cepstrum)
+                 a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build, a.noise_cepstrum, a.cepstrum_warp)
            for w in a.workloads.split(",")]
     if a.gmm:
         res.append(res_gmm)
