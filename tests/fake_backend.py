@@ -49,9 +49,10 @@ class OracleBackend:
             row[:] = 0
             if mode == 0:
                 f0, K = float(frame_f0[f]), int(frame_K[f])
-                amp, _ = O.iqhm_ls(sig[c - wl:c + wl + 1], np.arange(-K, K + 1) * f0, np.blackman(2 * wl + 1), fs)
+                amp, slo = O.iqhm_ls(sig[c - wl:c + wl + 1], np.arange(-K, K + 1) * f0, np.blackman(2 * wl + 1), fs)
                 A, eta, slots = amp[K + 1:], np.zeros(K), np.arange(K)
                 row[3 * Kmax] = amp[K].real
+                raw = amp, slo
             else:
                 f0 = f0_stale
                 while sp < len(seeds) and seeds[sp] <= c:        # visible to frames at or after the seeded row
@@ -67,6 +68,10 @@ class OracleBackend:
                 eta_t = fs / (2 * np.pi) * (amp_t.real * slo_t.imag - amp_t.imag * slo_t.real) / np.abs(amp_t) ** 2
                 A, eta, slots = amp_t[n + 1:], eta_t[n + 1:], nz
                 row[3 * Kmax] = amp_t[n].real
+                raw = amp_t, slo_t
+            if raw_amp is not None:      # write_record's layout: [negative | DC | positive], Kc complex128 as float64
+                for out, x in zip((raw_amp, raw_slope), raw):       # pairs, in the order the seam functions return
+                    out.numpy()[f, :2 * len(x)] = np.ascontiguousarray(x).view(np.float64)
             mag = np.abs(A)
             with np.errstate(divide="ignore"):
                 lg = 20 * np.log10(mag)
