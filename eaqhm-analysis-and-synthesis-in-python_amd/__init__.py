@@ -13,6 +13,7 @@ from .model import (SCALE_RANGE, cepstrum_phase, model_from_parameters, model_pa
                     scale_contour, unpack_model, allpass_warp, cepstrum_rewarp, cepstrum_warp, check_cepstrum_warp,
                     rewarp_matrix)
 from .convert import (check_conversion, check_conversion_arguments, check_gmm_arguments, check_gv_arguments,  # noqa: F401
+                      check_kmeans_arguments, kmeans, kmeans_assign,
                       conversion_apply, conversion_pairs, conversion_train, conversion_trajectory, dynamic_rows,
                       f0_statistics, global_variance, gmm_fit, gmm_posteriors, gv_statistics, pitch_conversion_contour)
 from .prologue import read_signal  # noqa: F401

@@ -44,6 +44,9 @@ extended with their delta features over a window of L instants a side before the
 the mixture is over the extended rows, and MAP.npz carries the span.  --conversion MAP.npz with such a map converts this
 file to the most likely trajectory under the static and the delta statistics (convert.conversion_trajectory, DESIGN.md
 §12.1) in place of the row-by-row rule, so that the converted envelope does not jump where the posterior changes component.
+--conversion-init axis|kmeans (with --conversion-train) chooses where EM starts: `axis`, the default, cuts the rows into
+equal runs along their principal axis; `kmeans` starts from a k-means codebook of M centres grown by splitting
+(convert.kmeans).
 --conversion-gv [S] (with --conversion-train and --conversion-span) also stores the target's global-variance statistics in
 MAP.npz (convert.gv_statistics of TARGET's cepstrum): the variance of each coefficient over the utterance, with a stated
 relative spread S (0.25 when left out: one utterance has no spread of its own).  --conversion MAP.npz with such a map adds
@@ -162,6 +165,9 @@ def parser():
     ap.add_argument("--conversion-span", type=int, default=None, metavar="L",
                     help="with --conversion-train: learn a dynamic map on rows extended with their delta features over L "
                          "instants a side, 1 to 8; --conversion then converts to the most likely trajectory")
+    ap.add_argument("--conversion-init", choices=("axis", "kmeans"), default=None,
+                    help="with --conversion-train: where EM starts, equal runs along the principal axis (axis, the "
+                         "default) or a k-means codebook (kmeans)")
     ap.add_argument("--conversion-gv", type=float, nargs="?", const=0.25, default=None, metavar="S",
                     help="with --conversion-train and --conversion-span: store the target's global variance in the map, "
                          "with the relative spread S, 0 < S <= 10 (0.25); S is optional, so the flag must not stand directly "
@@ -260,6 +266,8 @@ def main(argv=None):
         ap.error("--conversion-components needs --conversion-train")
     if a.conversion_span is not None and not train:
         ap.error("--conversion-span needs --conversion-train")
+    if a.conversion_init is not None and not train:
+        ap.error("--conversion-init needs --conversion-train")
     if train and convert:
         ap.error("--conversion applies a map, --conversion-train learns one: not together")
     if a.conversion_gv is not None and not (train and a.conversion_span is not None):
@@ -447,6 +455,11 @@ def gv_options(a):
     return kw
 
 
+def conversion_init(a):
+    """The init argument of conversion_train that --conversion-init sets: none for `axis`, today's start."""
+    return dict(init="kmeans") if a.conversion_init == "kmeans" else {}
+
+
 def train_conversion(a, gender, analysis_options, fs, det, **on_axis):
     """--conversion-train: analyses the target, aligns it to this file's model `det`, learns the map and saves it.
     on_axis is empty or cep_warp=a (--cepstral-warp): it reaches every fit and is stored in the map."""
@@ -459,7 +472,7 @@ def train_conversion(a, gender, analysis_options, fs, det, **on_axis):
     X, Y = conversion_pairs(p["ceps"], C_t, pairs, a.conversion_span)
     gv = None if a.conversion_gv is None else gv_statistics([C_t], rel_std=a.conversion_gv)
     conv = conversion_train(X, Y, 8 if a.conversion_components is None else a.conversion_components,
-                            span=a.conversion_span, gv=gv)
+                            span=a.conversion_span, gv=gv, **conversion_init(a))
     p_t = model_parameters(det_t, fs, order, lam, **on_axis)
     stats = [f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
     np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),

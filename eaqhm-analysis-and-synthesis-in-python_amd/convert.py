@@ -18,7 +18,11 @@
     gv_statistics(utterances, *, level=False, rel_std=None) -> dict(gv_mean[dys], gv_prec[dys]) for conversion_train(gv=)
     f0_statistics(f0, voiced) -> (mean, std) of ln f0 over the voiced instants
     pitch_conversion_contour(f0, voiced, src_stats, tgt_stats) -> pitch_scale contour float64[n]
-    check_gmm_arguments, check_conversion_arguments, check_conversion, check_gv_arguments: validation, no device work
+    kmeans(Z, k, *, iters=20, split_iters=2, split=None, scale=None, device_index=0)
+        -> dict(labels int64[N], centres[k, D'], counts int64[k], sse[k], rounds): a codebook grown by splitting (LBG)
+    kmeans_assign(centres, Z, *, device_index=0) -> int64[N]: the nearest centre of each row
+    check_gmm_arguments, check_conversion_arguments, check_conversion, check_gv_arguments, check_kmeans_arguments:
+        validation, no device work
 
 The definition is DESIGN.md §12: EM with full covariances on centred rows (Dempster, Laird & Rubin 1977), the
 regression of Stylianou, Cappe & Moulines (1998) in Kain & Macon's joint-density form.  Everything that scales with the
@@ -30,6 +34,9 @@ with their delta features (eaqhm_ceps_delta) and an utterance is converted to th
 the static and the delta statistics together (Tokuda et al. 2000): one banded positive-definite system per voiced run and
 cepstral dimension (eaqhm_mlpg_solve).  DESIGN.md §12.2 adds the same paper's global-variance term: from that trajectory,
 sweeps up the likelihood joined with a Gaussian prior on each column's variance over the utterance (eaqhm_gv_ascend).
+DESIGN.md §12.3 adds the vector-quantisation codebook of Linde, Buzo & Gray (1980): centres grown by splitting, each
+size settled by Lloyd rounds (eaqhm_kmeans_assign, eaqhm_kmeans_update); init="kmeans" starts the mixture from its
+labels, the split decisions run on the host from K x D sums.
 """
 import math
 
@@ -51,6 +58,10 @@ GV_CHUNKS_MAX = 512        # chunks at most
 GV_WEIGHT_RANGE = (1e-6, 1e6)
 GV_MAX_ITERS = 10000
 GV_REL_STD_MAX = 10.0
+KMEANS_MAX_CENTRES = 64
+KMEANS_MAX_ITERS = 1000
+KMEANS_MAX_SPLIT_ITERS = 100
+KMEANS_START = dict(iters=20, split_iters=2)   # the codebook behind init="kmeans": kmeans' own defaults
 
 
 def gmm_chunk_rows(N):
@@ -79,6 +90,11 @@ def gv_work_len(n, dy, span):
     return n * (2 * span + 2) * dy + n + n * dy + chunks * (5 * dy + 1) + 2 * dy
 
 
+def kmeans_work_len(N, D, K):
+    """Doubles of the k-means update's `work` (include/eaqhm_kmeans.h): ceil(N / R) K (2 D + 1), R the M-step's chunk."""
+    return -(-int(N) // gmm_chunk_rows(N)) * K * (2 * D + 1)
+
+
 # ---- validation (no device work)
 def _rows(Z, name, max_cols):
     A = np.asarray(Z)
@@ -104,7 +120,7 @@ def _real(x, name, lo, hi):
 
 def check_gmm_arguments(Z, components, iters=20, tol=1e-5, floor=1e-6, init=None, split=None):
     """Validates everything gmm_fit gets (no device work): returns (Z float64[N, D], M, iters, tol, floor, init, split),
-    init an int64[N] of labels or None."""
+    init an int64[N] of labels, "kmeans" or None."""
     Z = _rows(Z, "Z", GMM_MAX_COLUMNS)
     N, D = Z.shape
     M = _integer(components, "components")
@@ -119,7 +135,10 @@ def check_gmm_arguments(Z, components, iters=20, tol=1e-5, floor=1e-6, init=None
     if not np.isfinite(tol):
         raise ValueError("tol must be finite")
     floor = _real(floor, "floor", *GMM_FLOOR_RANGE)
-    if init is not None:
+    if isinstance(init, str):
+        if init != "kmeans":
+            raise ValueError('init must be None, "kmeans" or an integer array of labels, got %r' % init)
+    elif init is not None:
         lab = np.asarray(init)
         if lab.dtype.kind not in "iu" or lab.shape != (N,):
             raise ValueError("init must be an integer array of %d labels, one per row" % N)
@@ -135,6 +154,30 @@ def check_gmm_arguments(Z, components, iters=20, tol=1e-5, floor=1e-6, init=None
         if not 1 <= split <= D:
             raise ValueError("split must be in [1, %d], got %d" % (D, split))
     return Z, M, iters, tol, floor, init, split
+
+
+def check_kmeans_arguments(Z, k, iters=20, split_iters=2, split=None, scale=None):
+    """Validates everything kmeans gets (no device work): returns (Z float64[N, D], k, iters, split_iters, split, scale)."""
+    Z = _rows(Z, "Z", GMM_MAX_COLUMNS)
+    N, D = Z.shape
+    k = _integer(k, "k")
+    if not 1 <= k <= KMEANS_MAX_CENTRES:
+        raise ValueError("k must be in [1, %d], got %d" % (KMEANS_MAX_CENTRES, k))
+    if N < 2 * k:
+        raise ValueError("%d centres need at least %d rows, got %d" % (k, 2 * k, N))
+    iters = _integer(iters, "iters")
+    if not 0 <= iters <= KMEANS_MAX_ITERS:
+        raise ValueError("iters must be in [0, %d], got %d" % (KMEANS_MAX_ITERS, iters))
+    split_iters = _integer(split_iters, "split_iters")
+    if not 0 <= split_iters <= KMEANS_MAX_SPLIT_ITERS:
+        raise ValueError("split_iters must be in [0, %d], got %d" % (KMEANS_MAX_SPLIT_ITERS, split_iters))
+    if split is not None:
+        split = _integer(split, "split")
+        if not 1 <= split <= D:
+            raise ValueError("split must be in [1, %d], got %d" % (D, split))
+    if scale is not None and not (isinstance(scale, str) and scale == "std"):
+        raise ValueError('scale must be None or "std", got %r' % (scale,))
+    return Z, k, iters, split_iters, split, scale
 
 
 def check_span(span):
@@ -331,6 +374,48 @@ def gmm_init_labels(X, M):
     return labels
 
 
+def kmeans_rows(Z, split=None, scale=None):
+    """(rows, zbar, sd): the rows k-means sees, the first `split` columns of Z minus their mean and,
+    with scale="std", over their standard deviations (a constant column is left as it is); sd is ones without."""
+    X = Z[:, :split] if split else Z
+    zbar = X.mean(axis=0)
+    sd = np.ones(X.shape[1])
+    if scale:
+        sd = X.std(axis=0)
+        sd = np.where(sd > 0, sd, 1.0)
+    return np.ascontiguousarray((X - zbar) / sd if scale else X - zbar), zbar, sd
+
+
+def kmeans_moments(C, count, S1, Q):
+    """(centres, v, sse) from the sums of an update: the means S1 / n, the per-column variances max(Q / n - mean^2, 0) and
+    n sum_j v_j; a cluster without a row keeps its centre of `C` and has v = 0, sse = 0."""
+    full = (count > 0)[:, None]
+    n = np.maximum(count, 1)[:, None].astype(np.float64)
+    mean = np.where(full, S1 / n, C)
+    v = np.where(full, np.maximum(Q / n - mean * mean, 0.0), 0.0)
+    return mean, v, count * v.sum(axis=1)
+
+
+def kmeans_split(C, count, v, sse, k):
+    """Grows K = len(C) centres towards k: the min(K, k - K) clusters of largest sse among those with n >= 2 and sse > 0
+    (ties: the lower index first) are split, in that order, along their column j of largest variance (ties: the lowest):
+    the new centre c + sqrt(v_j) e_j is appended and the old one becomes c - sqrt(v_j) e_j.  LinAlgError when no cluster
+    qualifies."""
+    K = len(C)
+    able = np.flatnonzero((count >= 2) & (sse > 0))
+    if not len(able):
+        raise np.linalg.LinAlgError("k-means: the rows cannot be split further than %d centres (%d wanted): every cluster "
+                                    "is a single point" % (K, k))
+    chosen = able[np.argsort(-sse[able], kind="stable")][:min(K, k - K)]
+    C = np.vstack((C, C[chosen]))
+    for i, m in enumerate(chosen):
+        j = int(np.argmax(v[m]))
+        s = math.sqrt(v[m, j])
+        C[K + i, j] += s
+        C[m, j] -= s
+    return C
+
+
 def gmm_finish_mstep(S0, S1, S2, N, phi):
     """(w, mu, Sigma) from the sums; LinAlgError naming the component whose S0 < 1: there is no re-seeding."""
     if np.any(S0 < 1):
@@ -479,23 +564,137 @@ class _Mixture:
         return self.S0.cpu().numpy(), self.S1.cpu().numpy(), self.S2.cpu().numpy()
 
 
+class _Codebook:
+    """Rows on the device, float64 [N, ldz] of which the first D columns count, and the buffers of the two k-means steps
+    for up to k centres; `labels` int32[N] on the device, all 0 at first."""
+
+    def __init__(self, torch, c, dev, Z, D, k):
+        self.torch, self.c, self.dev, self.Z, self.D = torch, c, dev, Z, D
+        self.N, self.ldz = Z.shape
+        words = c.kmeans_work_len(self.N, D, k)
+        if words != kmeans_work_len(self.N, D, k):
+            raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the k-means update's work buffer")
+        self.words, self.k, self.work = words, k, None                  # the update's buffers come with the first update
+        self.labels = torch.zeros(self.N, dtype=torch.int32, device=dev)
+        self.changed = torch.empty(-(-self.N // 64), dtype=torch.int32, device=dev)
+
+    def assign(self, C):
+        """labels <- the nearest of the centres C float64[K, D]; the number of rows whose label moved."""
+        t = self.torch
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        g = (C * C).sum(axis=1)
+        self.c.kmeans_assign(self.Z, self.N, self.ldz, self.D, t.as_tensor(C, device=self.dev),
+                             t.as_tensor(g, device=self.dev), len(C), self.labels, self.changed)
+        return int(self.changed.sum().item())
+
+    def update(self, K):
+        """(count int64[K], S1[K, D], Q[K, D]) of the current labels, on the host."""
+        if self.work is None:
+            t, f64 = self.torch, self.torch.float64
+            self.work = t.empty(self.words, dtype=f64, device=self.dev)
+            self.count = t.empty(self.k, dtype=t.int64, device=self.dev)
+            self.S1 = t.empty((self.k, self.D), dtype=f64, device=self.dev)
+            self.Q = t.empty((self.k, self.D), dtype=f64, device=self.dev)
+        self.c.kmeans_update(self.Z, self.N, self.ldz, self.D, self.labels, K, self.work, self.count, self.S1, self.Q)
+        return self.count[:K].cpu().numpy(), self.S1[:K].cpu().numpy(), self.Q[:K].cpu().numpy()
+
+
+def kmeans_grow(book, k, iters, split_iters):
+    """The loop of DESIGN.md §12.3 on a _Codebook whose labels are all 0: (centres[k, D], counts, sse, rounds); the
+    labels stay in `book`.  Only K x D sums and a count of moved rows come back from the device."""
+    def lloyd(C):
+        C = kmeans_moments(C, *book.update(len(C)))[0]
+        return C, book.assign(C)
+    C, rounds = np.zeros((1, book.D)), 0
+    while len(C) < k:
+        count, S1, Q = book.update(len(C))
+        C, v, sse = kmeans_moments(C, count, S1, Q)
+        C = kmeans_split(C, count, v, sse, k)
+        book.assign(C)
+        for _ in range(split_iters):
+            C, _ = lloyd(C)
+            rounds += 1
+    for _ in range(iters):
+        C, changed = lloyd(C)
+        rounds += 1
+        if changed == 0:
+            break
+    count, S1, Q = book.update(k)
+    C, _, sse = kmeans_moments(C, count, S1, Q)
+    return C, count, sse, rounds
+
+
+def kmeans(Z, k, *, iters=20, split_iters=2, split=None, scale=None, device_index=0):
+    """A codebook of `k` centres in [1, 64] for the rows of `Z` float64[N, D] (all finite, D <= 128, N >= 2 k), grown by
+    splitting (Linde, Buzo & Gray 1980): from one centre, the clusters of largest squared error are split
+    along their column of largest variance until there are k, `split_iters` Lloyd rounds after every growth and up to
+    `iters` at k, stopping after a round in which no row moved.  Only the first `split` columns count when given.  The
+    distance is Euclidean on the centred rows (on cepstral rows a log-spectral distance); scale="std" divides every
+    column by its standard deviation first.  No random numbers: the same rows give the same codebook.  Returns
+    dict(labels int64[N], centres float64[k, D'] in Z's coordinates, counts int64[k], sse float64[k] (each cluster's
+    squared error about its centre, in the scaled coordinates when scale is given), rounds: the Lloyd rounds run).  Raises
+    numpy.linalg.LinAlgError when the rows have fewer than k distinct clusters to split."""
+    Z, k, iters, split_iters, split, scale = check_kmeans_arguments(Z, k, iters, split_iters, split, scale)
+    rows, zbar, sd = kmeans_rows(Z, split, scale)
+    torch, c, dev = _device(device_index)
+    book = _Codebook(torch, c, dev, torch.as_tensor(rows, device=dev), rows.shape[1], k)
+    C, count, sse, rounds = kmeans_grow(book, k, iters, split_iters)
+    return dict(labels=book.labels.cpu().numpy().astype(np.int64), centres=C * sd + zbar, counts=count, sse=sse,
+                rounds=rounds)
+
+
+def kmeans_assign(centres, Z, *, device_index=0):
+    """The label of each row of `Z` float64[N, D'] against a codebook `centres` float64[K, D'] (kmeans' centres, K <= 64,
+    D' <= 128): the index of the nearest centre in the Euclidean distance, the lowest on a tie; int64[N].  Both are
+    shifted by the mean of the centres before the scores are formed.  The distance is the plain Euclidean one: for a
+    codebook grown with scale="std" on rows Z0 divide the rows and the centres by the numbers kmeans divided by,
+    sd = Z0[:, :split].std(axis=0) with 1 in place of a 0, first: kmeans_assign(centres / sd, Z / sd)."""
+    C = _rows(centres, "centres", GMM_MAX_COLUMNS)
+    if len(C) > KMEANS_MAX_CENTRES:
+        raise ValueError("centres must have 1 to %d rows, got %d" % (KMEANS_MAX_CENTRES, len(C)))
+    Z = _rows(Z, "Z", GMM_MAX_COLUMNS)
+    if Z.shape[1] != C.shape[1]:
+        raise ValueError("Z must have the centres' %d columns, got %d" % (C.shape[1], Z.shape[1]))
+    cbar = C.mean(axis=0)
+    torch, c, dev = _device(device_index)
+    book = _Codebook(torch, c, dev, torch.as_tensor(Z - cbar, device=dev), Z.shape[1], len(C))
+    book.assign(C - cbar)
+    return book.labels.cpu().numpy().astype(np.int64)
+
+
+def _kmeans_responsibilities(mix, split):
+    """The one-hot responsibilities of init="kmeans", written on the device: the labels of kmeans_grow on the mixture's
+    own rows, their first `split` columns when given.  LinAlgError naming a final cluster without a row."""
+    book = _Codebook(mix.torch, mix.c, mix.dev, mix.Z, split or mix.D, mix.M)
+    _, count, _, _ = kmeans_grow(book, mix.M, **KMEANS_START)
+    if np.any(count == 0):
+        raise np.linalg.LinAlgError("the k-means start leaves component %d without a row"
+                                    % int(np.flatnonzero(count == 0)[0]))
+    return mix.gamma.zero_().scatter_(1, book.labels.long()[:, None], 1.0)
+
+
 def gmm_fit(Z, components, *, iters=20, tol=1e-5, floor=1e-6, init=None, split=None, device_index=0):
     """Fits a Gaussian mixture with full covariances to the rows of `Z` float64[N, D] (all finite, D <= 128) by EM
     (DESIGN.md §12): `components` = M in [1, 64], N >= 2 M.  E and M steps alternate for at most `iters` rounds and stop
     after an E-step whose mean log-likelihood per row rose by less than `tol`.  `floor` x the variance of each column
     is added to the diagonal of every covariance.  `init` is an int array [N] of labels in [0, M), every label present;
     None sorts the rows along the principal axis of the standardised columns (the first `split` of them, all by default)
-    and cuts them into M equal runs.  Returns dict(weights[M], means[M, D], covs[M, D, D], zbar[D], phi[D],
-    loglik[n_E_steps], n).  Raises numpy.linalg.LinAlgError naming the component when one is starved (its
+    and cuts them into M equal runs; "kmeans" takes the labels of a k-means codebook of M centres on the same columns
+    (kmeans with its defaults; LinAlgError naming a centre that ends without a row).  Returns
+    dict(weights[M], means[M, D], covs[M, D, D], zbar[D], phi[D], loglik[n_E_steps], n).  Raises numpy.linalg.LinAlgError naming the component when one is starved (its
     responsibilities sum to less than 1) or its covariance is not positive definite."""
     Z, M, iters, tol, floor, init, split = check_gmm_arguments(Z, components, iters, tol, floor, init, split)
     N, D = Z.shape
     zbar, phi = gmm_centre(Z, floor)
-    labels = gmm_init_labels(Z[:, :split] if split else Z, M) if init is None else init
     mix = _Mixture(Z, zbar, M, device_index)
-    onehot = np.zeros((N, M))
-    onehot[np.arange(N), labels] = 1.0
-    w, mu, Sigma = gmm_finish_mstep(*mix.mstep(mix.torch.as_tensor(onehot, device=mix.dev)), N, phi)
+    if isinstance(init, str):
+        first = _kmeans_responsibilities(mix, split)
+    else:
+        labels = gmm_init_labels(Z[:, :split] if split else Z, M) if init is None else init
+        onehot = np.zeros((N, M))
+        onehot[np.arange(N), labels] = 1.0
+        first = mix.torch.as_tensor(onehot, device=mix.dev)
+    w, mu, Sigma = gmm_finish_mstep(*mix.mstep(first), N, phi)
     loglik = []
     for _ in range(iters):
         gamma, ll = mix.estep(mu, *gmm_estep_parameters(w, mu, Sigma))
@@ -558,8 +757,8 @@ def conversion_train(X, Y, components=8, *, level=False, iters=20, tol=1e-5, flo
     """Learns the map from rows `X` float64[N, P + 1] to rows `Y` float64[N, Q + 1] (conversion_pairs') as a joint
     mixture of `components` Gaussians over [x | y].  level=False leaves column 0, the level c_0, out of
     both sides: conversion_apply copies it from the source row (a recording level is not a property of the speaker);
-    level=True maps it like any other column.  The default initialisation looks at the x columns only.  Returns a flat
-    dict of arrays that np.savez stores and np.load(allow_pickle=False) returns: gmm_fit's fields, dx, dy, level,
+    level=True maps it like any other column.  The default initialisation and init="kmeans" (gmm_fit) look at the x
+    columns only.  Returns a flat dict of arrays that np.savez stores and np.load(allow_pickle=False) returns: gmm_fit's fields, dx, dy, level,
     A[M, dy, dx], b[M, dy] and the marginal mixture's Wx[M, dx, dx], kx[M].
     With `span` in [1, 8] the rows are dynamic rows [c | delta c] (conversion_pairs(span=)) and the map is a dynamic one
     for conversion_trajectory: the mixture is over [x | delta x | y | delta y], level=False leaves

@@ -12,6 +12,7 @@
 // r of lane l is D[(l >> 4) + 4 r][l & 15].  Every operand comes from LDS, where rows and columns beyond the data are
 // zeros: no kernel reads past a row of its arguments.  No atomics: every output word has one writer.
 #include "eaqhm_common.h"
+#include "eaqhm_gmm_chunks.h"
 
 namespace eaqhm {
 
@@ -21,9 +22,6 @@ typedef double gd4 __attribute__((ext_vector_type(4)));
 constexpr int GMM_DMAX = 128;    // columns of Z at most
 constexpr int GMM_XMAX = 64;     // dx, dy at most
 constexpr int GMM_MMAX = 64;     // components at most
-constexpr int GMM_ROWS = 64;     // rows of a block's tile: four waves, one 16-row MFMA tile each
-constexpr int GMM_CHUNK_MIN = 512;    // rows of an M-step chunk at least
-constexpr int GMM_CHUNKS_MAX = 128;   // chunks at most: N = 10^6, M = 64, D = 128 needs 128 x 64 x 45 tiles = 755 MB
 constexpr i64 GMM_NMAX = (i64)1 << 36;
 constexpr int GMM_TILES_PER_WAVE = 12;   // ceil(45 / 4): D + 1 = 129 columns are 9 tile rows, 45 lower tiles
 
@@ -34,12 +32,7 @@ __host__ __device__ inline int gmm_stride_rowk(int d) { return ((d + 31) & ~31) 
 __host__ __device__ inline int gmm_stride_krow(int dp16) { return (dp16 & 16) ? dp16 : dp16 + 16; }
 __host__ __device__ inline int gmm_pad16(int d) { return (d + 15) & ~15; }
 
-// the M-step's chunking: a function of N only (and through the tile count of (D, M) for the size of `work`)
-__host__ __device__ inline i64 gmm_chunk_rows(i64 N) {
-  const i64 per = (N + GMM_CHUNKS_MAX - 1) / GMM_CHUNKS_MAX;
-  const i64 r = (per + GMM_ROWS - 1) / GMM_ROWS * GMM_ROWS;
-  return r > GMM_CHUNK_MIN ? r : GMM_CHUNK_MIN;
-}
+// (the M-step's chunking, gmm_chunk_rows, is in eaqhm_gmm_chunks.h)
 __host__ __device__ inline int gmm_tiles(int D) {
   const int nt = (D + 1 + 15) / 16;
   return nt * (nt + 1) / 2;

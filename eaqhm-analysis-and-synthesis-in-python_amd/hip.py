@@ -85,6 +85,12 @@ SYMBOLS_CEPWARP = (
     ("eaqhm_model_build_warped", C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _I32, _F64, _I32, _I32, _I32, _P, _F64]),
     ("eaqhm_noise_from_cepstrum_warped", C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _F64]),
 )
+# every symbol include/eaqhm_kmeans.h declares: likewise
+SYMBOLS_KMEANS = (
+    ("eaqhm_kmeans_work_len", _I64, [_I64, _I32, _I32]),
+    ("eaqhm_kmeans_assign", C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _P, _P]),
+    ("eaqhm_kmeans_update", C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -107,7 +113,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP:
+    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -366,6 +372,19 @@ class Context:
     def gv_ascend(self, P, r, n, dy, span, run_start, run_len, n_runs, gv_mean, gv_prec, iters, work, Y, trace=None):
         self._ck(self.lib.eaqhm_gv_ascend(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
                                           _ptr(gv_mean), _ptr(gv_prec), iters, _ptr(work), _ptr(Y), _ptr(trace)))
+
+    # the k-means codebook: Z [N][ldz] rows of which the first D columns count, labels int32 [N],
+    # changed int32 [ceil(N / 64)], count int64 [K]
+    def kmeans_work_len(self, N, D, K):
+        return int(self.lib.eaqhm_kmeans_work_len(N, D, K))
+
+    def kmeans_assign(self, Z, N, ldz, D, C_, g, K, labels, changed):
+        self._ck(self.lib.eaqhm_kmeans_assign(self.h, _ptr(Z), N, ldz, D, _ptr(C_), _ptr(g), K, _ptr(labels),
+                                              _ptr(changed)))
+
+    def kmeans_update(self, Z, N, ldz, D, labels, K, work, count, S1, Q):
+        self._ck(self.lib.eaqhm_kmeans_update(self.h, _ptr(Z), N, ldz, D, _ptr(labels), K, _ptr(work), _ptr(count),
+                                              _ptr(S1), _ptr(Q)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

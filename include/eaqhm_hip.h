@@ -513,6 +513,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_gv.h"
 /* the discrete cepstrum on an all-pass warped axis (additions under ABI 6): declared in eaqhm_cepwarp.h. */
 #include "eaqhm_cepwarp.h"
+/* the k-means codebook that starts the mixture (additions under ABI 6): declared in eaqhm_kmeans.h.    */
+#include "eaqhm_kmeans.h"
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,10 @@ session and to the same iteration in NumPy on the host's band, with the largest 
 --cepstrum-warp times every entry point of the warped cepstrum (include/eaqhm_cepwarp.h) next to its
 sibling on the linear axis, same session, same model, same rows' shapes, at the default order and at order 24 with
 a = cepstrum_warp(fs): the ratio to the sibling with the sibling's max - min beside it.
+--kmeans times the two steps of a Lloyd round of the k-means codebook (eaqhm_kmeans_assign and
+eaqhm_kmeans_update) at N = 10^6 with (D, K) = (36, 8) and (100, 32) next to torch (cdist + argmin, index_add_) and to one
+EM round (eaqhm_gmm_estep + eaqhm_gmm_mstep) at the same sizes, then the whole kmeans call with its rounds, and the mean
+log-likelihood of gmm_fit after 20 rounds from the axis start and from the k-means start on a seeded clustered set.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -239,6 +243,93 @@ def gmm_rows(torch, reps=20, runs=3, sizes=(65536, 1000000), shapes=((18, 18, 8)
             print(json.dumps(rows[-1]), flush=True)
             del Z, gamma, work, X, Y
             torch.cuda.empty_cache()
+    return rows
+
+
+def kmeans_clustered(N, D, K, seed):
+    """Seeded rows float64[N, D] around K centres 4 standard deviations of the noise apart on average, shuffled."""
+    rng = np.random.default_rng(seed)
+    centres = 4.0 * rng.standard_normal((K, D)) / np.sqrt(2.0)
+    return centres[rng.integers(0, K, size=N)] + rng.standard_normal((N, D))
+
+
+def kmeans_rows(torch, reps=20, runs=3, N=1000000, shapes=((36, 8), (100, 32))):
+    """One assignment and one update of the k-means codebook on seeded clustered rows, next to torch on
+    the same device (cdist + argmin; index_add_, one warmed call: a comparison, not a bar) and to one EM round of the mixture
+    (eaqhm_gmm_estep + eaqhm_gmm_mstep, M = K) at the same sizes.  Each time: median of `runs` warmed windows of `reps`
+    launches, and max - min of the windows.  The update is timed on the labels of the assignment (shuffled rows: the
+    running cluster changes at almost every row) and on sorted labels (it never changes inside a chunk).  Then the whole
+    kmeans call from host rows, once warmed, with its Lloyd rounds; and gmm_fit after 20 rounds (tol = 0) from both
+    starts on a clustered set of 20 000 x 16, 8 components."""
+    import eaqhm_amd
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for D, K in shapes:
+        Zh = kmeans_clustered(N, D, K, 1000 + D)
+        Z = torch.as_tensor(Zh - Zh.mean(axis=0), device=dev)
+        C = Z[:: N // K][:K].contiguous()
+        g = (C * C).sum(dim=1)
+        labels = torch.zeros(N, dtype=torch.int32, device=dev)
+        changed = torch.empty(-(-N // 64), dtype=torch.int32, device=dev)
+        work = torch.empty(c.kmeans_work_len(N, D, K), dtype=torch.float64, device=dev)
+        count = torch.empty(K, dtype=torch.int64, device=dev)
+        S1 = torch.empty((K, D), dtype=torch.float64, device=dev)
+        Q = torch.empty((K, D), dtype=torch.float64, device=dev)
+        a = med(lambda: c.kmeans_assign(Z, N, D, D, C, g, K, labels, changed))
+        u = med(lambda: c.kmeans_update(Z, N, D, D, labels, K, work, count, S1, Q))
+        sorted_labels = torch.sort(labels)[0].contiguous()
+        us = med(lambda: c.kmeans_update(Z, N, D, D, sorted_labels, K, work, count, S1, Q))
+        ll = labels.long()
+
+        def t_update():
+            return (torch.bincount(ll, minlength=K), torch.zeros_like(S1).index_add_(0, ll, Z),
+                    torch.zeros_like(Q).index_add_(0, ll, Z * Z))
+
+        ta = med(lambda: torch.cdist(Z, C).argmin(dim=1))
+        tu = (round(timed(torch, t_update, 1), 1), None)    # one warmed call: float64 index_add_ onto K rows takes seconds
+        mu = C.clone()
+        W = torch.eye(D, dtype=torch.float64, device=dev).repeat(K, 1, 1)
+        kk = torch.full((K,), -np.log(K) - 0.5 * D * np.log(2 * np.pi), dtype=torch.float64, device=dev)
+        gamma = torch.empty((N, K), dtype=torch.float64, device=dev)
+        lln = torch.empty(N, dtype=torch.float64, device=dev)
+        gwork = torch.empty(c.gmm_work_len(N, D, K), dtype=torch.float64, device=dev)
+        S0, S2 = torch.empty(K, dtype=torch.float64, device=dev), torch.empty((K, D, D), dtype=torch.float64, device=dev)
+        e = med(lambda: c.gmm_estep(Z, N, D, K, mu, W, kk, gamma, lln))
+        m_ = med(lambda: c.gmm_mstep(Z, gamma, N, D, K, gwork, S0, S1, S2))
+        del gamma, gwork, work, Z
+        torch.cuda.empty_cache()
+        whole = []
+        for _ in range(2):                              # the second call is the warmed one
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = eaqhm_amd.kmeans(Zh, K)
+            whole.append(round((time.perf_counter() - t0) * 1e3, 1))
+        rows.append(dict(N=N, D=D, K=K, assign_ms=a[0], assign_spread_ms=a[1], assign_torch_ms=ta[0],
+                         assign_torch_spread_ms=ta[1], update_ms=u[0], update_spread_ms=u[1], update_sorted_ms=us[0],
+                         update_sorted_spread_ms=us[1], update_torch_ms=tu[0], update_torch_spread_ms=tu[1],
+                         estep_ms=e[0], estep_spread_ms=e[1], mstep_ms=m_[0], mstep_spread_ms=m_[1],
+                         assign_gb_per_s=round(N * D * 8 / (a[0] * 1e-3) / 1e9, 1),
+                         update_gb_per_s=round(N * D * 8 / (u[0] * 1e-3) / 1e9, 1),
+                         kmeans_call_ms=whole, kmeans_rounds=int(out["rounds"]),
+                         kmeans_smallest_cluster=int(out["counts"].min())))
+        print(json.dumps(rows[-1]), flush=True)
+        del Zh
+    Zq = kmeans_clustered(20000, 16, 8, 77)
+    fits = {}
+    for name, init in (("axis", None), ("kmeans", "kmeans")):
+        try:
+            fits[name] = float(eaqhm_amd.gmm_fit(Zq, 8, iters=20, tol=0.0, init=init)["loglik"][-1])
+        except np.linalg.LinAlgError as err:
+            fits[name] = str(err)
+    rows.append(dict(quality_set="kmeans_clustered(20000, 16, 8, seed 77)", rounds=20, mean_loglik=fits))
+    print(json.dumps(rows[-1]), flush=True)
     return rows
 
 
@@ -954,8 +1045,19 @@ def main():
     ap.add_argument("--gv", action="store_true",
                     help="time eaqhm_gv_ascend next to eaqhm_mlpg_solve and the same iteration in NumPy on the host (random "
                          "rows; needs no workload: pass --workloads '')")
+    ap.add_argument("--kmeans", action="store_true",
+                    help="time eaqhm_kmeans_assign and eaqhm_kmeans_update next to torch and to one EM round, the whole "
+                         "kmeans call and the fit from both starts (seeded rows; needs no workload: pass --workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.kmeans:
+        import torch
+        res_kmeans = dict(kmeans=kmeans_rows(torch))
+        if not a.workloads and not a.gmm and not a.mlpg and not a.gv:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump([res_kmeans], f, indent=1)
+            return 0
     if a.gv:
         import torch
         res_gv = dict(gv=gv_rows(torch))
@@ -989,6 +1091,8 @@ def main():
         res.append(res_mlpg)
     if a.gv:
         res.append(res_gv)
+    if a.kmeans:
+        res.append(res_kmeans)
     for r in res:
         print(json.dumps(r))
     if a.out:
