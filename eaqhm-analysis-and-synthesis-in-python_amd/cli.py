@@ -229,10 +229,11 @@ def main(argv=None):
     if a.noise_from is not None and a.noise_cepstrum is None:
         a.noise_cepstrum = 63
     if a.noise_cepstrum is not None:
-        from .model import _cepstrum_order
+        from .cepstrum import _cepstrum_order
         _cepstrum_order(a.noise_cepstrum)
     if a.noise:
-        from .model import _mod_harmonics, _seed
+        from .args import _seed
+        from .noise import _mod_harmonics
         _seed(0 if a.noise_seed is None else a.noise_seed)
         if a.noise_modulation is not None:
             _mod_harmonics(a.noise_modulation, "--noise-modulation")
@@ -312,7 +313,7 @@ def main(argv=None):
     if a.align_band is not None and not (np.isfinite(a.align_band) and a.align_band >= 0):
         ap.error("--align-band must be finite and >= 0")
     if cepstral or vocode:   # 0: the flag without a value, the default order
-        from .model import _cepstrum_lambda, _cepstrum_order
+        from .cepstrum import _cepstrum_lambda, _cepstrum_order
         for order in (a.cepstral_envelope, a.from_parameters):
             if order:
                 _cepstrum_order(order)
@@ -322,7 +323,7 @@ def main(argv=None):
     curves = {}
     wmap = None
     if modify or vocode:   # reject bad scales and curves before the analysis runs
-        from .model import _scale
+        from .args import _scale
         _scale(1.0 if a.time_scale is None else a.time_scale, "--time-scale")
         _scale(1.0 if a.pitch_scale is None else a.pitch_scale, "--pitch-scale")
         _scale(1.0 if a.formant_scale is None else a.formant_scale, "--formant-scale")
@@ -520,7 +521,7 @@ def read_scale_curve(path, name):
 
 def read_warp_curve(path, name):
     """A formant warp file, lines 'Hz_in Hz_out': (f_in, f_out), validated as model.check_formant_warp does."""
-    from .model import _warp_rows
+    from .args import _warp_rows
     try:
         f_in, f_out = _warp_rows(_two_columns(path, name, "Hz in the model, Hz in the output"), 1, "file")
     except ValueError as e:

@@ -42,8 +42,10 @@ import math
 
 import numpy as np
 
-from .model import (CEPSTRUM_MAX_ORDER, SCALE_RANGE, _cepstrum_rows, _integer, _numeric_1d, _path,
-                    check_cepstrum_warp)
+from .align import _path
+from .args import SCALE_RANGE, _integer, _numeric_1d
+from .cepstrum import CEPSTRUM_MAX_ORDER, _cepstrum_rows, check_cepstrum_warp
+from .records import _device
 
 GMM_MAX_COLUMNS = 128      # D = dx + dy at most: nine 16-wide tile rows of [c | 1] in the M-step's registers
 GMM_MAX_SIDE = 64          # dx, dy at most
@@ -526,11 +528,6 @@ def gv_statistics(utterances, *, level=False, rel_std=None):
 
 
 # ---- device work
-def _device(device_index):
-    from . import model
-    return model._device(device_index)
-
-
 class _Mixture:
     """The rows of one fit on the device, centred, and the buffers of its E and M steps."""
 

@@ -266,10 +266,9 @@ class Recorder:
 
 
 def _recorded(monkeypatch, fn):
-    from eaqhm_amd import model
-    import torch
+    from eaqhm_amd import functions
     rec = Recorder()
-    monkeypatch.setattr(model, "_device", lambda device_index: (torch, rec, rec.device))
+    monkeypatch.setattr(functions, "_ctx", lambda device_index=0: rec)
     fn()
     return rec.calls
 
@@ -306,11 +305,11 @@ def test_cep_warp_zero_makes_the_old_calls(monkeypatch):
 
 
 def test_model_parameters_passes_the_axis_on(monkeypatch):
-    from eaqhm_amd import model
+    from eaqhm_amd import cepstrum, model
     det, n = _det(), 6
     calls = []
-    monkeypatch.setattr(model, "model_f0", lambda d, fs: np.full(n, 201.0))
-    monkeypatch.setattr(model, "model_cepstrum", lambda d, fs, order, lam, **kw: calls.append(kw) or np.ones((n, 7)))
+    monkeypatch.setattr(cepstrum, "model_f0", lambda d, fs: np.full(n, 201.0))
+    monkeypatch.setattr(cepstrum, "model_cepstrum", lambda d, fs, order, lam, **kw: calls.append(kw) or np.ones((n, 7)))
     p = model.model_parameters(det, 16000, 6, 1e-3)
     assert calls[-1] == dict(device_index=0) and "cep_warp" not in p
     p = model.model_parameters(det, 16000, 6, 1e-3, cep_warp=0.0)

@@ -243,15 +243,15 @@ def test_cepstrum_phase_arguments(no_device):
 
 
 def test_model_parameters_is_a_composition(monkeypatch):
-    from eaqhm_amd import model
+    from eaqhm_amd import cepstrum, model
     n, K = 6, 3
     det = dict(ti=np.arange(n) * 15, isVoiced=np.ones(n, bool), a0=np.zeros(n), amplitudes=np.full((n, K), 0.1),
                frange=np.tile([200.0, 400.0, 600.0], (n, 1)), pk=np.zeros((n, K)))
     det["amplitudes"][2] = 0.0
     det["isVoiced"][4] = False
     calls = []
-    monkeypatch.setattr(model, "model_f0", lambda d, fs: calls.append(("f0", d is det, fs)) or np.full(n, 201.0))
-    monkeypatch.setattr(model, "model_cepstrum", lambda d, fs, order, lam, device_index=0:
+    monkeypatch.setattr(cepstrum, "model_f0", lambda d, fs: calls.append(("f0", d is det, fs)) or np.full(n, 201.0))
+    monkeypatch.setattr(cepstrum, "model_cepstrum", lambda d, fs, order, lam, device_index=0:
                         calls.append(("ceps", d is det, fs, order, lam, device_index)) or np.ones((n, 7)))
     p = model.model_parameters(det, 16000, 6, 1e-3, device_index=2)
     assert calls == [("f0", True, 16000), ("ceps", True, 16000, 6, 1e-3, 2)]
