@@ -70,6 +70,10 @@ extern "C" int eaqhm_set_option(eaqhm_ctx* ctx, int32_t key, int32_t value) {
     ctx->ls_variant = value;
     return EAQHM_OK;
   }
+  if (key == EAQHM_OPT_A0_RESIDENT && (value == 0 || value == 1)) {
+    ctx->a0_resident = value;
+    return EAQHM_OK;
+  }
   if (key == EAQHM_OPT_DEBUG_KEEP) {
     ctx->dbg_keep = value;
     if (value && ctx->scratch && ctx->scratch_bytes >= 256)

@@ -17,6 +17,7 @@ struct eaqhm_ctx {
   int lds_bytes = 0;
   int clock_khz = 0;
   int ls_variant = 3;  // 2: MFMA Gramian + tile Cholesky through memory (any size), 3: all-on-chip tiles (+2 for big frames)
+  int a0_resident = 1; // 1: adaptation 0 of the tile classes by eaqhm_ls_a0tile_kernel when its LDS fits, 0: by the tile kernel
   int dbg_keep = 0;    // 1: in-kernel phase stamps on, accumulated across launches (diagnostics only)
   int dtw_phases = 0;  // 1: eaqhm_dtw runs the forward pass only, 2: the backtrack only (measurements), 0: both
   void* scratch = nullptr;

@@ -20,6 +20,12 @@
 
 namespace eaqhm {
 
+// frames of the tile classes (eaqhm_ls_tile_kernel and eaqhm_ls_a0tile_kernel): real systems of <= 7 tile rows
+#define A0_NS 7        // tiles per wave of a real system of <= 7 tile rows (order Kc + 1 <= 104) on 4 waves
+#define A0_M 7
+#define TZ_TB 104     // table stride: m = 0 .. 2 n <= 102
+#define TZ_NCH 8      // chunks of the t range (deterministic two-level summation)
+
 // Entries (gi0 + 4 r, gj), r = 0..3 — the four values of one lane of a 16x16 tile — of system `sys` (0 even, 1 odd), order
 // Kc + 1 with the right-hand side as row / column Kc.  Branch-free: every entry is  0.5 (s1 T[i1] + s2 T[i2])  of one
 // table, or one table value (right-hand side), or a constant (padding); the lanes of a tile differ in which, so the case
@@ -86,6 +92,20 @@ __host__ __device__ inline size_t a0_lds_doubles(int M, int PAR, int TB, int NCH
   return head + 3 * (size_t)WP + 2 * (size_t)NP + (size_t)PAR * (TL_TILE + 256 + 64 + 64 + 16 * M + 16 + 16 * M) +
          2 * 16 * (size_t)M + 16 + 2 + 4 * (size_t)Kcmax;
 }
+
+// LDS doubles of a frame of eaqhm_ls_a0tile_kernel (eaqhm_ls_a0tile.hip; M tile rows): the PAR = 2 layout with W2 / PA / PB / win / sig laid behind the
+// partial sums INSIDE the region the panels take over — nothing reads them once the tables exist — so that two
+// workgroups fit the LDS of a CU.  One function for the host's fit test and the kernel's carve-up.
+__host__ __device__ inline size_t a0res_head_doubles(int M, int TB, int NCH, int WP, int NP) {
+  const size_t pre = (size_t)(1 + NCH) * TZ_NQ * TB + 3 * (size_t)WP + 2 * (size_t)NP, tiles = (size_t)4 * M * TL_TILE;
+  return pre > tiles ? pre : tiles;
+}
+__host__ __device__ inline size_t a0res_lds_doubles(int M, int TB, int NCH, int WP, int NP, int Kcmax) {
+  return a0res_head_doubles(M, TB, NCH, WP, NP) + 2 * (size_t)(TL_TILE + 256 + 64 + 64 + 16 * M + 16 + 16 * M) +
+         2 * 16 * (size_t)M + 16 + 2 + 4 * (size_t)Kcmax;
+}
+// what a workgroup may ask for when two are to be resident on a CU of 160 KiB: dynamic LDS + the static cursor word
+#define A0RES_LDS_LIMIT (80 * 1024 - 16)
 
 // One frame.  NS: tiles per wave (>= ceil(M (M+1) / 2 / waves per system)), M: tile rows the LDS is laid out for.
 template <int NS, int M, int PAR>

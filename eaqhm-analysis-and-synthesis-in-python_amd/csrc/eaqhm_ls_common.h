@@ -144,8 +144,11 @@ __device__ inline double window_value(int blackman, int u, int N) {
 #define TZ_NQ 7       // c0, s1, c2, Re r0, Im r0, Re r1, Im r1
 __device__ inline void toeplitz_tables(double* tab, double* part, double* W2, double* PA, double* PB, double* ssq,
                                        const double* win, const double* sig, int n, int wl, double theta, int tid,
-                                       int TB, int NCH_) {
+                                       int TB, int NCH_, int cost_thr = 0) {
   const int mid = wl, nthr = blockDim.x;
+  // the chunk count is part of the summation order: a kernel whose workgroup is not the 512 threads the others use
+  // passes cost_thr = 512 and gets their sums bit for bit
+  const int cthr = cost_thr ? cost_thr : nthr;
   for (int t = tid; t <= wl; t += nthr) {
     const double w = win[mid + t], w2 = w * w, sp = sig[mid + t], sm = sig[mid - t];
     W2[t] = w2;
@@ -170,7 +173,7 @@ __device__ inline void toeplitz_tables(double* tab, double* part, double* W2, do
   {
     int best = 0x7fffffff;
     for (int q = 1; q <= NCH_; ++q) {
-      const int cost = ((nm * q + nthr - 1) / nthr) * ((wl + q - 1) / q + 4);   // (+4: the seeds of a task)
+      const int cost = ((nm * q + cthr - 1) / cthr) * ((wl + q - 1) / q + 4);   // (+4: the seeds of a task)
       if (cost < best) { best = cost; NCH = q; }
     }
   }

@@ -21,7 +21,8 @@
 //          11-12 tile rows: dealt out by the unit tables of eaqhm_ls_twunits.h, UA / UB / TB in tile_frame; 11 tile rows with
 //          the part-filled last basis tile column packed as [x_e | n x_e])
 //   B0     adaptation 0: no basis at all — the Gramian in closed form from Toeplitz tables, then two real systems of
-//          half the order factorised side by side (a0_frame, eaqhm_ls_a0.h)
+//          half the order factorised side by side (a0_frame, eaqhm_ls_a0.h).  A mode-0 launch whose LDS fits twice into
+//          a CU goes to eaqhm_ls_a0tile_kernel instead (eaqhm_ls_a0tile.hip: the same frame, two workgroups per CU)
 //   C      right-looking tile Cholesky with look-ahead, 2 workgroup barriers per tile row: trailing update with the
 //          previous panel (the next diagonal tile first); its owner wave factorises that tile on the matrix cores
 //          (diag_D: 2x2 block pivots, one rank-2 MFMA per plane and step, rows handed round by ds_bpermute) while a
@@ -40,7 +41,8 @@
 #include "eaqhm_ls_twunits.h"
 
 namespace eaqhm {
-
+bool ls_a0tile_fits(const LsArgs& A);                 // eaqhm_ls_a0tile.hip
+int launch_ls_a0tile(eaqhm_ctx* ctx, LsArgs A);
 
 // wave that owns the diagonal tile (jb, jb): see the ownership rules in tile_frame
 #define DIAG_OWNER(jb, nt) ((int)TL_DIAG[nt][jb])
@@ -50,12 +52,7 @@ namespace eaqhm {
 #define TL_NTMAX 13
 #define CI_STRIDE 20    // per-slot info: 16 chunk carries, qmid, 1/(am_mid+eps), rho.re, rho.im
 #define CI_NCH 16
-#define A0_NS 7        // adaptation 0: tiles per wave of a real system of <= 7 tile rows (order Kc + 1 <= 104) on 4 waves
-#define A0_M 7
-
-// (adaptation 0: closed-form Gramian and two real systems — eaqhm_ls_a0.h; table sizes for frames of this kernel)
-#define TZ_TB 104     // table stride: m = 0 .. 2 n <= 102
-#define TZ_NCH 8      // chunks of the t range (deterministic two-level summation)
+// (adaptation 0: closed-form Gramian and two real systems — A0_NS, A0_M, TZ_TB, TZ_NCH and a0_frame in eaqhm_ls_a0.h)
 
 // One frame with NS tiles per wave.  Not inlined: each register budget gets its own register allocation (inlining
 // the five budgets into one kernel body spills several hundred VGPRs).
@@ -960,6 +957,8 @@ int launch_ls_prepass(eaqhm_ctx* ctx, LsArgs A, long long track_t0) {
 // A.scratch / A.scratch_stride / A.zloc / A.ztot / A.cls / A.debug are set by the caller (eaqhm_ls_batch), after launch_ls_prepass.
 // Returns the largest number of tile rows handled (frames with more are left to the caller's fallback).
 int launch_ls_tile(eaqhm_ctx* ctx, LsArgs A, int grid) {
+  // adaptation 0: the kernel with two workgroups per CU when its LDS fits, else the mode-0 branch of the tile kernel
+  if (A.mode == 0 && ctx->a0_resident && ls_a0tile_fits(A)) return launch_ls_a0tile(ctx, A);
   const int Kcmax = A.Kcmax;
   const int ldx_max = 16 * TL_NTMAX + 16;
   const int TS = 32;

@@ -16,6 +16,8 @@ _P = C.c_void_p
 _I32, _I64, _F64 = C.c_int32, C.c_int64, C.c_double
 # EAQHM_ABI_VERSION (csrc/eaqhm_common.h) this binding was written for: argument lists change under unchanged names
 ABI_VERSION = 6
+# keys of eaqhm_set_option (EAQHM_OPT_* of the header)
+OPT_LS_VARIANT, OPT_DEBUG_KEEP, OPT_DTW_PHASES, OPT_A0_RESIDENT = 1, 2, 3, 4
 SYMBOLS = (
     ("eaqhm_ctx_create", C.c_int, [C.POINTER(_P), C.c_int]),
     ("eaqhm_ctx_destroy", C.c_int, [_P]),
@@ -156,9 +158,12 @@ class Context:
             self.close()
             raise HipUnavailable("%s has ABI version %d, this binding needs %d: stale build, rebuild"
                                  % (LIB_PATH, self.abi_version, ABI_VERSION))
-        v = os.environ.get("EAQHM_LS_VARIANT")          # A/B knob for measurements (include/eaqhm_hip.h)
+        v = os.environ.get("EAQHM_LS_VARIANT")          # A/B knobs for measurements (include/eaqhm_hip.h)
         if v:
-            self.set_option(1, int(v))
+            self.set_option(OPT_LS_VARIANT, int(v))
+        v = os.environ.get("EAQHM_A0_RESIDENT")
+        if v:
+            self.set_option(OPT_A0_RESIDENT, int(v))
         self.bind_stream()
 
     def bind_stream(self):

@@ -61,6 +61,12 @@ const char* eaqhm_last_error(eaqhm_ctx* ctx);
 #define EAQHM_OPT_DEBUG_KEEP 2   /* 1: accumulate the in-kernel phase stamps across launches; 2: also time diag_D */
 #define EAQHM_OPT_DTW_PHASES 3   /* measurements: 1 = eaqhm_dtw launches its forward pass only, 2 = its backtrack only
                                     (on a band that holds D and a ptr that is filled), 0 = both (default) */
+/*   EAQHM_OPT_A0_RESIDENT (an addition under ABI 6): 1 = the adaptation-0 frames of <= 13 tile rows are solved by a kernel
+ *                         of their own, two workgroups resident per CU, when the launch's wl_max and Kmax let its LDS
+ *                         fit 80 KiB (default; the records are bitwise those of 0), 0 = by the tile kernel, as a launch
+ *                         that does not fit is.  With EAQHM_OPT_DEBUG_KEEP on, word 15 of eaqhm_debug_read counts the
+ *                         frames that kernel solved. */
+#define EAQHM_OPT_A0_RESIDENT 4
 int eaqhm_set_option(eaqhm_ctx* ctx, int32_t key, int32_t value);
 /* diagnostics: shader-clock cycles per phase of the LS tile kernel summed over frames (thread 0 of each
  * workgroup): {setup, basis build, contraction, factorisation total..., see csrc/eaqhm_ls_tile.hip STAMP} */

@@ -26,3 +26,6 @@ tot = sum(d[k] for k in names)
 for k, n in names.items():
     print("%-40s %16d cycles %5.1f%%" % (n, d[k], 100.0 * d[k] / max(tot, 1)))
 print("workload", wl, "frames", eng.nf, "cycles/frame", tot / (launches * eng.nf))
+# word 15: frames solved by eaqhm_ls_a0tile_kernel (two workgroups per CU: the cycles above then overlap in pairs); 0 when the
+# launch went through the mode-0 branch of the tile kernel (EAQHM_A0_RESIDENT=0, or its LDS did not fit)
+print("frames solved by eaqhm_ls_a0tile_kernel per launch", d[15] / launches)
