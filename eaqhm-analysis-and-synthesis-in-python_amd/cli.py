@@ -53,6 +53,9 @@ relative spread S (0.25 when left out: one utterance has no spread of its own). 
 the global-variance term to the trajectory, which gives the converted coefficients the target's variance
 back; --conversion-no-gv switches it off, --conversion-gv-iters K (30) and --conversion-gv-weight G (1) set the number of
 sweeps and the weight of the term.
+--conversion-em-iters K (with --conversion and a dynamic map; K in 0..100) revises the mixture's component posteriors in
+the light of the trajectory and solves it again, K times, before the global-variance term
+(convert.conversion_trajectory_em); without the flag the conversion is convert.conversion_trajectory.
 --cepstral-warp A|mel|bark (with --cepstral-envelope, --from-parameters, --envelope-from, --timing-from, --conversion-train
 or --conversion) puts every cepstrum of the model on the all-pass warped frequency axis of DESIGN.md §9.8: a number in
 [-0.9, 0.9], or the coefficient model.cepstrum_warp gives for the file's sampling rate.  --conversion-train stores it in
@@ -178,6 +181,9 @@ def parser():
                     help="with --conversion and a map that carries the global variance: sweeps, 0 to 10000 (30)")
     ap.add_argument("--conversion-gv-weight", type=float, default=None, metavar="G",
                     help="with --conversion and a map that carries the global variance: weight of the term, 1e-6 to 1e6 (1)")
+    ap.add_argument("--conversion-em-iters", type=int, default=None, metavar="K",
+                    help="with --conversion and a dynamic map: refine the mixture sequence by K EM iterations, 0 to 100, "
+                         "before the global-variance term (convert.conversion_trajectory_em)")
     ap.add_argument("--conversion", default=None, metavar="MAP.npz",
                     help="also write <name>_modified.wav: amplitudes read off this file's cepstral envelope converted by "
                          "the map of a --conversion-train run; the pitch follows the target's statistics unless a "
@@ -278,6 +284,8 @@ def main(argv=None):
         ap.error("--conversion-no-gv, --conversion-gv-iters and --conversion-gv-weight need --conversion")
     if a.conversion_no_gv and tuned:
         ap.error("--conversion-no-gv leaves the term out: not with --conversion-gv-iters or --conversion-gv-weight")
+    if a.conversion_em_iters is not None and not convert:
+        ap.error("--conversion-em-iters needs --conversion")
     if convert or a.conversion_gv is not None:
         from .convert import GV_MAX_ITERS, GV_REL_STD_MAX, GV_WEIGHT_RANGE
         if a.conversion_gv is not None and not 0 < a.conversion_gv <= GV_REL_STD_MAX:
@@ -305,6 +313,13 @@ def main(argv=None):
             ap.error("--cepstral-lambda %g differs from the map's %g" % (a.cepstral_lambda, cmap[2]))
         if a.cepstral_warp is not None and axis != cmap[0].get("cep_warp", 0.0):
             ap.error("--cepstral-warp %g differs from the map's %g" % (axis, cmap[0].get("cep_warp", 0.0)))
+        if a.conversion_em_iters is not None:
+            from .convert import EM_MAX_ITERS
+            if not 0 <= a.conversion_em_iters <= EM_MAX_ITERS:
+                ap.error("--conversion-em-iters must be in [0, %d]" % EM_MAX_ITERS)
+            if "span" not in cmap[0]:
+                ap.error("%s is a static map (--conversion-span when it was learned): not with --conversion-em-iters"
+                         % a.conversion)
         if (a.conversion_no_gv or tuned) and "gv_mean" not in cmap[0]:
             ap.error("%s carries no global variance (--conversion-gv when it was learned): not with "
                      "--conversion-no-gv, --conversion-gv-iters or --conversion-gv-weight" % a.conversion)
@@ -388,7 +403,10 @@ def main(argv=None):
                     raise ValueError("%s was learned at %d Hz, the input is sampled at %d Hz" % (a.conversion, fs_map, fs))
                 synth_axis = dict(cep_warp=conv["cep_warp"]) if conv.get("cep_warp", 0.0) != 0.0 else {}
                 p = model_parameters(det, fs, c_order, c_lam, **synth_axis)
-                if "span" in conv:
+                if "span" in conv and a.conversion_em_iters is not None:
+                    converted = _convert.conversion_trajectory_em(conv, p["ceps"], em_iters=a.conversion_em_iters,
+                                                                  **gv_options(a))
+                elif "span" in conv:
                     converted = _convert.conversion_trajectory(conv, p["ceps"], **gv_options(a))
                 else:
                     converted = _convert.conversion_apply(conv, p["ceps"])

@@ -14,6 +14,10 @@
     conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace=False, device_index=0)
         -> float64[n, Q + 1]: the most likely trajectory under a dynamic map, with the global-variance term when the map
         or `gv` carries its statistics; with trace=True also the objective float64[gv_iters + 1, dys]
+    conversion_trajectory_em(conv, C, *, em_iters=4, em_tol=0.0, em_trace=False, gv=None, gv_weight=1.0, gv_iters=30,
+                             trace=False, device_index=0)
+        -> the same after `em_iters` EM refinements of the mixture sequence (reached as eaqhm_amd.convert.
+        conversion_trajectory_em); with em_trace=True also the mean log-likelihood float64[iterations + 1]
     global_variance(C, level=False) -> float64[cols]: the variance of each mapped static column over the non-empty rows
     gv_statistics(utterances, *, level=False, rel_std=None) -> dict(gv_mean[dys], gv_prec[dys]) for conversion_train(gv=)
     f0_statistics(f0, voiced) -> (mean, std) of ln f0 over the voiced instants
@@ -21,8 +25,8 @@
     kmeans(Z, k, *, iters=20, split_iters=2, split=None, scale=None, device_index=0)
         -> dict(labels int64[N], centres[k, D'], counts int64[k], sse[k], rounds): a codebook grown by splitting (LBG)
     kmeans_assign(centres, Z, *, device_index=0) -> int64[N]: the nearest centre of each row
-    check_gmm_arguments, check_conversion_arguments, check_conversion, check_gv_arguments, check_kmeans_arguments:
-        validation, no device work
+    check_gmm_arguments, check_conversion_arguments, check_conversion, check_gv_arguments, check_kmeans_arguments,
+    check_em_arguments: validation, no device work
 
 The definition is DESIGN.md §12: EM with full covariances on centred rows (Dempster, Laird & Rubin 1977), the
 regression of Stylianou, Cappe & Moulines (1998) in Kain & Macon's joint-density form.  Everything that scales with the
@@ -37,6 +41,8 @@ sweeps up the likelihood joined with a Gaussian prior on each column's variance 
 DESIGN.md §12.3 adds the vector-quantisation codebook of Linde, Buzo & Gray (1980): centres grown by splitting, each
 size settled by Lloyd rounds (eaqhm_kmeans_assign, eaqhm_kmeans_update); init="kmeans" starts the mixture from its
 labels, the split decisions run on the host from K x D sums.
+DESIGN.md §12.4 adds the 2007 paper's EM refinement of the mixture sequence: the component posteriors are revised in the
+light of the trajectory they produce (eaqhm_mlpg_estep) and the trajectory is solved again, a few times over.
 """
 import math
 
@@ -60,6 +66,7 @@ GV_CHUNKS_MAX = 512        # chunks at most
 GV_WEIGHT_RANGE = (1e-6, 1e6)
 GV_MAX_ITERS = 10000
 GV_REL_STD_MAX = 10.0
+EM_MAX_ITERS = 100         # refinements of the mixture sequence at most
 KMEANS_MAX_CENTRES = 64
 KMEANS_MAX_ITERS = 1000
 KMEANS_MAX_SPLIT_ITERS = 100
@@ -343,6 +350,22 @@ def check_gv_arguments(conv, gv=None, gv_weight=1.0, gv_iters=30, trace=False):
     if trace and stats is None:
         raise ValueError("trace=True needs the global-variance term: a map with gv_mean and gv_prec, or gv=")
     return stats, gv_weight, gv_iters, bool(trace)
+
+
+def check_em_arguments(em_iters=4, em_tol=0.0, em_trace=False):
+    """Validates the refinement arguments of conversion_trajectory_em (no device work): returns (em_iters, em_tol,
+    em_trace), em_iters an int in [0, 100], em_tol a finite float >= 0, em_trace a bool."""
+    em_iters = _integer(em_iters, "em_iters")
+    if not 0 <= em_iters <= EM_MAX_ITERS:
+        raise ValueError("em_iters must be in [0, %d], got %d" % (EM_MAX_ITERS, em_iters))
+    if isinstance(em_tol, (bool, np.bool_)):
+        raise ValueError("em_tol must be a number")
+    em_tol = _real(em_tol, "em_tol", 0.0, np.inf)
+    if not np.isfinite(em_tol):
+        raise ValueError("em_tol must be finite")
+    if not isinstance(em_trace, (bool, np.bool_)):
+        raise ValueError("em_trace must be True or False")
+    return em_iters, em_tol, bool(em_trace)
 
 
 def _has(conv, name):
@@ -836,6 +859,43 @@ def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace
     if "span" not in v:
         raise ValueError("this conversion is a static map (no span): use conversion_apply")
     stats, gv_weight, gv_iters, trace = check_gv_arguments(v, gv, gv_weight, gv_iters, trace)
+    out, objective, _ = _trajectory(v, C, stats, gv_weight, gv_iters, trace, device_index)
+    return (out, objective) if trace else out
+
+
+def conversion_trajectory_em(conv, C, *, em_iters=4, em_tol=0.0, em_trace=False, gv=None, gv_weight=1.0, gv_iters=30,
+                             trace=False, device_index=0):
+    """conversion_trajectory followed by the EM refinement of the mixture sequence (Toda, Black & Tokuda
+    2007): conversion_trajectory's estimate y^(0) takes the component posteriors from the source rows alone, pi_tm =
+    p(m | X_t).  Under the model the map implies, p(Y_t | X_t) = sum_m pi_tm N(Y_t; b_m + A_m X_t, diag(1 / py_m)) with
+    Y_t(y) = [y_t | (W y)_t], each of `em_iters` iterations (0 to 100) revises the posteriors in the light of the
+    trajectory, gamma_tm proportional to pi_tm N(Y_t(y^(i)); ..) (eaqhm_mlpg_estep), and solves conversion_trajectory's
+    systems again with P and r formed from them: the exact maximiser of EM's auxiliary function, so the log-likelihood
+    sum_t ln p(Y_t(y) | X_t) does not fall.  em_iters=0 is conversion_trajectory's result bit for bit.  The default of 4 is
+    a stated choice, not a tuned one: on the cases of DESIGN.md §12.4 the gain falls by about a factor of ten per
+    iteration.  With em_tol=0 all iterations run and nothing is read back between them; with em_tol > 0 the mean of the
+    rows' log-likelihoods is formed on the host after every E-step, and the loop stops, keeping the trajectory that E-step
+    scored, once the mean rose by less than em_tol over the previous iteration's.  The global-variance term (gv,
+    gv_weight, gv_iters, trace: conversion_trajectory's) then starts from the last P, r and y; the posteriors stay fixed
+    during the ascent.  Empty rows, level=False and the layout of `C` are conversion_trajectory's.  em_trace=True also
+    returns float64[k + 1], the mean log-likelihood of y^(0) .. y^(k), k the iterations done (one more E-step at the end;
+    a single 0 without a non-empty row).  Returns rows, then the objective if trace, then the log-likelihoods if
+    em_trace.  A static map is a ValueError naming conversion_apply."""
+    v = check_conversion(conv)
+    if "span" not in v:
+        raise ValueError("this conversion is a static map (no span): use conversion_apply")
+    stats, gv_weight, gv_iters, trace = check_gv_arguments(v, gv, gv_weight, gv_iters, trace)
+    em_iters, em_tol, em_trace = check_em_arguments(em_iters, em_tol, em_trace)
+    out, objective, loglik = _trajectory(v, C, stats, gv_weight, gv_iters, trace, device_index,
+                                         dict(iters=em_iters, tol=em_tol, trace=em_trace))
+    result = (out,) + ((objective,) if trace else ()) + ((loglik,) if em_trace else ())
+    return result if len(result) > 1 else out
+
+
+def _trajectory(v, C, stats, gv_weight, gv_iters, trace, device_index, em=None):
+    """What conversion_trajectory and conversion_trajectory_em share, from a validated dynamic map `v` and validated
+    arguments: (rows, the ascent's objective or None, the refinement's mean log-likelihoods or None).  `em` is None or
+    dict(iters, tol, trace); with None or iters = 0 the device work is conversion_trajectory's, launch for launch."""
     skip = 0 if v["level"] else 1
     span, dx, dy, M = v["span"], v["dx"], v["dy"], len(v["weights"])
     dxs, dys = dx // 2, dy // 2
@@ -847,7 +907,7 @@ def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace
     out[~full, 0] = -np.inf
     n = int(np.count_nonzero(full))
     if n == 0:
-        return (out, np.zeros((gv_iters + 1, dys))) if trace else out
+        return out, np.zeros((gv_iters + 1, dys)) if trace else None, np.zeros(1) if em and em["trace"] else None
     D = dynamic_rows(C, span, device_index=device_index)
     mu_c = v["means"] - v["zbar"]
     mix = _Mixture(_dynamic_columns(D[full], C.shape[1], skip), v["zbar"][:dx], M, device_index)
@@ -855,9 +915,11 @@ def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace
     t, dev = mix.torch, mix.dev
     py = v["py"]
     r = t.empty((n, dy), dtype=t.float64, device=dev)
-    mix.c.gmm_regress(mix.Z, gamma, t.as_tensor(np.ascontiguousarray(py[:, :, None] * v["A"]), device=dev),
-                      t.as_tensor(np.ascontiguousarray(py * (v["b"] + v["zbar"][dx:])), device=dev), n, dx, dy, M, r)
-    P = gamma @ t.as_tensor(py, device=dev)
+    pyA = t.as_tensor(np.ascontiguousarray(py[:, :, None] * v["A"]), device=dev)
+    pyb = t.as_tensor(np.ascontiguousarray(py * (v["b"] + v["zbar"][dx:])), device=dev)
+    mix.c.gmm_regress(mix.Z, gamma, pyA, pyb, n, dx, dy, M, r)
+    py_d = t.as_tensor(py, device=dev)
+    P = gamma @ py_d
     _, length = delta_runs(full)                       # the runs on the compacted rows: back to back
     start = np.concatenate(([0], np.cumsum(length)[:-1])).astype(np.int64)
     words = mix.c.mlpg_work_len(n, dys, span)
@@ -865,7 +927,35 @@ def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace
         raise RuntimeError("libeaqhm_hip.so and the host disagree on the size of the trajectory solve's work buffer")
     Y = t.empty((n, dys), dtype=t.float64, device=dev)
     P, start_d, length_d = P.contiguous(), t.as_tensor(start, device=dev), t.as_tensor(length, device=dev)
-    mix.c.mlpg_solve(P, r, n, dys, span, start_d, length_d, len(start), t.empty(words, dtype=t.float64, device=dev), Y)
+    work = t.empty(words, dtype=t.float64, device=dev)
+    mix.c.mlpg_solve(P, r, n, dys, span, start_d, length_d, len(start), work, Y)
+    loglik = None
+    if em and (em["iters"] or em["trace"]):            # X, pi = gamma, the scaled parameters, the runs and work stay put
+        kc = 0.5 * np.log(py).sum(axis=1) - dys * math.log(2.0 * math.pi)
+        A_d, bq_d, kc_d = (t.as_tensor(np.ascontiguousarray(a), device=dev) for a in (v["A"], v["b"] + v["zbar"][dx:], kc))
+        refined = t.empty((n, M), dtype=t.float64, device=dev)
+        ll = t.empty(n, dtype=t.float64, device=dev)
+        score = em["trace"] or em["tol"] > 0           # the only read-back of the loop: n doubles per E-step
+        means = []
+
+        def estep():
+            mix.c.mlpg_estep(mix.Z, gamma, A_d, bq_d, py_d, kc_d, Y, n, dx, dys, M, span, start_d, length_d, len(start),
+                             refined, ll)
+            if score:
+                means.append(math.fsum(ll.cpu().numpy()) / n)
+        stopped = False
+        for _ in range(em["iters"]):
+            estep()
+            if em["tol"] > 0 and len(means) > 1 and means[-1] - means[-2] < em["tol"]:
+                stopped = True                         # Y is the trajectory this E-step scored; P and r are the ones behind it
+                break
+            P = (refined @ py_d).contiguous()
+            mix.c.gmm_regress(mix.Z, refined, pyA, pyb, n, dx, dy, M, r)
+            mix.c.mlpg_solve(P, r, n, dys, span, start_d, length_d, len(start), work, Y)
+        if em["trace"]:
+            if not stopped:
+                estep()                                # the last trajectory's score; P and r do not follow it
+            loglik = np.array(means)
     objective = None
     if stats is not None:                              # P, r, the runs and y_ML stay where they are
         words = mix.c.gv_work_len(n, dys, span)
@@ -879,7 +969,7 @@ def conversion_trajectory(conv, C, *, gv=None, gv_weight=1.0, gv_iters=30, trace
     out[full, skip:] = Y.cpu().numpy()
     if skip:
         out[full, 0] = C[full, 0]
-    return (out, objective.cpu().numpy()) if trace else out
+    return out, objective.cpu().numpy() if trace else None, loglik
 
 
 # ---- pitch (host only)

@@ -8,16 +8,15 @@
 //   eaqhm_gmm_msum_kernel     adds the chunks in index order, mirrors S2, splits off S1 and S0
 //   eaqhm_gmm_regress_kernel  64 rows per block: X A_m^T + b_m on the matrix pipe, weighted by gamma and summed over m
 //
-// The MFMA's lane maps (tools/mfma_f64_probe.hip): lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15]; result register
-// r of lane l is D[(l >> 4) + 4 r][l & 15].  Every operand comes from LDS, where rows and columns beyond the data are
+// The MFMA's lane maps are in eaqhm_gmm_mfma.h, with the tile, the stride rules and the 16-lane sum that the conditional
+// E-step (eaqhm_mlpg_em.hip) shares.  Every operand comes from LDS, where rows and columns beyond the data are
 // zeros: no kernel reads past a row of its arguments.  No atomics: every output word has one writer.
 #include "eaqhm_common.h"
-#include "eaqhm_gmm_chunks.h"
+#include "eaqhm_gmm_mfma.h"
 
 namespace eaqhm {
 
 typedef long long i64;
-typedef double gd4 __attribute__((ext_vector_type(4)));
 
 constexpr int GMM_DMAX = 128;    // columns of Z at most
 constexpr int GMM_XMAX = 64;     // dx, dy at most
@@ -25,28 +24,10 @@ constexpr int GMM_MMAX = 64;     // components at most
 constexpr i64 GMM_NMAX = (i64)1 << 36;
 constexpr int GMM_TILES_PER_WAVE = 12;   // ceil(45 / 4): D + 1 = 129 columns are 9 tile rows, 45 lower tiles
 
-// LDS row strides in doubles.  "rowk": the 16 lanes of a quarter wave read 16 rows at the same k, the quarters k..k+3:
-// a stride = 2 (mod 32) spreads a half wave (the unit of a 64-bit LDS read) over all 64 banks.  "krow": the 16 lanes
-// read 16 consecutive doubles of one row, the quarters four consecutive rows: a stride = 16 (mod 32) does the same.
-__host__ __device__ inline int gmm_stride_rowk(int d) { return ((d + 31) & ~31) + 2; }
-__host__ __device__ inline int gmm_stride_krow(int dp16) { return (dp16 & 16) ? dp16 : dp16 + 16; }
-__host__ __device__ inline int gmm_pad16(int d) { return (d + 15) & ~15; }
-
 // (the M-step's chunking, gmm_chunk_rows, is in eaqhm_gmm_chunks.h)
 __host__ __device__ inline int gmm_tiles(int D) {
   const int nt = (D + 1 + 15) / 16;
   return nt * (nt + 1) / 2;
-}
-
-__device__ inline gd4 gmm_mfma(double a, double b, gd4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// sum over the 16 lanes that share lane >> 4
-__device__ inline double gmm_sum16(double x) {
-  x += __shfl_xor(x, 1);
-  x += __shfl_xor(x, 2);
-  x += __shfl_xor(x, 4);
-  x += __shfl_xor(x, 8);
-  return x;
 }
 
 // ------------------------------------------------------------------------------------------------

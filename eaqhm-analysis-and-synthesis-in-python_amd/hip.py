@@ -93,6 +93,10 @@ SYMBOLS_KMEANS = (
     ("eaqhm_kmeans_assign", C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _P, _P]),
     ("eaqhm_kmeans_update", C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
 )
+# every symbol include/eaqhm_mlpg_em.h declares: likewise
+SYMBOLS_MLPG_EM = (
+    ("eaqhm_mlpg_estep", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -115,7 +119,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS:
+    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -377,6 +381,13 @@ class Context:
     def gv_ascend(self, P, r, n, dy, span, run_start, run_len, n_runs, gv_mean, gv_prec, iters, work, Y, trace=None):
         self._ck(self.lib.eaqhm_gv_ascend(self.h, _ptr(P), _ptr(r), n, dy, span, _ptr(run_start), _ptr(run_len), n_runs,
                                           _ptr(gv_mean), _ptr(gv_prec), iters, _ptr(work), _ptr(Y), _ptr(trace)))
+
+    # the conditional E-step of the trajectory refinement: dy counts the static target columns, A
+    # [M][2 dy][dx], bq and py [M][2 dy], Y [n][dy]; rows outside every run are not written
+    def mlpg_estep(self, X, prior, A, bq, py, kc, Y, n, dx, dy, M, span, run_start, run_len, n_runs, gamma_out, ll_out):
+        self._ck(self.lib.eaqhm_mlpg_estep(self.h, _ptr(X), _ptr(prior), _ptr(A), _ptr(bq), _ptr(py), _ptr(kc), _ptr(Y), n,
+                                           dx, dy, M, span, _ptr(run_start), _ptr(run_len), n_runs, _ptr(gamma_out),
+                                           _ptr(ll_out)))
 
     # the k-means codebook: Z [N][ldz] rows of which the first D columns count, labels int32 [N],
     # changed int32 [ceil(N / 64)], count int64 [K]

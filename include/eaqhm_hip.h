@@ -521,6 +521,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_cepwarp.h"
 /* the k-means codebook that starts the mixture (additions under ABI 6): declared in eaqhm_kmeans.h.    */
 #include "eaqhm_kmeans.h"
+/* the conditional E-step of the trajectory refinement (additions under ABI 6): declared in eaqhm_mlpg_em.h. */
+#include "eaqhm_mlpg_em.h"
 
 #ifdef __cplusplus
 }

@@ -405,6 +405,67 @@ def mlpg_rows(torch, n=60000, dys=24, span=2, reps=5, runs=3):
     return rows
 
 
+def mlpg_em_rows(torch, n=60000, dxs=24, dys=24, span=2, components=(8, 32), reps=20, runs=3):
+    """eaqhm_mlpg_estep on n rows of 2 dxs source and dys static target columns, all rows in one run and
+    cut into 200 equal runs, for each number of components.  Beside it, on the same rows in the same session, its two
+    siblings eaqhm_gmm_estep (the marginal E-step on the 2 dxs source columns) and eaqhm_gmm_regress (2 dys columns), and
+    one whole refinement iteration: the E-step, P = gamma @ py, the regression and eaqhm_mlpg_solve.  Each time: median of
+    `runs` warmed windows of `reps` launches, and max - min of the windows.  The siblings are the comparison, not a bar."""
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+    dx, dy = 2 * dxs, 2 * dys
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for M in components:
+        g = torch.Generator(device=dev).manual_seed(n + dx + dys + M)
+        rnd = lambda *shape: torch.randn(*shape, dtype=torch.float64, device=dev, generator=g)   # noqa: E731
+        X, Y = rnd(n, dx), rnd(n, dys)
+        prior = torch.softmax(rnd(n, M), dim=1)
+        A, bq = rnd(M, dy, dx) * (0.5 / np.sqrt(dx)), 0.5 * rnd(M, dy)
+        py = torch.exp(0.5 * rnd(M, dy))
+        kc = 0.5 * torch.log(py).sum(dim=1) - dys * np.log(2 * np.pi)
+        pyA, pyb = (py[:, :, None] * A).contiguous(), (py * bq).contiguous()
+        mu = rnd(M, dx)
+        W = torch.tril(0.1 * rnd(M, dx, dx), -1) + torch.eye(dx, dtype=torch.float64, device=dev)
+        kx = torch.full((M,), -np.log(M) - 0.5 * dx * np.log(2 * np.pi), dtype=torch.float64, device=dev)
+        gamma = torch.empty((n, M), dtype=torch.float64, device=dev)
+        g0 = torch.empty((n, M), dtype=torch.float64, device=dev)
+        ll = torch.empty(n, dtype=torch.float64, device=dev)
+        r = torch.empty((n, dy), dtype=torch.float64, device=dev)
+        work = torch.empty(c.mlpg_work_len(n, dys, span), dtype=torch.float64, device=dev)
+        marginal = med(lambda: c.gmm_estep(X, n, dx, M, mu, W, kx, g0, ll))
+        for n_runs in (1, 200):
+            T = n // n_runs
+            start = torch.arange(n_runs, dtype=torch.int64, device=dev) * T
+            length = torch.full((n_runs,), T, dtype=torch.int64, device=dev)
+
+            def estep():
+                c.mlpg_estep(X, prior, A, bq, py, kc, Y, n, dx, dys, M, span, start, length, n_runs, gamma, ll)
+
+            def iteration():
+                estep()
+                P = (gamma @ py).contiguous()
+                c.gmm_regress(X, gamma, pyA, pyb, n, dx, dy, M, r)
+                c.mlpg_solve(P, r, n, dys, span, start, length, n_runs, work, Y)
+            e = med(estep)
+            reg = med(lambda: c.gmm_regress(X, gamma, pyA, pyb, n, dx, dy, M, r))
+            Y0 = Y.clone()
+            it = med(iteration)
+            Y.copy_(Y0)
+            flops = 2.0 * n * M * dx * dy
+            rows.append(dict(n=n, dx=dx, dys=dys, span=span, M=M, n_runs=n_runs, estep_ms=e[0], estep_spread_ms=e[1],
+                             estep_peak_fraction=round(flops / (e[0] * 1e-3) / FP64_MATRIX_PEAK, 4),
+                             gmm_estep_ms=marginal[0], gmm_estep_spread_ms=marginal[1], gmm_regress_ms=reg[0],
+                             gmm_regress_spread_ms=reg[1], iteration_ms=it[0], iteration_spread_ms=it[1]))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def host_gv(bands, n, span, mean, prec, iters, y):
     """The ascent of DESIGN.md §12.2 in NumPy on the host's bands [(start, ab [2 span + 1, T, dy], q [T, dy])], every
     column at once; y float64[n, dy] is y_ML, every row in a run."""
@@ -1048,12 +1109,15 @@ def main():
     ap.add_argument("--kmeans", action="store_true",
                     help="time eaqhm_kmeans_assign and eaqhm_kmeans_update next to torch and to one EM round, the whole "
                          "kmeans call and the fit from both starts (seeded rows; needs no workload: pass --workloads '')")
+    ap.add_argument("--mlpg-em", action="store_true",
+                    help="time eaqhm_mlpg_estep next to eaqhm_gmm_estep and eaqhm_gmm_regress, and one refinement iteration "
+                         "(random rows; needs no workload: pass --workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.kmeans:
         import torch
         res_kmeans = dict(kmeans=kmeans_rows(torch))
-        if not a.workloads and not a.gmm and not a.mlpg and not a.gv:
+        if not a.workloads and not a.gmm and not a.mlpg and not a.gv and not a.mlpg_em:
             if a.out:
                 with open(a.out, "w") as f:
                     json.dump([res_kmeans], f, indent=1)
@@ -1061,7 +1125,7 @@ def main():
     if a.gv:
         import torch
         res_gv = dict(gv=gv_rows(torch))
-        if not a.workloads and not a.gmm and not a.mlpg:
+        if not a.workloads and not a.gmm and not a.mlpg and not a.mlpg_em:
             if a.out:
                 with open(a.out, "w") as f:
                     json.dump([res_gv], f, indent=1)
@@ -1069,7 +1133,7 @@ def main():
     if a.mlpg:
         import torch
         res_mlpg = dict(mlpg=mlpg_rows(torch))
-        if not a.workloads and not a.gmm:
+        if not a.workloads and not a.gmm and not a.mlpg_em:
             if a.out:
                 with open(a.out, "w") as f:
                     json.dump([res_mlpg], f, indent=1)
@@ -1077,10 +1141,19 @@ def main():
     if a.gmm:
         import torch
         res_gmm = dict(gmm=gmm_rows(torch))
-        if not a.workloads:
+        if not a.workloads and not a.mlpg_em:
             if a.out:
                 with open(a.out, "w") as f:
                     json.dump([res_gmm], f, indent=1)
+            return 0
+    if a.mlpg_em:
+        import torch
+        res_em = dict(mlpg_em=mlpg_em_rows(torch))
+        if not a.workloads:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(([res_gmm] if a.gmm else []) + ([res_mlpg] if a.mlpg else []) + ([res_gv] if a.gv else [])
+                              + ([res_kmeans] if a.kmeans else []) + [res_em], f, indent=1)
             return 0
     res = [probe(w, a.reps, a.contours, a.formant, a.noise, a.shape, a.noise_formant,
                  a.noise_modulation, a.formant_warp, a.cepstrum, a.align, a.build, a.noise_cepstrum, a.cepstrum_warp)
@@ -1093,6 +1166,8 @@ def main():
         res.append(res_gv)
     if a.kmeans:
         res.append(res_kmeans)
+    if a.mlpg_em:
+        res.append(res_em)
     for r in res:
         print(json.dumps(r))
     if a.out:
