@@ -56,6 +56,10 @@ sweeps and the weight of the term.
 --conversion-em-iters K (with --conversion and a dynamic map; K in 0..100) revises the mixture's component posteriors in
 the light of the trajectory and solves it again, K times, before the global-variance term
 (convert.conversion_trajectory_em); without the flag the conversion is convert.conversion_trajectory.
+--conversion-nonparallel [R] (with --conversion-train; R in 1..50, default 8) is for a TARGET.wav that is NOT the same
+sentence: both cepstra are fitted as above, nothing is aligned, and the map is learned by up to R rounds of nearest-row
+pairing and training (nonparallel.conversion_train_nonparallel, INCA).  With --conversion-span (and
+--conversion-gv) the dynamic map is then trained from the last pairs.  MAP.npz has the same fields.
 --cepstral-warp A|mel|bark (with --cepstral-envelope, --from-parameters, --envelope-from, --timing-from, --conversion-train
 or --conversion) puts every cepstrum of the model on the all-pass warped frequency axis of DESIGN.md §9.8: a number in
 [-0.9, 0.9], or the coefficient model.cepstrum_warp gives for the file's sampling rate.  --conversion-train stores it in
@@ -171,6 +175,9 @@ def parser():
     ap.add_argument("--conversion-init", choices=("axis", "kmeans"), default=None,
                     help="with --conversion-train: where EM starts, equal runs along the principal axis (axis, the "
                          "default) or a k-means codebook (kmeans)")
+    ap.add_argument("--conversion-nonparallel", type=int, nargs="?", const=8, default=None, metavar="R",
+                    help="with --conversion-train: TARGET.wav is other speech, not the same sentence; no alignment, up to "
+                         "R rounds of nearest-row pairing and training, 1 to 50 (8)")
     ap.add_argument("--conversion-gv", type=float, nargs="?", const=0.25, default=None, metavar="S",
                     help="with --conversion-train and --conversion-span: store the target's global variance in the map, "
                          "with the relative spread S, 0 < S <= 10 (0.25); S is optional, so the flag must not stand directly "
@@ -275,6 +282,11 @@ def main(argv=None):
         ap.error("--conversion-span needs --conversion-train")
     if a.conversion_init is not None and not train:
         ap.error("--conversion-init needs --conversion-train")
+    if a.conversion_nonparallel is not None:
+        if not train:
+            ap.error("--conversion-nonparallel needs --conversion-train")
+        if not 1 <= a.conversion_nonparallel <= 50:
+            ap.error("--conversion-nonparallel must be in [1, 50]")
     if train and convert:
         ap.error("--conversion applies a map, --conversion-train learns one: not together")
     if a.conversion_gv is not None and not (train and a.conversion_span is not None):
@@ -366,7 +378,9 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
-        if train:
+        if train and a.conversion_nonparallel is not None:
+            train_conversion_nonparallel(a, gender, analysis_options, fs, det, **on_axis)
+        elif train:
             train_conversion(a, gender, analysis_options, fs, det, **on_axis)
         if modify or a.noise or vocode:
             from .model import eaQHMNoiseAnalysis, eaQHMNoiseModulation, eaQHMSynthesis, scale_contour
@@ -499,6 +513,37 @@ def train_conversion(a, gender, analysis_options, fs, det, **on_axis):
              **conv)
     print("wrote %s: %d pairs, %d components, mean log-likelihood %g"
           % (a.conversion_save, len(X), len(conv["weights"]), conv["loglik"][-1]))
+
+
+def train_conversion_nonparallel(a, gender, analysis_options, fs, det, **on_axis):
+    """--conversion-train with --conversion-nonparallel: analyses the target, fits both cepstra, learns the map without an
+    alignment (nonparallel.conversion_train_nonparallel) and saves train_conversion's fields.  With --conversion-span the
+    dynamic map is trained from the pairs of the returned map."""
+    from . import convert, nonparallel
+    from .model import model_cepstrum, model_parameters
+    order, lam = a.cepstral_envelope or None, 5e-4 if a.cepstral_lambda is None else a.cepstral_lambda
+    p = model_parameters(det, fs, order, lam, **on_axis)
+    fs_t, _ = wavfile.read(a.conversion_train)
+    if fs_t != fs:
+        raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (a.conversion_train, fs_t, fs))
+    _, _, det_t, _ = eaQHMAnalysisAndSynthesis(a.conversion_train, gender, **analysis_options)
+    C_t = model_cepstrum(det_t, fs, order, lam, **on_axis)
+    M = 8 if a.conversion_components is None else a.conversion_components
+    conv, info = nonparallel.conversion_train_nonparallel(p["ceps"], C_t, M, rounds=a.conversion_nonparallel,
+                                                          **conversion_init(a))
+    print("paired %s without an alignment: %d pairs after %d rounds, mean squared distance %g -> %g"
+          % (a.conversion_train, len(info["ix"]), info["rounds"], info["trace"][0], info["trace"][info["best"]]))
+    if a.conversion_span is not None:
+        gv = None if a.conversion_gv is None else convert.gv_statistics([C_t], rel_std=a.conversion_gv)
+        X, Y = (convert.dynamic_rows(C, a.conversion_span)[i] for C, i in ((p["ceps"], info["ix"]), (C_t, info["iy"])))
+        conv = convert.conversion_train(X, Y, M, span=a.conversion_span, gv=gv, **conversion_init(a))
+    p_t = model_parameters(det_t, fs, order, lam, **on_axis)
+    stats = [convert.f0_statistics(q["f0"], q["voiced"] & (q["f0"] > 0)) for q in (p, p_t)]
+    np.savez(a.conversion_save, order=np.int64(p["ceps"].shape[1] - 1), lam=np.float64(lam), fs=np.int64(fs),
+             src_f0=np.array(stats[0]), tgt_f0=np.array(stats[1]), **{k: np.float64(v) for k, v in on_axis.items()},
+             **conv)
+    print("wrote %s: %d pairs, %d components, mean log-likelihood %g"
+          % (a.conversion_save, len(info["ix"]), len(conv["weights"]), conv["loglik"][-1]))
 
 
 def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, noise_fc=None, **on_axis):

@@ -97,6 +97,12 @@ SYMBOLS_KMEANS = (
 SYMBOLS_MLPG_EM = (
     ("eaqhm_mlpg_estep", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I64, _P, _P]),
 )
+# every symbol include/eaqhm_nn.h declares: likewise
+SYMBOLS_NN = (
+    ("eaqhm_nn_splits", _I32, [_I64, _I64]),
+    ("eaqhm_nn_work_len", _I64, [_I64, _I64, _I32]),
+    ("eaqhm_nn_rows", C.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _I32, _P, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -119,7 +125,8 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, res, args in SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM:
+    for name, res, args in (SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM
+                            + SYMBOLS_NN):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -401,6 +408,18 @@ class Context:
     def kmeans_update(self, Z, N, ldz, D, labels, K, work, count, S1, Q):
         self._ck(self.lib.eaqhm_kmeans_update(self.h, _ptr(Z), N, ldz, D, _ptr(labels), K, _ptr(work), _ptr(count),
                                               _ptr(S1), _ptr(Q)))
+
+    # nearest rows: A [nA][lda], B [nB][ldb] rows of which the first D columns count, work float64
+    # [nn_work_len], index int64 [nA], dist2 float64 [nA]
+    def nn_splits(self, nA, nB):
+        return int(self.lib.eaqhm_nn_splits(nA, nB))
+
+    def nn_work_len(self, nA, nB, D):
+        return int(self.lib.eaqhm_nn_work_len(nA, nB, D))
+
+    def nn_rows(self, A, nA, lda, B, nB, ldb, D, work, index, dist2):
+        self._ck(self.lib.eaqhm_nn_rows(self.h, _ptr(A), nA, lda, _ptr(B), nB, ldb, D, _ptr(work), _ptr(index),
+                                        _ptr(dist2)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

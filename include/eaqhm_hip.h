@@ -523,6 +523,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_kmeans.h"
 /* the conditional E-step of the trajectory refinement (additions under ABI 6): declared in eaqhm_mlpg_em.h. */
 #include "eaqhm_mlpg_em.h"
+/* nearest rows, the search of the non-parallel training (additions under ABI 6): declared in eaqhm_nn.h. */
+#include "eaqhm_nn.h"
 
 #ifdef __cplusplus
 }

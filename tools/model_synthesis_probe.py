@@ -45,6 +45,9 @@ a = cepstrum_warp(fs): the ratio to the sibling with the sibling's max - min bes
 eaqhm_kmeans_update) at N = 10^6 with (D, K) = (36, 8) and (100, 32) next to torch (cdist + argmin, index_add_) and to one
 EM round (eaqhm_gmm_estep + eaqhm_gmm_mstep) at the same sizes, then the whole kmeans call with its rounds, and the mean
 log-likelihood of gmm_fit after 20 rounds from the axis start and from the k-means start on a seeded clustered set.
+--nn times the nearest-row search of the non-parallel training (eaqhm_nn_rows) on random rows at
+nA = nB = 60 000 with D = 24 and 48 and at nA = 2 000, nB = 60 000 (the split path) next to torch (cdist + argmin) on the
+same device, with the fraction of the FP64 matrix peak at 2 nA nB D flops.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -330,6 +333,36 @@ def kmeans_rows(torch, reps=20, runs=3, N=1000000, shapes=((36, 8), (100, 32))):
             fits[name] = str(err)
     rows.append(dict(quality_set="kmeans_clustered(20000, 16, 8, seed 77)", rounds=20, mean_loglik=fits))
     print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def nn_rows(torch, reps=20, runs=3, shapes=((60000, 60000, 24), (60000, 60000, 48), (2000, 60000, 24))):
+    """eaqhm_nn_rows (the norms, the search and the merge together) on seeded normal rows, next to torch on
+    the same device (cdist + argmin, windows of 5: a comparison, not a bar).  Each time: median of `runs` warmed windows of
+    `reps` launches, and max - min of the windows; the fraction of the FP64 matrix peak counts 2 nA nB D flops."""
+    from eaqhm_amd import nonparallel
+    from eaqhm_amd.functions import _ctx
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn, n=reps):
+        ts = sorted(timed(torch, fn, n) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for nA, nB, D in shapes:
+        rng = np.random.default_rng(nA + nB + D)
+        A = torch.as_tensor(rng.standard_normal((nA, D)), device=dev)
+        B = torch.as_tensor(rng.standard_normal((nB, D)), device=dev)
+        work = torch.empty(c.nn_work_len(nA, nB, D), dtype=torch.float64, device=dev)
+        index = torch.empty(nA, dtype=torch.int64, device=dev)
+        dist2 = torch.empty(nA, dtype=torch.float64, device=dev)
+        t = med(lambda: c.nn_rows(A, nA, D, B, nB, D, D, work, index, dist2))
+        tt = med(lambda: torch.cdist(A, B).argmin(dim=1), 5)
+        same = float((torch.cdist(A, B).argmin(dim=1) == index).double().mean().item())
+        rows.append(dict(nA=nA, nB=nB, D=D, splits=nonparallel.nn_splits(nA, nB), nn_rows_ms=t[0], nn_rows_spread_ms=t[1],
+                         peak_fraction=round(2.0 * nA * nB * D / (t[0] * 1e-3) / FP64_MATRIX_PEAK, 4),
+                         torch_cdist_argmin_ms=tt[0], torch_spread_ms=tt[1], same_index_as_torch=same))
     return rows
 
 
@@ -1112,8 +1145,20 @@ def main():
     ap.add_argument("--mlpg-em", action="store_true",
                     help="time eaqhm_mlpg_estep next to eaqhm_gmm_estep and eaqhm_gmm_regress, and one refinement iteration "
                          "(random rows; needs no workload: pass --workloads '')")
+    ap.add_argument("--nn", action="store_true",
+                    help="time eaqhm_nn_rows next to torch cdist + argmin (random rows; needs no workload: pass "
+                         "--workloads '')")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.nn:
+        import torch
+        res_nn = dict(nn=nn_rows(torch))
+        if not a.workloads and not (a.kmeans or a.gv or a.mlpg or a.gmm or a.mlpg_em):
+            print(json.dumps(res_nn))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump([res_nn], f, indent=1)
+            return 0
     if a.kmeans:
         import torch
         res_kmeans = dict(kmeans=kmeans_rows(torch))
@@ -1168,6 +1213,8 @@ def main():
         res.append(res_kmeans)
     if a.mlpg_em:
         res.append(res_em)
+    if a.nn:
+        res.append(res_nn)
     for r in res:
         print(json.dumps(r))
     if a.out:
