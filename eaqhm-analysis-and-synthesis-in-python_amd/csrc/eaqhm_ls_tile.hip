@@ -244,14 +244,20 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
 
     // three-weight Gramian: basis pair x = wave + 8 slot (pairs numbered row by row, I >= J): pair counts per SIMD
     // (waves w and w + 4) equal to within one
+    // T = 4 (ten pairs; pairs 8 and 9 whole in the second slot of waves 0 and 1 would be 27 / 27 / 18 / 18 MFMAs per k-step
+    // on the four SIMDs): the second slot of waves 0..3 takes half of pair 8 (waves 0, 1) or of pair 9 (waves 2, 3) — wave
+    // 2 h + b the k-steps 4 b .. 4 b + 3 of every chunk — 22.5 per SIMD.  The two partial tiles of a split pair are added
+    // in a fixed order before the gather (first half + second half).
     constexpr int TWA = TW ? TW : 1;
+    const bool split = TW > 0 && NS == 5 && T == 4;
     d4 g[TWA][9];
-    int gI[TWA], gJ[TWA];
+    int gI[TWA], gJ[TWA], gx[TWA];
     bool glive[TWA];
 #pragma unroll
     for (int sl = 0; sl < TWA; ++sl) {
-      const int x = wave + 8 * sl;
-      glive[sl] = TW && x < npair;
+      const int x = (split && sl == 1) ? 8 + (wave >> 1) : wave + 8 * sl;
+      glive[sl] = TW && x < npair && !(split && sl == 1 && wave >= 4);
+      gx[sl] = __builtin_amdgcn_readfirstlane(x);
       int I = 0, J = 0;
       if (glive[sl]) tile_of(x, I, J);
       gI[sl] = __builtin_amdgcn_readfirstlane(I);
@@ -373,7 +379,8 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         // Whole pairs first — a pair's three weights share the four LDS reads and the n-scaled operands of a k-step (the
         // f64 vector instructions that prepare operands do not run beside the f64 MFMAs here: dealt out as 63 single units
         // with their own scaling, the contraction was slower than the stacked one in spite of 30 % fewer MFMAs) — then the
-        // single units.  Not software-pipelined, like the whole-pair loop below.
+        // single units.  Not software-pipelined, like the whole-pair loop below: every loop kind was tried with the operands
+        // of k-step ks + 1 read ahead of the MFMAs of k-step ks, and no class gained (profiles/tw_pipeline/README.md).
         const int plane = TS * ldx_max;
         const int kn = (ksl < 8) ? ksl : 8;
 #pragma unroll
@@ -474,10 +481,18 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           int nk = (lq & 1) ? d0 + (lq >> 1) : -d0 - (lq >> 1) - 1;
           asm volatile("" : "+v"(rb), "+v"(nk));   // (hoisted out of the chunk loop, these spill)
           const int plane = TS * ldx_max;
-          // (not software-pipelined: the operands of the next k-step do not fit beside 2 x 9 accumulators)
-          const int kn = (ksl < 8) ? ksl : 8;
+          // (not software-pipelined: the registers allow it — no spill with the operands of the next k-step read ahead, moved
+          // or in a loop of two k-steps — but it measured no faster, with the moves 3.5 % slower: the LDS round trip is not
+          // exposed, the SIMD's other wave fills it; what the loop loses against the MFMA rate is the FP64 vector work of the
+          // scalings, which shares the pipe.  profiles/tw_pipeline/README.md)
+          int kn = (ksl < 8) ? ksl : 8;
+          int ks = 0;
+          if (split && sl == 1) {   // this wave's half of the chunk's k-steps
+            if (wave & 1) { ks = 4; rb += 16 * ldx; nk += (lq & 1) ? 8 : -8; }
+            else kn = (kn < 4) ? kn : 4;
+          }
 #pragma clang loop unroll(disable)
-          for (int ks = 0; ks < kn; ++ks) {
+          for (; ks < kn; ++ks) {
             const int sw = (sw0 + 2 * ks) & 15;
             const double aR = Xre[rb + ca + sw], aI = Xre[rb + ca + sw + plane];
             const double bR = Xre[rb + cb + sw], bI = Xre[rb + cb + sw + plane];
@@ -588,12 +603,13 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
 #pragma unroll
       for (int sl = 0; sl < TWA; ++sl) {
         if (!glive[sl]) continue;
-        const int x = wave + 8 * sl;
+        const int x = gx[sl];
+        const bool second = split && sl == 1 && (wave & 1);   // second halves: planes of their own behind the 3 npair tiles
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           const d4 p1 = g[sl][3 * p], p2 = g[sl][3 * p + 1];
           const d4 re = p1 + p2, im = g[sl][3 * p + 2] + (p1 - p2);
-          double* gt = Gs + (size_t)(p * npair + x) * 512;
+          double* gt = Gs + (size_t)(second ? 3 * npair + 3 * (x - 8) + p : p * npair + x) * 512;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int o = 2 * (16 * (lq + 4 * r) + lcol);
@@ -602,35 +618,102 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         }
       }
       __syncthreads();
+      if (split) {   // tile (p, pair 8 + h) = first half + second half; six tiles, three complex values per thread
+        double2 c1[3], c2[3];
 #pragma unroll
-      for (int sl = 0; sl < NS; ++sl) {   // every slot, empty ones too: nothing of accR / accI lives through the contraction
+        for (int k = 0; k < 3; ++k) {
+          const int q = tid + k * TL_THREADS, t = q >> 8, e = 2 * (q & 255);
+          c1[k] = *(const double2*)(Gs + (size_t)((t % 3) * npair + 8 + t / 3) * 512 + e);
+          c2[k] = *(const double2*)(Gs + (size_t)(3 * npair + t) * 512 + e);
+        }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int R = 16 * tP[sl] + lq + 4 * r, C = 16 * tQ[sl] + lcol;
-          const bool pad = !live[sl] || R > 2 * Kc || C > 2 * Kc;
-          const bool rs = R >= Kc && R < 2 * Kc, cs = C >= Kc && C < 2 * Kc;
-          const int a = (R == 2 * Kc) ? Kc : rs ? R - Kc : R, b = (C == 2 * Kc) ? Kc : cs ? C - Kc : C;
-          const int p = (int)rs + (int)cs;
-          const bool lo = (a >> 4) >= (b >> 4);
-          const int I = lo ? (a >> 4) : (b >> 4), J = lo ? (b >> 4) : (a >> 4);
-          const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
-          double vr = 0.0, vi = 0.0;
-          if (!pad) {
+        for (int k = 0; k < 3; ++k) {
+          const int q = tid + k * TL_THREADS, t = q >> 8, e = 2 * (q & 255);
+          *(double2*)(Gs + (size_t)((t % 3) * npair + 8 + t / 3) * 512 + e) = make_double2(c1[k].x + c2[k].x, c1[k].y + c2[k].y);
+        }
+        __syncthreads();
+      }
+      if constexpr (UN > 0) {
+        // H units hold (Re, RI): Im = RI - RI^T in place, so that the gather reads every tile alike and needs no second
+        // value per entry (packed tables: the corner has plane 0 only).  A thread takes both entries of a transposed pair
+        // (i, j), i <= j: 136 pairs per diagonal tile, rows r and 15 - r of the triangle side by side (17 entries);
+        // T = TWU_TT[TB] here.  Every load ahead of the first store and no branch but in the last round: one round trip
+        // through the L2, not one per tile.
+        constexpr int TT = TWU_TT[TB], HN = (PK ? 3 * (TT - 1) + 1 : 3 * TT) * 136, HF = HN / TL_THREADS, HT = HF + (HN % TL_THREADS ? 1 : 0);
+        double ha[HT], hb[HT];
+        int hoa[HT], hob[HT];
+#pragma unroll
+        for (int k = 0; k < HT; ++k) {
+          const int q = tid + k * TL_THREADS, qc = (q < HN) ? q : 0;
+          const int t = qc / 136, e = qc - 136 * t, r = e / 17, c = e - 17 * r;
+          const int i = (c < 16 - r) ? r : 15 - r, j = (c < 16 - r) ? r + c : c - 1;
+          const int TD = PK ? TT - 1 : TT, pl = (t < 3 * TD) ? t / TD : 0, I = (t < 3 * TD) ? t - pl * TD : TT - 1;   // (packed: the corner last)
+          const int tile = (pl * npair + I * (I + 1) / 2 + I) * 512;
+          hoa[k] = tile + 2 * (16 * i + j) + 1; hob[k] = tile + 2 * (16 * j + i) + 1;
+          ha[k] = Gs[hoa[k]]; hb[k] = Gs[hob[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < HT; ++k) {
+          if (k < HF || tid + k * TL_THREADS < HN) {
+            Gs[hoa[k]] = ha[k] - hb[k];
+            Gs[hob[k]] = hb[k] - ha[k];   // (i = j: the same place, the same zero)
+          }
+        }
+        __syncthreads();
+      }
+      // Every slot, empty ones too: nothing of accR / accI lives through the contraction.  The loads of the gather are
+      // issued unconditionally (padding positions and empty slots read the first value of the area and drop it) and consumed
+      // afterwards: the values come out of the L2, and a load inside a branch of its own is waited for before the next address
+      // is even computed — one exposed round trip per value, 4 NS of them per frame (22 k to 52 k cycles, 6-7 % of a frame),
+      // instead of one per batch.
+      constexpr int GBT = (NS > 7) ? 1 : NS;   // slots per batch (the 9- and 10-slot budgets have no registers to spare)
+#pragma unroll
+      for (int s0 = 0; s0 < NS; s0 += GBT) {
+        double2 gv[GBT][4];
+        int gfl[GBT];   // bits r, 4 + r: lo, padding
+#pragma unroll
+        for (int sb = 0; sb < GBT; ++sb) {
+          const int sl = s0 + sb;
+          if (sl >= NS) continue;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int R = 16 * tP[sl] + lq + 4 * r, C = 16 * tQ[sl] + lcol;
+            const bool pad = !live[sl] || R > 2 * Kc || C > 2 * Kc;
+            const bool rs = R >= Kc && R < 2 * Kc, cs = C >= Kc && C < 2 * Kc;
+            const int a = (R == 2 * Kc) ? Kc : rs ? R - Kc : R, b = (C == 2 * Kc) ? Kc : cs ? C - Kc : C;
+            const int p = (int)rs + (int)cs;
+            const bool lo = (a >> 4) >= (b >> 4);
+            const int I = lo ? (a >> 4) : (b >> 4), J = lo ? (b >> 4) : (a >> 4);
+            const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
             // packed last tile column (i < 8 there): weights 0 and 1 of (E, J) in rows i and i + 8 of edge unit q = 0, weight
             // 2 in row i + 8 of q = 1; entry (i + 8 pa, j + 8 pb), pa + pb = p, of the corner
             const bool edge = PK && I == T - 1;
             const int q = (edge && I != J) ? (int)(p == 2) : edge ? 0 : p;
             const int ii = edge ? i + ((I != J) ? 8 * (p - q) : (p >= 1 ? 8 : 0)) : i;
             const int jj = (edge && I == J && p == 2) ? j + 8 : j;
-            const double* gt = Gs + (size_t)(q * npair + I * (I + 1) / 2 + J) * 512;
-            const double2 v = *(const double2*)(gt + 2 * (16 * ii + jj));
-            vr = v.x; vi = lo ? v.y : -v.y;
-            if (UN > 0 && I == J) vi = v.y - gt[2 * (16 * jj + ii) + 1];   // H unit (lo holds): Im = RI - RI^T
+            const size_t tile = pad ? 0 : (size_t)(q * npair + I * (I + 1) / 2 + J) * 512;
+            const int o = pad ? 0 : 2 * (16 * ii + jj);
+            gv[sb][r] = *(const double2*)(Gs + tile + o);
+            gfl[sb] = (r ? gfl[sb] : 0) | ((int)lo << r) | ((int)pad << (4 + r));
           }
-          accR[sl][r] = vr; accI[sl][r] = vi;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // every request of the batch ahead of the first use
+#pragma unroll
+        for (int sb = 0; sb < GBT; ++sb) {
+          const int sl = s0 + sb;
+          if (sl >= NS) continue;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double2 v = gv[sb][r];
+            const bool lo = (gfl[sb] >> r) & 1, pad = (gfl[sb] >> (4 + r)) & 1;
+            const double vr = v.x, vi = lo ? v.y : -v.y;   // (a diagonal pair: lo holds)
+            accR[sl][r] = pad ? 0.0 : vr; accI[sl][r] = pad ? 0.0 : vi;
+          }
         }
       }
-      LS_STAMP(2);
+      // the gather on a slot of its own (9), so that slot 2 is the k-step loops and the chunk's closing barrier alone; with
+      // the diag_D diagnostics on, slot 9 is theirs and the gather stays in slot 2
+      LS_STAMP(uni((int)A.debug_diag) ? 2 : 9);
     }
 
     {
@@ -935,7 +1018,7 @@ bool ls_tile_applicable(int Kcmax, int Nmax) {
 
 size_t ls_tile_scratch_stride(int nmax, int Nmax) {
   const size_t Npad = (size_t)((Nmax + 63) >> 6) << 6;
-  const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512;   // three-weight G_p tiles of T <= 6 (nt <= 12)
+  const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512;   // three-weight G_p tiles of T <= 6 (nt <= 12; T = 4: 30 + the 6 second halves)
   return ((bridged > gram ? bridged : gram) + 15) & ~(size_t)15;
 }
 

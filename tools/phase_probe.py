@@ -9,14 +9,16 @@ wl = args[0] if args else "synth16k_60s"
 fs, s, grid, frames, fstep = bench.load_workload(wl)
 plan = FramePlan(len(s), fs, grid, frames, fstep, 15, 3, 32, 0)
 eng = DeviceAnalysis(s, s, plan, 160, 5)
-eng.ctx.set_option(2, 2 if "--diag" in sys.argv else 1)     # --diag: also time diag_D and the gaps (slows the kernel ~8 %)
+diag = "--diag" in sys.argv
+eng.ctx.set_option(2, 2 if diag else 1)     # --diag: also time diag_D and the gaps (slows the kernel ~8 %)
 eng.run()
 d = eng.ctx.debug_read()
-names = ["setup + slot preparation", "build: barrier wait", "contraction (a>=1) / closed-form fill (a=0)", "(end of factorisation)",
+names = ["setup + slot preparation", "build: barrier wait",
+         "contraction: k loops + the chunk's closing barrier%s (a>=1) / closed-form fill (a=0)" % (" + gather" if diag else ""), "(end of factorisation)",
          "back substitution", "record", "wait at barrier A (the diagonal pipeline of another wave)", "panel (X = T W^H)",
-         "trailing update (own tiles)", "-", "barrier C wait + next diagonal tile's update + diagonal role (when wave 0 has one)",
+         "trailing update (own tiles)", "-" if diag else "gather of the G_p tiles (three-weight classes; with --diag inside the contraction)", "barrier C wait + next diagonal tile's update + diagonal role (when wave 0 has one)",
          "-", "build: basis rows (wave 0)"]
-tot = sum(d[:9]) + d[10] + d[12]
+tot = sum(d[:9]) + d[10] + d[12] + (0 if diag else d[9])
 for n, v in zip(names, d[:13]):
     print("%-90s %14d cycles  %5.1f%%" % (n, v, 100.0 * v / max(tot, 1)))
 if d[13]:
