@@ -39,6 +39,7 @@
 #include "eaqhm_ls_a0.h"
 #include "eaqhm_ls_tilemap.h"
 #include "eaqhm_ls_twunits.h"
+#include "eaqhm_ls_gather.h"
 
 namespace eaqhm {
 bool ls_a0tile_fits(const LsArgs& A);                 // eaqhm_ls_a0tile.hip
@@ -578,6 +579,17 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       // (signal row), likewise b for C, p = the number of slope indices among R and C.  Every G_p is Hermitian (n is
       // real): entries above the tile diagonal of G_p are conjugates of computed ones.
       double* Gs = Qs;
+      // The gather's index table (eaqhm_ls_gather.h), one entry per row / column index of the frame, and the zero that
+      // padding positions and empty slots read: written beside the tile stores, published by the barrier behind them.
+      // The table lies at the start of region U: the basis chunk is done with (the chunk's closing barrier), and nothing
+      // is written there again before the barrier that follows the gather.
+      int4* gtab = (int4*)U;
+      if (tid < 16 * nt) {
+        const GatherEntry e = gather_entry(tid, Kc, npair, T, PK);
+        gtab[2 * tid] = make_int4(e.lo, e.hi, e.trow, e.tcol);
+        if constexpr (PK) gtab[2 * tid + 1] = make_int4(e.mask, e.val, 0, 0);
+      }
+      if (tid == TL_THREADS - 1) *(double2*)((char*)Gs + GI_ZCELL) = make_double2(0.0, 0.0);
       if constexpr (UN > 0) {
         // a unit's tile: (Re, Im) for K3 and K4, (Re, RI) for H — the gather below takes Im = RI - RI^T there
 #pragma unroll
@@ -662,53 +674,57 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         __syncthreads();
       }
       // Every slot, empty ones too: nothing of accR / accI lives through the contraction.  The loads of the gather are
-      // issued unconditionally (padding positions and empty slots read the first value of the area and drop it) and consumed
-      // afterwards: the values come out of the L2, and a load inside a branch of its own is waited for before the next address
-      // is even computed — one exposed round trip per value, 4 NS of them per frame (22 k to 52 k cycles, 6-7 % of a frame),
-      // instead of one per batch.
-      constexpr int GBT = (NS > 7) ? 1 : NS;   // slots per batch (the 9- and 10-slot budgets have no registers to spare)
+      // issued unconditionally and consumed afterwards: the values come out of the L2, and a load inside a branch of its own
+      // is waited for before the next address is even computed — one exposed round trip per value, 4 NS of them per frame
+      // (22 k to 52 k cycles, 6-7 % of a frame).
+      // One batch for every budget: a value is loaded into its accumulator registers — padding reads the zero cell, so
+      // nothing is selected afterwards — and only the sign of the imaginary part is left to fix: one word per slot holds
+      // the four `up` bits (bit 31 - 3 + r for row r).  The address is the wave-uniform Gs plus a 32-bit byte offset.
+      typedef const __attribute__((address_space(1))) char* gather_base_t;
+      gather_base_t Gb = (gather_base_t)(const char*)Gs;
+      unsigned gup[NS];
 #pragma unroll
-      for (int s0 = 0; s0 < NS; s0 += GBT) {
-        double2 gv[GBT][4];
-        int gfl[GBT];   // bits r, 4 + r: lo, padding
+      for (int sl = 0; sl < NS; ++sl) {
+        // column entry once per slot (an empty slot: index 16 nt - 1, which is padding in every frame: 2 Kc + 1 is odd)
+        const int cx = live[sl] ? 16 * tQ[sl] + lcol : 16 * nt - 1;
+        const int4* rt = gtab + 2 * (16 * tP[sl] + lq);
+        int4 c0 = gtab[2 * cx], c1 = make_int4(0, 0, 0, 0), r0[4], r1[4];
+        if constexpr (PK) c1 = gtab[2 * cx + 1];
 #pragma unroll
-        for (int sb = 0; sb < GBT; ++sb) {
-          const int sl = s0 + sb;
-          if (sl >= NS) continue;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int R = 16 * tP[sl] + lq + 4 * r, C = 16 * tQ[sl] + lcol;
-            const bool pad = !live[sl] || R > 2 * Kc || C > 2 * Kc;
-            const bool rs = R >= Kc && R < 2 * Kc, cs = C >= Kc && C < 2 * Kc;
-            const int a = (R == 2 * Kc) ? Kc : rs ? R - Kc : R, b = (C == 2 * Kc) ? Kc : cs ? C - Kc : C;
-            const int p = (int)rs + (int)cs;
-            const bool lo = (a >> 4) >= (b >> 4);
-            const int I = lo ? (a >> 4) : (b >> 4), J = lo ? (b >> 4) : (a >> 4);
-            const int i = lo ? (a & 15) : (b & 15), j = lo ? (b & 15) : (a & 15);
-            // packed last tile column (i < 8 there): weights 0 and 1 of (E, J) in rows i and i + 8 of edge unit q = 0, weight
-            // 2 in row i + 8 of q = 1; entry (i + 8 pa, j + 8 pb), pa + pb = p, of the corner
-            const bool edge = PK && I == T - 1;
-            const int q = (edge && I != J) ? (int)(p == 2) : edge ? 0 : p;
-            const int ii = edge ? i + ((I != J) ? 8 * (p - q) : (p >= 1 ? 8 : 0)) : i;
-            const int jj = (edge && I == J && p == 2) ? j + 8 : j;
-            const size_t tile = pad ? 0 : (size_t)(q * npair + I * (I + 1) / 2 + J) * 512;
-            const int o = pad ? 0 : 2 * (16 * ii + jj);
-            gv[sb][r] = *(const double2*)(Gs + tile + o);
-            gfl[sb] = (r ? gfl[sb] : 0) | ((int)lo << r) | ((int)pad << (4 + r));
-          }
+        for (int r = 0; r < 4; ++r) {
+          r0[r] = rt[8 * r];
+          if constexpr (PK) r1[r] = rt[8 * r + 1];
         }
-        __builtin_amdgcn_sched_barrier(0);   // every request of the batch ahead of the first use
+        // (the entries whole, ahead of their use: left alone the compiler sinks each word's read into a branch on `up` and
+        // waits for it there)
+        asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.w));
+        if constexpr (PK) asm volatile("" : "+v"(c1.x), "+v"(c1.y));
 #pragma unroll
-        for (int sb = 0; sb < GBT; ++sb) {
-          const int sl = s0 + sb;
-          if (sl >= NS) continue;
+        for (int r = 0; r < 4; ++r) {
+          asm volatile("" : "+v"(r0[r].x), "+v"(r0[r].y), "+v"(r0[r].z));
+          if constexpr (PK) asm volatile("" : "+v"(r1[r].x), "+v"(r1[r].y));
+        }
+        unsigned ups = 0;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double2 v = gv[sb][r];
-            const bool lo = (gfl[sb] >> r) & 1, pad = (gfl[sb] >> (4 + r)) & 1;
-            const double vr = v.x, vi = lo ? v.y : -v.y;   // (a diagonal pair: lo holds)
-            accR[sl][r] = pad ? 0.0 : vr; accI[sl][r] = pad ? 0.0 : vi;
-          }
+        for (int r = 0; r < 4; ++r) {
+          const int dt = r0[r].z - c0.w;   // < 0: above the tile diagonal, the conjugate of a stored entry (eaqhm_ls_gather.h)
+          unsigned off = (unsigned)((dt < 0 ? r0[r].y : r0[r].x) + (dt < 0 ? c0.x : c0.y));
+          if constexpr (PK) off += (unsigned)((dt < 0 ? c1.x : r1[r].x) & (dt < 0 ? r1[r].y : c1.y));
+          off = off < (unsigned)GI_ZCELL ? off : (unsigned)GI_ZCELL;
+          ups = (ups >> 1) | ((unsigned)dt & 0x80000000u);
+          typedef double gather_d2 __attribute__((ext_vector_type(2)));
+          const gather_d2 v = *(const __attribute__((address_space(1))) gather_d2*)(Gb + off);
+          accR[sl][r] = v.x; accI[sl][r] = v.y;
+        }
+        gup[sl] = ups;
+      }
+      __builtin_amdgcn_sched_barrier(0);   // every request ahead of the first use: one round trip through the L2 per frame
+#pragma unroll
+      for (int sl = 0; sl < NS; ++sl) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {   // -im where `up`: the sign bit
+          const double vi = accI[sl][r];
+          accI[sl][r] = __hiloint2double(__double2hiint(vi) ^ (int)((gup[sl] << (3 - r)) & 0x80000000u), __double2loint(vi));
         }
       }
       // the gather on a slot of its own (9), so that slot 2 is the k-step loops and the chunk's closing barrier alone; with
@@ -1018,7 +1034,8 @@ bool ls_tile_applicable(int Kcmax, int Nmax) {
 
 size_t ls_tile_scratch_stride(int nmax, int Nmax) {
   const size_t Npad = (size_t)((Nmax + 63) >> 6) << 6;
-  const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512;   // three-weight G_p tiles of T <= 6 (nt <= 12; T = 4: 30 + the 6 second halves)
+  // three-weight G_p tiles of T <= 6 (nt <= 12; T = 4: 30 + the 6 second halves) and the gather's zero cell behind them (GI_ZCELL)
+  const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512 + 2;
   return ((bridged > gram ? bridged : gram) + 15) & ~(size_t)15;
 }
 
