@@ -64,7 +64,9 @@ pairing and training (nonparallel.conversion_train_nonparallel, INCA, DESIGN.md 
 or --conversion) puts every cepstrum of the model on the all-pass warped frequency axis of DESIGN.md §9.8: a number in
 [-0.9, 0.9], or the coefficient model.cepstrum_warp gives for the file's sampling rate.  --conversion-train stores it in
 MAP.npz, and --conversion MAP.npz fits at the map's axis (a map without the entry lies on the linear axis); a different
-explicit --cepstral-warp is an error.  The noise flags keep their linear rows."""
+explicit --cepstral-warp is an error.  The noise flags keep their linear rows.
+--pitch-device takes the pitch track of the analysis, and of the analyses of --envelope-from, --timing-from, --noise-from
+and --conversion-train, from the device (pitch.analysis_pitch_track) in place of the host's swipe.swipep."""
 import argparse
 
 import numpy as np
@@ -88,6 +90,16 @@ def cepstral_warp_argument(text):
     return a
 
 
+def analyse(path, gender, analysis_options):
+    """eaQHMAnalysisAndSynthesis(path, gender, **analysis_options); with the entry pitch_device (--pitch-device) the pitch
+    track is pitch.analysis_pitch_track's."""
+    options = dict(analysis_options)
+    if options.pop("pitch_device", False):
+        from .pitch import analysis_pitch_track
+        options["pitch_track"] = analysis_pitch_track(path, gender, options.get("fc", 0))
+    return eaQHMAnalysisAndSynthesis(path, gender, **options)
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="eaqhm_amd", description="eaQHM analysis/resynthesis on MI355X")
     ap.add_argument("wav")
@@ -100,6 +112,8 @@ def parser():
     ap.add_argument("--fc", type=int, default=0)
     ap.add_argument("--partials", type=int, default=0)
     ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--pitch-device", action="store_true",
+                    help="SWIPE' on the device (pitch.analysis_pitch_track) for every analysis of this run")
     ap.add_argument("--track-budget-mb", type=float, default=0.0,
                     help="long files: device memory for the dense tracks (streamed in time blocks, same results); 0 = automatic: "
                          "resident while they fit comfortably, streamed otherwise")
@@ -371,8 +385,10 @@ def main(argv=None):
                             analysisWindow=a.analysis_window, fullWaveform=not a.voiced_only, fc=a.fc,
                             partials=a.partials, printPrompts=True, loadingScreen=False,
                             track_budget_bytes=int(a.track_budget_mb * 2 ** 20) if a.track_budget_mb > 0 else "auto")
+    if a.pitch_device:
+        analysis_options["pitch_device"] = True
     on_axis = dict(cep_warp=axis) if axis != 0.0 else {}     # without the flag every call below is made without it
-    s_recon, srer, det, t = eaQHMAnalysisAndSynthesis(a.wav, gender, **analysis_options)
+    s_recon, srer, det, t = analyse(a.wav, gender, analysis_options)
     if not a.no_write:
         fs, _ = wavfile.read(a.wav)
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
@@ -526,7 +542,7 @@ def train_conversion_nonparallel(a, gender, analysis_options, fs, det, **on_axis
     fs_t, _ = wavfile.read(a.conversion_train)
     if fs_t != fs:
         raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (a.conversion_train, fs_t, fs))
-    _, _, det_t, _ = eaQHMAnalysisAndSynthesis(a.conversion_train, gender, **analysis_options)
+    _, _, det_t, _ = analyse(a.conversion_train, gender, analysis_options)
     C_t = model_cepstrum(det_t, fs, order, lam, **on_axis)
     M = 8 if a.conversion_components is None else a.conversion_components
     conv, info = nonparallel.conversion_train_nonparallel(p["ceps"], C_t, M, rounds=a.conversion_nonparallel,
@@ -554,7 +570,7 @@ def align_other(path, gender, analysis_options, fs, ceps, order, lam, band_s, no
     fs_o, _ = wavfile.read(path)
     if fs_o != fs:
         raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (path, fs_o, fs))
-    s_recon_o, _, det_o, _ = eaQHMAnalysisAndSynthesis(path, gender, **analysis_options)
+    s_recon_o, _, det_o, _ = analyse(path, gender, analysis_options)
     C_o = model_cepstrum(det_o, fs, order, lam, **on_axis)
     r = max(int(round(band_s * fs / unpack_model(det_o)["step"])), band_min_radius(len(ceps), len(C_o)))
     pairs, cost = model_align(ceps, C_o, band=r)

@@ -103,6 +103,13 @@ SYMBOLS_NN = (
     ("eaqhm_nn_work_len", _I64, [_I64, _I64, _I32]),
     ("eaqhm_nn_rows", C.c_int, [_P, _P, _I64, _I64, _P, _I64, _I64, _I32, _P, _P, _P]),
 )
+# every symbol include/eaqhm_swipe.h declares: likewise
+SYMBOLS_SWIPE = (
+    ("eaqhm_swipe_loudness", C.c_int, [_P, _P, _I64, _I32, _I32, _I64, _I64, _P, _F64, _F64, _P, _P, _P, _I32, _P, _I64]),
+    ("eaqhm_swipe_scores", C.c_int, [_P, _P, _I32, _I64, _P, _I64, _I64, _I32, _P]),
+    ("eaqhm_swipe_pick", C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F64, _P, _P, _P, _P, _I32, _P, _P,
+                                    _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -126,7 +133,7 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, res, args in (SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM
-                            + SYMBOLS_NN):
+                            + SYMBOLS_NN + SYMBOLS_SWIPE):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -420,6 +427,23 @@ class Context:
     def nn_rows(self, A, nA, lda, B, nB, ldb, D, work, index, dist2):
         self._ck(self.lib.eaqhm_nn_rows(self.h, _ptr(A), nA, lda, _ptr(B), nB, ldb, D, _ptr(work), _ptr(index),
                                         _ptr(dist2)))
+
+    # SWIPE' (DESIGN.md §13): x [n], window [w], lo int32 [nE], xlo, df [nE], L [nframes][ld]; K [cand][ldk], Si
+    # [cand][nframes]; the windows of a pick are a sequence of (Si, j0, ncand, nframes, mu, tshift), S is None or [npc][T]
+    def swipe_loudness(self, x, n, w, hop, pad, nframes, window, fs, sumw2, lo, xlo, df, nE, L, ld):
+        self._ck(self.lib.eaqhm_swipe_loudness(self.h, _ptr(x), n, w, hop, pad, nframes, _ptr(window), float(fs),
+                                               float(sumw2), _ptr(lo), _ptr(xlo), _ptr(df), nE, _ptr(L), ld))
+
+    def swipe_scores(self, K, cand, ldk, L, nframes, ldl, nE, Si):
+        self._ck(self.lib.eaqhm_swipe_scores(self.h, _ptr(K), cand, ldk, _ptr(L), nframes, ldl, nE, _ptr(Si)))
+
+    def swipe_pick(self, windows, t, T, npc, pc0, ntc, nftc, ptab, nf, nfmax, p, s, S=None):
+        n = len(windows)
+        ptrs = lambda k: (_P * n)(*[_ptr(w[k]) for w in windows])  # noqa: E731
+        self._ck(self.lib.eaqhm_swipe_pick(self.h, n, ptrs(0), (_I32 * n)(*[w[1] for w in windows]),
+                                           (_I32 * n)(*[w[2] for w in windows]), (_I64 * n)(*[w[3] for w in windows]),
+                                           ptrs(4), ptrs(5), _ptr(t), T, npc, float(pc0), _ptr(ntc), _ptr(nftc),
+                                           _ptr(ptab), _ptr(nf), nfmax, _ptr(p), _ptr(s), _ptr(S)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

@@ -525,6 +525,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_mlpg_em.h"
 /* nearest rows, the search of the non-parallel training (additions under ABI 6): declared in eaqhm_nn.h. */
 #include "eaqhm_nn.h"
+/* the SWIPE' pitch estimator's loudness, scores and pick stages (additions under ABI 6): declared in eaqhm_swipe.h. */
+#include "eaqhm_swipe.h"
 
 #ifdef __cplusplus
 }

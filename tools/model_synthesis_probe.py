@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--out FILE]
+                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--swipe] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -48,6 +48,10 @@ log-likelihood of gmm_fit after 20 rounds from the axis start and from the k-mea
 --nn times the nearest-row search of the non-parallel training (eaqhm_nn_rows) on random rows at
 nA = nB = 60 000 with D = 24 and 48 and at nA = 2 000, nB = 60 000 (the split path) next to torch (cdist + argmin) on the
 same device, with the fraction of the FP64 matrix peak at 2 nA nB D flops.
+--swipe times the device SWIPE'  on the 60 s synthetic signals of --workloads at the workloads' own plim
+([160, 300]) and at [70, 500]: each of the three kernels per window size, the whole swipep_device call from a host array
+to the host result as wall time with a cold and with a cached plan, and swipe.swipep in the same process (one run after
+one warm-up), with the number of instants whose pitch differs.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -363,6 +367,69 @@ def nn_rows(torch, reps=20, runs=3, shapes=((60000, 60000, 24), (60000, 60000, 4
         rows.append(dict(nA=nA, nB=nB, D=D, splits=nonparallel.nn_splits(nA, nB), nn_rows_ms=t[0], nn_rows_spread_ms=t[1],
                          peak_fraction=round(2.0 * nA * nB * D / (t[0] * 1e-3) / FP64_MATRIX_PEAK, 4),
                          torch_cdist_argmin_ms=tt[0], torch_spread_ms=tt[1], same_index_as_torch=same))
+    return rows
+
+
+def swipe_rows(torch, workloads, reps=20, runs=3):
+    """The device SWIPE'  on the 60 s synthetic signals: per kernel and window size the median of `runs`
+    warmed HIP-event windows of `reps` launches with their max - min; the whole pitch.swipep_device call (host array in,
+    host track out) as wall time, cold (no plan, no device copy of it) and with the plan cached (median of five); and
+    swipe.swipep on this host in this process, one run after one warm-up."""
+    from eaqhm_amd import pitch
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.swipe import swipep
+    from eaqhm_amd.synth import synth_speech_int16
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        return out, time.perf_counter() - t0
+
+    rows = []
+    for wl in workloads:
+        fs = {"synth16k_60s": 16000, "synth48k_60s": 48000}[wl]
+        x = synth_speech_int16(60.0, fs) / 32768.0
+        for plim in ((160, 300), (70, 500)):
+            for cache in (pitch._PLANS, pitch._KERNELS, pitch._DEVICE_PLANS):
+                cache.clear()
+            got, cold = wall(lambda: pitch.swipep_device(x, fs, plim))
+            cached = sorted(wall(lambda: pitch.swipep_device(x, fs, plim))[1] for _ in range(5))
+            _, t_plan = wall(lambda: (pitch._PLANS.clear(), pitch._KERNELS.clear(), pitch.swipe_plan(len(x), fs, plim)))
+            swipep(x, fs, list(plim))
+            ref, host = wall(lambda: swipep(x, fs, list(plim)))
+            plan = pitch.swipe_plan(len(x), float(fs), plim)
+            on = pitch._device_plan(plan, torch, dev)
+            x_d = torch.as_tensor(x, device=dev)
+            nE, T, npc = len(plan["fERBs"]), len(plan["t"]), len(plan["pc"])
+            kernels, wins = [], []
+            for w, w_d in zip(plan["windows"], on["windows"]):
+                L = torch.empty((w["nframes"], nE), dtype=torch.float64, device=dev)
+                Si = torch.empty((w["ncand"], w["nframes"]), dtype=torch.float64, device=dev)
+                tl = med(lambda: c.swipe_loudness(x_d, len(x), w["w"], w["hop"], w["pad"], w["nframes"], w_d["window"], fs,
+                                                  w["sumw2"], w_d["lo"], w_d["xlo"], w_d["df"], nE, L, nE))
+                tsc = med(lambda: c.swipe_scores(w_d["K"], w["ncand"], nE, L, w["nframes"], nE, nE, Si))
+                kernels.append(dict(w=w["w"], nframes=w["nframes"], ncand=w["ncand"], loudness_ms=tl[0],
+                                    loudness_spread_ms=tl[1], scores_ms=tsc[0], scores_spread_ms=tsc[1]))
+                wins.append((Si, w["j0"], w["ncand"], w["nframes"], w_d["mu"], w_d["tshift"]))
+            ps = torch.empty((2, T), dtype=torch.float64, device=dev)
+            tp = med(lambda: c.swipe_pick(wins, on["t"], T, npc, plan["pc"][0], on["ntc"], on["nftc"], on["ptab"], on["nf"],
+                                          plan["nfmax"], ps[0], ps[1], None))
+            rows.append(dict(workload=wl, plim=list(plim), samples=len(x), instants=T, candidates=npc, erb_points=nE,
+                             kernels=kernels, pick_ms=tp[0], pick_spread_ms=tp[1],
+                             device_call_cold_s=round(cold, 4), device_call_cached_s=round(cached[2], 4),
+                             device_call_cached_min_max_s=[round(cached[0], 4), round(cached[-1], 4)],
+                             host_plan_s=round(t_plan, 4), host_swipep_s=round(host, 4),
+                             host_over_device_cached=round(host / cached[2], 2),
+                             pitch_differs=int((got[:, 1] != ref[:, 1]).sum()),
+                             strength_max_abs_diff=float(np.abs(got[:, 2] - ref[:, 2]).max())))
+            print(json.dumps(rows[-1]), flush=True)
     return rows
 
 
@@ -1148,8 +1215,18 @@ def main():
     ap.add_argument("--nn", action="store_true",
                     help="time eaqhm_nn_rows next to torch cdist + argmin (random rows; needs no workload: pass "
                          "--workloads '')")
+    ap.add_argument("--swipe", action="store_true",
+                    help="time the device SWIPE' kernels and the whole swipep_device call next to swipe.swipep on the "
+                         "60 s signals of --workloads (nothing else runs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.swipe:
+        import torch
+        res_swipe = [dict(swipe=swipe_rows(torch, a.workloads.split(",")))]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res_swipe, f, indent=1)
+        return 0
     if a.nn:
         import torch
         res_nn = dict(nn=nn_rows(torch))
