@@ -1,12 +1,13 @@
-"""The argument rules that take no model: scales, contours, breakpoint curves, integers, seeds, frequency grids and
-formant-warp breakpoints.  Host only, NumPy only; every other module of the model layer validates through these.
+"""The argument rules that take no model: scales, contours, breakpoint curves, integers, reals in a range, rows of
+numbers, seeds, frequency grids and formant-warp breakpoints.  Host only, NumPy only; every other module of the model layer validates through these.
 
     SCALE_RANGE = (0.25, 4.0): the range of every scale and of every segment slope of a formant warp
     FORMANT_WARP_MAX = 16: breakpoints of a formant warp at most
     check_curve(times_s, values, name="curve") -> (times, values) float64, validated
 
-The underscore helpers are shared by records, cepstrum, align, noise, model, convert and cli: _scale, _sample_rate,
-_is_contour, _numeric_1d, _in_range, _contour, _integer, _seed, _freq_grid, _warp_rows, _warp_excludes_scale.
+The underscore helpers are shared by records, cepstrum, align, noise, model, mixture, dynamics, mapping, convert,
+nonparallel and cli: _scale, _sample_rate, _is_contour, _numeric_1d, _in_range, _contour, _integer, _real, _rows, _seed,
+_freq_grid, _warp_rows, _warp_excludes_scale.
 """
 import numpy as np
 
@@ -132,6 +133,28 @@ def _integer(x, name):
     if not ok:
         raise ValueError("%s must be an integer, got %r" % (name, x))
     return int(x)
+
+
+def _real(x, name, lo, hi):
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number" % name) from None
+    if not (lo <= v <= hi):                       # NaN fails both
+        raise ValueError("%s must be in [%g, %g], got %r" % (name, lo, hi, x))
+    return v
+
+
+def _rows(Z, name, max_cols):
+    A = np.asarray(Z)
+    if A.dtype.kind not in "iuf" or A.ndim != 2 or A.shape[0] < 1:
+        raise ValueError("%s must be a 2-D array of numbers, one row per observation" % name)
+    if not 1 <= A.shape[1] <= max_cols:
+        raise ValueError("%s must have 1 to %d columns, got %d" % (name, max_cols, A.shape[1]))
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if not np.all(np.isfinite(A)):
+        raise ValueError("%s must be finite" % name)
+    return A
 
 
 def _seed(seed):

@@ -26,10 +26,10 @@ import math
 import numpy as np
 
 from . import convert
+from .args import _integer, _real, _rows
 from .cepstrum import _cepstrum_rows
-from .convert import GMM_MAX_COLUMNS, _real, _rows, check_conversion_arguments
-from .args import _integer
-from .records import _device
+from .convert import GMM_MAX_COLUMNS, check_conversion_arguments
+from .records import _agree, _device
 
 NN_SPLIT_MIN = 4096        # rows of B of a split at least
 NN_BLOCKS = 1024           # splits are added until about this many blocks exist
@@ -62,8 +62,8 @@ def nearest_rows(A, B, *, device_index=0):
     (nA, D), nB = A.shape, B.shape[0]
     words = nn_work_len(nA, nB, D)
     torch, c, dev = _device(device_index)
-    if c.nn_work_len(nA, nB, D) != words or c.nn_splits(nA, nB) != nn_splits(nA, nB):
-        raise RuntimeError("libeaqhm_hip.so and the host disagree on the splits of the nearest-row search")
+    _agree("the splits of the nearest-row search", (c.nn_work_len(nA, nB, D), c.nn_splits(nA, nB)),
+           (words, nn_splits(nA, nB)))
     A_d, B_d = torch.as_tensor(A, device=dev), torch.as_tensor(B, device=dev)
     work = torch.empty(words, dtype=torch.float64, device=dev)
     index = torch.empty(nA, dtype=torch.int64, device=dev)

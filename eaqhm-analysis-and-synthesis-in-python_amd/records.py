@@ -14,7 +14,8 @@ of contours, and the formant scale and warp rules that need the model's length.
 
 `DetComponents` is either form eaQHMAnalysisAndSynthesis returns: the list of Deterministic (det_format="structs") or
 the dict of arrays (det_format="arrays"), edited or not.  _device gives every module above this one its library
-context, from functions._ctx; _device_records puts the records on that device.
+context, from functions._ctx; _device_records puts the records on that device; _agree holds a size the library reports
+to the host's own mirror of it.
 """
 from itertools import chain, compress, repeat
 from operator import itemgetter
@@ -276,6 +277,12 @@ def _device(device_index):
     from .functions import _ctx
     c = _ctx(device_index)
     return torch, c, c.device
+
+
+def _agree(what, lib_value, host_value):
+    """RuntimeError naming `what` unless the library's value is the host mirror's."""
+    if lib_value != host_value:
+        raise RuntimeError("libeaqhm_hip.so and the host disagree on " + what)
 
 
 def _device_records(model, dev):

@@ -178,7 +178,7 @@ def test_quality_case():
 
 # ---- the host side through a NumPy stand-in for the two kernels
 class FakeBook:
-    """convert._Codebook with kmeans_ref in place of the library; Z a CPU torch tensor."""
+    """mixture._Codebook with kmeans_ref in place of the library; Z a CPU torch tensor."""
     made = 0
 
     def __init__(self, torch, c, dev, Z, D, k):
@@ -199,7 +199,7 @@ class FakeBook:
 
 
 class FakeMixture:
-    """convert._Mixture with gmm_ref in place of the library."""
+    """mixture._Mixture with gmm_ref in place of the library."""
 
     def __init__(self, Z, zbar, M, device_index):
         import torch
@@ -219,13 +219,15 @@ class FakeMixture:
 
 @pytest.fixture()
 def stand_in(monkeypatch, no_device):
+    """eaqhm_amd.mixture, where kmeans and gmm_fit look their names up, with the fakes in place of the device classes.
+    conversion_train reaches them through gmm_fit; nothing here runs conversion_apply, which makes a _Mixture of its own."""
     import torch
-    from eaqhm_amd import convert
-    monkeypatch.setattr(convert, "_Codebook", FakeBook)
-    monkeypatch.setattr(convert, "_Mixture", FakeMixture)
-    monkeypatch.setattr(convert, "_device", lambda i: (torch, None, "cpu"))
+    from eaqhm_amd import mixture
+    monkeypatch.setattr(mixture, "_Codebook", FakeBook)
+    monkeypatch.setattr(mixture, "_Mixture", FakeMixture)
+    monkeypatch.setattr(mixture, "_device", lambda i: (torch, None, "cpu"))
     FakeBook.made = 0
-    return convert
+    return mixture
 
 
 @pytest.mark.parametrize("name", ["polytope3", "corners5"])
@@ -270,9 +272,10 @@ def test_init_kmeans_reaches_kmeans_and_none_does_not(stand_in, monkeypatch):
     def fit_stub(Zj, M, **kw):
         got.update(kw)
         raise KeyError("stop")
-    monkeypatch.setattr(stand_in, "gmm_fit", fit_stub)
+    from eaqhm_amd import convert, mapping
+    monkeypatch.setattr(mapping, "gmm_fit", fit_stub)
     with pytest.raises(KeyError):
-        stand_in.conversion_train(np.hstack((zero, Z[:, :2])), np.hstack((zero, Z[:, 1:])), 4, init="kmeans")
+        convert.conversion_train(np.hstack((zero, Z[:, :2])), np.hstack((zero, Z[:, 1:])), 4, init="kmeans")
     assert got["init"] == "kmeans" and got["split"] == 2
 
 

@@ -263,7 +263,7 @@ NEW_ARGUMENT_COUNTS = dict(eaqhm_ceps_delta=6, eaqhm_mlpg_work_len=3, eaqhm_mlpg
 
 def test_symbols():
     import eaqhm_amd  # noqa: F401
-    from eaqhm_amd import hip
+    from eaqhm_amd import convert, hip
     assert hip.ABI_VERSION == 6
     bound = {name: len(args) for name, _, args in hip.SYMBOLS_MLPG}
     assert not set(bound) & {name for name, _, _ in hip.SYMBOLS}                      # a table of their own
@@ -279,7 +279,7 @@ def test_symbols():
         assert callable(getattr(hip.Context, name))
     lib = hip.load_library()
     for n, dy, span in ((1, 1, 1), (700, 17, 2), (60000, 24, 2), (2 ** 31, 64, 8)):
-        assert lib.eaqhm_mlpg_work_len(n, dy, span) == n * (2 * span + 2) * dy
+        assert lib.eaqhm_mlpg_work_len(n, dy, span) == convert.mlpg_work_len(n, dy, span) == n * (2 * span + 2) * dy
     for n, dy, span in ((0, 1, 1), (1, 0, 1), (1, 65, 1), (1, 1, 0), (1, 1, 9), (2 ** 31 + 1, 1, 1), (-1, 1, 1)):
         assert lib.eaqhm_mlpg_work_len(n, dy, span) == -1, (n, dy, span)
     assert lib.eaqhm_ceps_delta(None, None, 1, 1, 1, None) == -1                       # no context: EAQHM_EINVAL, no device

@@ -1,6 +1,7 @@
 """The Python surface of the model layer (no GPU, no library load): the public names of `eaqhm_amd` and of
-`eaqhm_amd.model`, their signatures and docstrings, against tests/golden/python_api.json, and the import order of the
-modules behind model.py.
+`eaqhm_amd.model`, their signatures and docstrings, against tests/golden/python_api.json, the same for
+`eaqhm_amd.convert` against tests/golden/python_api_convert.json, and the import order of the modules behind model.py
+and behind convert.py.
 
 The fixture was recorded from the commit before model.py was split, from the repository root, by
 
@@ -33,7 +34,9 @@ from conftest import GOLDEN, ROOT
 PACKAGE = os.path.join(ROOT, "eaqhm-analysis-and-synthesis-in-python_amd")
 LAYERS = ("args", "records", "cepstrum", "align", "noise", "model")     # each imports only from the ones before it
 ALLOWED = {m: set(LAYERS[:i + 1]) for i, m in enumerate(LAYERS)}
-ALLOWED["convert"] = {"args", "records", "cepstrum", "align", "convert"}
+# the conversion branches off after align: neither noise nor model
+CONVERT_LAYERS = ("args", "records", "cepstrum", "align", "mixture", "dynamics", "mapping", "convert", "nonparallel")
+ALLOWED.update({m: set(CONVERT_LAYERS[:i + 1]) for i, m in enumerate(CONVERT_LAYERS) if i >= 4})
 
 # `import eaqhm_amd.<m>` runs the package's __init__ first, which imports model before anything else; so <m> is also
 # imported under a bare package (the directory on __path__, no __init__): then it is the first module of the package to
@@ -71,6 +74,27 @@ def test_public_surface_is_the_recorded_one():
         assert not changed, (m.__name__, changed)
     surface = recorded["eaqhm_amd.model"].values()
     assert sum("repr" in e for e in surface) == 14 and sum("signature" in e for e in surface) == 67
+
+
+def test_convert_surface_is_the_recorded_one():
+    """eaqhm_amd.convert against tests/golden/python_api_convert.json, recorded by the script above applied to convert,
+    from the commit before convert.py was split by layer; "underscore" lists that commit's single-underscore names, which
+    all stay attributes of convert.  "added" and "added_underscore" were written in by hand: what the split itself added."""
+    from eaqhm_amd import convert
+    with open(os.path.join(GOLDEN, "python_api_convert.json")) as f:
+        recorded = json.load(f)
+    assert sorted(recorded) == ["added", "added_underscore", "eaqhm_amd.convert", "underscore"]
+    surface = recorded["eaqhm_amd.convert"]
+    assert len(surface) == 59 and sum("signature" in e for e in surface.values()) == 39
+    assert sum("repr" in e for e in surface.values()) == 20 and len(recorded["underscore"]) == 18
+    assert sorted(recorded["added"]) == ["mlpg_work_len"] and not set(recorded["added"]) & set(surface)
+    now = {n: _entry(v) for n, v in vars(convert).items() if not n.startswith("_") and _own(v)}
+    want = dict(surface, **recorded["added"])
+    assert sorted(now) == sorted(want), set(now) ^ set(want)
+    changed = [n for n in want if now[n] != want[n]]
+    assert not changed, changed
+    missing = [n for n in recorded["underscore"] + recorded["added_underscore"] if not hasattr(convert, n)]
+    assert not missing, missing
 
 
 def test_each_module_imports_first():
