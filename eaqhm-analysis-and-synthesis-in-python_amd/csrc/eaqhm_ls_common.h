@@ -250,10 +250,12 @@ __device__ inline void toeplitz_rhs(const double* tab, int TB, int p, int b, int
 //          [2] / [3] pointers to the slot's fm / am window (track or bridged copy),
 //          [STRIDE-3] 1/(am_mid+eps), [STRIDE-2..STRIDE-1] rho = exp(j 2 pi fm_mid / fs)      (functions.py:508-518, :284-285)
 // masks: [n][nchs] nonzero masks of the 64-sample chunks of the slots with gaps, gappy: [n] flags (work space).
+// fstash (may be null): [n] the centre frequency of every gap-free slot as loaded here, -1 for the others — write_record
+// takes it from there instead of loading it a second time at the end of the frame.
 template <int STRIDE, int NWAVES>
 __device__ inline void prepare_slots(const LsArgs& A, double* Qf, double* Af, int Npad, double* ci,
                                      unsigned long long* masks, int* gappy, const int* mycols, int n, int N, int mid,
-                                     int c, int wl, bool seeds, int lane, int wave, int nchs) {
+                                     int c, int wl, bool seeds, int lane, int wave, int nchs, double* fstash = nullptr) {
   const double eps = 10e-5;  // functions.py:517
   const int nch = (N + 63) >> 6;
   const long long t0 = (long long)c - wl;
@@ -294,6 +296,7 @@ __device__ inline void prepare_slots(const LsArgs& A, double* Qf, double* Af, in
     ((const double**)(ci + j * STRIDE))[2] = g ? (Qf + (size_t)j * Npad) : (fm_all + trk);
     ((const double**)(ci + j * STRIDE))[3] = g ? (Af + (size_t)j * Npad) : (am_all + trk);
     if (!g) centre(j, fmc, amc);   // (a seeded slot 0 is never gap-free)
+    if (fstash) fstash[j] = g ? -1.0 : fmc;
   }
   if (!__syncthreads_or(anyg)) return;
   // slots with gaps: nonzero masks of every 64-sample chunk first, then the bridged window
@@ -354,6 +357,40 @@ __device__ inline double scan16(double x) {
   x += dpp_row<0x112>(x);  // row_shr:2
   x += dpp_row<0x114>(x);  // row_shr:4
   x += dpp_row<0x118>(x);  // row_shr:8
+  return x;
+}
+// Sum over each aligned group of 16 lanes, valid in the group's FIRST lane, in the pairing of the xor butterfly
+// (x += __shfl_xor(x, o), o = 8, 4, 2, 1): lane 0 adds lane 8, then lane 4 (which added lane 12), ... — the same additions,
+// operands swapped in some, so the same bits; row shifts in place of eight ds_bpermute_b32 through the LDS crossbar.
+__device__ inline double sum16_first(double x) {
+  x += dpp_row<0x108>(x);  // row_shl:8
+  x += dpp_row<0x104>(x);  // row_shl:4
+  x += dpp_row<0x102>(x);  // row_shl:2
+  x += dpp_row<0x101>(x);  // row_shl:1
+  return x;
+}
+// (x of rows 0 + 1) + (x of rows 2 + 3), lane by lane, valid in row 0 (lanes 0-15): what x += __shfl_xor(x, 16);
+// x += __shfl_xor(x, 32) leaves there, by the row and half swaps of gfx950 (vector ALU, no LDS crossbar).  Both operands of
+// a swap are x, so each result holds one row (half) of a pair twice whichever way the instruction hands them out.
+__device__ inline double sum4rows_first(double x) {
+  {
+    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(x), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(x), false, false);
+    x = __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
+  }
+  const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(x), false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(x), false, false);
+  return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
+}
+// Maximum of NON-NEGATIVE values over the wave, valid in lane 63: the zeros that the shifts and broadcasts bring in are
+// the identity, and a maximum does not depend on the order it is taken in.
+__device__ inline double max64_nonneg_last(double x) {
+  x = fmax(x, dpp_row<0x111>(x));  // row_shr:1, 2, 4, 8: lane 15 of every row holds the row's maximum
+  x = fmax(x, dpp_row<0x112>(x));
+  x = fmax(x, dpp_row<0x114>(x));
+  x = fmax(x, dpp_row<0x118>(x));
+  x = fmax(x, dpp_row<0x142>(x));  // row_bcast:15: lane 15 of a row to the next row
+  x = fmax(x, dpp_row<0x143>(x));  // row_bcast:31: lane 31 to the upper half
   return x;
 }
 
@@ -428,8 +465,15 @@ __device__ inline void cholesky_solve(double* __restrict__ Lt, int M, int ldl, d
 // Phase D: raw solution (optional), frequency mismatch (functions.py:297), amplitude floor and acceptance
 // (:309-315), record row (:316-324, :303).  xs = [amplitudes (Kc) | slopes (Kc)] interleaved complex in LDS;
 // sh needs 8 doubles (one partial maximum per wave at sh[1..]).
+// ROW (eaqhm_ls_tile.hip, where the stamps favour it): fstash holds the centre frequencies prepare_slots kept, -1 where the
+// slot has to go through track_fm; row is 3 Kmax + 1 doubles of LDS free in this phase — the record row is put together
+// there (zeros, then the accepted slots) and written out once, in order, instead of being zeroed and then scattered into
+// in global memory; the partial maxima come from row shifts.  With ROW the function does NOT end on a barrier: the caller
+// sees to it that nobody writes the row (nor fstash, by another thread than its reader) before the workgroup's next one.
+template <bool ROW = false>
 __device__ inline void write_record(const LsArgs& A, const double* xs, double* sh, const int* mycols, int f, int n,
-                                    int inst, int c, double f0, bool seeds) {
+                                    int inst, int c, double f0, bool seeds, const double* fstash = nullptr,
+                                    double* row = nullptr) {
   const int tid = threadIdx.x, nt = blockDim.x, Kc = 2 * n + 1;
   if (A.raw_amp) {
     // in the order the seam functions return them.  Adaptation 0: f0range = (-K..K) f0 (functions.py:189), while the
@@ -447,8 +491,14 @@ __device__ inline void write_record(const LsArgs& A, const double* xs, double* s
     double ar = xs[2 * (n + 1 + j)], ai = xs[2 * (n + 1 + j) + 1];
     amax = fmax(amax, sqrt(ar * ar + ai * ai));   // (amplitudes are O(1): no overflow to guard against)
   }
-  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
-  if ((tid & 63) == 0) sh[1 + (tid >> 6)] = amax;
+  if constexpr (ROW) {
+    amax = max64_nonneg_last(amax);
+    if ((tid & 63) == 63) sh[1 + (tid >> 6)] = amax;
+    for (int k = tid; k < 3 * A.Kmax; k += nt) row[k] = 0.0;   // ahead of the barrier the partial maxima need anyway
+  } else {
+    for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+    if ((tid & 63) == 0) sh[1 + (tid >> 6)] = amax;
+  }
   __syncthreads();
   amax = 0.0;
   for (int w = 0; w < (nt >> 6); ++w) amax = fmax(amax, sh[1 + w]);
@@ -457,8 +507,11 @@ __device__ inline void write_record(const LsArgs& A, const double* xs, double* s
   const double floor_mag = amax * 3.1622776601683795e-08;
   const double h = f0 / (double)(A.a_iter + 1);  // functions.py:310
   double* rec = A.records + (size_t)inst * (3 * A.Kmax + 1);
-  for (int k = tid; k < 3 * A.Kmax; k += nt) rec[k] = 0.0;
-  __syncthreads();
+  double* dst = ROW ? row : rec;
+  if constexpr (!ROW) {
+    for (int k = tid; k < 3 * A.Kmax; k += nt) rec[k] = 0.0;
+    __syncthreads();
+  }
   for (int j = tid; j < n; j += nt) {
     const int k = (A.mode == 0) ? j : mycols[j];
     double ar = xs[2 * (n + 1 + j)], ai = xs[2 * (n + 1 + j) + 1];
@@ -467,19 +520,21 @@ __device__ inline void write_record(const LsArgs& A, const double* xs, double* s
     double eta = 0.0;
     if (A.mode == 1) eta = A.fs / (2.0 * M_PI) * ((ar * bi - ai * br) / (mag * mag));  // functions.py:297
     if (mag > floor_mag && fabs(eta) < h) {
-      rec[k] = mag;
-      rec[2 * A.Kmax + k] = atan2(ai, ar);
+      dst[k] = mag;
+      dst[2 * A.Kmax + k] = atan2(ai, ar);
       double fmv;
       if (A.mode == 0) fmv = (double)(k + 1) * f0;
       else {
-        double cur = track_fm(A, k, c, c, seeds);
+        double cur = (ROW && fstash[j] >= 0.0) ? fstash[j] : track_fm(A, k, c, c, seeds);
         fmv = (f0 > A.f0min) ? cur + eta : cur;
       }
-      rec[A.Kmax + k] = fmv;
+      dst[A.Kmax + k] = fmv;
     }
   }
-  if (tid == 0) rec[3 * A.Kmax] = xs[2 * n];  // Re(a_DC) (functions.py:303)
+  if (tid == 0) dst[3 * A.Kmax] = xs[2 * n];  // Re(a_DC) (functions.py:303)
   __syncthreads();
+  if constexpr (ROW)
+    for (int k = tid; k <= 3 * A.Kmax; k += nt) rec[k] = row[k];
 }
 
 }  // namespace eaqhm

@@ -40,6 +40,7 @@
 #include "eaqhm_ls_tilemap.h"
 #include "eaqhm_ls_twunits.h"
 #include "eaqhm_ls_gather.h"
+#include "eaqhm_ls_tilelds.h"
 
 namespace eaqhm {
 bool ls_a0tile_fits(const LsArgs& A);                 // eaqhm_ls_a0tile.hip
@@ -50,10 +51,26 @@ int launch_ls_a0tile(eaqhm_ctx* ctx, LsArgs A);
 #define TL_THREADS 512
 #define TL_WAVES 8
 #define TL_CW 8         // all waves own tiles
-#define TL_NTMAX 13
-#define CI_STRIDE 20    // per-slot info: 16 chunk carries, qmid, 1/(am_mid+eps), rho.re, rho.im
-#define CI_NCH 16
+// (TL_NTMAX, CI_STRIDE, CI_NCH, TL_NSLOT and the LDS budget: eaqhm_ls_tilelds.h)
+static_assert(TLL_TILE == TL_TILE && TLL_DG_TILE == DG_TILE, "eaqhm_ls_tilelds.h and eaqhm_ls_chol.h disagree");
 // (adaptation 0: closed-form Gramian and two real systems — A0_NS, A0_M, TZ_TB, TZ_NCH and a0_frame in eaqhm_ls_a0.h)
+
+// The next frame's header, by one wave (see TlHead); the barrier that follows publishes it.
+__device__ inline void fetch_next_header(const LsArgs& A, TlHead* hd, int C, int nbuf, int lane) {
+  int* cls = uni(A.cls);
+  int item = 0;
+  if (lane == 0) item = atomicAdd(cls + 8 + C, 1);
+  item = uni(item);
+  int f = -1;
+  if (item < uni(cls[C])) f = uni(cls[16 + (size_t)C * uni(A.n_frames) + item]);
+  if (f >= 0) {
+    const int* tab = (lane == 0) ? A.ncol : (lane == 1) ? A.frame_c : (lane == 2) ? A.frame_wl : A.frame_inst;
+    if (lane < 4) (&hd->n)[lane] = tab[f];
+    const int Kmax = uni(A.Kmax);
+    if (lane < TL_NSLOT && lane < Kmax) hd->cols[nbuf][lane] = A.cols[(size_t)f * Kmax + lane];   // (the frame's row of `cols` has Kmax entries)
+  }
+  if (lane == 0) { hd->f = f; hd->buf = nbuf; hd->cls = C; }
+}
 
 // One frame with NS tiles per wave.  Not inlined: each register budget gets its own register allocation (inlining
 // the five budgets into one kernel body spills several hundred VGPRs).
@@ -139,14 +156,25 @@ __device__ inline void twu_edge_k4(d4 (&g0)[2], d4 (&g1)[2], double aR, double a
 // Packed tables (TWU_PACKED[TB]; classes whose last basis tile column E = T - 1 has at most 8 live columns): the chunk holds
 // that tile column as [x_e | n x_e], so E^H X_J carries weights 0 and 1 of the pair (E, J) in its upper and lower eight rows
 // and E^H (n X_J) weights 1 and 2 — two edge units in place of three — and the corner E^H E, one H unit, all three.
+// f_ >= 0: the frame, fetched by the caller (who set buf = 1 in the workgroup's TlHead).  f_ < 0: the frame whose header
+// the previous one left there.  The frame's class, whose cursor the next header is drawn from, is the one that runs this register budget.
 template <int NS, int TW, int UA = 0, int UB = 0, int TB = 0>
 __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, int ldx_max_, double* lds, int f_) {
-  const int TS = uni(TS_), ldx_max = uni(ldx_max_), f = uni(f_);
+  constexpr int C = NS == 12 ? 5 : NS == 10 ? 4 : NS == 9 ? 3 : NS == 7 ? 2 : NS == 6 ? 1 : 0;   // (RUN_CLASS in the kernel)
+  static_assert(NS == 12 || NS == 10 || NS == 9 || NS == 7 || NS == 6 || NS == 5, "a register budget per class");
+  // What each budget keeps of the serial-phase changes is what its class gained by more than three times the run-to-run
+  // spread (profiles/serial_phases): the next frame's header everywhere but at 12 tile rows, the record row
+  // in LDS at 11 tile rows only.
+  constexpr bool NEXT_HEAD = NS != 10, REC_ROW = NS == 9;
+  const bool pre = uni(f_) < 0;
+  const int TS = uni(TS_), ldx_max = uni(ldx_max_);
   const int tid = threadIdx.x, nt_thr = TL_THREADS;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // ---- LDS carve-up: region U is the basis chunk (+ slot info) in the Gramian phase, tile storage afterwards
   double* U = uni(lds);
+  TlHead* hd = (TlHead*)(U + tl_head_offset());      // (behind the tile storage: xv + 32 below)
+  const int f = pre ? uni(hd->f) : uni(f_);
   double* Xre = U;
   double* Xim = Xre + (size_t)TS * ldx_max;
   const size_t usize_g = (size_t)2 * TS * ldx_max;
@@ -162,8 +190,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
   double* Zc = Dc + DG_TILE;                         // [DG_TILE]   its inverse in the making
   double* zv = Zc + DG_TILE;                        // 2*16*NT
   double* xv = zv + 2 * 16 * TL_NTMAX;               // 2*16
-  const size_t usize_c = (size_t)(xv + 32 - U);
-  double* xs = U + usize_c;                          // 4*Kcmax   solution in natural order
+  double* xs = xv + 32 + TL_HEAD_DOUBLES;            // 4*Kcmax   solution in natural order
   double* sh = xs + 4 * uni(A.Kcmax);                // 16
   double* win = sh + 16;                             // [64*CI_NCH] analysis window of the frame
   double* sig = win + 64 * CI_NCH;                   // [64*CI_NCH] signal window of the frame
@@ -172,7 +199,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
   const int Npad = ((uni(A.Nmax) + 63) >> 6) << 6;
   double* Qs = uni(A.scratch) + (size_t)blockIdx.x * (size_t)uni((int)A.scratch_stride);  // bridged fm[j][t]
   double* Rs = Qs + (size_t)Npad * uni(A.nmax);                                           // bridged am[j][t]
-  const bool seeds = uni((int)(A.any_seed && (*A.any_seed != 0))) != 0;
+  const bool seeds = uni(hd->seeds) != 0;            // (A.any_seed && *A.any_seed != 0, read once by the kernel)
   // phases are q * (2 pi / fs) here, (2 pi q) / fs in the reference (functions.py:513, :453): one rounding each way,
   // <= 2 ulp of the phase apart, and no IEEE division per basis sample
   const double w1 = uni(2.0 * M_PI / A.fs);
@@ -183,10 +210,11 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
   unsigned long long t_prev = 0;
 
   {
-    const int n = uni(A.ncol[f]);
+    const int n = pre ? uni(hd->n) : uni(A.ncol[f]);
     const int Kc = 2 * n + 1, Ms = 2 * Kc + 1;   // stacked columns incl. the signal
     const int nt = (Ms + 15) >> 4;
-    const int c = uni(A.frame_c[f]), wl = uni(A.frame_wl[f]), inst = uni(A.frame_inst[f]);
+    const int c = pre ? uni(hd->c) : uni(A.frame_c[f]), wl = pre ? uni(hd->wl) : uni(A.frame_wl[f]);
+    const int inst = pre ? uni(hd->inst) : uni(A.frame_inst[f]);
     const int N = 2 * wl + 1, mid = wl;
     const int T = (Kc + 16) >> 4;                      // three-weight basis: tile columns of X = w [E2 | s]
     constexpr int UN = UA + UB;                        // unit slots of a wave
@@ -202,19 +230,32 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     const int npair = T * (T + 1) / 2;
     const int is = 2 * Kc - 16 * (nt - 1);  // position of the signal column inside the last tile row (2,6,10,14)
     const double f0 = uni(A.f0_stale);
-    const int* mycols = uni(A.cols) + (size_t)f * uni(A.Kmax);
+    const int* mycols = pre ? (const int*)hd->cols[uni(hd->buf)] : uni(A.cols) + (size_t)f * uni(A.Kmax);
     const int npairs = mid + 1;  // pairs e = 0..mid: (u, v) = (e-1, N-1-e)
 
-    if (dbg && tid == 0) t_prev = __builtin_amdgcn_s_memtime();
-    // region U may hold tiles of the previous frame: make the basis chunk finite and its padding zero
-    for (int q = tid; q < 2 * TS * ldx_max; q += nt_thr) Xre[q] = 0.0;
-    for (int t = tid; t < N; t += nt_thr) {
-      win[t] = window_value(false, t, N);
-      sig[t] = sA[(size_t)(c - wl) + t];
+    if (dbg && tid == 0) {   // slot 11: from the previous frame's last stamp to here (the hand-out, the call, the header)
+      t_prev = __builtin_amdgcn_s_memtime();
+      if (hd->t_last && !uni((int)A.debug_diag)) atomicAdd(dbg + 11, t_prev - hd->t_last);
     }
-    __syncthreads();
+    // The signal window is requested first and stored last: its round trip runs under the window values and the zeroing.
+    // No barrier of its own: prepare_slots writes none of this and ends on a barrier.
+    double sv[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int t = tid + r * nt_thr;
+      sv[r] = (t < N) ? sA[(size_t)(c - wl) + t] : 0.0;
+    }
+    // region U may hold tiles of the previous frame: make the basis chunk finite and its padding zero — the TS x ldx
+    // cells of either plane that this frame's class writes and reads
+    for (int q = tid; q < TS * ldx; q += nt_thr) { Xre[q] = 0.0; Xim[q] = 0.0; }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int t = tid + r * nt_thr;
+      if (t < N) { win[t] = window_value(false, t, N); sig[t] = sv[r]; }
+    }
     int* gappy = (int*)(masks + (size_t)52 * CI_NCH);   // [52] flags
-    prepare_slots<CI_STRIDE, TL_WAVES>(A, Qs, Rs, Npad, ci, masks, gappy, mycols, n, N, mid, c, wl, seeds, lane, wave, CI_NCH);
+    prepare_slots<CI_STRIDE, TL_WAVES>(A, Qs, Rs, Npad, ci, masks, gappy, mycols, n, N, mid, c, wl, seeds, lane, wave, CI_NCH,
+                                       REC_ROW ? hd->fmc : nullptr);
     LS_STAMP(0);
 
     // system tiles of this wave
@@ -816,6 +857,14 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
           }
         }
         LS_STAMP(8);
+        // Stage 0 has no trailing update: every wave but the owner of the first diagonal tile and its helper is about to
+        // wait at barrier A.  The first of them fetches the next frame's header meanwhile (TlHead).
+        // Its slot list goes to the buffer this frame's is not in.
+        if (NEXT_HEAD && jb == 0) {
+          int pfw = 0;
+          while (pfw == DIAG_OWNER(0, nt) || pfw == (int)TL_HELP[nt][0]) ++pfw;
+          if (wave == pfw) fetch_next_header(A, hd, C, uni(hd->buf) ^ 1, lane);
+        }
         // The helper wave builds the inverse (eaqhm_ls_tilemap.h) — AFTER its own trailing tiles: diag_D's posts wait for
         // it in LDS and it runs through them without the owner's pace, so its tiles are not what the stage ends on.
         if (!mine && wave == (int)TL_HELP[nt][jb])
@@ -893,8 +942,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             xr = wr * zr - wi * zi;
             xi = wr * zi + wi * zr;
           }
-#pragma unroll
-          for (int o = 8; o > 0; o >>= 1) { xr += __shfl_xor(xr, o); xi += __shfl_xor(xi, o); }
+          xr = sum16_first(xr); xi = sum16_first(xi);   // (the xor butterfly's additions, by row shifts)
           if (k == 0) {
             xv[2 * i] = xr; xv[2 * i + 1] = xi;
             const int q = 16 * P + i;   // natural order: amplitudes then slopes
@@ -913,8 +961,7 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             sr += lr * xr + li * xi;
             si += lr * xi - li * xr;
           }
-          sr += __shfl_xor(sr, 16); si += __shfl_xor(si, 16);
-          sr += __shfl_xor(sr, 32); si += __shfl_xor(si, 32);
+          sr = sum4rows_first(sr); si = sum4rows_first(si);   // ((s0 + s1) + (s2 + s3)) over the four row groups
           if (lq == 0) {
             zv[2 * (16 * tQ[sl] + lcol)] -= sr;
             zv[2 * (16 * tQ[sl] + lcol) + 1] -= si;
@@ -925,8 +972,15 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
       LS_STAMP(4);
     }
 
-    write_record(A, xs, sh, mycols, f, n, inst, c, f0, seeds);
+    // REC_ROW: the record row is put together where the chunk masks of the slot set-up lie, if it fits: dead tile storage
+    // now, and the next frame writes there only after its first barrier, so that no barrier is needed behind the row's
+    // way out (nothing else that write_record reads after its last barrier is written by the next frame's head).
+    if (REC_ROW && 3 * uni(A.Kmax) + 1 <= TL_NSLOT * CI_NCH)
+      write_record<true>(A, xs, sh, mycols, f, n, inst, c, f0, seeds, hd->fmc, (double*)masks);
+    else
+      write_record(A, xs, sh, mycols, f, n, inst, c, f0, seeds);
     LS_STAMP(5);
+    if (dbg && tid == 0) hd->t_last = t_prev;
   }
 }
 
@@ -991,13 +1045,24 @@ extern "C" __global__ void __launch_bounds__(256) eaqhm_ls_zero_prefix_kernel(co
 
 // One persistent launch for every frame size: each workgroup works through the size classes, largest first, with
 // the register budget (tiles per wave) of the class.
+// A frame of class C per turn.  Where the previous frame of the class left the next one's header (TlHead; mode 1 only), the
+// item comes from there; otherwise — a workgroup's first frame, the first one of a class — from the cursor, as the header's
+// was.  Every draw is used exactly once, and a workgroup draws one item past the end of each class, either way.
 extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(LsArgs A, int TS, int ldx_max) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int nxt;
+  TlHead* hd = (TlHead*)(lds + tl_head_offset());   // (mode 0: a0_frame lays the LDS out its own way, no header)
+  if (threadIdx.x == 0 && A.mode != 0) { hd->cls = -1; hd->t_last = 0ull; hd->seeds = (A.any_seed && *A.any_seed != 0) ? 1 : 0; }
+  __syncthreads();
 #define TW_UNITS(TB) 0, TWU_UA, TWU_UB, TB   /* template arguments TW, UA, UB, TB of a class that contracts units by table TB */
 #define RUN_CLASS(NSV, TWV, C)                                                             \
   for (;;) {                                                                             \
-    if (threadIdx.x == 0) nxt = atomicAdd(A.cls + 8 + C, 1);                             \
+    if (A.mode != 0 && hd->cls == C) {                                                   \
+      if (hd->f < 0) break;                                                              \
+      tile_frame<NSV, TWV>(A, TS, ldx_max, lds, -1);                                     \
+      continue;                                                                          \
+    }                                                                                    \
+    if (threadIdx.x == 0) { nxt = atomicAdd(A.cls + 8 + C, 1); if (A.mode != 0) hd->buf = 1; }   \
     __syncthreads();                                                                     \
     const int item = nxt;                                                                \
     __syncthreads();                                                                     \
@@ -1015,22 +1080,7 @@ extern "C" __global__ void __launch_bounds__(TL_THREADS) eaqhm_ls_tile_kernel(Ls
 #undef TW_UNITS
 }
 
-// dynamic LDS the kernel may ask for: it also has a static __shared__ word (the frame cursor), and dynamic + static must
-// fit the 160 KiB of a workgroup
-#define TL_LDS_LIMIT (159 * 1024)
-static size_t tl_usize_c() {
-  return (size_t)4 * TL_NTMAX * TL_TILE + 2 * TL_TILE + 2 * DG_TILE + 2 * 16 * TL_NTMAX + 32;
-}
-static size_t tl_usize_g(int TS, int ldx_max) { return (size_t)2 * TS * ldx_max + (size_t)CI_STRIDE * 52 + 52 * CI_NCH + 32; }
-static size_t tl_lds_doubles(int Kcmax, int TS, int ldx_max) {
-  const size_t c = tl_usize_c(), g = tl_usize_g(TS, ldx_max);
-  return (c > g ? c : g) + 4 * (size_t)Kcmax + 16 + 2 * 64 * CI_NCH + 16 * TL_NTMAX;
-}
-
-// the tile variant needs its LDS budget (which grows with Kmax through the solution vector) to fit
-bool ls_tile_applicable(int Kcmax, int Nmax) {
-  return Nmax <= 64 * CI_NCH && tl_lds_doubles(Kcmax, 32, 16 * TL_NTMAX + 16) * sizeof(double) <= TL_LDS_LIMIT;
-}
+bool ls_tile_applicable(int Kcmax, int Nmax) { return tl_applicable(Kcmax, Nmax); }   // (eaqhm_ls_tilelds.h)
 
 size_t ls_tile_scratch_stride(int nmax, int Nmax) {
   const size_t Npad = (size_t)((Nmax + 63) >> 6) << 6;
@@ -1064,6 +1114,7 @@ int launch_ls_tile(eaqhm_ctx* ctx, LsArgs A, int grid) {
   const int TS = 32;
   const size_t lds_bytes = tl_lds_doubles(Kcmax, TS, ldx_max) * sizeof(double);
   if (lds_bytes > TL_LDS_LIMIT) return ctx->fail(EAQHM_EINVAL, "eaqhm_ls_batch: LDS budget exceeded (tile variant)");
+  if (!tl_layout_ok(TS, ldx_max)) return ctx->fail(EAQHM_EINVAL, "eaqhm_ls_batch: LDS layout (tile variant)");
   if (a0_lds_doubles(A0_M, 2, TZ_TB, TZ_NCH, 520, 64 * CI_NCH, Kcmax) * sizeof(double) > lds_bytes)
     return ctx->fail(EAQHM_EINVAL, "eaqhm_ls_batch: LDS budget exceeded (adaptation 0, tile variant)");
   HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_ls_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));

@@ -17,8 +17,8 @@ names = ["setup + slot preparation", "build: barrier wait",
          "contraction: k loops + the chunk's closing barrier%s (a>=1) / closed-form fill (a=0)" % (" + gather" if diag else ""), "(end of factorisation)",
          "back substitution", "record", "wait at barrier A (the diagonal pipeline of another wave)", "panel (X = T W^H)",
          "trailing update (own tiles)", "-" if diag else "gather of the G_p tiles (three-weight classes; with --diag inside the contraction)", "barrier C wait + next diagonal tile's update + diagonal role (when wave 0 has one)",
-         "-", "build: basis rows (wave 0)"]
-tot = sum(d[:9]) + d[10] + d[12] + (0 if diag else d[9])
+         "-" if diag else "between two frames of a workgroup (hand-out, call, header of the frame)", "build: basis rows (wave 0)"]
+tot = sum(d[:9]) + d[10] + d[12] + (0 if diag else d[9] + d[11])
 for n, v in zip(names, d[:13]):
     print("%-90s %14d cycles  %5.1f%%" % (n, v, 100.0 * v / max(tot, 1)))
 if d[13]:
