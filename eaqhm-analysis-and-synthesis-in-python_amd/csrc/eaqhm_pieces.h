@@ -17,7 +17,8 @@ __device__ inline double spline_piece(double y0, double y1, double m0, double m1
 // so everything that does not depend on r is prepared once: no division and no array indexing per sample (a
 // wave that holds a single short-run interval runs both branches for all of its lanes).
 struct FmPiece {
-  int kind;  // 2: spline piece, 3: single cubic through 4 points (short run, functions.py:368-371)
+  int kind;  // 2: spline piece, 3: single cubic through 4 points (short run, functions.py:368-371; a polynomial of
+             // lower degree where pad instants are knots of the run comes as the cubic through 4 of its own points)
   double y0, y1, m0, m1, hinv, h2_6;
   double p0, p1, p2, p3, w0, w1, w2, w3, x0;  // nodes and weights y_p / prod_{q != p}(x_p - x_q) of the short-run cubic
   __device__ double operator()(int r) const {
@@ -56,6 +57,21 @@ __device__ inline FmPiece make_piece(const SlotT& S, int i, int ci) {
       const int row = pad ? p : (rs + p - npad);
       px[p] = pad ? (double)(p * step) : (double)row * h;
       py[p] = (pad && !(p < S.A.No_ti && S.code(p) != 0)) ? 0.0 : S.fm(row);
+    }
+    if (rs < npad) {
+      // Pad instants coincide with the run's own knots (a 2-run at 0-1 or 1-2, a 3-run at 0-2).  The nodes are then
+      // the instants 0 .. c-1, c = rs + m < 4 (pad instants below rs, then the knots), and the piece is the polynomial
+      // of degree c-1 through them.  It enters the four-node form by degree elevation: the instants
+      // c .. 3 become nodes that carry that polynomial's own values, so the cubic through all four is the polynomial.
+      const int c = rs + m;
+      double v[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) v[q] = (q < c && (q >= rs || S.code(q) != 0)) ? S.fm(q) : 0.0;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) px[p] = (double)(p * step);
+      py[0] = v[0]; py[1] = v[1];
+      py[2] = (c == 3) ? v[2] : 2.0 * v[1] - v[0];
+      py[3] = (c == 3) ? (v[0] - 3.0 * v[1]) + 3.0 * v[2] : 3.0 * v[1] - 2.0 * v[0];
     }
     P.p0 = px[0]; P.p1 = px[1]; P.p2 = px[2]; P.p3 = px[3];
     P.w0 = py[0] / ((px[0] - px[1]) * (px[0] - px[2]) * (px[0] - px[3]));
