@@ -66,7 +66,11 @@ or --conversion) puts every cepstrum of the model on the all-pass warped frequen
 MAP.npz, and --conversion MAP.npz fits at the map's axis (a map without the entry lies on the linear axis); a different
 explicit --cepstral-warp is an error.  The noise flags keep their linear rows.
 --pitch-device takes the pitch track of the analysis, and of the analyses of --envelope-from, --timing-from, --noise-from
-and --conversion-train, from the device (pitch.analysis_pitch_track) in place of the host's swipe.swipep."""
+and --conversion-train, from the device (pitch.analysis_pitch_track) in place of the host's swipe.swipep.
+--pitch-viterbi takes it from pitch.analysis_pitch_track_viterbi instead: the device's strengths, and
+the pitch along the best continuous path through them rather than at each instant's own maximum; it implies the device
+estimator.  --pitch-jump-cost C (4) is the cost of a jump per octave, and --pitch-unvoiced U (0.2 is a usual value) adds an
+unvoiced state with the score U per instant, so that the path decides voicing too; both need --pitch-viterbi."""
 import argparse
 
 import numpy as np
@@ -92,9 +96,15 @@ def cepstral_warp_argument(text):
 
 def analyse(path, gender, analysis_options):
     """eaQHMAnalysisAndSynthesis(path, gender, **analysis_options); with the entry pitch_device (--pitch-device) the pitch
-    track is pitch.analysis_pitch_track's."""
+    track is pitch.analysis_pitch_track's, with the entry pitch_viterbi (--pitch-viterbi: a dict of
+    analysis_pitch_track_viterbi's options, possibly empty) that function's."""
     options = dict(analysis_options)
-    if options.pop("pitch_device", False):
+    viterbi = options.pop("pitch_viterbi", None)
+    if viterbi is not None:
+        from .pitch import analysis_pitch_track_viterbi
+        options.pop("pitch_device", None)
+        options["pitch_track"] = analysis_pitch_track_viterbi(path, gender, options.get("fc", 0), **viterbi)
+    elif options.pop("pitch_device", False):
         from .pitch import analysis_pitch_track
         options["pitch_track"] = analysis_pitch_track(path, gender, options.get("fc", 0))
     return eaQHMAnalysisAndSynthesis(path, gender, **options)
@@ -114,6 +124,13 @@ def parser():
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--pitch-device", action="store_true",
                     help="SWIPE' on the device (pitch.analysis_pitch_track) for every analysis of this run")
+    ap.add_argument("--pitch-viterbi", action="store_true",
+                    help="the pitch along the best continuous path through the device's SWIPE' strengths "
+                         "(pitch.analysis_pitch_track_viterbi) for every analysis of this run; implies --pitch-device")
+    ap.add_argument("--pitch-jump-cost", type=float, default=None, metavar="C",
+                    help="with --pitch-viterbi: the cost of a pitch jump per octave, >= 0 (4)")
+    ap.add_argument("--pitch-unvoiced", type=float, default=None, metavar="U",
+                    help="with --pitch-viterbi: add an unvoiced state with the score U per instant (0.2 is a usual value)")
     ap.add_argument("--track-budget-mb", type=float, default=0.0,
                     help="long files: device memory for the dense tracks (streamed in time blocks, same results); 0 = automatic: "
                          "resident while they fit comfortably, streamed otherwise")
@@ -238,6 +255,15 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.noise_seed is not None and not a.noise:
         ap.error("--noise-seed needs --noise")
+    if (a.pitch_jump_cost is not None or a.pitch_unvoiced is not None) and not a.pitch_viterbi:
+        ap.error("--pitch-jump-cost and --pitch-unvoiced need --pitch-viterbi")
+    if a.pitch_viterbi:   # reject bad values before the analysis runs
+        from .pitch import _check_unvoiced, viterbi_costs
+        try:
+            viterbi_costs(3, **{k: v for k, v in viterbi_options(a).items() if k == "jump_cost"})
+            _check_unvoiced(a.pitch_unvoiced, 1.0)
+        except ValueError as e:
+            ap.error("--pitch-viterbi: %s" % e)
     if a.noise_formant and not a.noise:
         ap.error("--noise-formant needs --noise")
     warped = a.formant_warp_curve is not None or a.formant_vtln is not None
@@ -387,6 +413,8 @@ def main(argv=None):
                             track_budget_bytes=int(a.track_budget_mb * 2 ** 20) if a.track_budget_mb > 0 else "auto")
     if a.pitch_device:
         analysis_options["pitch_device"] = True
+    if a.pitch_viterbi:
+        analysis_options["pitch_viterbi"] = viterbi_options(a)
     on_axis = dict(cep_warp=axis) if axis != 0.0 else {}     # without the flag every call below is made without it
     s_recon, srer, det, t = analyse(a.wav, gender, analysis_options)
     if not a.no_write:
@@ -490,6 +518,16 @@ def main(argv=None):
                 wavfile.write(out, fs, np.float32(s_voc))
                 print("wrote", out)
     return 0
+
+
+def viterbi_options(a):
+    """The arguments of pitch.analysis_pitch_track_viterbi that --pitch-jump-cost and --pitch-unvoiced set."""
+    kw = {}
+    if a.pitch_jump_cost is not None:
+        kw["jump_cost"] = a.pitch_jump_cost
+    if a.pitch_unvoiced is not None:
+        kw["unvoiced"] = a.pitch_unvoiced
+    return kw
 
 
 def gv_options(a):

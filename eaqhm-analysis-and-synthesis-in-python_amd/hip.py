@@ -110,6 +110,12 @@ SYMBOLS_SWIPE = (
     ("eaqhm_swipe_pick", C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F64, _P, _P, _P, _P, _I32, _P, _P,
                                     _P]),
 )
+# every symbol include/eaqhm_viterbi.h declares: likewise
+SYMBOLS_VITERBI = (
+    ("eaqhm_viterbi_forward", C.c_int, [_P, _P, _I32, _I64, _P, _I32, _I32, _F64, _F64, _P, _P, _P]),
+    ("eaqhm_viterbi_backtrack", C.c_int, [_P, _P, _P, _P, _I32, _I64, _P]),
+    ("eaqhm_viterbi_refine", C.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P, _I32, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -133,7 +139,7 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, res, args in (SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM
-                            + SYMBOLS_NN + SYMBOLS_SWIPE):
+                            + SYMBOLS_NN + SYMBOLS_SWIPE + SYMBOLS_VITERBI):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -444,6 +450,20 @@ class Context:
                                            (_I32 * n)(*[w[2] for w in windows]), (_I64 * n)(*[w[3] for w in windows]),
                                            ptrs(4), ptrs(5), _ptr(t), T, npc, float(pc0), _ptr(ntc), _ptr(nftc),
                                            _ptr(ptab), _ptr(nf), nfmax, _ptr(p), _ptr(s), _ptr(S)))
+
+    # the continuous pitch track: S [npc][T], cost [W + 1] on the device, bp int16 [T][npc + 1], tilemap
+    # int16 [ceil(T / 8)][npc + 1], last [npc + 1], q int32 [T]; unvoiced is None or (uv, vcost)
+    def viterbi_forward(self, S, npc, T, cost, W, unvoiced, bp, tilemap, last):
+        uv, vcost = unvoiced or (0.0, 0.0)
+        self._ck(self.lib.eaqhm_viterbi_forward(self.h, _ptr(S), npc, T, _ptr(cost), W, int(unvoiced is not None),
+                                                float(uv), float(vcost), _ptr(bp), _ptr(tilemap), _ptr(last)))
+
+    def viterbi_backtrack(self, bp, tilemap, last, npc, T, q):
+        self._ck(self.lib.eaqhm_viterbi_backtrack(self.h, _ptr(bp), _ptr(tilemap), _ptr(last), npc, T, _ptr(q)))
+
+    def viterbi_refine(self, S, q, npc, T, pc, ntc, nftc, ptab, nf, nfmax, p, s):
+        self._ck(self.lib.eaqhm_viterbi_refine(self.h, _ptr(S), _ptr(q), npc, T, _ptr(pc), _ptr(ntc), _ptr(nftc),
+                                               _ptr(ptab), _ptr(nf), nfmax, _ptr(p), _ptr(s)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

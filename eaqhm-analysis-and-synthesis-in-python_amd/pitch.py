@@ -6,6 +6,12 @@
     analysis_pitch_track(speechFile, gender, fc=0, *, device_index=0) -> the track the analysis would compute for the
         file, ready for pitch_track= / pitch_tracks=[...]
     check_swipe_arguments(x, fs, plim) -> (x float64[n], fs, (lo, hi)): validation, no device work
+    swipep_viterbi(x, fs, plim, *, jump_cost=4.0, free_jump=1/48, max_jump=0.5, unvoiced=None, voicing_cost=1.0, ...)
+        -> the same layout, the pitch taken along the best CONTINUOUS path through the strengths
+    viterbi_costs(npc, jump_cost, free_jump, max_jump) -> the cost of a step of k candidates, float64[W + 1]
+    viterbi_track(S, cost, *, unvoiced=None, voicing_cost=1.0) -> (q int32[T], last float64[npc + 1]): the decode alone,
+        over any host matrix
+    analysis_pitch_track_viterbi(speechFile, gender, fc=0, **options) -> analysis_pitch_track with swipep_viterbi
 
 This module is reached as eaqhm_amd.pitch; the package does not re-export it, and the analysis keeps calling swipe.swipep
 unless it is handed a track.
@@ -28,6 +34,9 @@ SWIPE_WINDOW_MAX = 8192        # EAQHM_SWIPE_WMAX
 SWIPE_ERB_MAX = 1024           # EAQHM_SWIPE_EMAX
 SWIPE_WINDOWS_MAX = 8          # EAQHM_SWIPE_WINDOWS
 SWIPE_FINE_MAX = 64            # EAQHM_SWIPE_FINE
+VITERBI_TILE = 8               # EAQHM_VITERBI_TILE
+VITERBI_NPC_MAX = 1024         # EAQHM_VITERBI_NPC
+VITERBI_JUMP_MAX = 256         # EAQHM_VITERBI_JUMP
 _PLANS, _KERNELS, _DEVICE_PLANS = OrderedDict(), OrderedDict(), OrderedDict()
 _CACHED = 8                    # plans, kernel matrices and device copies kept
 
@@ -262,3 +271,181 @@ def analysis_pitch_track(speechFile, gender, fc=0, *, device_index=0):
     fs, s = prologue.read_signal(speechFile, fc)
     f0min, f0max = prologue.pitch_limits(gender)
     return swipep_device(s, fs, [f0min, f0max], device_index=device_index)
+
+
+# ---- the continuous track
+def _number(v, name, lo=None):
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, v)) from None
+    if not np.isfinite(v) or (lo is not None and v < lo):
+        raise ValueError("%s must be finite%s, got %r" % (name, "" if lo is None else " and >= %g" % lo, v))
+    return v
+
+
+def viterbi_costs(npc, jump_cost=4.0, free_jump=1 / 48, max_jump=0.5):
+    """The cost of a step of k candidates between neighbouring instants, float64[W + 1].  The arguments are in octaves
+    per step (a candidate is 1/96 octave): jump_cost >= 0 per octave beyond the free part, 0 <= free_jump <= max_jump.
+        W = min(npc - 1, 256, max(0, round(96 max_jump))), k0 = round(96 free_jump), cost[k] = jump_cost max(0, k - k0) / 96
+    ValueError for anything else, and for npc outside [3, 1024]."""
+    npc = _candidates(npc)
+    jump_cost = _number(jump_cost, "jump_cost", 0)
+    free_jump = _number(free_jump, "free_jump", 0)
+    max_jump = _number(max_jump, "max_jump", 0)
+    if free_jump > max_jump:
+        raise ValueError("free_jump %g exceeds max_jump %g" % (free_jump, max_jump))
+    W = min(npc - 1, VITERBI_JUMP_MAX, max(0, int(round(96 * min(max_jump, 1e6)))))
+    k0 = int(round(96 * min(free_jump, 1e6)))
+    return jump_cost * np.maximum(0, np.arange(W + 1) - k0) / 96
+
+
+def _candidates(npc):
+    if isinstance(npc, bool) or not isinstance(npc, (int, np.integer)):
+        raise ValueError("npc must be an integer, got %r" % (npc,))
+    if not 3 <= npc <= VITERBI_NPC_MAX:
+        raise ValueError("%d pitch candidates: the decode takes 3 to %d" % (npc, VITERBI_NPC_MAX))
+    return int(npc)
+
+
+def _check_cost(cost, npc):
+    cost = np.asarray(cost)
+    if cost.ndim != 1 or cost.dtype == object or not np.issubdtype(cost.dtype, np.number) or np.iscomplexobj(cost):
+        raise ValueError("cost must be a 1-D array of real numbers")
+    cost = np.ascontiguousarray(cost, dtype=np.float64)
+    if not 1 <= len(cost) <= min(npc - 1, VITERBI_JUMP_MAX) + 1:
+        raise ValueError("cost has %d entries: 1 to min(npc - 1, %d) + 1 = %d are possible"
+                         % (len(cost), VITERBI_JUMP_MAX, min(npc - 1, VITERBI_JUMP_MAX) + 1))
+    if not (np.isfinite(cost).all() and (cost >= 0).all()):
+        raise ValueError("cost must be finite and >= 0")
+    return cost
+
+
+def _check_unvoiced(unvoiced, voicing_cost):
+    """None, or (uv, vcost) as floats."""
+    if unvoiced is None:
+        return None
+    return _number(unvoiced, "unvoiced"), _number(voicing_cost, "voicing_cost", 0)
+
+
+def _device_index(device_index):
+    if isinstance(device_index, bool) or not isinstance(device_index, (int, np.integer)) or device_index < 0:
+        raise ValueError("device_index must be a non-negative integer, got %r" % (device_index,))
+    return int(device_index)
+
+
+def _decode(torch, c, dev, S_d, npc, T, cost, unvoiced):
+    """Forward and backtrack over the device matrix S_d: (q int32[T], last float64[npc + 1]) on the device."""
+    ntiles = -(-T // VITERBI_TILE)
+    cost_d = torch.as_tensor(cost, device=dev)
+    bp = torch.empty((T, npc + 1), dtype=torch.int16, device=dev)
+    tilemap = torch.empty((ntiles, npc + 1), dtype=torch.int16, device=dev)
+    last = torch.empty(npc + 1, dtype=torch.float64, device=dev)
+    q = torch.empty(T, dtype=torch.int32, device=dev)
+    c.viterbi_forward(S_d, npc, T, cost_d, len(cost) - 1, unvoiced, bp, tilemap, last)
+    c.viterbi_backtrack(bp, tilemap, last, npc, T, q)
+    return q, last
+
+
+def viterbi_track(S, cost, *, unvoiced=None, voicing_cost=1.0, device_index=0):
+    """The best path through S float64[npc, T] (any host matrix: SWIPE' strengths, or those plus a term of the caller's)
+    under the step costs `cost` (viterbi_costs, or any finite table >= 0 of at most min(npc - 1, 256) + 1 entries): the
+    path maximises the sum of S[q[t], t] minus cost[|q[t] - q[t-1]|], steps beyond len(cost) - 1 candidates excluded.
+    With `unvoiced` = the score of an unvoiced instant, state npc is "unvoiced", entered and left at voicing_cost.
+    Returns (q int32[T], last float64[npc + 1]): the path and the scores of the last instant, last[npc] = -inf without
+    the unvoiced state.  The recurrence and its tie rules are DESIGN.md §13.1; the same bits on every call."""
+    S = np.asarray(S)
+    if S.ndim != 2 or S.dtype == object or not np.issubdtype(S.dtype, np.number) or np.iscomplexobj(S):
+        raise ValueError("S must be a 2-D array of real numbers [candidates, instants]")
+    npc = _candidates(S.shape[0])
+    T = S.shape[1]
+    if not 1 <= T < 2 ** 31:
+        raise ValueError("S has %d instants, 1 to 2^31 - 1 are possible" % T)
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if not np.isfinite(S).all():
+        raise ValueError("S must be finite")
+    cost = _check_cost(cost, npc)
+    unvoiced = _check_unvoiced(unvoiced, voicing_cost)
+    device_index = _device_index(device_index)
+    from .records import _device
+    torch, c, dev = _device(device_index)
+    q, last = _decode(torch, c, dev, torch.as_tensor(S, device=dev), npc, T, cost, unvoiced)
+    return q.cpu().numpy(), last.cpu().numpy()
+
+
+def fill_unvoiced(p, voiced, default):
+    """The pitch column of a track with unvoiced instants: an unvoiced instant carries the pitch of the nearest EARLIER
+    voiced instant, else of the next later one; without any voiced instant `default` everywhere."""
+    p = np.array(p, dtype=np.float64)
+    voiced = np.asarray(voiced, dtype=bool)
+    at = np.flatnonzero(voiced)
+    if len(at) == 0:
+        p[:] = default
+        return p
+    i = np.searchsorted(at, np.arange(len(p)), side="right") - 1      # the last voiced instant at or before each
+    return p[at[np.maximum(i, 0)]]
+
+
+def _strengths_on_device(x, plan, torch, c, dev):
+    """swipep_device's three stages with the strength matrix kept: S float64[npc, T] on the device."""
+    on = _device_plan(plan, torch, dev)
+    x_d = torch.as_tensor(x, device=dev)
+    fs, nE, T, npc = plan["fs"], len(plan["fERBs"]), len(plan["t"]), len(plan["pc"])
+    wins = []
+    for w, w_d in zip(plan["windows"], on["windows"]):
+        L = torch.empty((w["nframes"], nE), dtype=torch.float64, device=dev)
+        Si = torch.empty((w["ncand"], w["nframes"]), dtype=torch.float64, device=dev)
+        c.swipe_loudness(x_d, len(x), w["w"], w["hop"], w["pad"], w["nframes"], w_d["window"], fs, w["sumw2"], w_d["lo"],
+                         w_d["xlo"], w_d["df"], nE, L, nE)
+        c.swipe_scores(w_d["K"], w["ncand"], nE, L, w["nframes"], nE, nE, Si)
+        wins.append((Si, w["j0"], w["ncand"], w["nframes"], w_d["mu"], w_d["tshift"]))
+    ps = torch.empty((2, T), dtype=torch.float64, device=dev)
+    S = torch.empty((npc, T), dtype=torch.float64, device=dev)
+    c.swipe_pick(wins, on["t"], T, npc, plan["pc"][0], on["ntc"], on["nftc"], on["ptab"], on["nf"], plan["nfmax"], ps[0],
+                 ps[1], S)
+    return on, S
+
+
+def swipep_viterbi(x, fs, plim, *, jump_cost=4.0, free_jump=1 / 48, max_jump=0.5, unvoiced=None, voicing_cost=1.0,
+                   device_index=0, return_path=False):
+    """swipep_device's track with the pitch taken along the best continuous path through the strengths instead of at
+    each instant's own maximum: float64[T, 3] [time s, pitch Hz, strength], the time column bit for
+    bit swipep's.  A step of k candidates costs viterbi_costs(npc, jump_cost, free_jump, max_jump)[k].  With `unvoiced`
+    (the score of an unvoiced instant, 0.2 is a usual value) the path decides voicing too, at voicing_cost a change; an
+    unvoiced instant carries the pitch of the nearest earlier voiced instant (else of the next later one) and strength
+    0, and a track without a voiced instant carries pc[0].  On the path the pitch and strength are swipep's refinement
+    of the path's candidate; on an edge candidate they are that candidate's pitch and strength (swipep maps both edges
+    to pc[0]).  The strengths stay on the device; only the result comes back.  With return_path=True:
+    (track, q int32[T] with len(pc) for unvoiced, voiced bool[T])."""
+    x, fs, plim = check_swipe_arguments(x, fs, plim)
+    plan = swipe_plan(len(x), fs, plim)
+    npc, T = len(plan["pc"]), len(plan["t"])
+    if npc > VITERBI_NPC_MAX:
+        raise ValueError("plim [%g, %g] gives %d pitch candidates, the limit of the decode is %d"
+                         % (plim[0], plim[1], npc, VITERBI_NPC_MAX))
+    cost = viterbi_costs(npc, jump_cost, free_jump, max_jump)
+    unvoiced = _check_unvoiced(unvoiced, voicing_cost)
+    device_index = _device_index(device_index)
+    from .records import _device
+    torch, c, dev = _device(device_index)
+    on, S = _strengths_on_device(x, plan, torch, c, dev)
+    q, _ = _decode(torch, c, dev, S, npc, T, cost, unvoiced)
+    if "pc" not in on:
+        on["pc"] = torch.as_tensor(np.ascontiguousarray(plan["pc"]), device=dev)
+    ps = torch.empty((2, T), dtype=torch.float64, device=dev)
+    c.viterbi_refine(S, q, npc, T, on["pc"], on["ntc"], on["nftc"], on["ptab"], on["nf"], plan["nfmax"], ps[0], ps[1])
+    ps_h, q_h = ps.cpu().numpy(), q.cpu().numpy()
+    voiced = q_h < npc
+    track = np.column_stack((plan["t"], fill_unvoiced(ps_h[0], voiced, plan["pc"][0]), ps_h[1]))
+    return (track, q_h, voiced) if return_path else track
+
+
+def analysis_pitch_track_viterbi(speechFile, gender, fc=0, *, device_index=0, **options):
+    """analysis_pitch_track with swipep_viterbi in place of swipep_device; `options` are swipep_viterbi's (jump_cost,
+    free_jump, max_jump, unvoiced, voicing_cost).  Hand the result over as pitch_track= (or in pitch_tracks=[...])."""
+    if "return_path" in options:
+        raise ValueError("analysis_pitch_track_viterbi returns the track alone: no return_path")
+    from . import prologue
+    fs, s = prologue.read_signal(speechFile, fc)
+    f0min, f0max = prologue.pitch_limits(gender)
+    return swipep_viterbi(s, fs, [f0min, f0max], device_index=device_index, **options)

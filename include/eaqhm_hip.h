@@ -527,6 +527,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_nn.h"
 /* the SWIPE' pitch estimator's loudness, scores and pick stages (additions under ABI 6): declared in eaqhm_swipe.h. */
 #include "eaqhm_swipe.h"
+/* the continuous pitch track: Viterbi forward pass, backtrack and refinement (additions under ABI 6): declared in eaqhm_viterbi.h. */
+#include "eaqhm_viterbi.h"
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--swipe] [--out FILE]
+                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--swipe] [--viterbi] [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -52,6 +52,9 @@ same device, with the fraction of the FP64 matrix peak at 2 nA nB D flops.
 ([160, 300]) and at [70, 500]: each of the three kernels per window size, the whole swipep_device call from a host array
 to the host result as wall time with a cold and with a cached plan, and swipe.swipep in the same process (one run after
 one warm-up), with the number of instants whose pitch differs.
+--viterbi times the continuous pitch track on the same signals and limits: the forward pass (without and
+with the unvoiced state, also per step in cycles), the backtrack and the refinement, and the whole swipep_viterbi call with
+a cached plan next to swipep_device and to swipe.swipep in the same process.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -429,6 +432,81 @@ def swipe_rows(torch, workloads, reps=20, runs=3):
                              host_over_device_cached=round(host / cached[2], 2),
                              pitch_differs=int((got[:, 1] != ref[:, 1]).sum()),
                              strength_max_abs_diff=float(np.abs(got[:, 2] - ref[:, 2]).max())))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def viterbi_rows(torch, workloads, reps=20, runs=3):
+    """The continuous pitch track on the 60 s synthetic signals at [160, 300] and [70, 500]: the forward
+    pass, the backtrack (both launches) and the refinement as the median of `runs` warmed HIP-event windows of `reps`
+    launches with their max - min, without and with the unvoiced state; the forward pass per step in ns and in cycles of
+    the device's clock; the whole pitch.swipep_viterbi call (host array in, host track out) with the plan cached (median
+    of five) next to pitch.swipep_device and to swipe.swipep on this host in the same process (one run after one
+    warm-up); and what the path changes: steps of more than 8 candidates, raw and along the path."""
+    from eaqhm_amd import pitch
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.swipe import swipep
+    from eaqhm_amd.synth import synth_speech_int16
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        return out, time.perf_counter() - t0
+
+    rows = []
+    for wl in workloads:
+        fs = {"synth16k_60s": 16000, "synth48k_60s": 48000}[wl]
+        x = synth_speech_int16(60.0, fs) / 32768.0
+        for plim in ((160, 300), (70, 500)):
+            pitch.swipep_viterbi(x, fs, plim)                                   # the plan, its device copy, the code objects
+            got, _ = wall(lambda: pitch.swipep_viterbi(x, fs, plim, return_path=True))
+            cached = sorted(wall(lambda: pitch.swipep_viterbi(x, fs, plim))[1] for _ in range(5))
+            cached_uv = sorted(wall(lambda: pitch.swipep_viterbi(x, fs, plim, unvoiced=0.2))[1] for _ in range(5))
+            device = sorted(wall(lambda: pitch.swipep_device(x, fs, plim))[1] for _ in range(5))
+            swipep(x, fs, list(plim))
+            ref, host = wall(lambda: swipep(x, fs, list(plim)))
+            plan = pitch.swipe_plan(len(x), float(fs), plim)
+            on, S = pitch._strengths_on_device(x, plan, torch, dev=dev, c=c)
+            T, npc = len(plan["t"]), len(plan["pc"])
+            cost = pitch.viterbi_costs(npc)
+            cost_d = torch.as_tensor(cost, device=dev)
+            ntiles = -(-T // pitch.VITERBI_TILE)
+            bp = torch.empty((T, npc + 1), dtype=torch.int16, device=dev)
+            tm = torch.empty((ntiles, npc + 1), dtype=torch.int16, device=dev)
+            last = torch.empty(npc + 1, dtype=torch.float64, device=dev)
+            q = torch.empty(T, dtype=torch.int32, device=dev)
+            ps = torch.empty((2, T), dtype=torch.float64, device=dev)
+            pc_d = torch.as_tensor(np.ascontiguousarray(plan["pc"]), device=dev)
+            W = len(cost) - 1
+            tf = med(lambda: c.viterbi_forward(S, npc, T, cost_d, W, None, bp, tm, last))
+            tfu = med(lambda: c.viterbi_forward(S, npc, T, cost_d, W, (0.2, 1.0), bp, tm, last))
+            tb = med(lambda: c.viterbi_backtrack(bp, tm, last, npc, T, q))
+            tr = med(lambda: c.viterbi_refine(S, q, npc, T, pc_d, on["ntc"], on["nftc"], on["ptab"], on["nf"],
+                                              plan["nfmax"], ps[0], ps[1]))
+            raw = S.argmax(dim=0).cpu().numpy()
+            path = got[1]
+            big = lambda v: int((np.abs(np.diff(v.astype(np.int64))) > 8).sum())  # noqa: E731
+            rows.append(dict(workload=wl, plim=list(plim), instants=T, candidates=npc, W=W, clock_khz=c.clock_khz,
+                             forward_ms=tf[0], forward_spread_ms=tf[1], forward_unvoiced_ms=tfu[0],
+                             forward_unvoiced_spread_ms=tfu[1], backtrack_ms=tb[0], backtrack_spread_ms=tb[1],
+                             refine_ms=tr[0], refine_spread_ms=tr[1],
+                             forward_ns_per_step=round(tf[0] * 1e6 / T, 1),
+                             forward_cycles_per_step=round(tf[0] * 1e-3 / T * c.clock_khz * 1e3, 0),
+                             forward_unvoiced_cycles_per_step=round(tfu[0] * 1e-3 / T * c.clock_khz * 1e3, 0),
+                             viterbi_call_cached_s=round(cached[2], 4),
+                             viterbi_call_cached_min_max_s=[round(cached[0], 4), round(cached[-1], 4)],
+                             viterbi_unvoiced_call_cached_s=round(cached_uv[2], 4),
+                             device_call_cached_s=round(device[2], 4), host_swipep_s=round(host, 4),
+                             host_over_viterbi_cached=round(host / cached[2], 2),
+                             big_steps_raw=big(raw), big_steps_path=big(path),
+                             pitch_differs_from_swipep=int((got[0][:, 1] != ref[:, 1]).sum())))
             print(json.dumps(rows[-1]), flush=True)
     return rows
 
@@ -1218,8 +1296,19 @@ def main():
     ap.add_argument("--swipe", action="store_true",
                     help="time the device SWIPE' kernels and the whole swipep_device call next to swipe.swipep on the "
                          "60 s signals of --workloads (nothing else runs)")
+    ap.add_argument("--viterbi", action="store_true",
+                    help="time the forward, backtrack and refine kernels of the continuous pitch track and the whole "
+                         "swipep_viterbi call next to swipep_device and swipe.swipep on the 60 s signals of --workloads "
+                         "(nothing else runs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.viterbi:
+        import torch
+        res_viterbi = [dict(viterbi=viterbi_rows(torch, a.workloads.split(",")))]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res_viterbi, f, indent=1)
+        return 0
     if a.swipe:
         import torch
         res_swipe = [dict(swipe=swipe_rows(torch, a.workloads.split(",")))]
