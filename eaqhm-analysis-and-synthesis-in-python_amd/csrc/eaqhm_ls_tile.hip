@@ -41,6 +41,7 @@
 #include "eaqhm_ls_twunits.h"
 #include "eaqhm_ls_gather.h"
 #include "eaqhm_ls_tilelds.h"
+#include "eaqhm_ls_tilexch.h"
 
 namespace eaqhm {
 bool ls_a0tile_fits(const LsArgs& A);                 // eaqhm_ls_a0tile.hip
@@ -53,6 +54,7 @@ int launch_ls_a0tile(eaqhm_ctx* ctx, LsArgs A);
 #define TL_CW 8         // all waves own tiles
 // (TL_NTMAX, CI_STRIDE, CI_NCH, TL_NSLOT and the LDS budget: eaqhm_ls_tilelds.h)
 static_assert(TLL_TILE == TL_TILE && TLL_DG_TILE == DG_TILE, "eaqhm_ls_tilelds.h and eaqhm_ls_chol.h disagree");
+static_assert(TX_DFLAG_BYTE == 8 * (4 * TL_NTMAX * TL_TILE + 2 * TL_TILE + DGP_DOUBLES + 128 + 256), "eaqhm_ls_tilexch.h: where tile_frame puts dflag");
 // (adaptation 0: closed-form Gramian and two real systems — A0_NS, A0_M, TZ_TB, TZ_NCH and a0_frame in eaqhm_ls_a0.h)
 
 // The next frame's header, by one wave (see TlHead); the barrier that follows publishes it.
@@ -220,6 +222,11 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
     constexpr int UN = UA + UB;                        // unit slots of a wave
     constexpr int GA = UA / 3, GB = UB / 3;            // ... of which 3 GA + 3 GB hold whole pairs (weights 0, 1, 2 in a row)
     constexpr bool G3 = TW > 0 || UN > 0;              // three-weight Gramian (whole pairs or units)
+    // The G_p tiles change hands in LDS (eaqhm_ls_tilexch.h) where whole pairs are contracted, T <= 5: the budgets of <= 10
+    // tile rows.  The unit tables (T = 6: one plane per round) keep the workgroup's scratch area: their budgets are the
+    // ones that spill already, and through three rounds the accumulators of the planes still to be stored stay live beside
+    // the gathered system tiles.
+    constexpr bool LDS_XCH = TW > 0;
     static_assert(TW == 0 || UN == 0, "whole pairs or units");
     static_assert(UN == 0 || (UA == TWU_UA && UB == TWU_UB), "slot layout of eaqhm_ls_twunits.h");
     static_assert(TB >= 0 && TB < TWU_NTB, "unit table");
@@ -613,8 +620,148 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
         accI[sl] = accI[sl] + (p1 - p2);
       }
     }
-    if constexpr (G3) {
-      // The G_p tiles go through the workgroup's scratch area (the bridged track rows are dead now; <= 3 * 21 tiles of
+    if constexpr (LDS_XCH) {
+      // The G_p tiles change hands in LDS (eaqhm_ls_tilexch.h): region U is dead between the last chunk's closing barrier and
+      // the barrier in front of the factorisation.  Y = [X_E | n X_E | s] with X = [X_E | s], so entry (R, C) of Y^H Y is
+      // G_p[a][b]: a = R (amplitude row), R - Kc (slope row) or Kc (signal row), likewise b for C, p = the number of slope
+      // indices among R and C.  Every G_p is Hermitian (n is real): entries above the tile diagonal of G_p are conjugates of
+      // computed ones.  A round: stores of its planes, barrier, the gather of the entries stored in it, and a barrier before
+      // the next round's stores; the last round closes on the barrier in front of the factorisation (dflag, which thread 0
+      // zeroes ahead of that barrier, lies behind the exchange area).  PPR planes per round: all three for T <= 4 (class of
+      // <= 8 tile rows), {0, 1} then {2} for T = 5 (9 and 10 tile rows).
+      constexpr int PPR = NS == 5 ? 3 : 2, NR = NS == 5 ? 1 : 2;
+      static_assert(PPR == tx_planes_per_round(NS == 5 ? 4 : 5) && NR == tx_rounds(NS == 5 ? 4 : 5), "rounds of eaqhm_ls_tilexch.h");
+      typedef __attribute__((address_space(3))) char* xch_base_t;
+      typedef int xch_i4 __attribute__((ext_vector_type(4)));
+      typedef double xch_d2 __attribute__((ext_vector_type(2)));
+      typedef __attribute__((address_space(3))) xch_d2* xch_cell_t;
+      xch_base_t Xb = (xch_base_t)(char*)U;
+      // The gather's index table (eaqhm_ls_gather.h), one entry per row / column index of the frame, and the zero that
+      // padding positions and empty slots read: in `win` and at the start of `sig`, which nothing reads once the last chunk is
+      // built; written beside the first round's stores, published by the barrier behind them.
+      const unsigned tabB = (unsigned)tx_table_byte(uni(A.Kcmax)), zcB = (unsigned)tx_zcell_byte(uni(A.Kcmax));
+      const __attribute__((address_space(3))) xch_i4* gtab = (const __attribute__((address_space(3))) xch_i4*)(Xb + tabB);
+      if (tid < 16 * nt) {
+        const GatherEntry e = gather_entry(tid, Kc, npair, T, false);
+        *(__attribute__((address_space(3))) xch_i4*)(Xb + tabB + 32 * tid) = (xch_i4){e.lo, e.hi, e.trow, e.tcol};
+      }
+      if (tid == TL_THREADS - 1) *(xch_cell_t)(Xb + zcB) = (xch_d2){0.0, 0.0};
+      const unsigned span = (unsigned)(PPR * TX_TILE_BYTES * npair);   // bytes of a round's planes
+      static_assert(NR == 1 || (NR == 2 && PPR == 2), "a round after the first holds G_2 alone");
+      unsigned gup[NS];
+#pragma unroll
+      for (int rd = 0; rd < NR; ++rd) {
+        // ---- stores: entry (i, j) = (lq + 4 r, lcol) of this lane, its 16-byte cell XOR the row (tx_swizzle).  The second
+        // halves of a split pair (T = 4) wait for the first halves and are added in place, first half + second half.
+#pragma unroll
+        for (int sl = 0; sl < TWA; ++sl) {
+          if (!glive[sl]) continue;
+          const bool second = split && sl == 1 && (wave & 1);
+          if (second) continue;
+#pragma unroll
+          for (int p = 0; p < 3; ++p) {
+            if (p / PPR != rd) continue;
+            const d4 p1 = g[sl][3 * p], p2 = g[sl][3 * p + 1];
+            const d4 re = p1 + p2, im = g[sl][3 * p + 2] + (p1 - p2);
+            const unsigned tb = (unsigned)(TX_TILE_BYTES * ((p % PPR) * npair + gx[sl]));
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              *(xch_cell_t)(Xb + tb + tx_swizzle((unsigned)(256 * (lq + 4 * r) + 16 * lcol))) = (xch_d2){re[r], im[r]};
+          }
+        }
+        __syncthreads();
+        if (NS == 5 && split) {
+          if (glive[TWA - 1] && (wave & 1)) {   // (the second halves live in the last slot of waves 1 and 3)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+              const d4 p1 = g[TWA - 1][3 * p], p2 = g[TWA - 1][3 * p + 1];
+              const d4 re = p1 + p2, im = g[TWA - 1][3 * p + 2] + (p1 - p2);
+              const unsigned tb = (unsigned)(TX_TILE_BYTES * (p * npair + gx[TWA - 1]));
+              xch_d2 c1[4];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) c1[r] = *(xch_cell_t)(Xb + tb + tx_swizzle((unsigned)(256 * (lq + 4 * r) + 16 * lcol)));
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                *(xch_cell_t)(Xb + tb + tx_swizzle((unsigned)(256 * (lq + 4 * r) + 16 * lcol))) = (xch_d2){c1[r].x + re[r], c1[r].y + im[r]};
+            }
+          }
+          __syncthreads();
+        }
+        // ---- gather.  Every slot, empty ones too: nothing of accR / accI lives through the contraction.  The first round
+        // loads every value — an entry of a later round and padding read the zero cell — straight into the accumulator
+        // registers, all requests ahead of the first use.  The second round (G_2 alone: entries whose row and column are
+        // both slope indices) is skipped by the slots that cannot have one — wave-uniform, from where Kc and 2 Kc fall in
+        // the tile's rows and columns —, the others look their offsets up again (kept from the first round they cost
+        // the 7-slot budget its registers: vector scratch, and 2.8 k cycles in the back substitution) and take the value
+        // where the entry's plane is in the round.  Only the sign of the imaginary part is left to fix afterwards: one
+        // word per slot holds the four `up` bits.
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+          if (rd > 0) {
+            const int r0 = 16 * tP[sl], c0 = 16 * tQ[sl];
+            if (!(r0 + 15 >= Kc && r0 < 2 * Kc && c0 + 15 >= Kc && c0 < 2 * Kc)) continue;
+          }
+          unsigned off[4];
+          {
+            // column entry once per slot (an empty slot: index 16 nt - 1, which is padding in every frame: 2 Kc + 1 is odd)
+            const int cx = live[sl] ? 16 * tQ[sl] + lcol : 16 * nt - 1;
+            const __attribute__((address_space(3))) xch_i4* rt = gtab + 2 * (16 * tP[sl] + lq);
+            xch_i4 c0 = gtab[2 * cx], r0[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) r0[r] = rt[8 * r];
+            // (the entries whole, ahead of their use: left alone the compiler sinks each word's read into a branch on `up`
+            // and waits for it there)
+            asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.w));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(r0[r].x), "+v"(r0[r].y), "+v"(r0[r].z));
+            unsigned ups = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int dt = r0[r].z - c0.w;   // < 0: above the tile diagonal, the conjugate of a stored entry (eaqhm_ls_gather.h)
+              const unsigned o = (unsigned)((dt < 0 ? r0[r].y : r0[r].x) + (dt < 0 ? c0.x : c0.y));
+              off[r] = o < (unsigned)GI_ZCELL ? o : (unsigned)GI_ZCELL;
+              ups = (ups >> 1) | ((unsigned)dt & 0x80000000u);
+            }
+            if (rd == 0) gup[sl] = ups;
+          }
+          if (rd == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // (one round: off < span for every entry but padding)
+              const xch_d2 v = *(xch_cell_t)(Xb + (off[r] < span ? tx_swizzle(off[r]) : zcB));
+              accR[sl][r] = v.x; accI[sl][r] = v.y;
+            }
+          } else {
+            bool in[4];
+            xch_d2 v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              off[r] -= (unsigned)rd * span;   // (padding: GI_ZCELL lies more than a span behind the last plane)
+              in[r] = off[r] < span;
+              v[r] = *(xch_cell_t)(Xb + (in[r] ? tx_swizzle(off[r]) : zcB));
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              accR[sl][r] = in[r] ? v[r].x : accR[sl][r];
+              accI[sl][r] = in[r] ? v[r].y : accI[sl][r];
+            }
+          }
+        }
+        if (rd + 1 < NR) __syncthreads();   // the round's tiles are read: the next round's stores may overwrite them
+      }
+#pragma unroll
+      for (int sl = 0; sl < NS; ++sl) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {   // -im where `up`: the sign bit
+          const double vi = accI[sl][r];
+          accI[sl][r] = __hiloint2double(__double2hiint(vi) ^ (int)((gup[sl] << (3 - r)) & 0x80000000u), __double2loint(vi));
+        }
+      }
+      // the exchange on a slot of its own (9), so that slot 2 is the k-step loops and the chunk's closing barrier alone; with
+      // the diag_D diagnostics on, slot 9 is theirs and the exchange stays in slot 2
+      LS_STAMP(uni((int)A.debug_diag) ? 2 : 9);
+    }
+    if constexpr (G3 && !LDS_XCH) {
+      // The unit tables (UN > 0): the G_p tiles go through the workgroup's scratch area (the bridged track rows are dead now; <= 3 * 21 tiles of
       // 16 x 16 complex values, see ls_tile_scratch_stride), then every wave gathers its system tiles.  Y = [X_E | n X_E | s]
       // with X = [X_E | s], so entry (R, C) of Y^H Y is G_p[a][b]: a = R (amplitude row), R - Kc (slope row) or Kc
       // (signal row), likewise b for C, p = the number of slope indices among R and C.  Every G_p is Hermitian (n is
@@ -652,40 +799,8 @@ __device__ __attribute__((noinline)) void tile_frame(const LsArgs& A, int TS_, i
             gt[o] = re[r]; gt[o + 1] = im[r];
           }
         }
-      } else
-#pragma unroll
-      for (int sl = 0; sl < TWA; ++sl) {
-        if (!glive[sl]) continue;
-        const int x = gx[sl];
-        const bool second = split && sl == 1 && (wave & 1);   // second halves: planes of their own behind the 3 npair tiles
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          const d4 p1 = g[sl][3 * p], p2 = g[sl][3 * p + 1];
-          const d4 re = p1 + p2, im = g[sl][3 * p + 2] + (p1 - p2);
-          double* gt = Gs + (size_t)(second ? 3 * npair + 3 * (x - 8) + p : p * npair + x) * 512;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int o = 2 * (16 * (lq + 4 * r) + lcol);
-            gt[o] = re[r]; gt[o + 1] = im[r];
-          }
-        }
       }
       __syncthreads();
-      if (split) {   // tile (p, pair 8 + h) = first half + second half; six tiles, three complex values per thread
-        double2 c1[3], c2[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int q = tid + k * TL_THREADS, t = q >> 8, e = 2 * (q & 255);
-          c1[k] = *(const double2*)(Gs + (size_t)((t % 3) * npair + 8 + t / 3) * 512 + e);
-          c2[k] = *(const double2*)(Gs + (size_t)(3 * npair + t) * 512 + e);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int q = tid + k * TL_THREADS, t = q >> 8, e = 2 * (q & 255);
-          *(double2*)(Gs + (size_t)((t % 3) * npair + 8 + t / 3) * 512 + e) = make_double2(c1[k].x + c2[k].x, c1[k].y + c2[k].y);
-        }
-        __syncthreads();
-      }
       if constexpr (UN > 0) {
         // H units hold (Re, RI): Im = RI - RI^T in place, so that the gather reads every tile alike and needs no second
         // value per entry (packed tables: the corner has plane 0 only).  A thread takes both entries of a transposed pair
@@ -1084,7 +1199,8 @@ bool ls_tile_applicable(int Kcmax, int Nmax) { return tl_applicable(Kcmax, Nmax)
 
 size_t ls_tile_scratch_stride(int nmax, int Nmax) {
   const size_t Npad = (size_t)((Nmax + 63) >> 6) << 6;
-  // three-weight G_p tiles of T <= 6 (nt <= 12; T = 4: 30 + the 6 second halves) and the gather's zero cell behind them (GI_ZCELL)
+  // three-weight G_p tiles of the unit tables (T = 6, 11 and 12 tile rows; T <= 5 exchanges them in LDS) and the gather's zero
+  // cell behind them (GI_ZCELL)
   const size_t bridged = 2 * Npad * nmax, gram = (size_t)3 * 21 * 512 + 2;
   return ((bridged > gram ? bridged : gram) + 15) & ~(size_t)15;
 }

@@ -43,7 +43,7 @@ struct TlHead {
 static_assert(sizeof(TlHead) % 16 == 0, "TlHead: a multiple of 16 bytes");
 #define TL_HEAD_DOUBLES ((sizeof(TlHead) + 7) / 8)
 
-TLL_HD inline size_t tl_usize_c() {
+TLL_HD constexpr inline size_t tl_usize_c() {
   return (size_t)4 * TL_NTMAX * TLL_TILE + 2 * TLL_TILE + 2 * TLL_DG_TILE + 2 * 16 * TL_NTMAX + 32;
 }
 TLL_HD inline size_t tl_usize_g(int TS, int ldx_max) {
