@@ -264,21 +264,40 @@ __device__ __forceinline__ void noise_warp_frame(const double* __restrict__ sigm
     return;
   }
 
-  // r'[l] on lane l: P'[t] is one address for the wave; the table index (l t) mod 2M folds onto [0, M]
+  // r'[l] on lane l: P'[t] is one address for the wave; the table index (l t) mod 2M folds onto [0, M].  Where the read
+  // angle is held at pi over part of the grid (alpha < 1, a map that passes fs/2) the terms of lag 0 are one constant
+  // there, and a running sum that adds one constant 128 times rounds the same way every time: up to 150 x the model's
+  // own rounding error.  Such a frame sets its running sums aside every 64 grid points (16 terms each);
+  // a frame without a held stretch is summed in one run, bit for bit as it always was.
   auto ct = [&](int t) {
     const int idx = (lane * t) & (2 * NW_M - 1);
     return tab[idx > NW_M ? 2 * NW_M - idx : idx];
   };
+  const bool held = rd.grid(NW_M - 1) == M_PI;     // uniform over the wave
   double r0 = 0.5 * P[0], r1 = 0.0, r2 = 0.0, r3 = ((lane & 1) ? -0.5 : 0.5) * P[NW_M];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
   for (int t = 1; t + 3 < NW_M; t += 4) {
     r0 = fma(P[t], ct(t), r0);
     r1 = fma(P[t + 1], ct(t + 1), r1);
     r2 = fma(P[t + 2], ct(t + 2), r2);
     r3 = fma(P[t + 3], ct(t + 3), r3);
+    if (held && (t & 63) == 61) {
+      s0 += r0;
+      s1 += r1;
+      s2 += r2;
+      s3 += r3;
+      r0 = r1 = r2 = r3 = 0.0;
+    }
   }
   r0 = fma(P[NW_M - 3], ct(NW_M - 3), r0);
   r1 = fma(P[NW_M - 2], ct(NW_M - 2), r1);
   r2 = fma(P[NW_M - 1], ct(NW_M - 1), r2);
+  if (held) {
+    r0 += s0;
+    r1 += s1;
+    r2 += s2;
+    r3 += s3;
+  }
   const double r = ((r0 + r1) + (r2 + r3)) / (double)NW_M;
 
   double kk = 0.0;
