@@ -70,7 +70,12 @@ and --conversion-train, from the device (pitch.analysis_pitch_track, DESIGN.md ย
 --pitch-viterbi takes it from pitch.analysis_pitch_track_viterbi instead (DESIGN.md ยง13.1): the device's strengths, and
 the pitch along the best continuous path through them rather than at each instant's own maximum; it implies the device
 estimator.  --pitch-jump-cost C (4) is the cost of a jump per octave, and --pitch-unvoiced U (0.2 is a usual value) adds an
-unvoiced state with the score U per instant, so that the path decides voicing too; both need --pitch-viterbi."""
+unvoiced state with the score U per instant, so that the path decides voicing too; both need --pitch-viterbi.
+--formants-out FILE measures the formants of the input (formant.signal_allpole, formant_candidates, formant_tracks,
+DESIGN.md ยง14) and writes one line per 5 ms frame: seconds, F1..FN, B1..BN in Hz, nan where a formant is absent;
+--formant-count N (1 to 4, default 3) sets N.  --formant-warp-from OTHER.wav measures both files' formants and moves this
+file's spectral envelope along the piecewise-linear map from its own median formants to OTHER's
+(formant.formant_warp_from_tracks); it writes `<name>_modified.wav` and excludes the other four formant flags."""
 import argparse
 
 import numpy as np
@@ -155,6 +160,13 @@ def parser():
     fs_.add_argument("--formant-vtln", type=float, default=None, metavar="ALPHA",
                      help="like --formant-warp-curve, with the VTLN map: slope ALPHA up to the knee, then straight to "
                           "(fs/2, fs/2)")
+    fs_.add_argument("--formant-warp-from", default=None, metavar="OTHER.wav",
+                     help="like --formant-warp-curve, with the map from this file's median formants to OTHER.wav's "
+                          "(formant.formant_warp_from_tracks)")
+    ap.add_argument("--formants-out", default=None, metavar="FILE",
+                    help="write the formant tracks of the input: lines 'seconds F1..FN B1..BN' (Hz, nan: absent)")
+    ap.add_argument("--formant-count", type=int, default=None, metavar="N",
+                    help="with --formants-out / --formant-warp-from: the number of formants, 1 to 4 (3)")
     ap.add_argument("--formant-knee", type=float, default=None, metavar="K",
                     help="with --formant-vtln: the knee as a fraction of fs/2 (0.875)")
     ap.add_argument("--no-envelope", action="store_true",
@@ -266,7 +278,13 @@ def main(argv=None):
             ap.error("--pitch-viterbi: %s" % e)
     if a.noise_formant and not a.noise:
         ap.error("--noise-formant needs --noise")
-    warped = a.formant_warp_curve is not None or a.formant_vtln is not None
+    warped = a.formant_warp_curve is not None or a.formant_vtln is not None or a.formant_warp_from is not None
+    if a.formant_count is not None:
+        from .formant import FORMANT_TRACKS_MAX
+        if a.formants_out is None and a.formant_warp_from is None:
+            ap.error("--formant-count needs --formants-out or --formant-warp-from")
+        if not 1 <= a.formant_count <= FORMANT_TRACKS_MAX:
+            ap.error("--formant-count must be in [1, %d]" % FORMANT_TRACKS_MAX)
     if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None and not warped:
         ap.error("--noise-formant needs --formant-scale, --formant-scale-curve, --formant-warp-curve or --formant-vtln")
     if a.formant_knee is not None and a.formant_vtln is None:
@@ -422,6 +440,8 @@ def main(argv=None):
         out = a.wav[:len(a.wav) - 4] + "_reconstructed.wav"
         wavfile.write(out, fs, np.float32(s_recon))
         print("wrote", out)
+        if a.formants_out is not None:
+            write_formants(a.formants_out, *formant_table(a.wav, a.fc, a.formant_count or 3))
         if train and a.conversion_nonparallel is not None:
             train_conversion_nonparallel(a, gender, analysis_options, fs, det, **on_axis)
         elif train:
@@ -440,6 +460,8 @@ def main(argv=None):
             if a.formant_vtln is not None:
                 from .model import formant_warp_vtln
                 wmap = formant_warp_vtln(fs, a.formant_vtln, 0.875 if a.formant_knee is None else a.formant_knee)
+            if a.formant_warp_from is not None:
+                wmap = formant_warp_between(a.wav, a.formant_warp_from, a.fc, a.formant_count or 3, fs)
             nz = None
             if a.noise:
                 from .prologue import read_signal
@@ -518,6 +540,37 @@ def main(argv=None):
                 wavfile.write(out, fs, np.float32(s_voc))
                 print("wrote", out)
     return 0
+
+
+def formant_table(path, fc, n):
+    """The formant tracks of a file's signal (DESIGN.md ยง14): formant.signal_allpole, formant_candidates and
+    formant_tracks with their defaults.  Returns (fs, seconds float64[T], F float64[T, n], B float64[T, n])."""
+    from . import formant
+    from .prologue import read_signal
+    fs, s = read_signal(path, fc)
+    model = formant.signal_allpole(s, fs)
+    F, B = formant.formant_tracks(formant.formant_candidates(model), n)
+    return fs, np.arange(len(F)) * model["hop"] / float(fs), F, B
+
+
+def write_formants(out, fs, seconds, F, B):
+    """--formants-out: one line per frame, seconds, F1..FN, B1..BN."""
+    n = F.shape[1]
+    head = "seconds " + " ".join("F%d" % (i + 1) for i in range(n)) + " " + " ".join("B%d" % (i + 1) for i in range(n))
+    np.savetxt(out, np.column_stack((seconds, F, B)), fmt="%.6f", header=head)
+    print("wrote", out)
+
+
+def formant_warp_between(path, other, fc, n, fs):
+    """--formant-warp-from: the warp from `path`'s median formants to `other`'s, (f_in, f_out)."""
+    from .formant import formant_warp_from_tracks
+    fs_a, _, FA, _ = formant_table(path, fc, n)
+    fs_b, _, FB, _ = formant_table(other, fc, n)
+    if fs_b != fs_a:
+        raise ValueError("%s is sampled at %d Hz, the input at %d Hz" % (other, fs_b, fs_a))
+    f_in, f_out = formant_warp_from_tracks(FA, FB, fs)
+    print("formant warp from %s: %s -> %s Hz" % (other, np.round(f_in, 1).tolist(), np.round(f_out, 1).tolist()))
+    return f_in, f_out
 
 
 def viterbi_options(a):

@@ -116,6 +116,13 @@ SYMBOLS_VITERBI = (
     ("eaqhm_viterbi_backtrack", C.c_int, [_P, _P, _P, _P, _I32, _I64, _P]),
     ("eaqhm_viterbi_refine", C.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P, _I32, _P, _P]),
 )
+# every symbol include/eaqhm_formant.h declares: likewise
+SYMBOLS_FORMANT = (
+    ("eaqhm_allpole_roots", C.c_int, [_P, _P, _I64, _I32, _P, _P]),
+    ("eaqhm_formant_candidates", C.c_int, [_P, _P, _P, _I64, _I32, _F64, _F64, _F64, _F64, _P, _P, _P]),
+    ("eaqhm_formant_forward", C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _F64, _F64, _P, _P]),
+    ("eaqhm_formant_backtrack", C.c_int, [_P, _P, _P, _I32, _I64, _P, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -139,7 +146,7 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, res, args in (SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM
-                            + SYMBOLS_NN + SYMBOLS_SWIPE + SYMBOLS_VITERBI):
+                            + SYMBOLS_NN + SYMBOLS_SWIPE + SYMBOLS_VITERBI + SYMBOLS_FORMANT):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -464,6 +471,22 @@ class Context:
     def viterbi_refine(self, S, q, npc, T, pc, ntc, nftc, ptab, nf, nfmax, p, s):
         self._ck(self.lib.eaqhm_viterbi_refine(self.h, _ptr(S), _ptr(q), npc, T, _ptr(pc), _ptr(ntc), _ptr(nftc),
                                                _ptr(ptab), _ptr(nf), nfmax, _ptr(p), _ptr(s)))
+
+    # formant tracks: refl [Nf][p], roots [Nf][p][2], iters int32 [Nf]; cand_f, cand_b [Nf][8], count int32
+    # [Nf]; L [T][N][8], lf [T][8], states int8 [S][N], bp int16 [T][S], last [S], q int32 [T], total [1]
+    def allpole_roots(self, refl, Nf, p, roots, iters):
+        self._ck(self.lib.eaqhm_allpole_roots(self.h, _ptr(refl), Nf, p, _ptr(roots), _ptr(iters)))
+
+    def formant_candidates(self, roots, iters, Nf, p, fs, fmin, fmax, bw_max, cand_f, cand_b, count):
+        self._ck(self.lib.eaqhm_formant_candidates(self.h, _ptr(roots), _ptr(iters), Nf, p, float(fs), float(fmin),
+                                                   float(fmax), float(bw_max), _ptr(cand_f), _ptr(cand_b), _ptr(count)))
+
+    def formant_forward(self, L, lf, count, states, N, T, w_jump, absent_cost, bp, last):
+        self._ck(self.lib.eaqhm_formant_forward(self.h, _ptr(L), _ptr(lf), _ptr(count), _ptr(states), N, T,
+                                                float(w_jump), float(absent_cost), _ptr(bp), _ptr(last)))
+
+    def formant_backtrack(self, bp, last, N, T, q, total):
+        self._ck(self.lib.eaqhm_formant_backtrack(self.h, _ptr(bp), _ptr(last), N, T, _ptr(q), _ptr(total)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

@@ -529,6 +529,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_swipe.h"
 /* the continuous pitch track: Viterbi forward pass, backtrack and refinement (additions under ABI 6): declared in eaqhm_viterbi.h. */
 #include "eaqhm_viterbi.h"
+/* formant tracks: the poles of the all-pole envelope, the candidates and their Viterbi decode (additions under ABI 6): declared in eaqhm_formant.h. */
+#include "eaqhm_formant.h"
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,9 @@ one warm-up), with the number of instants whose pitch differs.
 --viterbi times the continuous pitch track on the same signals and limits: the forward pass (without and
 with the unvoiced state, also per step in cycles), the backtrack and the refinement, and the whole swipep_viterbi call with
 a cached plan next to swipep_device and to swipe.swipep in the same process.
+--formant-tracks times the formant tracks on the all-pole models of the same signals
+(formant.signal_allpole: 12 000 frames, p = 18 and 50): eaqhm_allpole_roots, eaqhm_formant_candidates, the forward pass
+at N = 3 and 4 (also per step) and the backtrack, next to a numpy.roots loop over the same frames on the host.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -508,6 +511,68 @@ def viterbi_rows(torch, workloads, reps=20, runs=3):
                              big_steps_raw=big(raw), big_steps_path=big(path),
                              pitch_differs_from_swipep=int((got[0][:, 1] != ref[:, 1]).sum())))
             print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def formant_track_rows(torch, workloads, reps=20, runs=3):
+    """Formant tracks on the all-pole models of the 60 s synthetic signals (formant.signal_allpole at the
+    noise model's defaults: 12 000 frames, p = 18 at 16 kHz and 50 at 48 kHz): eaqhm_allpole_roots,
+    eaqhm_formant_candidates, eaqhm_formant_forward (N = 3 and 4) and eaqhm_formant_backtrack as the median of `runs`
+    warmed HIP-event windows of `reps` launches with their max - min; the forward pass per step in ns; the steps the
+    iteration took; and a numpy.roots loop over the same frames on this host, one run."""
+    from eaqhm_amd import formant
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.synth import synth_speech_int16
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for wl in workloads:
+        fs = {"synth16k_60s": 16000, "synth48k_60s": 48000}[wl]
+        x = synth_speech_int16(60.0, fs) / 32768.0
+        model = formant.signal_allpole(x, fs)
+        Nf, p = model["refl"].shape
+        refl = torch.as_tensor(model["refl"], device=dev)
+        roots = torch.empty((Nf, p, 2), dtype=torch.float64, device=dev)
+        iters = torch.empty(Nf, dtype=torch.int32, device=dev)
+        f = torch.empty((Nf, 8), dtype=torch.float64, device=dev)
+        b = torch.empty((Nf, 8), dtype=torch.float64, device=dev)
+        count = torch.empty(Nf, dtype=torch.int32, device=dev)
+        tr = med(lambda: c.allpole_roots(refl, Nf, p, roots, iters))
+        tc = med(lambda: c.formant_candidates(roots, iters, Nf, p, fs, 50.0, min(5500.0, fs / 2), 1000.0, f, b, count))
+        it = iters.cpu().numpy()
+        cand = dict(f=f.cpu().numpy(), b=b.cpu().numpy(), count=count.cpu().numpy())
+        row = dict(workload=wl, frames=Nf, order=p, roots_ms=tr[0], roots_spread_ms=tr[1], candidates_ms=tc[0],
+                   candidates_spread_ms=tc[1], steps_mean=round(float(it.mean()), 2), steps_max=int(it.max()),
+                   unfinished=int((it == formant.FORMANT_ITMAX + 1).sum()),
+                   candidates_mean=round(float(cand["count"].mean()), 2))
+        for N in (3, 4):
+            L, lf = formant.formant_cost_tables(cand, N, (550, 1650, 2750, 3850))
+            st = formant.formant_states(N)
+            L_d, lf_d, st_d = (torch.as_tensor(np.ascontiguousarray(a), device=dev) for a in (L, lf, np.array(st)))
+            bp = torch.empty((Nf, len(st)), dtype=torch.int16, device=dev)
+            last = torch.empty(len(st), dtype=torch.float64, device=dev)
+            q = torch.empty(Nf, dtype=torch.int32, device=dev)
+            total = torch.empty(1, dtype=torch.float64, device=dev)
+            tf = med(lambda: c.formant_forward(L_d, lf_d, count, st_d, N, Nf, 1.0, 2.0, bp, last))
+            tb = med(lambda: c.formant_backtrack(bp, last, N, Nf, q, total))
+            row.update({"forward_N%d_ms" % N: tf[0], "forward_N%d_spread_ms" % N: tf[1],
+                        "forward_N%d_ns_per_step" % N: round(tf[0] * 1e6 / Nf, 1),
+                        "backtrack_N%d_ms" % N: tb[0], "backtrack_N%d_spread_ms" % N: tb[1]})
+        t0 = time.perf_counter()
+        for k in model["refl"]:
+            a = np.array([1.0])
+            for ki in k:
+                a = np.concatenate((a, [0.0])) + ki * np.concatenate(([0.0], a[::-1]))
+            np.roots(a)
+        row["host_numpy_roots_s"] = round(time.perf_counter() - t0, 3)
+        row["host_over_device_roots"] = round(row["host_numpy_roots_s"] * 1e3 / tr[0], 1)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
     return rows
 
 
@@ -1300,8 +1365,18 @@ def main():
                     help="time the forward, backtrack and refine kernels of the continuous pitch track and the whole "
                          "swipep_viterbi call next to swipep_device and swipe.swipep on the 60 s signals of --workloads "
                          "(nothing else runs)")
+    ap.add_argument("--formant-tracks", action="store_true",
+                    help="time the roots, candidates, forward and backtrack kernels of the formant tracks next to a "
+                         "numpy.roots loop on the all-pole models of the 60 s signals of --workloads (nothing else runs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.formant_tracks:
+        import torch
+        res_formant = [dict(formant_tracks=formant_track_rows(torch, a.workloads.split(",")))]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res_formant, f, indent=1)
+        return 0
     if a.viterbi:
         import torch
         res_viterbi = [dict(viterbi=viterbi_rows(torch, a.workloads.split(",")))]
