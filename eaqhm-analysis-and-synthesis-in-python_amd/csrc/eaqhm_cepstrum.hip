@@ -49,7 +49,7 @@ __device__ inline double cep_lane(double x, int src) {
 }
 
 // The warped axis (§9.8): Omega_a(w) = w + 2 atan2(a sin w, 1 - a cos w), |a| <= 0.9.  The fit takes it as it is, once
-// per node.  The readouts need only its cosine and sine, which are a rational map of those of w / 2: with
+// per node.  The readouts need only functions of Omega that are a rational map of sin and cos of w / 2: with
 // u = (1 + a) sin(w/2), v = (1 - a) cos(w/2), tan(Omega/2) = u / v, so
 //   cos Omega = (v - u)(v + u) / (u^2 + v^2),   sin Omega = 2 u v / (u^2 + v^2):
 // one division, no atan2, and a denominator of two squares (>= (1 - |a|)^2) that cannot cancel.
@@ -62,20 +62,33 @@ __device__ inline double cep_omega(double a, double w) {
   return w + 2.0 * atan2(a * sn, 1.0 - a * cs);
 }
 
-// cs = cos Omega_a(w) (and sn = sin Omega_a(w)) from wh = w / 2
-__device__ inline double cep_axis_cos(const CepAxis& X, double wh) {
+// The readouts on this axis run Clenshaw's recurrence in Reinsch's form.  Omega_a crowds a whole band towards 0 (a < 0)
+// or pi (a > 0), where cos Omega, rounded once, no longer tells Omega: the plain recurrence from 2 cos Omega multiplies
+// that rounding by up to p^2 (264 x the model's own float64 error at a = -0.9, P = 63, 2.3 kHz).
+// Reinsch's form takes dl = -4 sin^2(Omega/2) = -4 u^2 / (u^2 + v^2) on the half cos Omega >= 0 and
+// dl = 4 cos^2(Omega/2) = 4 v^2 / (u^2 + v^2) on the other, both without a subtraction; with sg = +-1 for the half,
+//   d_p = c_p + dl b_{p+1} + sg d_{p+1},   b_p = d_p + sg b_{p+1}       (d_p = b_p - sg b_{p+1}),
+// b_p the plain recurrence's, so  sum_p c_p cos(p Omega) = dl b_1 / 2 + sg d_1  and  sum_p c_p sin(p Omega) = b_1 sn.
+struct CepAngle { double dl, sg, sn; };   // of Omega_a(w): dl and sg as above, sn = sin Omega
+
+__device__ inline CepAngle cep_axis_angle(const CepAxis& X, double wh) {   // wh = w / 2 in [0, pi/2]: u, v >= 0
   double sh, ch;
   sincos(wh, &sh, &ch);
   const double u = X.p * sh, v = X.m * ch;
-  return ((v - u) * (v + u)) / (u * u + v * v);
+  const double uu = u * u, vv = v * v;
+  const double r = 1.0 / (uu + vv);
+  const bool low = vv >= uu;   // cos Omega = (v - u)(v + u) / (u^2 + v^2) >= 0
+  return CepAngle{low ? -4.0 * (uu * r) : 4.0 * (vv * r), low ? 1.0 : -1.0, (2.0 * (u * v)) * r};
 }
-__device__ inline void cep_axis_sincos(const CepAxis& X, double wh, double& sn, double& cs) {
-  double sh, ch;
-  sincos(wh, &sh, &ch);
-  const double u = X.p * sh, v = X.m * ch;
-  const double r = 1.0 / (u * u + v * v);
-  cs = ((v - u) * (v + u)) * r;
-  sn = (2.0 * (u * v)) * r;
+
+// leaves b = b_1 and d = d_1
+__device__ inline void cep_recur_reinsch(const double* c, int P, const CepAngle& A, double& b, double& d) {
+  b = 0.0;
+  d = 0.0;
+  for (int p = P; p >= 1; --p) {   // one LDS address for the wave: a broadcast
+    d = c[p] + (A.dl * b + A.sg * d);
+    b = d + A.sg * b;
+  }
 }
 
 extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
@@ -137,24 +150,24 @@ __device__ inline double cep_read_phase(const CepRead& R, const WarpRow& W, doub
   return -2.0 * (b1 * sn);
 }
 
-// The two readouts on the warped axis (§9.8): the read frequency and the hold as above, in Hz, then cos and sin of
-// Omega_a through cep_axis_*.  (Helpers of their own, like cep_recur: cep_read and cep_read_phase keep their text.)
+// The two readouts on the warped axis (§9.8): the read frequency and the hold as above, in Hz, then Omega_a through
+// cep_axis_angle and the recurrence in Reinsch's form.  (Helpers of their own: cep_read and cep_read_phase keep their text.)
 __device__ inline double cep_read_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
   double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
   x = fmin(fmax(x, 0.0), 0.5 * R.fs);
-  const double cw2 = 2.0 * cep_axis_cos(X, (M_PI * x) / R.fs);
-  double b1, b2;
-  cep_recur(R.c, R.P, cw2, b1, b2);
-  return 2.0 * (0.5 * cw2 * b1 - b2) + R.c[0];
+  const CepAngle A = cep_axis_angle(X, (M_PI * x) / R.fs);
+  double b, d;
+  cep_recur_reinsch(R.c, R.P, A, b, d);
+  return 2.0 * (0.5 * A.dl * b + A.sg * d) + R.c[0];
 }
 
 __device__ inline double cep_read_phase_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
   double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
   x = fmin(fmax(x, 0.0), 0.5 * R.fs);
-  double sn, cs, b1, b2;
-  cep_axis_sincos(X, (M_PI * x) / R.fs, sn, cs);
-  cep_recur(R.c, R.P, 2.0 * cs, b1, b2);
-  return -2.0 * (b1 * sn);
+  const CepAngle A = cep_axis_angle(X, (M_PI * x) / R.fs);
+  double b, d;
+  cep_recur_reinsch(R.c, R.P, A, b, d);
+  return -2.0 * (b * A.sn);
 }
 
 // LDS of the two readout kernels (doubles): per wave the row's coefficients [CEP_PMAX + 1] and its row of the map

@@ -1,6 +1,6 @@
 // eaqhm_cepstrum_build.inc — the body of eaqhm_model_build_kernel and of its warped sibling (DESIGN.md §9.7, §9.8),
 // included once by each with CEP_WARPED 0 or 1 (see eaqhm_cepstrum_fit.inc): the warped kernel has one more argument,
-// cep_a, and takes the cell's sine and cosine through the rational map.
+// cep_a, and takes the cell's angle through the rational map and the recurrence in Reinsch's form (cep_axis_angle).
   __shared__ double sc[CEP_WAVES][CEP_PMAX + 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
@@ -18,15 +18,19 @@
     const double fm = __dmul_rn(h, fi);
     double a = 0.0, f = 0.0, ph = 0.0;
     if (rowlive && k < Kcap && fm < half) {
-      double sn, cs, b1, b2;
 #if CEP_WARPED
-      cep_axis_sincos(cep_axis(cep_a), (M_PI * fm) / fs, sn, cs);
+      double b1, d1;
+      const CepAngle A = cep_axis_angle(cep_axis(cep_a), (M_PI * fm) / fs);
+      const double sn = A.sn;
+      cep_recur_reinsch(c, P, A, b1, d1);
+      a = exp(2.0 * (0.5 * A.dl * b1 + A.sg * d1) + c[0]);
 #else
+      double sn, cs, b1, b2;
       sincos(((2.0 * M_PI) * fm) / fs, &sn, &cs);
-#endif
       const double cw2 = 2.0 * cs;
       cep_recur(c, P, cw2, b1, b2);
       a = exp(2.0 * (0.5 * cw2 * b1 - b2) + c[0]);
+#endif
       if (a != 0.0) {
         const double hs = __dmul_rn(h, th);           // the product rounded as the definition rounds it, then frac
         double x = __dmul_rn(2.0 * M_PI, hs - floor(hs));

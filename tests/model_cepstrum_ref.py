@@ -12,14 +12,15 @@ An instant without nodes gives (-inf, 0, .., 0).
     system(w, v, P, lam, dtype) -> (G, b)                      the normal equations
     fit(records, fs, P, lam, dtype) -> [No_ti, P + 1]          the normal equations solved in `dtype`
     fit_qr(records, fs, P, lam) -> float64[No_ti, P + 1]       the augmented system [M; sqrt(lam R)] by QR, refined
-    readout(ceps, fs, q) -> [n, len(q)]                        the direct cosine sum at min(max(q, 0), fs/2)
-    clenshaw(ceps, fs, q) -> [n, len(q)]                       the same by Clenshaw's recurrence from one cos
+    readout(ceps, fs, q, dtype) -> [n, len(q)]                 the direct cosine sum at min(max(q, 0), fs/2)
+    clenshaw(ceps, fs, q, dtype) -> [n, len(q)]                the same by Clenshaw's recurrence from one cos
     read_frequency(q, alpha=None, warp=None) -> q, q / alpha or V(q)
-    envelope(ceps, fs, freqs, alpha=None, warp=None) -> [n, F]
-    amplitudes(am, fm, fs, beta, ceps, alpha=None, warp=None) -> A' (float64[No_ti, Kmax])
+    envelope(ceps, fs, freqs, alpha=None, warp=None, dtype) -> [n, F]
+    amplitudes(am, fm, fs, beta, ceps, alpha=None, warp=None, dtype) -> A' ([No_ti, Kmax])
 
-`dtype` selects the arithmetic (np.float64: the definition; np.longdouble: the yardstick the GPU tests take the fit's
-bar from).  The inputs are float64 values in either case.  `warp` is (x [B], y [B] or [n, B]) in Hz.
+`dtype` selects the arithmetic (np.float64: the definition; np.longdouble: the yardstick the GPU tests take their bars
+from).  The inputs are float64 values in either case, and so is the held read frequency, as in cepstrum_warp_ref: the
+series is what `dtype` computes.  `warp` is (x [B], y [B] or [n, B]) in Hz.
 """
 import numpy as np
 
@@ -118,26 +119,26 @@ def _held(q, fs):
     return np.minimum(np.maximum(np.asarray(q, dtype=np.float64), 0.0), fs / 2)
 
 
-def readout(ceps, fs, q):
+def readout(ceps, fs, q, dtype=np.float64):
     """C_i(q) = c_0 + 2 sum_p c_p cos(2 pi p q^ / fs) as the direct sum; q is [F] or [n, F].  c_0 is added last."""
-    C = np.asarray(ceps, dtype=np.float64)
+    C = np.asarray(ceps, dtype=np.float64).astype(dtype)
     n, P = C.shape[0], C.shape[1] - 1
-    x = np.broadcast_to(_held(q, fs), (n, np.shape(q)[-1]))
-    theta = 2 * np.pi * x / fs
-    s = np.zeros(x.shape)
+    x = np.broadcast_to(_held(q, fs), (n, np.shape(q)[-1])).astype(dtype)
+    theta = 2 * _pi(dtype) * x / dtype(fs)
+    s = np.zeros(x.shape, dtype=dtype)
     for p in range(1, P + 1):
         s += C[:, p, None] * np.cos(p * theta)
     return 2 * s + C[:, 0, None]
 
 
-def clenshaw(ceps, fs, q):
+def clenshaw(ceps, fs, q, dtype=np.float64):
     """The same by Clenshaw's recurrence from cos(theta) alone: b_p = c_p + 2 cos(theta) b_{p+1} - b_{p+2},
     sum = b_1 cos(theta) - b_2."""
-    C = np.asarray(ceps, dtype=np.float64)
+    C = np.asarray(ceps, dtype=np.float64).astype(dtype)
     n, P = C.shape[0], C.shape[1] - 1
-    x = np.broadcast_to(_held(q, fs), (n, np.shape(q)[-1]))
-    cw2 = 2 * np.cos(2 * np.pi * x / fs)
-    b1, b2 = np.zeros(x.shape), np.zeros(x.shape)
+    x = np.broadcast_to(_held(q, fs), (n, np.shape(q)[-1])).astype(dtype)
+    cw2 = 2 * np.cos(2 * _pi(dtype) * x / dtype(fs))
+    b1, b2 = np.zeros(x.shape, dtype=dtype), np.zeros(x.shape, dtype=dtype)
     for p in range(P, 0, -1):
         b1, b2 = C[:, p, None] + (cw2 * b1 - b2), b1
     return 2 * (0.5 * cw2 * b1 - b2) + C[:, 0, None]
@@ -155,18 +156,18 @@ def read_frequency(q, n, alpha=None, warp=None):
     return q.copy()
 
 
-def envelope(ceps, fs, freqs, alpha=None, warp=None):
+def envelope(ceps, fs, freqs, alpha=None, warp=None, dtype=np.float64):
     n = np.shape(ceps)[0]
     with np.errstate(invalid="ignore"):
-        return readout(ceps, fs, read_frequency(freqs, n, alpha, warp))
+        return readout(ceps, fs, read_frequency(freqs, n, alpha, warp), dtype)
 
 
-def amplitudes(am, fm, fs, beta, ceps, alpha=None, warp=None):
+def amplitudes(am, fm, fs, beta, ceps, alpha=None, warp=None, dtype=np.float64):
     """A'[i][k] = exp(C_i(read_i(beta_i f_k))) for an active slot, 0 for an inactive one and where beta_i f_k >= fs/2.
     No unit rule."""
     n = am.shape[0]
     bf = np.broadcast_to(np.asarray(beta, dtype=np.float64), (n,))[:, None] * fm
     active = (am != 0) & (fm > 0)
     with np.errstate(invalid="ignore"):
-        A = np.exp(readout(ceps, fs, read_frequency(np.where(active, bf, 0.0), n, alpha, warp)))
-    return np.where(active & (bf < fs / 2), A, 0.0)
+        A = np.exp(readout(ceps, fs, read_frequency(np.where(active, bf, 0.0), n, alpha, warp), dtype))
+    return np.where(active & (bf < fs / 2), A, dtype(0))
