@@ -10,6 +10,7 @@
 // The forward pass is one launch per tile anti-diagonal I + J = t on the context's stream: a tile reads what the tiles
 // above, left and above-left of it wrote, and those ran in earlier launches.  No workgroup waits on another.
 #include "eaqhm_common.h"
+#include "eaqhm_wave.h"
 
 namespace eaqhm {
 
@@ -105,12 +106,6 @@ __device__ inline double lane_shr1(double x) {   // lane l gets lane l-1's x; la
   return __hiloint2double(hi, lo);
 }
 
-__device__ inline double lane_read(double x, int src) {   // src is wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), src);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src);
-  return __hiloint2double(hi, lo);
-}
-
 struct BandView {
   int nA, nB, r;
   i64 W;
@@ -156,7 +151,7 @@ extern "C" __global__ void __launch_bounds__(64)
   if (lane == 0) diag = corner;
   for (int s = 0; s < 127; ++s) {
     double up = lane_shr1(prev);
-    const double t_s = lane_read(top, s & 63);
+    const double t_s = wave_lane(top, s & 63);
     if (lane == 0) up = s < 64 ? t_s : INFINITY;
     const int jj = s - lane;
     if (jj >= 0 && jj < 64) {

@@ -3,18 +3,20 @@
 //   C(w) = c_0 + 2 sum_{p=1..P} c_p cos(p w),   w = 2 pi f / fs,
 // fitted to the instant's partial peaks by regularised least squares (Galas & Rodet 1990; Cappe & Moulines 1996).
 //
-//   eaqhm_model_cepstrum_kernel       one wave per instant: the fit (nodes to LDS, the cosine sums T_d, in-wave Cholesky)
+//   eaqhm_model_cepstrum_kernel<WARP> one wave per instant: the fit (nodes to LDS, the cosine sums T_d, in-wave Cholesky)
 //   eaqhm_modify_amp_cepstrum_kernel  one wave per instant: the knot amplitudes A' read off a supplied cepstrum
 //   eaqhm_cepstrum_envelope_kernel    one wave per row: the envelope on a frequency grid
 //   eaqhm_cepstrum_phase_kernel       its sibling: the minimum-phase response Phi of the envelope on the grid (§9.7)
-//   eaqhm_model_build_kernel          one wave per instant: the records of a harmonic model from f0 and a cepstrum (§9.7)
+//   eaqhm_model_build_kernel<WARP>    one wave per instant: the records of a harmonic model from f0 and a cepstrum (§9.7)
 // The readouts share cep_read: the read frequency (none, / alpha, or the inverse formant warp of eaqhm_warp.h), the hold
 // outside [0, fs/2] and Clenshaw's recurrence from one cos; cep_recur gives the kernels of §9.7 the sine sum as well.
-// Every kernel has a *_warped sibling (§9.8; include/eaqhm_cepwarp.h) on the all-pass warped axis Omega_a(w): the same
-// body, shared as a template where that leaves the unwarped kernel's machine code as it was (tools/isa_diff.py) and as
-// an included text (eaqhm_cepstrum_fit.inc, eaqhm_cepstrum_build.inc) where it does not.
+// Every kernel has a sibling (§9.8; include/eaqhm_cepwarp.h) on the all-pass warped axis Omega_a(w).  The fit and the
+// build are kernel templates <bool WARP> (the body is compiled as the kernel: both instantiations keep the machine code
+// they had as separate texts, tools/isa_diff.py; profilers show them under their C++ names); the readouts inline a
+// shared device template into a *_kernel and a *_warped_kernel wrapper, which left their unwarped code as it was.
 #include "eaqhm_common.h"
 #include "eaqhm_warp.h"
+#include "eaqhm_wave.h"
 
 namespace eaqhm {
 
@@ -39,13 +41,6 @@ __device__ inline double cep_gram(const double* T, int r, int q, double lam) {
   double g = 2.0 * (T[r - q] + T[r + q]);
   if (r == q) g += lam * ((8.0 * M_PI * M_PI) * (double)(r * r));
   return g;
-}
-
-// x of the lane `src` (wave-uniform) in every lane
-__device__ inline double cep_lane(double x, int src) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), src);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src);
-  return __hiloint2double(hi, lo);
 }
 
 // The warped axis (§9.8): Omega_a(w) = w + 2 atan2(a sin w, 1 - a cos w), |a| <= 0.9.  The fit takes it as it is, once
@@ -91,20 +86,96 @@ __device__ inline void cep_recur_reinsch(const double* c, int P, const CepAngle&
   }
 }
 
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+// WARP (§9.8): the nodes are staged at Omega_a(w_n), a = cep_a (0.0 and not read without it).
+template <bool WARP>
+__global__ void __launch_bounds__(64 * CEP_WAVES)
     eaqhm_model_cepstrum_kernel(const double* __restrict__ records, int No_ti, int K, double fs, int P, double lam,
-                                double* __restrict__ ceps) {
-#define CEP_WARPED 0
-#include "eaqhm_cepstrum_fit.inc"
-#undef CEP_WARPED
-}
+                                double* __restrict__ ceps, double cep_a) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
+  if (i >= No_ti) return;   // the waves of a block share no data: no block barrier below
+  const int n = P + 1, LS = cep_stride(P);
+  double* sw = lds + (size_t)w * cep_wave_doubles(K, P);
+  double* sv = sw + K;
+  double* T = sv + K;
+  double* A = T + (2 * P + 2);
+  const double* row = records + (size_t)i * (3 * K + 1);
+  double* out = ceps + (size_t)i * n;
 
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
-    eaqhm_model_cepstrum_warped_kernel(const double* __restrict__ records, int No_ti, int K, double fs, int P,
-                                       double lam, double* __restrict__ ceps, double cep_a) {
-#define CEP_WARPED 1
-#include "eaqhm_cepstrum_fit.inc"
-#undef CEP_WARPED
+  // ---- 1. the nodes: the active slots (am != 0, f > 0) in slot order
+  int nn = 0;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane;
+    const bool act = k < K && row[k] != 0.0 && row[K + k] > 0.0;
+    const unsigned long long m = __ballot(act);
+    if (act) {
+      const int p = nn + __popcll(m & ((1ull << lane) - 1ull));
+      const double wn = ((2.0 * M_PI) * row[K + k]) / fs;
+      if constexpr (WARP) sw[p] = cep_omega(cep_a, wn);
+      else sw[p] = wn;
+      sv[p] = log(row[k]);
+    }
+    nn += __popcll(m);
+  }
+  if (nn == 0) {   // an empty instant: -inf, 0, .., 0
+    if (lane < n) out[lane] = lane == 0 ? -INFINITY : 0.0;
+    return;
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // ---- 2. T_d = sum_n cos(d w_n), d = 0..2P, and b_p = sum_n v_n m_p(w_n), p = 0..P: lanes over d, every lane walks
+  // the nodes (one LDS address for the wave: a broadcast).  Each cosine is taken at d w_n itself, so there is no
+  // phasor to drift.  d <= P <= 63 falls in the first round: b_r ends up in lane r, the owner of row r.
+  double b = 0.0;
+  for (int d = lane; d <= 2 * P; d += 64) {
+    const double dd = (double)d;
+    double t = 0.0, bv = 0.0;
+    for (int q = 0; q < nn; ++q) {
+      const double c = cos(dd * sw[q]);
+      t += c;
+      bv += sv[q] * c;
+    }
+    T[d] = t;
+    if (d <= P) b = d == 0 ? bv : 2.0 * bv;
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // ---- 3. Cholesky G = L L^T, column by column (left-looking): lane r >= j forms G_rj - sum_{k<j} L_rk L_jk from its
+  // own row and row j (a broadcast); the pivot comes from lane j.  A pivot that is not finite or not > 0 ends the fit
+  // with a NaN row.
+  const int r = lane;
+  bool bad = false;
+  for (int j = 0; j < n; ++j) {
+    double s = 0.0;
+    if (r >= j && r < n) {
+      s = cep_gram(T, r, j, lam);
+      for (int k = 0; k < j; ++k) s -= A[r * LS + k] * A[j * LS + k];
+    }
+    const double piv = wave_lane(s, j);
+    if (!(piv > 0.0) || !(piv < INFINITY)) { bad = true; break; }   // wave-uniform
+    const double dj = sqrt(piv);
+    if (r >= j && r < n) A[r * LS + j] = r == j ? dj : s / dj;
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (bad) {
+    if (r < n) out[r] = NAN;
+    return;
+  }
+  // forward: L y = b, column by column; lane j keeps y_j
+  double y = b;
+  for (int j = 0; j < n; ++j) {
+    const double yj = wave_lane(y, j) / A[j * LS + j];
+    if (r == j) y = yj;
+    else if (r > j && r < n) y -= A[r * LS + j] * yj;
+  }
+  // backward: L^T c = y; lane r < j reads L_jr along row j (consecutive addresses)
+  for (int j = n - 1; j >= 0; --j) {
+    const double cj = wave_lane(y, j) / A[j * LS + j];
+    if (r == j) y = cj;
+    else if (r < j) y -= A[j * LS + r] * cj;
+  }
+  if (r < n) out[r] = y;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -113,9 +184,14 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
 // -inf of an empty row stays -inf.  c: the row's P + 1 coefficients (LDS).
 struct CepRead { const double* c; int P; double fs; int mode; double alpha; };
 
+// the read frequency of all four readouts, in Hz: read(q) by the mode, held at [0, fs/2]
+__device__ inline double cep_read_freq(const CepRead& R, const WarpRow& W, double q) {
+  const double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
+  return fmin(fmax(x, 0.0), 0.5 * R.fs);
+}
+
 __device__ inline double cep_read(const CepRead& R, const WarpRow& W, double q) {
-  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
-  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double x = cep_read_freq(R, W, q);
   const double cw2 = 2.0 * cos(((2.0 * M_PI) * x) / R.fs);
   double b1 = 0.0, b2 = 0.0;
   for (int p = R.P; p >= 1; --p) {   // one LDS address for the wave: a broadcast
@@ -142,8 +218,7 @@ __device__ inline void cep_recur(const double* c, int P, double cw2, double& b1,
 // Phi(q) = -2 sum_p c_p sin(p wq) at the read frequency of cep_read: the minimum-phase response of the envelope; an
 // empty row (every c_p = 0) reads 0.
 __device__ inline double cep_read_phase(const CepRead& R, const WarpRow& W, double q) {
-  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
-  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double x = cep_read_freq(R, W, q);
   double sn, cs, b1, b2;
   sincos(((2.0 * M_PI) * x) / R.fs, &sn, &cs);
   cep_recur(R.c, R.P, 2.0 * cs, b1, b2);
@@ -151,10 +226,9 @@ __device__ inline double cep_read_phase(const CepRead& R, const WarpRow& W, doub
 }
 
 // The two readouts on the warped axis (§9.8): the read frequency and the hold as above, in Hz, then Omega_a through
-// cep_axis_angle and the recurrence in Reinsch's form.  (Helpers of their own: cep_read and cep_read_phase keep their text.)
+// cep_axis_angle and the recurrence in Reinsch's form.
 __device__ inline double cep_read_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
-  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
-  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double x = cep_read_freq(R, W, q);
   const CepAngle A = cep_axis_angle(X, (M_PI * x) / R.fs);
   double b, d;
   cep_recur_reinsch(R.c, R.P, A, b, d);
@@ -162,8 +236,7 @@ __device__ inline double cep_read_warped(const CepRead& R, const CepAxis& X, con
 }
 
 __device__ inline double cep_read_phase_warped(const CepRead& R, const CepAxis& X, const WarpRow& W, double q) {
-  double x = R.mode == 1 ? q / R.alpha : R.mode == 2 ? warp_inverse(W, q) : q;
-  x = fmin(fmax(x, 0.0), 0.5 * R.fs);
+  const double x = cep_read_freq(R, W, q);
   const CepAngle A = cep_axis_angle(X, (M_PI * x) / R.fs);
   double b, d;
   cep_recur_reinsch(R.c, R.P, A, b, d);
@@ -303,24 +376,58 @@ extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
 // not the empty row, k < Kcap, h f0_i < fs/2 (this product, as the host forms it) and exp did not underflow; every other
 // cell is written as 0 by the same stores.  One sincos per cell serves C and Phi through cep_recur.  The row's
 // coefficients sit in the wave's own LDS: the waves of a block share no data, so there is no block barrier.
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
+// WARP (§9.8): the row lies on the warped axis, a = cep_a (0.0 and not read without it): the cell's angle through the
+// rational map and the recurrence in Reinsch's form (cep_axis_angle).
+template <bool WARP>
+__global__ void __launch_bounds__(64 * CEP_WAVES)
     eaqhm_model_build_kernel(const double* __restrict__ f0, const double* __restrict__ theta,
                              const unsigned char* __restrict__ voiced, const double* __restrict__ ceps, int P,
                              const double* __restrict__ a0, int n, double fs, int Kmax, int Kcap, int zero_phase,
-                             double* __restrict__ records) {
-#define CEP_WARPED 0
-#include "eaqhm_cepstrum_build.inc"
-#undef CEP_WARPED
-}
-
-extern "C" __global__ void __launch_bounds__(64 * CEP_WAVES)
-    eaqhm_model_build_warped_kernel(const double* __restrict__ f0, const double* __restrict__ theta,
-                                    const unsigned char* __restrict__ voiced, const double* __restrict__ ceps, int P,
-                                    const double* __restrict__ a0, int n, double fs, int Kmax, int Kcap, int zero_phase,
-                                    double* __restrict__ records, double cep_a) {
-#define CEP_WARPED 1
-#include "eaqhm_cepstrum_build.inc"
-#undef CEP_WARPED
+                             double* __restrict__ records, double cep_a) {
+  __shared__ double sc[CEP_WAVES][CEP_PMAX + 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * CEP_WAVES + w);   // one wave per instant: scalar
+  if (i >= n) return;
+  double* c = sc[w];
+  if (lane <= P) c[lane] = ceps[(size_t)i * (P + 1) + lane];
+  __builtin_amdgcn_wave_barrier();
+  const bool rowlive = voiced[i] != 0 && c[0] != -INFINITY;
+  const double fi = f0[i], th = theta[i], half = 0.5 * fs;
+  double* row = records + (size_t)i * (3 * (size_t)Kmax + 1);
+  for (int k0 = 0; k0 < Kmax; k0 += 64) {
+    const int k = k0 + lane;
+    if (k >= Kmax) break;
+    const double h = (double)(k + 1);
+    const double fm = __dmul_rn(h, fi);
+    double a = 0.0, f = 0.0, ph = 0.0;
+    if (rowlive && k < Kcap && fm < half) {
+      double sn, b1;   // sin of the cell's angle and b_1 of its recurrence: Phi = -2 b_1 sn
+      if constexpr (WARP) {
+        double d1;
+        const CepAngle A = cep_axis_angle(cep_axis(cep_a), (M_PI * fm) / fs);
+        sn = A.sn;
+        cep_recur_reinsch(c, P, A, b1, d1);
+        a = exp(2.0 * (0.5 * A.dl * b1 + A.sg * d1) + c[0]);
+      } else {
+        double cs, b2;
+        sincos(((2.0 * M_PI) * fm) / fs, &sn, &cs);
+        const double cw2 = 2.0 * cs;
+        cep_recur(c, P, cw2, b1, b2);
+        a = exp(2.0 * (0.5 * cw2 * b1 - b2) + c[0]);
+      }
+      if (a != 0.0) {
+        const double hs = __dmul_rn(h, th);           // the product rounded as the definition rounds it, then frac
+        double x = __dmul_rn(2.0 * M_PI, hs - floor(hs));
+        if (!zero_phase) x += -2.0 * (b1 * sn);
+        ph = x - (2.0 * M_PI) * ceil((x - M_PI) / (2.0 * M_PI));   // into (-pi, pi]
+        f = fm;
+      }
+    }
+    row[k] = a;
+    row[Kmax + k] = f;
+    row[2 * Kmax + k] = ph;
+  }
+  if (lane == 0) row[3 * (size_t)Kmax] = a0[i];
 }
 }  // namespace eaqhm
 
@@ -358,17 +465,10 @@ static int model_cepstrum_launch(eaqhm_ctx* ctx, const char* fn, const double* r
   const size_t lds = (size_t)CEP_WAVES * cep_wave_doubles(Kmax, order) * sizeof(double);
   if (lds > CEPSTRUM_LDS_MAX) return cep_fail(ctx, fn, "Kmax too large for the nodes");
   const dim3 grid((unsigned)((No_ti + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
-  if (warp) {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_warped_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(eaqhm_model_cepstrum_warped_kernel, grid, block, lds, ctx->stream, records, (int)No_ti, (int)Kmax,
-                       fs, (int)order, lambda, ceps, *warp);
-  } else {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)eaqhm_model_cepstrum_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(eaqhm_model_cepstrum_kernel, grid, block, lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs,
-                       (int)order, lambda, ceps);
-  }
+  const auto kernel = warp ? eaqhm_model_cepstrum_kernel<true> : eaqhm_model_cepstrum_kernel<false>;
+  HIP_TRY(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, records, (int)No_ti, (int)Kmax, fs, (int)order, lambda, ceps,
+                     warp ? *warp : 0.0);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
@@ -484,13 +584,9 @@ static int model_build_launch(eaqhm_ctx* ctx, const char* fn, const double* f0, 
   if (zero_phase != 0 && zero_phase != 1) return cep_fail(ctx, fn, "zero_phase is 0 or 1");
   if (!warp_ok(warp)) return cep_fail(ctx, fn, WARP_MSG);
   const dim3 grid((unsigned)((n + CEP_WAVES - 1) / CEP_WAVES)), block(64 * CEP_WAVES);
-  if (warp)
-    hipLaunchKernelGGL(eaqhm_model_build_warped_kernel, grid, block, 0, ctx->stream, f0, theta,
-                       (const unsigned char*)voiced, ceps, (int)order, a0, (int)n, fs, (int)Kmax, (int)Kcap,
-                       (int)zero_phase, records, *warp);
-  else
-    hipLaunchKernelGGL(eaqhm_model_build_kernel, grid, block, 0, ctx->stream, f0, theta, (const unsigned char*)voiced,
-                       ceps, (int)order, a0, (int)n, fs, (int)Kmax, (int)Kcap, (int)zero_phase, records);
+  hipLaunchKernelGGL(warp ? eaqhm_model_build_kernel<true> : eaqhm_model_build_kernel<false>, grid, block, 0, ctx->stream,
+                     f0, theta, (const unsigned char*)voiced, ceps, (int)order, a0, (int)n, fs, (int)Kmax, (int)Kcap,
+                     (int)zero_phase, records, warp ? *warp : 0.0);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -20,6 +20,7 @@
 // The host model rounds every operation once, so nothing here may be contracted into an fma.  No atomics: every output
 // word has one writer.
 #include "eaqhm_common.h"
+#include "eaqhm_wave.h"
 #include "../../include/eaqhm_formant.h"
 
 #pragma clang fp contract(off)
@@ -34,25 +35,6 @@ constexpr int FM_KC = EAQHM_FORMANT_CAND;
 constexpr int FM_THREADS = 512;                   // the forward kernel's block: one thread per state, 495 at most
 constexpr int FM_JROW = FM_KC + 1;                // a row of J: absent, then the candidates
 
-// v of lane j, j the same on every lane: two v_readlane, the value lands in scalar registers
-__device__ __forceinline__ double fm_lane_value(double v, int j) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), j);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
-  return __hiloint2double(hi, lo);
-}
-
-// stepup_lanes of eaqhm_noise.hip, a copy (a shared function would change that unit's machine code): lane i holds k_i
-// in kk (lanes 1..p); a_j comes back on lane j (a_0 = 1).  a_j += k_i a_{i-j}, j = 1..i, from the old values.
-__device__ __forceinline__ double fm_stepup_lanes(double kk, int p, int lane) {
-  double a = lane == 0 ? 1.0 : 0.0;
-  for (int i = 1; i <= p; ++i) {
-    const double k = __shfl(kk, i, 64);
-    const double ar = __shfl(a, (i - lane) & 63, 64);
-    if (lane >= 1 && lane <= i) a += k * ar;
-  }
-  return a;
-}
-
 extern "C" __global__ void __launch_bounds__(64 * FM_WAVES)
     eaqhm_allpole_roots_kernel(const double* __restrict__ refl, i64 Nf, int p, double* __restrict__ roots,
                                int* __restrict__ iters) {
@@ -60,13 +42,13 @@ extern "C" __global__ void __launch_bounds__(64 * FM_WAVES)
   const i64 m = (i64)blockIdx.x * FM_WAVES + wave;
   if (m >= Nf) return;   // the kernel has no barrier
   const double kin = (lane >= 1 && lane <= p) ? refl[(size_t)m * p + (lane - 1)] : 0.0;
-  const double a = fm_stepup_lanes(kin, p, lane);
+  const double a = stepup_lanes(kin, p, lane);
   const unsigned long long live = __ballot(kin != 0.0);   // bit i: k_i != 0 (bit 0 is never set)
   const int pe = __builtin_amdgcn_readfirstlane(live ? 63 - __clzll((long long)live) : 0);
   double zr = 0.0, zi = 0.0;
   int it = 0;
   if (pe > 0) {
-    const double ape = fm_lane_value(a, pe);
+    const double ape = wave_lane(a, pe);
     const double r0 = exp(log(fabs(ape)) / (double)pe);
     const double ang = 2.0 * M_PI * (double)lane / (double)pe + M_PI / (2.0 * (double)pe);
     double sn, cs;
@@ -80,7 +62,7 @@ extern "C" __global__ void __launch_bounds__(64 * FM_WAVES)
       double pr = 1.0, pi = 0.0, dr = 0.0, di = 0.0, s = 1.0;
       const double az = sqrt(zr * zr + zi * zi);
       for (int j = 1; j <= pe; ++j) {
-        const double aj = fm_lane_value(a, j);
+        const double aj = wave_lane(a, j);
         const double ndr = (dr * zr - di * zi) + pr;
         const double ndi = (dr * zi + di * zr) + pi;
         const double npr = (pr * zr - pi * zi) + aj;
@@ -103,7 +85,7 @@ extern "C" __global__ void __launch_bounds__(64 * FM_WAVES)
       // S = sum_{j != k} 1 / (z_k - z_j), ascending j, over the old iterate
       double Sr = 0.0, Si = 0.0;
       for (int j = 0; j < pe; ++j) {
-        const double er = zr - fm_lane_value(zr, j), ei = zi - fm_lane_value(zi, j);
+        const double er = zr - wave_lane(zr, j), ei = zi - wave_lane(zi, j);
         const double dd = er * er + ei * ei;
         const double qr = er / dd, qi = ei / dd;
         if (j != lane) {
@@ -147,7 +129,7 @@ extern "C" __global__ void __launch_bounds__(64 * FM_WAVES)
   const unsigned long long mask = __ballot(ok);
   int rank = 0;
   for (int j = 0; j < p; ++j) {
-    const double fj = fm_lane_value(f, j);
+    const double fj = wave_lane(f, j);
     if (((mask >> j) & 1ull) && (fj < f || (fj == f && j < lane))) ++rank;
   }
   const int n = __popcll(mask), cnt = n < FM_KC ? n : FM_KC;

@@ -11,14 +11,13 @@
 //                              instants: pass 0 chunk aggregates, pass 1 applies the carries), giving the unwrapped
 //                              knot phase R and the phase of each run's first knot.
 //   eaqhm_modify_carry_kernel  one wave per slot: exclusive segmented scan of the chunk aggregates (the carries).
-//   eaqhm_modify_eval_kernel   blocks of output samples: the touched intervals are integrated once into LDS (as
-//                              stage 1 of eaqhm_eval_kernel), then per (sample, slot) A * cos(phase), per sample the
-//                              a0 spline and the sum over slots in slot order.
-//   eaqhm_modify_eval_curve_kernel  the eval body with the cumulative time map C of the contours in place of
-//                              tau = n'/rho (eaqhm_modify_body.inc holds the body of both).
-//   eaqhm_modify_eval_shape_kernel, eaqhm_modify_eval_curve_shape_kernel  the two eval bodies once more with the
-//                              shape-invariant phase of DESIGN.md §11: Psi unweighted plus (k+1) times the phase
-//                              advance of the fundamental, from the per-instant tracks f0 and S.
+//   eaqhm_modify_eval_kernel<CURVE, SHAPE>  blocks of output samples: the touched intervals are integrated once into
+//                              LDS (as stage 1 of eaqhm_eval_kernel), then per (sample, slot) A * cos(phase), per
+//                              sample the a0 spline and the sum over slots in slot order.  A kernel template, four
+//                              instantiations (profilers show them under these C++ names):
+//                                CURVE  the cumulative time map C of the contours in place of tau = n'/rho;
+//                                SHAPE  the shape-invariant phase of DESIGN.md §11: Psi unweighted plus (k+1) times the
+//                                       phase advance of the fundamental, from the per-instant tracks f0 and S.
 //   eaqhm_model_envelope_kernel  reads the envelope itself out on a frequency grid.
 //   eaqhm_modify_amp_warp_kernel, eaqhm_model_envelope_warp_kernel  the amplitudes A' and the readout with the
 //                              piecewise-linear formant warp of DESIGN.md §9.4 (eaqhm_warp.h) in place of / alpha.
@@ -422,6 +421,9 @@ struct MEvalArgs {
 // (the last entry is rho_{n-1}, past the last knot) and phase weight g_j per interval.
 struct MCurve { const double* C; const double* rate; const double* gain; };
 
+// The contour map as the eval kernel sees it (R holds the weighted phase G, the phase weight g_j is per interval): where
+// a sample lies (locate; bound and stage prepare a block: the staged rows [NR][3] (C_j, r_j, g_j) follow the codes in
+// LDS), the isolated knots of a sample (iso_range) and tau for the a0 spline.
 struct CurveMap {
   MCurve G;
   int last;          // No_ti - 1
@@ -479,83 +481,184 @@ __device__ inline double shape_advance(const MShape& Sh, int j, double r, double
   return Sh.S[j] + r * (sgm * sf + r * (sgm * (Sh.f0[j + 1] - sf) / (2.0 * (double)D)));
 }
 
-// ---- the phase term of the shape kernels (§11): Psi weighs 1 and stage 2 adds 2 pi (k+1) s to each phase; s of the
-// block's samples [TBS] follows the time-map rows in LDS (MAP_CROW doubles per row).  Without it every macro is empty.
-#define EAQHM_MODIFY_SHAPE 0
-#define SHAPE_WEIGHT(g) g
-#define SHAPE_INIT
-#define SHAPE_ADD
-#define SHAPE_SAMPLE
-
-// ---- the scalar kernels: tau = n'/rho, phase weight beta rho
-#define EAQHM_MODIFY_CURVE 0
-#define MAP_CROW 0
-#define MAP_G E.beta * E.rho
-#define MAP_INIT
-#define MAP_LOCATE(n, j, r) locate(n, E.rho, D, j, r)
-#define MAP_BOUND
-#define MAP_STAGE
-#define MAP_BLOCK_WEIGHT const double br = SHAPE_WEIGHT(E.beta * E.rho);
-#define MAP_INTERVAL_WEIGHT
-#define MAP_PSI(loc) Rj + (loc)
-#define MAP_OFF ph0
-#define MAP_ISO_RANGE                                                                                               \
-  const double tau = (double)n / E.rho;                                                                             \
-  const double hw = 0.5 / E.rho + 1.0;                                                                              \
-  const int ilo = max(0, (int)floor((tau - hw) / (double)D)), ihi = min(A.No_ti - 1, (int)floor((tau + hw) / (double)D) + 1);
-#define MAP_ISO_AT(i) (long long)rint(E.rho * ((double)i * (double)D)) == n
-#define MAP_TAU (double)n / E.rho
-#include "eaqhm_modify_body.inc"
-#include "eaqhm_modify_shape.inc"   // the same map with the shape term: eaqhm_modify_eval_shape_kernel
-#undef EAQHM_MODIFY_CURVE
-#undef MAP_CROW
-#undef MAP_G
-#undef MAP_INIT
-#undef MAP_LOCATE
-#undef MAP_BOUND
-#undef MAP_STAGE
-#undef MAP_BLOCK_WEIGHT
-#undef MAP_INTERVAL_WEIGHT
-#undef MAP_PSI
-#undef MAP_OFF
-#undef MAP_ISO_RANGE
-#undef MAP_ISO_AT
-#undef MAP_TAU
-
-// ---- the contour kernels: R holds the weighted phase G, the phase weight g_j is per interval, and
-// the staged rows [NR][3] (C_j, r_j, g_j) follow the codes
-#define EAQHM_MODIFY_CURVE 1
-#define MAP_CROW 3
-#define MAP_G Cu.gain[j]
-#define MAP_INIT CurveMap Mp{Cu, A.No_ti - 1, D, 0, A.No_ti - 2, nullptr, 0, -1};
-#define MAP_LOCATE(n, j, r) Mp.locate(n, D, j, r)
-#define MAP_BOUND Mp.bound(jfirst, jlast, A.No_ti);
-#define MAP_STAGE Mp.stage((double*)(ccode + (((size_t)NR * K + 7) & ~(size_t)7)), C.r0, C.r1, tid, blockDim.x);
-#define MAP_BLOCK_WEIGHT
-#define MAP_INTERVAL_WEIGHT const double br = SHAPE_WEIGHT(Mp.gv(j)), o = ph0 + Rj;
-#define MAP_PSI(loc) (loc)
-#define MAP_OFF o
-#define MAP_ISO_RANGE                                                                                               \
-  int ilo, ihi;                                                                                                     \
-  Mp.iso_range(n, j, A.No_ti, ilo, ihi);
-#define MAP_ISO_AT(i) (long long)rint(Mp.Cv(i)) == n
-#define MAP_TAU Mp.tau(sj[s], sr[s])
-#include "eaqhm_modify_body.inc"
-#include "eaqhm_modify_shape.inc"   // eaqhm_modify_eval_curve_shape_kernel
-#undef EAQHM_MODIFY_CURVE
-#undef MAP_CROW
-#undef MAP_G
-#undef MAP_INIT
-#undef MAP_LOCATE
-#undef MAP_BOUND
-#undef MAP_STAGE
-#undef MAP_BLOCK_WEIGHT
-#undef MAP_INTERVAL_WEIGHT
-#undef MAP_PSI
-#undef MAP_OFF
-#undef MAP_ISO_RANGE
-#undef MAP_ISO_AT
-#undef MAP_TAU
+// ------------------------------------------------------------------------------------------------
+// The eval kernel, one body for its four instantiations: CURVE picks the time map (tau = n'/rho with the phase weight
+// beta rho, §9; or CurveMap with g_j per interval, §9.1) and SHAPE the shape-invariant phase term (§11).  The kernel itself is the template, so each instantiation is compiled as a
+// kernel of its own; the same body inlined into four extern "C" wrappers cost the scalar one an occupancy step (§9.1).
+// Cu is read only with CURVE and Sh only with SHAPE.
+// Block of TBS consecutive output samples x all slots.
+//   stage 0  per sample: interval j and offset r (LDS); with SHAPE also the fundamental's phase advance s(n') in
+//            cycles (§11), one more double per sample after the map's staged rows.
+//   stage 1  one thread per (interval, slot) touching the block: the interval's local phase
+//            Psi(u) = R_j + sum_{v=1..u} w(v) - sum_{v=0..u} sin(pi v/D) er, u = 0..D, in the eval kernel's summation
+//            order; at each of the block's samples in the interval the phase P0 + beta rho ((1-fr) Psi(u0) + fr Psi(u0+1))
+//            goes to X[k][s].  A run's last knot (tau = c_b) is the end u = D of its last interval.  With SHAPE Psi
+//            weighs 1 (§11).
+//   stage 2  one thread per (sample, slot group): amplitude, A cos(phase), isolated knots (with SHAPE 2 pi (k+1) s(n')
+//            is first added to the phases of the thread's cells); then one thread per sample adds the slots in slot
+//            order and the a0 spline.
+template <bool CURVE, bool SHAPE>
+__global__ void __launch_bounds__(256) eaqhm_modify_eval_kernel(MEvalArgs E, MCurve Cu, MShape Sh, int TBS, int NR) {
+  constexpr int CROW = CURVE ? 3 : 0;   // doubles per staged row that the time map adds
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const ModArgs& A = E.M;
+  const int D = A.step, K = A.Kmax, TP = TBS + 1;
+  double* ft = lds;                                   // D+1
+  double* X = lds + ((D + 1 + 1) & ~1);               // [K][TP]
+  double* sr = X + (size_t)K * TP;                    // [TBS] r of each sample
+  double* crec = sr + TBS;                            // [NR][3K+1]
+  double* cmom = crec + (size_t)NR * (3 * K + 1);     // [NR][K+1]
+  int* sj = (int*)(cmom + (size_t)NR * (K + 1));      // [TBS] interval of each sample
+  unsigned char* ccode = (unsigned char*)(sj + ((TBS + 1) & ~1));   // [NR][K]
+  double* crow = (double*)(ccode + (((size_t)NR * K + 7) & ~(size_t)7));   // [NR][CROW] the map's staged rows
+  double* ss = crow + (size_t)NR * CROW;              // [TBS] s of each sample (SHAPE)
+  const int tid = threadIdx.x;
+  const long long t0 = E.t_lo + (long long)blockIdx.x * TBS;
+  const long long t1 = (t0 + TBS < E.t_hi) ? (t0 + TBS) : E.t_hi;
+  const int ns = (int)(t1 - t0);
+  CurveMap Mp{Cu, A.No_ti - 1, D, 0, A.No_ti - 2, nullptr, 0, -1};   // CURVE only
+  auto locate_n = [&](long long n, int& j, double& r) {
+    if constexpr (CURVE) Mp.locate(n, D, j, r);
+    else locate(n, E.rho, D, j, r);
+  };
+  int jfirst, jlast;
+  double rdummy;
+  locate_n(t0, jfirst, rdummy);
+  locate_n(t1 - 1, jlast, rdummy);
+  if constexpr (CURVE) Mp.bound(jfirst, jlast, A.No_ti);
+  // intervals met by the block: one before the first sample's (a run's last knot) up to the last sample's
+  const int jlo = max(0, jfirst - 1), jhi = min(A.No_ti - 2, jlast);
+  MCache C;
+  {
+    C.r0 = max(0, jlo - 1);
+    C.r1 = min(A.No_ti - 1, jhi + 2);
+    if (C.r1 > C.r0 + NR - 1) C.r1 = C.r0 + NR - 1;
+    if (C.r1 < C.r0) C.r1 = C.r0 - 1;
+    C.rec = crec; C.mom = cmom; C.code = ccode;
+    const int nrow = C.r1 - C.r0 + 1, RS = 3 * K + 1;
+    for (int q = tid; q < nrow * RS; q += blockDim.x) crec[q] = A.records[(size_t)C.r0 * RS + q];
+    for (int q = tid; q < nrow * (K + 1); q += blockDim.x) cmom[q] = A.mom[(size_t)C.r0 * (K + 1) + q];
+    for (int q = tid; q < nrow * K; q += blockDim.x) ccode[q] = A.code[(size_t)C.r0 * K + q];
+    if constexpr (CURVE) Mp.stage(crow, C.r0, C.r1, tid, blockDim.x);
+  }
+  for (int u = tid; u <= D; u += blockDim.x) ft[u] = sin(M_PI * (double)u / (double)D);
+  for (int s = tid; s < ns; s += blockDim.x) {
+    int j; double r;
+    locate_n(t0 + s, j, r);
+    sj[s] = j; sr[s] = r;
+    if constexpr (SHAPE)   // g_j from memory: the staged rows are not visible before the barrier
+      ss[s] = (j < A.No_ti - 1) ? shape_advance(Sh, j, r, (CURVE ? Cu.gain[j] : E.beta * E.rho) - 1.0, D, A.fs)
+                                : Sh.S[A.No_ti - 1];
+  }
+  __syncthreads();
+  const double bw = E.beta * E.rho;   // the scalar map's phase weight, one for the block
+  // ---- stage 1
+  if (jhi >= jlo) {
+    const int nint = jhi - jlo + 1;
+    const double scale = 2.0 * M_PI / A.fs;
+    double S = 0.0;   // sum_{v=0..D} sin(pi v/D), in order
+    for (int u = 0; u <= D; ++u) S += ft[u];
+    for (int p = tid; p < nint * K; p += blockDim.x) {
+      const int jj = p / K, k = p - jj * K, j = jlo + jj;
+      CSlot Sl{A, C, k};
+      const int cj = Sl.code(j);
+      if (cj == 0 || Sl.code(j + 1) == 0) continue;
+      // the block's samples in this interval: [sa, sb), plus the run's last knot when j+1 ends the run
+      int sa = 0, hi = ns;
+      while (sa < hi) { const int mid = (sa + hi) >> 1; if (sj[mid] < j) sa = mid + 1; else hi = mid; }
+      int sb = sa;
+      while (sb < ns && sj[sb] == j) ++sb;
+      const bool ends = Sl.code(j + 2) == 0;
+      const int sl = (ends && sb < ns && sj[sb] == j + 1 && sr[sb] == 0.0) ? sb : -1;
+      if (sa == sb && sl < 0) continue;
+      const FmPiece P = make_piece(Sl, j, cj);
+      double w0, acc, emis, Mr;
+      interval_close(Sl, P, j, D, scale, w0, acc, emis, Mr);
+      // a run's last interval closes its mismatch completely: the model's phase at that knot is the integrated one
+      const double er = ends ? emis / S : M_PI * emis / (2.0 * (double)D);
+      const double Rj = E.R[(size_t)j * K + k], ph0 = E.P0[(size_t)j * K + k];
+      // the phase is P0 + g (R_j + local) under the scalar map and, R holding the weighted phase, (P0 + R_j) + g_j local
+      // under the contours: a sum is not to be reordered, so the two add R_j at different places
+      const double br = SHAPE ? 1.0 : CURVE ? Mp.gv(j) : bw, o = CURVE ? ph0 + Rj : ph0;
+      acc = w0;
+      double c = ft[0] * er;
+      double prev = CURVE ? ((acc - w0) - c) : Rj + ((acc - w0) - c);
+      int q = sa;
+      // u = 0: samples on the knot itself
+      while (q < sb && sr[q] == 0.0) { X[(size_t)k * TP + q] = o + br * prev; ++q; }
+      for (int u = 1; u <= D; ++u) {
+        acc += scale * P(u);
+        c += ft[u] * er;
+        const double psi = CURVE ? ((acc - w0) - c) : Rj + ((acc - w0) - c);
+        while (q < sb) {
+          const double rq = sr[q], u0 = floor(rq), fr = rq - u0;
+          if ((int)u0 == u - 1 && fr > 0.0) X[(size_t)k * TP + q] = o + br * ((1.0 - fr) * prev + fr * psi);
+          else if ((int)u0 == u && fr == 0.0) X[(size_t)k * TP + q] = o + br * psi;
+          else break;
+          ++q;
+        }
+        prev = psi;
+      }
+      if (sl >= 0) X[(size_t)k * TP + sl] = o + br * prev;
+    }
+  }
+  __syncthreads();
+  // ---- stage 2
+  const int s = tid % TBS, g = tid / TBS, G = blockDim.x / TBS;
+  const bool live = s < ns;
+  const long long n = t0 + s;
+  if (live) {
+    const int j = sj[s];
+    const double r = sr[s];
+    int ilo, ihi;   // the instants whose isolated knot can land on this sample
+    if constexpr (CURVE) {
+      Mp.iso_range(n, j, A.No_ti, ilo, ihi);
+    } else {
+      const double tau = (double)n / E.rho;
+      const double hw = 0.5 / E.rho + 1.0;
+      ilo = max(0, (int)floor((tau - hw) / (double)D));
+      ihi = min(A.No_ti - 1, (int)floor((tau + hw) / (double)D) + 1);
+    }
+    if constexpr (SHAPE) {
+      const double shs = ss[s];
+      for (int k = g; k < K; k += G) X[(size_t)k * TP + s] += (2.0 * M_PI * (double)(k + 1)) * shs;
+    }
+    for (int k = g; k < K; k += G) {
+      CSlot Sl{A, C, k};
+      auto inrun = [&](int q) { return q >= 0 && q <= A.No_ti - 2 && Sl.code(q) != 0 && Sl.code(q + 1) != 0; };
+      double cell = 0.0;
+      int jj = -1;
+      double rr = r;
+      if (inrun(j)) jj = j;
+      else if (r == 0.0 && inrun(j - 1)) { jj = j - 1; rr = (double)D; }
+      if (jj >= 0) {
+        const double a0v = E.amp[(size_t)jj * K + k], a1v = E.amp[(size_t)(jj + 1) * K + k];
+        const double Av = ((a1v - a0v) / (double)D) * rr + a0v;
+        cell = (Av != 0.0) ? Av * cos(X[(size_t)k * TP + s]) : 0.0;
+      }
+      for (int i = ilo; i <= ihi; ++i) {   // isolated accepted knots land on the output sample nearest to their image
+        if (Sl.code(i) == 1 && (long long)rint(CURVE ? Mp.Cv(i) : E.rho * ((double)i * (double)D)) == n)
+          cell += E.amp[(size_t)i * K + k] * cos(Sl.ph(i));
+      }
+      X[(size_t)k * TP + s] = cell;   // this thread is the only reader of the cell
+    }
+  }
+  __syncthreads();
+  if (tid < TBS && live) {
+    double synth = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < K; ++k) synth += X[(size_t)k * TP + s];
+    const double tau = CURVE ? Mp.tau(sj[s], sr[s]) : (double)n / E.rho;
+    int ia = sj[s];
+    if (ia > A.No_ti - 2) ia = A.No_ti - 2;
+    if (ia < 0) ia = 0;
+    CSlot S0{A, C, K};   // column K of mom = the a0 spline; its knots are the last record column
+    const int RS = 3 * K + 1;
+    const double a0v = spline_piece(S0.recv(ia, RS - 1), S0.recv(ia + 1, RS - 1), S0.mom(ia), S0.mom(ia + 1),
+                                    tau - (double)ia * (double)D, (double)D);
+    E.out[n] = a0v + 2.0 * synth;
+  }
+}
 }  // namespace eaqhm
 
 using namespace eaqhm;
@@ -629,19 +732,18 @@ static int modify_block_samples(int Kmax, int step, double rho, int crow, int sh
   return 16;
 }
 
-// one eval launch: the kernel's LDS limit, the launch, the error check.  P is deduced from the kernel and from the
-// arguments alike, so each argument must have exactly its parameter's type: nothing is converted at the launch.
-template <class... P>
-static int modify_eval_launch(eaqhm_ctx* ctx, void (*kernel)(P...), long long nblocks, size_t lds_bytes, P... args) {
+// one eval launch: the instantiation's LDS limit, the launch, the error check
+static int modify_eval_launch(eaqhm_ctx* ctx, void (*kernel)(MEvalArgs, MCurve, MShape, int, int), long long nblocks,
+                              size_t lds_bytes, const MEvalArgs& E, const MCurve& Cu, const MShape& Sh, int TBS, int NR) {
   HIP_TRY(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, args...);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), lds_bytes, ctx->stream, E, Cu, Sh, TBS, NR);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }
 
 // The time map is the contours'  when C, rate and gain are given, else tau = n'/rho; the phase is the
-// shape-invariant one (§11; the prep ran without gain) when f0 and S are given, else each slot's own.  Two groups, four
-// kernels.
+// shape-invariant one (§11; the prep ran without gain) when f0 and S are given, else each slot's own.  Two groups, the
+// four instantiations of one kernel.
 extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const uint8_t* code, const double* mom,
                                   const double* amp, const double* R, const double* ph0, int32_t No_ti, int32_t Kmax,
                                   int32_t step, double fs, double rho, double beta, int64_t L_out, int64_t t_lo,
@@ -669,11 +771,9 @@ extern "C" int eaqhm_modify_synth(eaqhm_ctx* ctx, const double* records, const u
   const MCurve Cu{C, rate, gain};
   const MShape Sh{f0, S};
   const long long nblocks = (t_hi - t_lo + TBS - 1) / TBS;
-  if (curve)
-    return shape ? modify_eval_launch(ctx, eaqhm_modify_eval_curve_shape_kernel, nblocks, lds_bytes, E, Cu, Sh, TBS, NR)
-                 : modify_eval_launch(ctx, eaqhm_modify_eval_curve_kernel, nblocks, lds_bytes, E, Cu, TBS, NR);
-  return shape ? modify_eval_launch(ctx, eaqhm_modify_eval_shape_kernel, nblocks, lds_bytes, E, Sh, TBS, NR)
-               : modify_eval_launch(ctx, eaqhm_modify_eval_kernel, nblocks, lds_bytes, E, TBS, NR);
+  const auto kernel = curve ? (shape ? eaqhm_modify_eval_kernel<true, true> : eaqhm_modify_eval_kernel<true, false>)
+                            : (shape ? eaqhm_modify_eval_kernel<false, true> : eaqhm_modify_eval_kernel<false, false>);
+  return modify_eval_launch(ctx, kernel, nblocks, lds_bytes, E, Cu, Sh, TBS, NR);
 }
 
 // ---- envelope readout

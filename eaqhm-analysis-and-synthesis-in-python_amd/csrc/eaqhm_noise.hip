@@ -10,13 +10,15 @@
 //                                DESIGN.md §10.3 (eaqhm_warp.h) as the read frequency in place of w / alpha
 //   eaqhm_noise_cepstrum_kernel  one wave per frame: the cepstrum of the frame's log spectrum by the LPC-to-cepstrum
 //                                recursion, lanes over the terms of each step
-//   eaqhm_noise_from_cepstrum_kernel  one wave per row: the spectrum of a cepstral row on the warp kernel's grid by
-//                                Clenshaw's recurrence, then that kernel's lag sums and Levinson-Durbin recursion
+//   eaqhm_noise_from_cepstrum_kernel<WARP>  one wave per row: the spectrum of a cepstral row on the warp kernel's grid
+//                                by Clenshaw's recurrence, then that kernel's lag sums and Levinson-Durbin recursion;
+//                                WARP: the row lies on the all-pass warped axis (§9.8)
 //   eaqhm_noise_modulation_kernel   one wave per frame, lanes over the frame's samples: the Fourier coefficients of the
 //                                   residual's power over the fundamental's phase
 //   eaqhm_noise_combine_mod_kernel  the combine kernel with each frame's pitch-synchronous gain g_q(n')
 #include "eaqhm_common.h"
 #include "eaqhm_warp.h"
+#include "eaqhm_wave.h"
 
 // The synthesis follows the NumPy model of the definition operation by operation (no fused multiply-add), so the two
 // differ only where a library function does (cos); the autocorrelation sums ask for their FMAs by name.
@@ -26,12 +28,6 @@ namespace eaqhm {
 
 constexpr int NA_WAVES = 4;   // frames (waves) per block of the analysis kernel
 constexpr int NA_PAD = 64;    // zeros in front of each wave's frame: x[v - l] for v < l reads them (l <= 63)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 // LDS: NA_WAVES x (NA_PAD + 4 hop) doubles
 extern "C" __global__ void __launch_bounds__(64 * NA_WAVES)
@@ -69,25 +65,10 @@ extern "C" __global__ void __launch_bounds__(64 * NA_WAVES)
   double r = (r0 + r1) + (r2 + r3);
   sw2 = wave_sum(sw2);
 
-  // Levinson-Durbin: a_j on lane j (a_0 = 1), the reversed vectors by a cross-lane read, the sum by a wave reduction
+  // Levinson-Durbin in the wave (eaqhm_wave.h), r[0] inflated by the -90 dB white floor
   const double r00 = __shfl(r, 0, 64);
   double kk = 0.0, E = 0.0;
-  if (r00 > 0.0) {
-    if (lane == 0) r *= (1.0 + 1e-9);
-    E = __shfl(r, 0, 64);
-    double a = lane == 0 ? 1.0 : 0.0;
-    for (int i = 1; i <= p; ++i) {
-      const int src = (i - lane) & 63;
-      const double rr = __shfl(r, src, 64);
-      const double acc = __shfl(wave_sum(lane < i ? a * rr : 0.0), 0, 64);
-      const double k = -acc / E;
-      if (!(fabs(k) < 1.0)) break;
-      const double ar = __shfl(a, src, 64);
-      if (lane >= 1 && lane <= i) a += k * ar;      // lane i: 0 + k a_0
-      if (lane == i) kk = k;
-      E *= (1.0 - k * k);
-    }
-  }
+  if (r00 > 0.0) E = levinson_lanes<true>(r, p, lane, kk);
   if (lane == 0) sigma[m] = r00 > 0.0 ? sqrt(E / sw2) : 0.0;
   if (lane >= 1 && lane <= p) refl[(size_t)m * p + (lane - 1)] = kk;
 }
@@ -160,41 +141,6 @@ extern "C" __global__ void __launch_bounds__(256)
 constexpr int NW_M = 1024;    // grid intervals on [0, pi] (M of the definition)
 constexpr int NW_WAVES = 8;   // frames (waves) per block of the warp kernel
 constexpr int NE_WAVES = 4;   // frames (waves) per block of the envelope kernel
-
-// The Levinson-Durbin recursion of eaqhm_noise_analyse_kernel on r[l] of lane l (r[0] > 0), a second copy: calling one
-// function from both changed the analysis kernel's machine code (tools/isa_diff.py).  Leaves k_lane in kk (lanes 1..p;
-// 0 from the stage it stopped at) and returns E.  Inflate = false leaves r[0] as it is: the -90 dB white floor that
-// steadies an analysed frame would be the whole error of the exact way back from a cepstrum.
-template <bool Inflate = true>
-__device__ __forceinline__ double levinson_lanes(double r, int p, int lane, double& kk) {
-  if (Inflate && lane == 0) r *= (1.0 + 1e-9);
-  double E = __shfl(r, 0, 64);
-  double a = lane == 0 ? 1.0 : 0.0;
-  for (int i = 1; i <= p; ++i) {
-    const int src = (i - lane) & 63;
-    const double rr = __shfl(r, src, 64);
-    const double acc = __shfl(wave_sum(lane < i ? a * rr : 0.0), 0, 64);
-    const double k = -acc / E;
-    if (!(fabs(k) < 1.0)) break;
-    const double ar = __shfl(a, src, 64);
-    if (lane >= 1 && lane <= i) a += k * ar;      // lane i: 0 + k a_0
-    if (lane == i) kk = k;
-    E *= (1.0 - k * k);
-  }
-  return E;
-}
-
-// A(z) of reflection coefficients: lane i holds k_i in kk (lanes 1..p); a_j comes back on lane j (a_0 = 1).  The
-// model's step-up operation by operation: a_j += k_i a_{i-j}, j = 1..i, from the old values.
-__device__ __forceinline__ double stepup_lanes(double kk, int p, int lane) {
-  double a = lane == 0 ? 1.0 : 0.0;
-  for (int i = 1; i <= p; ++i) {
-    const double k = __shfl(kk, i, 64);
-    const double ar = __shfl(a, (i - lane) & 63, 64);
-    if (lane >= 1 && lane <= i) a += k * ar;
-  }
-  return a;
-}
 
 // |A(e^{jw})|^2, a[0..p] in LDS (one address for the wave).  One sincos, then e^{jiw} by rotation: its error grows like
 // i ulp, the size of the rounding of the product i w in the model.
@@ -428,26 +374,83 @@ extern "C" __global__ void __launch_bounds__(64 * NC_WAVES)
 
 // The way back, by the route of the warp kernel: P[t] = exp(2 (C(w_t) - c_0)) = exp(4 sum_q c_q cos(q w_t)) on the grid
 // w_t = pi t / M (Clenshaw's recurrence from cos w_t, which is the block's table entry t), the lag sums and the
-// Levinson-Durbin recursion of noise_warp_frame (without the inflation of r[0]), written a second time so that the warp
-// kernels' machine code stays as it is, and sigma = exp(c_0) sqrt(E).  c_0 never enters P: the reflection coefficients do not depend on it.  An empty
-// row (c_0 = -inf) gives a silent frame.  LDS (static): the cosine table (shared by the block), and per wave P[0..M]
-// and the row c[0..63]: 77 968 bytes, two blocks per CU.  Every wave of the block reaches both barriers.
-extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
+// Levinson-Durbin recursion of noise_warp_frame (without the inflation of r[0]; the lag sums are written a second time,
+// without that body's held stretches), and sigma = exp(c_0) sqrt(E).  c_0 never enters P: the reflection coefficients
+// do not depend on it.  An empty row (c_0 = -inf) gives a silent frame.  LDS (static): the cosine table (shared by the
+// block), and per wave P[0..M] and the row c[0..63]: 77 968 bytes, two blocks per CU.  Every wave of the block reaches
+// both barriers.
+// WARP (include/eaqhm_cepwarp.h): the row lies on the all-pass warped axis with parameter cep_a (0.0 and
+// not read without it), so Clenshaw runs from cos Omega_a(w_t) = (v - u)(v + u) / (u^2 + v^2), u = (1 + a) sin(w_t / 2),
+// v = (1 - a) cos(w_t / 2), taken at the half angle itself (one sincospi per cell beside the Q steps of the recurrence:
+// the table's cos w_t would lose the stretched band to cancellation at |a| near 0.9).  The lag sums and the recursion
+// read the table either way.
+template <bool WARP>
+__global__ void __launch_bounds__(64 * NW_WAVES)
     eaqhm_noise_from_cepstrum_kernel(const double* __restrict__ ceps, int Nf, int Q, int p,
-                                     double* __restrict__ sigma_out, double* __restrict__ refl_out) {
-#define CEP_WARPED 0
-#include "eaqhm_noise_from_cepstrum.inc"
-#undef CEP_WARPED
-}
+                                     double* __restrict__ sigma_out, double* __restrict__ refl_out, double cep_a) {
+  __shared__ double tab[NW_M + 1];
+  __shared__ double Pw[NW_WAVES][NW_M + 2];
+  __shared__ double cw[NW_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x * NW_WAVES + wave;
+  const bool live = m < Nf;
+  for (int j = threadIdx.x; j <= NW_M; j += 64 * NW_WAVES) tab[j] = cospi((double)j / (double)NW_M);
+  const double cl = (live && lane <= Q) ? ceps[(size_t)m * (Q + 1) + lane] : 0.0;
+  double* c = cw[wave];
+  double* P = Pw[wave];
+  c[lane] = cl;
+  const double c0 = __shfl(cl, 0, 64);
+  const bool work = live && c0 != -INFINITY;       // uniform over the wave
+  __syncthreads();
+  if (work) {
+    for (int t = lane; t <= NW_M; t += 64) {
+      double cw2;
+      if constexpr (WARP) {
+        double sh, ch;
+        sincospi((double)t / (double)(2 * NW_M), &sh, &ch);
+        const double u = (1.0 + cep_a) * sh, v = (1.0 - cep_a) * ch;
+        cw2 = 2.0 * (((v - u) * (v + u)) / (u * u + v * v));
+      } else {
+        cw2 = 2.0 * tab[t];
+      }
+      double b1 = 0.0, b2 = 0.0;
+      for (int q = Q; q >= 1; --q) {               // one LDS address for the wave: a broadcast
+        const double b0 = c[q] + (cw2 * b1 - b2);
+        b2 = b1;
+        b1 = b0;
+      }
+      P[t] = exp(4.0 * (0.5 * cw2 * b1 - b2));
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (!work) {
+    if (lane == 0) sigma_out[m] = 0.0;
+    if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = 0.0;
+    return;
+  }
 
-// the same on the all-pass warped axis (include/eaqhm_cepwarp.h)
-extern "C" __global__ void __launch_bounds__(64 * NW_WAVES)
-    eaqhm_noise_from_cepstrum_warped_kernel(const double* __restrict__ ceps, int Nf, int Q, int p,
-                                            double* __restrict__ sigma_out, double* __restrict__ refl_out,
-                                            double cep_a) {
-#define CEP_WARPED 1
-#include "eaqhm_noise_from_cepstrum.inc"
-#undef CEP_WARPED
+  // r[l] on lane l, as in noise_warp_frame
+  auto ct = [&](int t) {
+    const int idx = (lane * t) & (2 * NW_M - 1);
+    return tab[idx > NW_M ? 2 * NW_M - idx : idx];
+  };
+  double r0 = 0.5 * P[0], r1 = 0.0, r2 = 0.0, r3 = ((lane & 1) ? -0.5 : 0.5) * P[NW_M];
+  for (int t = 1; t + 3 < NW_M; t += 4) {
+    r0 = fma(P[t], ct(t), r0);
+    r1 = fma(P[t + 1], ct(t + 1), r1);
+    r2 = fma(P[t + 2], ct(t + 2), r2);
+    r3 = fma(P[t + 3], ct(t + 3), r3);
+  }
+  r0 = fma(P[NW_M - 3], ct(NW_M - 3), r0);
+  r1 = fma(P[NW_M - 2], ct(NW_M - 2), r1);
+  r2 = fma(P[NW_M - 1], ct(NW_M - 1), r2);
+  const double r = ((r0 + r1) + (r2 + r3)) / (double)NW_M;
+
+  double kk = 0.0;
+  const double E = levinson_lanes<false>(r, p, lane, kk);
+  if (lane == 0) sigma_out[m] = exp(c0) * sqrt(E);
+  if (lane >= 1 && lane <= p) refl_out[(size_t)m * p + (lane - 1)] = kk;
 }
 
 // ---- pitch-synchronous modulation of the noise (tests/noise_modulation_ref.py)
@@ -724,12 +727,8 @@ static int noise_from_cepstrum_launch(eaqhm_ctx* ctx, const char* fn, const doub
     return ctx->fail(EAQHM_EINVAL, msg);
   }
   const dim3 grid((unsigned)(((int64_t)Nf + NW_WAVES - 1) / NW_WAVES)), block(64 * NW_WAVES);
-  if (warp)
-    hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_warped_kernel, grid, block, 0, ctx->stream, ceps, (int)Nf,
-                       (int)ceps_order, (int)order, sigma_out, refl_out, *warp);
-  else
-    hipLaunchKernelGGL(eaqhm_noise_from_cepstrum_kernel, grid, block, 0, ctx->stream, ceps, (int)Nf, (int)ceps_order,
-                       (int)order, sigma_out, refl_out);
+  hipLaunchKernelGGL(warp ? eaqhm_noise_from_cepstrum_kernel<true> : eaqhm_noise_from_cepstrum_kernel<false>, grid, block,
+                     0, ctx->stream, ceps, (int)Nf, (int)ceps_order, (int)order, sigma_out, refl_out, warp ? *warp : 0.0);
   HIP_TRY(ctx, hipGetLastError());
   return EAQHM_OK;
 }

@@ -14,6 +14,7 @@
 // The host's NumPy code rounds every operation once, so nothing here may be contracted into an fma: the decisions (which
 // candidate, which fine-grid point) are compared with the host's.  No atomics: every output word has one writer.
 #include "eaqhm_gmm_mfma.h"
+#include "eaqhm_wave.h"
 #include "../../include/eaqhm_swipe.h"
 
 #pragma clang fp contract(off)
@@ -212,19 +213,6 @@ __device__ inline double sw_strength(int c, int nwin, const SwipeWin* wins, cons
   return acc;
 }
 
-// the larger value, the lower index on equal values, over the wave; every lane returns lane 0's answer
-__device__ inline void sw_first_max(double& v, int& i) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const double ov = __shfl_xor(v, d);
-    const int oi = __shfl_xor(i, d);
-    const bool take = ov > v || (ov == v && oi < i);
-    v = take ? ov : v;
-    i = take ? oi : i;
-  }
-  v = __shfl(v, 0);
-  i = __shfl(i, 0);
-}
-
 extern "C" __global__ void __launch_bounds__(256)
     eaqhm_swipe_pick_kernel(SwipeWins a, int nwin, const double* __restrict__ t, i64 T, int npc, double pc0,
                             const double* __restrict__ ntc, const double* __restrict__ nftc,
@@ -268,7 +256,7 @@ extern "C" __global__ void __launch_bounds__(256)
       bi = c;
     }
   }
-  sw_first_max(bv, bi);
+  wave_first_max(bv, bi);
   if (bi == 0 || bi == npc - 1) {   // swipe.py: a maximum on either edge maps to the first candidate
     if (live && lane == 0) {
       p[it] = pc0;
@@ -292,7 +280,7 @@ extern "C" __global__ void __launch_bounds__(256)
     fv = (c2 * xf + c1) * xf + c0;   // Horner, as numpy.polyval
     fi = lane;
   }
-  sw_first_max(fv, fi);
+  wave_first_max(fv, fi);
   if (live && lane == 0) {
     p[it] = ptab[(size_t)bi * nfmax + fi];
     s[it] = fv;

@@ -21,6 +21,7 @@
 // The recurrence has no product; the refinement has, and the host model rounds every operation once, so nothing here
 // may be contracted into an fma.  No atomics: every output word has one writer.
 #include "eaqhm_common.h"
+#include "eaqhm_wave.h"
 #include "../../include/eaqhm_viterbi.h"
 
 #pragma clang fp contract(off)
@@ -49,19 +50,6 @@ __host__ __device__ inline size_t vt_lds_bytes(int K, int W) {
 // traffic only.  __syncthreads() would also wait for the step's back-pointer stores (and the fetch of the next tile) to
 // come back from memory, which nothing in the kernel reads (at 88 and 273 candidates a step measured the same either way).
 __device__ inline void vt_sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// the larger value, the lower index on equal values, over the wave; every lane returns lane 0's answer
-__device__ inline void vt_first_max(double& v, int& i) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const double ov = __shfl_xor(v, d);
-    const int oi = __shfl_xor(i, d);
-    const bool take = ov > v || (ov == v && oi < i);
-    v = take ? ov : v;
-    i = take ? oi : i;
-  }
-  v = __shfl(v, 0);
-  i = __shfl(i, 0);
-}
 
 // element e of a staged tile: candidate e / TILE, instant t0 + e % TILE (a row of S is TILE neighbouring doubles)
 template <int K>
@@ -116,7 +104,7 @@ __global__ void __launch_bounds__(VT_THREADS)
         bv = d[i];
         bi = c0 + i;
       }
-    vt_first_max(bv, bi);
+    wave_first_max(bv, bi);
     if (lane == 0) {
       wmv[4 * buf + wv] = bv;
       wmi[4 * buf + wv] = bi;
@@ -293,7 +281,7 @@ extern "C" __global__ void __launch_bounds__(VT_THREADS)
       bi = c;
     }
   }
-  vt_first_max(bv, bi);
+  wave_first_max(bv, bi);
   if (lane == 0) {
     wmv[wv] = bv;
     wmi[wv] = bi;

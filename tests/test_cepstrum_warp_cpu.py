@@ -345,10 +345,21 @@ def test_binding_header_and_library():
     # a null context is EINVAL before anything else is read
     assert lib.eaqhm_model_cepstrum_warped(None, None, 1, 1, 16000.0, 4, 5e-4, None, 0.42) == -1
     assert lib.eaqhm_noise_from_cepstrum_warped(None, None, 1, 4, 4, None, None, 0.42) == -1
-    makefile = open(os.path.join(ROOT, "eaqhm-analysis-and-synthesis-in-python_amd", "csrc", "Makefile")).read()
+    csrc = os.path.join(ROOT, "eaqhm-analysis-and-synthesis-in-python_amd", "csrc")
+    makefile = open(os.path.join(csrc, "Makefile")).read()
     assert "eaqhm_cepwarp.h" in makefile
-    for inc in ("eaqhm_cepstrum_fit.inc", "eaqhm_cepstrum_build.inc", "eaqhm_noise_from_cepstrum.inc"):
-        assert inc in makefile
+    # the library is rebuilt when any file it is compiled from changes: every file that a source names in an
+    # #include "..." and that exists in the tree is a prerequisite, listed in SRC or HDR
+    listed = set()
+    for var in ("SRC", "HDR"):
+        listed |= {os.path.normpath(os.path.join(csrc, f))
+                   for f in re.search(r"^%s\s*:?=\s*(.*)$" % var, makefile, re.M).group(1).split()}
+    units = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".inc"))]
+    assert units
+    for unit in units:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, unit)).read(), re.M):
+            path = os.path.normpath(os.path.join(csrc, inc))
+            assert not os.path.exists(path) or path in listed, "%s includes %s: not in the Makefile" % (unit, inc)
     for name in ("cepstrum_rewarp", "cepstrum_warp", "allpass_warp", "rewarp_matrix", "check_cepstrum_warp"):
         assert callable(getattr(eaqhm_amd, name))
 

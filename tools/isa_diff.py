@@ -1,16 +1,20 @@
 """Device-code diff of the library against a git revision: does a refactor leave the machine code as it was?
 
-    python tools/isa_diff.py [REV] [-D FLAG ...] [--keep DIR]
+    python tools/isa_diff.py [REV] [-D FLAG ...] [--rename OLD=NEW ...] [--keep DIR]
 
 Builds the gfx950 device assembly of every source in csrc/Makefile's SRC, from the working tree and from REV (default
 HEAD, extracted with git archive), with the Makefile's flags plus --offload-device-only -S and the -D flags given (to
 both builds).  Each .s is normalised: comments, blank lines, .file / .loc / .ident directives and the __hip_cuid_*
 symbol (it differs between two builds of the same source) are dropped, and the local labels (.LBB*, .Ltmp*,
 .Lfunc_end*) are renumbered in order of appearance within each function.  A function's text runs from the directives
-that open it (.text / .protected / .globl / .p2align ahead of its .type) to those of the next one, or to the padding
-that closes the text section, so that a function added next to it leaves it identical.  Reports every function (kernels
-and non-inlined device functions): identical, or differs with its VGPR / AGPR / SGPR counts and scratch / LDS bytes before
--> after.  Exit status 0 when every function and everything outside them compares equal.
+that open it (.text or, for a template's instantiation, its own .section ... comdat; .protected / .globl / .p2align
+ahead of its .type) to those of the next one, or to the padding that closes the text section, so that a function added
+next to it leaves it identical.  Reports every function (kernels and non-inlined device functions): identical, or
+differs with its VGPR / AGPR / SGPR counts and scratch / LDS bytes before -> after.  --rename OLD=NEW (repeatable)
+compares REV's function OLD with the working tree's NEW, for a kernel that changed its symbol (an extern "C" kernel that
+became an instantiation of a kernel template: NEW is the mangled name): OLD is rewritten to NEW in REV's text of the
+function, and the section directive that a comdat function has in place of .text is read as .text on both sides.  Exit
+status 0 when every function and everything outside them compares equal.
 """
 import argparse
 import os
@@ -28,6 +32,7 @@ FLAGS = ["-O3", "-std=c++17", "-fno-strict-aliasing", "--offload-arch=gfx950", "
 
 LABEL = re.compile(r"\.(LBB\d+_\d+|Ltmp\d+|Lfunc_end\d+)\b")
 OPENERS = (".text", ".protected", ".globl", ".p2align", ".weak")
+COMDAT = re.compile(r'^\s*\.section\s+\.text\.\S+,"axG",@progbits,\S+,comdat$')
 FUNC = re.compile(r"^\s*\.type\s+([^,\s]+),@function")
 KD_FIELDS = {  # .amdhsa_* directive of the kernel descriptor -> column of the report
     "next_free_vgpr": "vgpr", "accum_offset": "agpr_off", "next_free_sgpr": "sgpr",
@@ -71,7 +76,8 @@ def split(path):
             m = FUNC.match(line)
             if m or s.startswith((".amdgpu_metadata", ".p2alignl")):
                 head = []   # what opens the next function (or the closing padding) is not the one before's
-                while (m or s.startswith(".p2alignl")) and cur and cur[-1].split()[0] in OPENERS:
+                while ((m or s.startswith(".p2alignl")) and cur
+                       and (cur[-1].split()[0] in OPENERS or COMDAT.match(cur[-1]))):
                     head.insert(0, cur.pop())
                 parts.setdefault(name, []).extend(cur)
                 cur, name = head, (m.group(1) if m else "<outside functions>")
@@ -82,6 +88,18 @@ def split(path):
         parts[k] = [LABEL.sub(lambda m: ".%s_%d" % (re.match(r"[A-Za-z_]+", m.group(1)).group(0),
                                                      ids.setdefault(m.group(1), len(ids))), l) for l in lines]
     return parts
+
+
+def renamed(parts_old, parts_new, renames):
+    """REV's function OLD under the working tree's name NEW; both without the comdat section directives."""
+    for old, new in renames.items():
+        if old not in parts_old or new in parts_old:
+            continue
+        word = re.compile(r"(?<![A-Za-z0-9_$])%s(?![A-Za-z0-9_$])" % re.escape(old))
+        parts_old[new] = [word.sub(new, l) for l in parts_old.pop(old)]
+        for parts in (parts_old, parts_new):
+            if new in parts:
+                parts[new] = ["\t.text" if COMDAT.match(l) else l for l in parts[new]]
 
 
 def resources(lines):
@@ -101,10 +119,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("rev", nargs="?", default="HEAD")
     ap.add_argument("-D", dest="defines", action="append", default=[], help="preprocessor define for both builds")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="compare REV's function OLD with the working tree's function NEW")
     ap.add_argument("--keep", help="write the .s files under this directory and keep them")
     ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
     defines = ["-D" + d for d in a.defines]
+    renames = dict(r.split("=", 1) for r in a.rename)
+    was = {new: old for old, new in renames.items()}
     work = a.keep or tempfile.mkdtemp(prefix="isa_diff_")
     try:
         base_tree = os.path.join(work, "rev_tree")
@@ -124,11 +146,12 @@ def main():
                 same = False
                 continue
             po, pn = split(old[src]), split(new[src])
+            renamed(po, pn, renames)
             print(src)
             for fn in sorted(set(po) | set(pn), key=lambda k: (k.startswith("<"), k)):
                 lo, ln = po.get(fn), pn.get(fn)
                 if lo == ln:
-                    print("  identical  %s" % fn)
+                    print("  identical  %s%s" % (fn, "  (was %s)" % was[fn] if fn in was else ""))
                     continue
                 same = False
                 if lo is None or ln is None:
@@ -137,7 +160,8 @@ def main():
                 ro, rn = resources(lo), resources(ln)
                 keys = [k for k in ("vgpr", "agpr", "agpr_off", "sgpr", "scratch", "lds") if k in ro or k in rn]
                 nd = sum(1 for x, y in zip(lo, ln) if x != y) + abs(len(lo) - len(ln))
-                print("  DIFFERS    %s  (%d of %d lines)" % (fn, nd, len(lo)))
+                print("  DIFFERS    %s%s  (%d of %d -> %d lines)"
+                      % (fn, "  (was %s)" % was[fn] if fn in was else "", nd, len(lo), len(ln)))
                 print("             " + "  ".join("%s %s -> %s" % (k, ro.get(k, "?"), rn.get(k, "?")) for k in keys))
         print("all identical" if same else "device code differs")
         return 0 if same else 1
