@@ -75,7 +75,12 @@ unvoiced state with the score U per instant, so that the path decides voicing to
 DESIGN.md §14) and writes one line per 5 ms frame: seconds, F1..FN, B1..BN in Hz, nan where a formant is absent;
 --formant-count N (1 to 4, default 3) sets N.  --formant-warp-from OTHER.wav measures both files' formants and moves this
 file's spectral envelope along the piecewise-linear map from its own median formants to OTHER's
-(formant.formant_warp_from_tracks); it writes `<name>_modified.wav` and excludes the other four formant flags."""
+(formant.formant_warp_from_tracks); it writes `<name>_modified.wav` and excludes the other four formant flags.
+--protect-transients (with --time-scale, --time-scale-curve or --timing-from) finds the input's transient onsets on the
+device (transient.onset_strength, transient.onsets) and replaces the time scale by the contour that plays
+them at their own duration and stretches the rest a little more, to the same total length
+(transient.protect_time_scale); --phase shape goes well with it.  --transient-delta D (0.5) sets the detector's threshold.
+--onsets-out FILE writes the onsets, one line `seconds strength` each; it works with or without --protect-transients."""
 import argparse
 
 import numpy as np
@@ -169,6 +174,13 @@ def parser():
                     help="with --formants-out / --formant-warp-from: the number of formants, 1 to 4 (3)")
     ap.add_argument("--formant-knee", type=float, default=None, metavar="K",
                     help="with --formant-vtln: the knee as a fraction of fs/2 (0.875)")
+    ap.add_argument("--protect-transients", action="store_true",
+                    help="with --time-scale, --time-scale-curve or --timing-from: bursts and sharp attacks keep their own "
+                         "duration, the rest is stretched a little more (transient.protect_time_scale)")
+    ap.add_argument("--transient-delta", type=float, default=None, metavar="D",
+                    help="with --protect-transients / --onsets-out: the onset detector's threshold, >= 0 (0.5)")
+    ap.add_argument("--onsets-out", default=None, metavar="FILE",
+                    help="write the transient onsets of the input: lines 'seconds strength'")
     ap.add_argument("--no-envelope", action="store_true",
                     help="with --pitch-scale: partials keep their amplitudes instead of the spectral envelope's")
     ap.add_argument("--phase", choices=("independent", "shape"), default="independent",
@@ -285,6 +297,16 @@ def main(argv=None):
             ap.error("--formant-count needs --formants-out or --formant-warp-from")
         if not 1 <= a.formant_count <= FORMANT_TRACKS_MAX:
             ap.error("--formant-count must be in [1, %d]" % FORMANT_TRACKS_MAX)
+    if a.protect_transients and a.time_scale is None and a.time_scale_curve is None and a.timing_from is None:
+        ap.error("--protect-transients needs --time-scale, --time-scale-curve or --timing-from")
+    if a.transient_delta is not None:
+        if not a.protect_transients and a.onsets_out is None:
+            ap.error("--transient-delta needs --protect-transients or --onsets-out")
+        from .transient import check_peak_arguments
+        try:
+            check_peak_arguments(delta=a.transient_delta)
+        except ValueError as e:
+            ap.error("--transient-delta: %s" % e)
     if a.noise_formant and a.formant_scale is None and a.formant_scale_curve is None and not warped:
         ap.error("--noise-formant needs --formant-scale, --formant-scale-curve, --formant-warp-curve or --formant-vtln")
     if a.formant_knee is not None and a.formant_vtln is None:
@@ -442,6 +464,11 @@ def main(argv=None):
         print("wrote", out)
         if a.formants_out is not None:
             write_formants(a.formants_out, *formant_table(a.wav, a.fc, a.formant_count or 3))
+        onset_times = None
+        if a.onsets_out is not None or a.protect_transients:
+            onset_times, strength = onset_table(a.wav, a.fc, a.transient_delta)
+            if a.onsets_out is not None:
+                write_onsets(a.onsets_out, onset_times, strength)
         if train and a.conversion_nonparallel is not None:
             train_conversion_nonparallel(a, gender, analysis_options, fs, det, **on_axis)
         elif train:
@@ -514,6 +541,11 @@ def main(argv=None):
                     noise_rows = warp_rows(noise_cepstrum(nz_o, a.noise_cepstrum), j)
             if convert:
                 ceps = converted
+            if a.protect_transients:   # the same total length, the onsets at rate 1
+                from .transient import protect_time_scale
+                rho, kept = protect_time_scale(det, fs, len(s_recon), rho, onset_times, return_info=True)
+                print("protected %d transients: the rest runs at %.4g x its time scale%s"
+                      % (len(onset_times), kept["c"], ", %d instants clipped" % kept["clipped"] if kept["clipped"] else ""))
             if a.noise_cepstrum is not None:
                 from .model import noise_cepstrum, noise_from_cepstrum
                 if a.noise_from is None:
@@ -558,6 +590,22 @@ def write_formants(out, fs, seconds, F, B):
     n = F.shape[1]
     head = "seconds " + " ".join("F%d" % (i + 1) for i in range(n)) + " " + " ".join("B%d" % (i + 1) for i in range(n))
     np.savetxt(out, np.column_stack((seconds, F, B)), fmt="%.6f", header=head)
+    print("wrote", out)
+
+
+def onset_table(path, fc, delta=None):
+    """The transient onsets of a file's signal: transient.onset_strength and transient.onsets with their
+    defaults, the threshold `delta` unless None.  Returns (seconds float64[K], strength float64[K])."""
+    from . import transient
+    from .prologue import read_signal
+    fs, s = read_signal(path, fc)
+    on = transient.onsets(transient.onset_strength(s, fs), **({} if delta is None else dict(delta=delta)))
+    return on["times"], on["strength"]
+
+
+def write_onsets(out, seconds, strength):
+    """--onsets-out: one line per onset, seconds and strength."""
+    np.savetxt(out, np.column_stack((seconds, strength)).reshape(-1, 2), fmt="%.6f", header="seconds strength")
     print("wrote", out)
 
 

@@ -123,6 +123,12 @@ SYMBOLS_FORMANT = (
     ("eaqhm_formant_forward", C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _F64, _F64, _P, _P]),
     ("eaqhm_formant_backtrack", C.c_int, [_P, _P, _P, _I32, _I64, _P, _P]),
 )
+# every symbol include/eaqhm_onset.h declares: likewise
+SYMBOLS_ONSET = (
+    ("eaqhm_onset_bands", C.c_int, [_P, _P, _I64, _I32, _I32, _I64, _P, _F64, _P, _I32, _F64, _P, _I64]),
+    ("eaqhm_onset_flux", C.c_int, [_P, _P, _I64, _I64, _I32, _I32, _I64, _I64, _P]),
+    ("eaqhm_onset_peaks", C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _I32, _F64, _P]),
+)
 
 
 class HipUnavailable(RuntimeError):
@@ -146,7 +152,7 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailable("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, res, args in (SYMBOLS + SYMBOLS_MLPG + SYMBOLS_GV + SYMBOLS_CEPWARP + SYMBOLS_KMEANS + SYMBOLS_MLPG_EM
-                            + SYMBOLS_NN + SYMBOLS_SWIPE + SYMBOLS_VITERBI + SYMBOLS_FORMANT):
+                            + SYMBOLS_NN + SYMBOLS_SWIPE + SYMBOLS_VITERBI + SYMBOLS_FORMANT + SYMBOLS_ONSET):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -487,6 +493,19 @@ class Context:
 
     def formant_backtrack(self, bp, last, N, T, q, total):
         self._ck(self.lib.eaqhm_formant_backtrack(self.h, _ptr(bp), _ptr(last), N, T, _ptr(q), _ptr(total)))
+
+    # transient onsets: x [n], window [w], k a HOST sequence of B + 1 bin edges, L [nframes][ld]; d [nframes];
+    # flag uint8 [nframes]
+    def onset_bands(self, x, n, w, hop, nframes, window, inv_sumw2, k, B, floor, L, ld):
+        self._ck(self.lib.eaqhm_onset_bands(self.h, _ptr(x), n, w, hop, nframes, _ptr(window), float(inv_sumw2),
+                                            (_I32 * (B + 1))(*[int(v) for v in k]), B, float(floor), _ptr(L), ld))
+
+    def onset_flux(self, L, nframes, ld, B, lag, whole_lo, whole_hi, d):
+        self._ck(self.lib.eaqhm_onset_flux(self.h, _ptr(L), nframes, ld, B, lag, whole_lo, whole_hi, _ptr(d)))
+
+    def onset_peaks(self, d, nframes, pre_max, post_max, pre_avg, post_avg, delta, flag):
+        self._ck(self.lib.eaqhm_onset_peaks(self.h, _ptr(d), nframes, pre_max, post_max, pre_avg, post_avg, float(delta),
+                                            _ptr(flag)))
 
     # the cepstrum on an all-pass warped axis: each is its sibling above plus cep_warp, |cep_warp| <= 0.9
     def model_cepstrum_warped(self, records, No_ti, Kmax, fs, order, lam, ceps, cep_warp):

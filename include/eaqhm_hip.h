@@ -531,6 +531,8 @@ int eaqhm_gmm_regress(eaqhm_ctx* ctx, const double* X, const double* gamma, cons
 #include "eaqhm_viterbi.h"
 /* formant tracks: the poles of the all-pole envelope, the candidates and their Viterbi decode (additions under ABI 6): declared in eaqhm_formant.h. */
 #include "eaqhm_formant.h"
+/* transient onsets: log band energies, their flux and the peak rule (additions under ABI 6): declared in eaqhm_onset.h. */
+#include "eaqhm_onset.h"
 
 #ifdef __cplusplus
 }

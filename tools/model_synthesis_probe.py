@@ -3,7 +3,8 @@ eaqhm_eval_synth on the same records, output samples per second, and unpack_mode
 
     python tools/model_synthesis_probe.py [--workloads synth16k_60s,synth48k_60s] [--reps 5] [--contours] [--formant]
                                           [--noise] [--noise-formant] [--noise-modulation] [--shape] [--formant-warp]
-                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--swipe] [--viterbi] [--out FILE]
+                                          [--cepstrum] [--align] [--build] [--noise-cepstrum] [--swipe] [--viterbi] [--onsets]
+                                          [--out FILE]
 
 Models: one analysis run of the 60 s synthetic workloads (female, maxAdpt=5 at 16 kHz, 1 at 48 kHz).  Settings: rho in
 {0.5, 1, 2} x beta in {1, 1.25}.  --contours adds the contour path (eaqhm_modify_prep with gain and
@@ -58,6 +59,8 @@ a cached plan next to swipep_device and to swipe.swipep in the same process.
 --formant-tracks times the formant tracks on the all-pole models of the same signals
 (formant.signal_allpole: 12 000 frames, p = 18 and 50): eaqhm_allpole_roots, eaqhm_formant_candidates, the forward pass
 at N = 3 and 4 (also per step) and the backtrack, next to a numpy.roots loop over the same frames on the host.
+--onsets times the transient onset detector on the same signals at its defaults: eaqhm_onset_bands (also
+per frame), eaqhm_onset_flux and eaqhm_onset_peaks, and the whole onset_strength + onsets call as wall time.
 EAQHM_LIB selects another build of
 the library.  Device times are warmed HIP-event windows around synchronised launches; per-kernel
 times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/model_synthesis_probe.py` run."""
@@ -571,6 +574,51 @@ def formant_track_rows(torch, workloads, reps=20, runs=3):
             np.roots(a)
         row["host_numpy_roots_s"] = round(time.perf_counter() - t0, 3)
         row["host_over_device_roots"] = round(row["host_numpy_roots_s"] * 1e3 / tr[0], 1)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def onset_rows(torch, workloads, reps=20, runs=3):
+    """The transient onset detector on the 60 s synthetic signals at its defaults (12 000 frames; window
+    256 at 16 kHz, 512 at 48 kHz; 24 bands): eaqhm_onset_bands, eaqhm_onset_flux and eaqhm_onset_peaks as the median of
+    `runs` warmed HIP-event windows of `reps` launches with their max - min; the bands kernel per frame in ns; and the
+    whole onset_strength + onsets call (host array in, host result out) as wall time, the median of five."""
+    from eaqhm_amd import transient
+    from eaqhm_amd.functions import _ctx
+    from eaqhm_amd.synth import synth_speech_int16
+    c = _ctx(0)
+    dev = c.device
+
+    def med(fn):
+        ts = sorted(timed(torch, fn, reps) for _ in range(runs))
+        return round(ts[len(ts) // 2], 4), round(ts[-1] - ts[0], 4)
+
+    rows = []
+    for wl in workloads:
+        fs = {"synth16k_60s": 16000, "synth48k_60s": 48000}[wl]
+        s = synth_speech_int16(60.0, fs) / 32768.0
+        x, fs_, hop, win, k, lag, floor = transient.check_onset_arguments(s, fs)
+        n, w, B = len(x), len(win), len(k) - 1
+        Nf = (n - 1) // hop + 1
+        lo, hi = transient.whole_frames(n, hop, w)
+        x_d, win_d = torch.as_tensor(x, device=dev), torch.as_tensor(win, device=dev)
+        L = torch.empty((Nf, B), dtype=torch.float64, device=dev)
+        d = torch.empty(Nf, dtype=torch.float64, device=dev)
+        flag = torch.empty(Nf, dtype=torch.uint8, device=dev)
+        inv = 1.0 / float(win.sum()) ** 2
+        tb = med(lambda: c.onset_bands(x_d, n, w, hop, Nf, win_d, inv, k, B, floor, L, B))
+        tf = med(lambda: c.onset_flux(L, Nf, B, B, lag, lo, hi, d))
+        tp = med(lambda: c.onset_peaks(d, Nf, 3, 3, 20, 6, 0.5, flag))
+        walls = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            on = transient.onsets(transient.onset_strength(s, fs))
+            walls.append(time.perf_counter() - t0)
+        row = dict(workload=wl, frames=Nf, window=w, hop=hop, bands=B, bands_ms=tb[0], bands_spread_ms=tb[1],
+                   bands_ns_per_frame=round(tb[0] * 1e6 / Nf, 1), flux_ms=tf[0], flux_spread_ms=tf[1], peaks_ms=tp[0],
+                   peaks_spread_ms=tp[1], whole_call_ms=round(sorted(walls)[2] * 1e3, 3), onsets=len(on["frames"]),
+                   flagged=int(flag.sum().item()))
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
@@ -1368,8 +1416,18 @@ def main():
     ap.add_argument("--formant-tracks", action="store_true",
                     help="time the roots, candidates, forward and backtrack kernels of the formant tracks next to a "
                          "numpy.roots loop on the all-pole models of the 60 s signals of --workloads (nothing else runs)")
+    ap.add_argument("--onsets", action="store_true",
+                    help="time the bands, flux and peaks kernels of the transient onset detector and the whole "
+                         "onset_strength + onsets call on the 60 s signals of --workloads (nothing else runs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.onsets:
+        import torch
+        res_onsets = [dict(onsets=onset_rows(torch, a.workloads.split(",")))]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res_onsets, f, indent=1)
+        return 0
     if a.formant_tracks:
         import torch
         res_formant = [dict(formant_tracks=formant_track_rows(torch, a.workloads.split(",")))]
